@@ -3,7 +3,7 @@
 
 Contract: `python bench.py --gpus N --steps K --warmup W`.  N > 1: one rank per GPU -- either launched by the caller
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, the driver's form) or, when no rank environment is set, by
-bench.py itself (it re-executes under torch.distributed.run on 127.0.0.1); `--gpus` must equal the number of ranks, a box with fewer GPUs is
+bench.py itself (it runs torch.distributed.run on 127.0.0.1 as a child process); `--gpus` must equal the number of ranks, a box with fewer GPUs is
 refused with a non-zero exit, and the line carries `rccl_ranks` (ncclCommCount of the communicator the timed region all-reduced over).
 One STEP = one pass of the hot path over one batch of synthetic input: `--batch` (per GPU) full RunRegister-equivalent
 registrations (initial transform -> iterate to the reference's own termination rule or max_iteration), all scans
@@ -20,7 +20,11 @@ scans i = r (mod N) and one all-to-all per 32 scans hands out the shards (bit-id
 same registrations are also timed in replica mode (whole registrations per GPU, no collective) and reported under "replica".
 The timed launches carry no instrumentation: the work counters (C, V, tested candidates) come from one untimed pass of the same step.
 
-At N = 1 the default command also times, in the same process and under `configs`, the other single-GPU BASELINE configurations:
+A plain run sets up, warms up, times the steps, writes the last step's results if `--dump-outputs DIR` is given and prints the line.
+Everything else below -- the work-counter pass and `roofline`, the CPU baseline and pose parity, the side legs, `configs` -- runs only
+with `--full`.
+
+With `--full` at N = 1 the command also times, in the same process and under `configs`, the other single-GPU BASELINE configurations:
   C3_gicp      GICP 131072 / 10M (configs[2]; the reference's shipped default method), + vgicp / avgicp at the same sizes,
   C4_shard     VGICP, 32768-point scans (the per-rank shard of a 262144-point scan at N = 8) vs the 50M-point map, 2048 registrations
                through 256 slots: what ONE rank of `bench.py --gpus 8 --method 2 --scan-points 262144 --map-points 50000000 --batch 256
@@ -31,13 +35,13 @@ each with its own `roofline` (from a counter pass committed AT THAT leg's operat
 
 Prints ONE JSON line on rank 0 with
   * `inputs`: SHA-1 of every uploaded scan + initial guess (the workload is bit-reproducible: seeded, BLAS-free),
-  * `roofline`: dominant kernel and the unit that binds it -- VALU issue for the grid kernel: SQ_INSTS_VALU per SIMD-cycle of the
+  * with `--full`, `roofline`: dominant kernel and the unit that binds it -- VALU issue for the grid kernel: SQ_INSTS_VALU per SIMD-cycle of the
     committed rocprofv3 --pmc pass of this command AT THIS batch / slots (refused otherwise) x the kernel's mean issue cost
     (tools/probes/valu_probe + tools/valu_mix.py), with the hipEvent-measured launch time it belongs to; under
     `hbm` the HBM stream (measured fabric bytes/unit x this run's units per launch / launch time against 8 TB/s), the compulsory
     stream, the bytes the points REQUEST from the kernel's own structures and the SURVEY 8(d) figure of the REFERENCE's walk.  No
     fraction above 1 is ever printed: the model charges a launch at most the part of the index its scans can touch.
-  * at N=1 `cpu_baseline`: the CPU oracle on the host cores, SURVEY 8(d) protocol (3 warm-ups, >= 20 timed
+  * with `--full` at N=1 `cpu_baseline`: the CPU oracle on the host cores, SURVEY 8(d) protocol (3 warm-ups, >= 20 timed
     registrations, median / p10 / p90, correspondence-vs-total split, 10 threads and all cores, a full-map sample),
     `pose_err_vs_cpu`, `reference_api` (RunRegister on host buffers, one call at a time) and `hard_guess` (the 0.5 m /
     2 deg initial-guess set timed the same way).
@@ -110,7 +114,9 @@ def free_port():
 def launch_ranks(args, argv):
     """`python bench.py --gpus N` with N > 1 and no torch.distributed.run environment: become the launcher -- one rank per GPU of this
     node, rendezvous on 127.0.0.1 (the form the driver itself uses for N > 1).  A box with fewer than N GPUs is refused HERE, loudly:
-    a run labelled N GPUs never silently measures one."""
+    a run labelled N GPUs never silently measures one.  The launcher runs as a child process and this one exits with its status: the
+    device count below has initialised the GPU, and a process that holds the GPU must not replace itself (exec) with another program."""
+    import subprocess
     if not args.dry_launch:
         import torch
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -121,7 +127,8 @@ def launch_ranks(args, argv):
            "--master-port", str(free_port()), os.path.abspath(__file__)] + argv
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, dict(os.environ))
+    rc = subprocess.run(cmd, env=dict(os.environ)).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)  # (killed by a signal: the shell's 128 + signal number)
 
 
 def generate_inputs(world, args, rank, world_size, dist, guess, n_keep, keep_own, consume, stats=None):
@@ -582,6 +589,26 @@ def emit(full, path=None):
     return text
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: the results of the last timed step as DIR/<name>.npy, float64, row i = registration i in input order (the pose, the
+    6x6 covariance, the fitness figures, flags and counts of elm_reg_result).  A batch whose arrays would exceed 64 MB is written as a fixed
+    sample (seed 0) of its registrations; `registration.npy` holds the row indices either way."""
+    arrays = {"T": np.stack([r["T"] for r in out]), "local_cov": np.stack([r["local_cov"] for r in out])}
+    for k in ("fitness_score", "d_fitness", "is_success", "iterations", "gate", "path", "n_corr_last", "point_iterations"):
+        arrays[k] = np.array([r[k] for r in out], dtype=np.float64)
+    per_reg = 8 + sum(a[0].size * 8 for a in arrays.values())
+    keep = np.arange(len(out))
+    if len(out) * per_reg > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(out), DUMP_LIMIT_BYTES // per_reg, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "registration.npy"), keep.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a[keep], dtype=np.float64))
+
+
 def single_process_leg(args, n, out, timeout_s=120, devices=""):
     """The same N GPUs driven by ONE process (a device group, `bench.py --single-process`) -- the reference node's process model -- as a
     CHILD process of rank 0 after this job's own timed region, bounded by a timeout: a smaller batch at the same slots, its poses compared
@@ -594,7 +621,7 @@ def single_process_leg(args, n, out, timeout_s=120, devices=""):
     per_gpu = min(256, args.batch)
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--single-process", "--batch", str(per_gpu), "--steps", "3", "--warmup", "1",
            "--method", str(args.method), "--scan-points", str(args.scan_points), "--map-points", str(args.map_points), "--slots", str(args.slots),
-           "--guess", args.guess, "--world", args.world, "--dump-poses", poses] + (["--devices", devices] if devices else [])
+           "--guess", args.guess, "--world", args.world, "--dump-poses", poses, "--full"] + (["--devices", devices] if devices else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK",
                                                             "LOCAL_WORLD_SIZE", "ROLE_WORLD_SIZE", "TORCHELASTIC_RUN_ID", "GROUP_WORLD_SIZE", "ROLE_NAME")}
     t0 = time.time()
@@ -755,15 +782,20 @@ def main():
                     "through host memory -- the one-GPU test form)")
     ap.add_argument("--dump-poses", default="", help="write the final poses / iteration counts of the last step to this .npz (rank 0)")
     ap.add_argument("--dry-launch", action="store_true", help="launcher + rendezvous + sharded input generation only, gloo, no GPU (CPU test of the N > 1 path)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the work-counter pass and `roofline`, the CPU baseline and "
+                    "pose parity, the latency / reference-API / host-fed / hard-guess / replica / single-process legs, the `configs` legs and the C caller "
+                    "(--no-cpu, --no-extras and --legs narrow it).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the results of the last timed step (the arrays a "
+                    "caller of the timed path receives, float64, one row per registration) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
-    extras = not (args.no_extras or args.no_latency)
+    extras = args.full and not (args.no_extras or args.no_latency)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.single_process:
         extras = False
         args.no_cpu = True
     if args.gpus > 1 and "RANK" not in os.environ and not args.single_process:
-        launch_ranks(args, sys.argv[1:])  # does not return
+        launch_ranks(args, sys.argv[1:])  # does not return (exits with the ranks' status)
 
     # stdout carries exactly ONE JSON line: everything libraries print (RCCL banners, gloo notices) goes to stderr
     sys.stdout.flush()
@@ -982,7 +1014,7 @@ def main():
     ncpu, phys, cpu_model = host_cpu_info()
     threads = 10  # the reference's shipped max_thread (config/localization.ini:95)
     O = None
-    want_cpu = rank == 0 and world_size == 1 and not args.no_cpu and args.cpu_sample > 0
+    want_cpu = args.full and rank == 0 and world_size == 1 and not args.no_cpu and args.cpu_sample > 0
     if want_cpu:
         from oracle import oracle as O  # noqa: N811  (the checker: CPU baseline + pose parity only)
 
@@ -1076,7 +1108,7 @@ def main():
     info = vm.info()
     t_map = time.time() - t0
     n_batch = args.batch * ranks  # weak scaling: per-GPU points per launch fixed
-    n_keep = max(args.cpu_sample, 0 if args.no_cpu else min(args.pose_sample, args.batch), 8) if (rank == 0 and world_size == 1) else 0  # full host copies kept for the CPU / reference-API legs (N = 1)
+    n_keep = max(args.cpu_sample, 0 if args.no_cpu else min(args.pose_sample, args.batch), 8) if (args.full and rank == 0 and world_size == 1) else 0  # full host copies kept for the CPU / reference-API legs (N = 1)
     guess = dict(max_trans=0.15, max_rot_deg=0.5) if args.guess == "easy" else dict(max_trans=0.5, max_rot_deg=2.0)
     want_replica = extras and distributed and args.slots > 0 and (world_size > 1 or bool(os.environ.get("ELM_BENCH_FORCE_REPLICA")))
 
@@ -1132,9 +1164,13 @@ def main():
     regs = n_batch * args.steps
     value = regs / elapsed
     iters = np.array([r["iterations"] for r in out])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # The timed launches carry no instrumentation.  The work counters (candidates C / occupied voxels V of the reference's walk, candidates
-    # this kernel distance-tests) come from ONE untimed pass of the same step with the counters compiled in: same poses, bit for bit.
-    if args.slots > 0:
+    # this kernel distance-tests) come from ONE untimed pass of the same step with the counters compiled in: same poses, bit for bit (--full).
+    if not args.full:
+        cvt = None
+    elif args.slots > 0:
         cvt = work_counters(step, out)
     else:
         ctx.set_work_counters(True)
@@ -1144,7 +1180,7 @@ def main():
         cvt = (float(sum(r["n_cand_total"] for r in out_c)) / pt, float(sum(r["n_occ_total"] for r in out_c)) / pt, float(sum(r["n_tested_total"] for r in out_c)) / pt,
                float(sum(r["fallback_blocks"] for r in out_c)) / pt)
     info = vm.info()
-    roofline = leg_roofline(method, vm, prof, args.steps, out, cvt, op_point, elapsed)
+    roofline = leg_roofline(method, vm, prof, args.steps, out, cvt, op_point, elapsed) if cvt else None
 
     result = {
         "metric": "ICP registrations/sec, 128k-pt scan vs 10M-pt map; pose err vs CPU ref",
@@ -1187,8 +1223,7 @@ def main():
             "map_points_retained": int(info.n_points),
             "map_voxels": int(info.n_voxels),
             "map_layout_flags": int(info.layout_flags),  # include/elimaloc_hip.h; bits 7 / 8: the map holds asymmetric covariances (side records)
-            "candidates_per_point_C": cvt[0],
-            "occupied_voxels_per_point_V": cvt[1],
+            **({"candidates_per_point_C": cvt[0], "occupied_voxels_per_point_V": cvt[1]} if cvt else {}),
             "map_build_s": t_map,
             "input_gen_s": t_in,
             "input_generation": ("every scan generated on this rank" if world_size == 1 else

@@ -112,8 +112,8 @@ def test_n2_flow_rehearsed_on_one_gpu():
     sharded registrations with one exchange per iteration, hard-guess leg, replica leg, the single-process device-group child, the line.
     It measures nothing (`rehearsal: true`); it shows that the pieces the driver's first multi-GPU run executes do execute, and that the
     three process models agree on the poses."""
-    p = run(["--gpus", "2", "--batch", "24", "--slots", "8", "--steps", "1", "--warmup", "1", "--scan-points", "6001", "--map-points", "200000"],
-            env_extra={"ELM_BENCH_SHARED_GPU": "1"}, timeout=900)
+    p = run(["--gpus", "2", "--batch", "24", "--slots", "8", "--steps", "1", "--warmup", "1", "--scan-points", "6001", "--map-points", "200000",
+             "--full"], env_extra={"ELM_BENCH_SHARED_GPU": "1"}, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -123,3 +123,29 @@ def test_n2_flow_rehearsed_on_one_gpu():
     sp = line["single_process"]
     assert "error" not in sp and sp["devices"] == 2 and sp["iterations_match"] is True and sp["max_abs_pose_diff_vs_ranks"] < 1e-9
     assert len(lines[0]) < 6000
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1` without --full: the timed steps and the line only (no work-counter pass, no roofline, no CPU legs); --dump-outputs
+    writes the last step's results, and a second run on the same arguments writes the same arrays (seeded inputs)."""
+    args = ["--gpus", "1", "--batch", "16", "--slots", "8", "--steps", "3", "--warmup", "1", "--scan-points", "4001", "--map-points", "200000"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        p = run(args + ["--dump-outputs", str(d)], timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert abs(line["value"] - 16 * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+        assert line["roofline"] is None and "cpu_baseline" not in line and "configs" not in line and "hard_guess" not in line
+        arrays = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert arrays["T"].shape == (16, 4, 4) and arrays["local_cov"].shape == (16, 6, 6)
+        assert all(a.dtype == np.float64 and a.shape[0] == 16 for a in arrays.values())
+        assert np.array_equal(arrays["registration"], np.arange(16)) and set(np.unique(arrays["is_success"])) <= {0.0, 1.0}
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k

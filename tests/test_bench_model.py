@@ -5,6 +5,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -213,3 +214,25 @@ def test_footprints_overlap_before_they_tile_the_map():
     a = bench.index_touch_bound(1.0e9, 1e12, 1e6, 235, 50_000_000, shard_of=8)
     assert 0.18e9 < a + bench.L2_TOTAL_BYTES < 0.20e9  # 1 - exp(-0.214), not 0.214 (minus what the L2s keep between launches)
     assert bench.index_touch_bound(0.25e9, 1e12, 1e6, 235, 10_000_000) > 0.249e9 - bench.L2_TOTAL_BYTES
+
+
+def test_dump_outputs_writes_float64_rows_and_samples_a_large_batch(tmp_path, monkeypatch):
+    """--dump-outputs: one row per registration in input order, float64; above the size limit a fixed sample of rows (the same every run)"""
+    rng = np.random.default_rng(5)
+    out = [dict(T=rng.standard_normal((4, 4)), local_cov=rng.standard_normal((6, 6)), fitness_score=0.1 * i, d_fitness=0.0, is_success=i % 3 > 0,
+                iterations=i % 7, gate=0, path=1, n_corr_last=100.0 + i, point_iterations=1e3 * i) for i in range(50)]
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    a = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert set(a) == {"registration", "T", "local_cov", "fitness_score", "d_fitness", "is_success", "iterations", "gate", "path", "n_corr_last",
+                      "point_iterations"}
+    assert all(v.dtype == np.float64 and v.shape[0] == 50 for v in a.values())
+    assert np.array_equal(a["T"][7], out[7]["T"]) and a["iterations"][13] == 6 and a["is_success"][3] == 0.0
+    per_reg = 8 * (1 + 16 + 36 + 8)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20 * per_reg)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"s{k}"), out)
+    s0, s1 = ({f.stem: np.load(f) for f in (tmp_path / f"s{k}").glob("*.npy")} for k in range(2))
+    idx = s0["registration"].astype(int)
+    assert len(idx) == 20 and np.all(np.diff(idx) > 0) and sum(v.nbytes for v in s0.values()) <= 20 * per_reg
+    assert np.array_equal(s0["T"], np.stack([out[i]["T"] for i in idx]))
+    assert all(np.array_equal(s0[k], s1[k]) for k in s0)

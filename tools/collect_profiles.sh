@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="${BENCH_ARGS:-} --no-cpu --no-extras --warmup ${PROF_WARMUP:-1} --steps ${PROF_STEPS:-3} --batch ${PROF_BATCH:-4096}"
+ARGS="${BENCH_ARGS:-} --full --no-cpu --no-extras --warmup ${PROF_WARMUP:-1} --steps ${PROF_STEPS:-3} --batch ${PROF_BATCH:-4096}"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $R/bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 pass() { # name counters...
   local name=$1; shift
@@ -27,7 +27,7 @@ if [ -n "${PROF_STALLS:-}" ]; then  # where the waves wait (AVGICP / GICP / hard
   pass st2 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_LEVEL_LDS SQ_INST_CYCLES_VMEM SQ_INSTS_LDS SQ_WAVES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES
   pass st3 TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_TA_TCP_STATE_READ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum GRBM_GUI_ACTIVE
 fi
-[ -n "${PROF_NO_FINAL:-}" ] || python $R/bench.py ${BENCH_ARGS:-} ${FINAL_ARGS:---no-cpu} > $OUT/bench.json 2> $OUT/bench.err
+[ -n "${PROF_NO_FINAL:-}" ] || python $R/bench.py --full ${BENCH_ARGS:-} ${FINAL_ARGS:---no-cpu} > $OUT/bench.json 2> $OUT/bench.err
 python $R/tools/summarise_profiles.py $OUT
 # the rocprofv3 databases stay on the box (gpurun merges at most 64 MiB back): the summaries are what gets committed
 rm -rf $OUT/trace $OUT/pmc_*/

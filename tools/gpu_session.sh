@@ -4,10 +4,10 @@
 #
 #   suite                      python -m pytest tests -x -q -m gpu
 #   tests:<-k expression>      the GPU tests selected by a -k expression (use + for spaces: tests:asymmetric+or+two_ranks)
-#   bench[:name[:args]]        python bench.py <args> (default: --gpus 1 --steps 20 --warmup 5; args with _ for spaces... or BENCH_<NAME>_ARGS)
+#   bench[:name[:args]]        python bench.py --full <args> (default: --gpus 1 --steps 20 --warmup 5; args with _ for spaces... or BENCH_<NAME>_ARGS)
 #   dist1                      the default command under torch.distributed.run --nproc-per-node 1 (one-rank RCCL communicator)
 #   ab:<name>:<tags>[:args]    A/B of prebuilt library variants build_ab/lib_<tag>.so (comma list, each run twice, interleaved) on
-#                              `bench.py --no-cpu --no-extras <args, _ for spaces> $AB_ARGS`
+#                              `bench.py --full --no-cpu --no-extras <args, _ for spaces> $AB_ARGS`
 #   fuzz:<cases>:<seed0>[:ENV=1,ENV2=x;--extra_args]   tools/fuzz_parity.py (environment assignments, then extra arguments with _ for spaces)
 #   profiles[:legs]            tools/r6_profiles.sh (legs comma list: p2p,gicp,vgicp,avgicp,hard,c4)
 #   timeline                   kernel timeline of one ICP iteration on the one-rank RCCL path (tools/trace_gaps_dist1.sh)
@@ -42,14 +42,14 @@ for step in "$@"; do
       python -m pytest tests -x -q -m gpu -k "${a//+/ }" > $O/tests_$(echo "$a" | tr -c 'a-zA-Z0-9\n' '_' | cut -c1-40).txt 2>&1; tail -3 $O/tests_*.txt | tail -3 ;;
     bench)
       name=${a:-default}; v="BENCH_$(echo $name | tr a-z A-Z)_ARGS"; args=${!v:-${b//_/ }}; [ -z "$args" ] && args="--gpus 1 --steps 20 --warmup 5"
-      ( time python bench.py $args > $O/$name.json 2> $O/$name.err ) 2> $O/$name.time || tail -5 $O/$name.err
+      ( time python bench.py --full $args > $O/$name.json 2> $O/$name.err ) 2> $O/$name.time || tail -5 $O/$name.err
       summ $name $O/$name.json ;;
     dist1)
-      python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --legs none > $O/dist1.json 2> $O/dist1.err || tail -5 $O/dist1.err
+      python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --legs none > $O/dist1.json 2> $O/dist1.err || tail -5 $O/dist1.err
       summ dist1 $O/dist1.json ;;
     ab)
       for rep in 1 2; do for L in ${b//,/ }; do
-        ELM_LIB=$PWD/build_ab/lib_$L.so python bench.py --no-cpu --no-extras ${c//_/ } ${AB_ARGS:-} > $O/ab_${a}_${L}_$rep.json 2> $O/ab_${a}_${L}_$rep.err || tail -3 $O/ab_${a}_${L}_$rep.err
+        ELM_LIB=$PWD/build_ab/lib_$L.so python bench.py --full --no-cpu --no-extras ${c//_/ } ${AB_ARGS:-} > $O/ab_${a}_${L}_$rep.json 2> $O/ab_${a}_${L}_$rep.err || tail -3 $O/ab_${a}_${L}_$rep.err
         summ "$a/$L" $O/ab_${a}_${L}_$rep.json
       done; done ;;
     sq)   # sq:<name>:<lib tag>[:args]  one SQ counter pass of a prebuilt variant: VALU instructions per wave / per SIMD-cycle, TA busy

@@ -5,7 +5,7 @@ O=gpurun_out/${1:-r06ab}
 mkdir -p $O
 run() { # name lib args...
   local name=$1 lib=$2; shift 2
-  ELM_LIB=$lib python bench.py "$@" --no-cpu --no-extras --steps 6 --warmup 2 > $O/$name.json 2> $O/$name.err
+  ELM_LIB=$lib python bench.py "$@" --full --no-cpu --no-extras --steps 6 --warmup 2 > $O/$name.json 2> $O/$name.err
   python - $O/$name.json $name <<'PY' >> $O/ab.txt
 import json,sys
 l=json.load(open(sys.argv[1])); r=l["roofline"]

@@ -6,10 +6,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 O=gpurun_out/${1:-r06z}
 mkdir -p $O
 ( time python -m pytest tests -x -q -m gpu > $O/pytest.txt 2>&1 ) 2> $O/pytest.time; tail -3 $O/pytest.txt | tr '\n' ' '; grep real $O/pytest.time
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/default_line.json 2> $O/default.err ) 2> $O/default.time; cp bench_full.json $O/default_full.json
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/default_line.json 2> $O/default.err ) 2> $O/default.time; cp bench_full.json $O/default_full.json
 wc -c $O/default_line.json; grep real $O/default.time
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --legs none > $O/dist1_line.json 2> $O/dist1.err; cp bench_full.json $O/dist1_full.json
-python bench.py --gpus 2 --single-process --devices 0,0 --batch 512 --steps 3 --warmup 1 > $O/group00_line.json 2> $O/group00.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --legs none > $O/dist1_line.json 2> $O/dist1.err; cp bench_full.json $O/dist1_full.json
+python bench.py --gpus 2 --single-process --devices 0,0 --batch 512 --steps 3 --warmup 1 --full > $O/group00_line.json 2> $O/group00.err
 tools/default_trace.sh > $O/default_trace.txt 2>&1; cp gpurun_out/prof_default/kernel_stats.csv $O/default_kernel_stats.csv; cp gpurun_out/prof_default/bench_trace.json $O/default_bench_under_rocprof.json
 python - $O <<'PY'
 import json, sys, os
