@@ -123,6 +123,19 @@ class DeskewTables(C.Structure):
     ]
 
 
+class RelocConfigC(C.Structure):
+    """elm_reloc_config (include/elimaloc_hip.h, relocalization)."""
+    _fields_ = [("radius_xy_m", C.c_double), ("step_xy_m", C.c_double), ("yaw_range_deg", C.c_double), ("step_yaw_deg", C.c_double),
+                ("score_max_range_m", C.c_double), ("max_score_points", C.c_int32), ("top_k", C.c_int32), ("nms_xy_m", C.c_double),
+                ("nms_yaw_deg", C.c_double), ("lds_budget_bytes", C.c_int64), ("bitmap_max_bytes", C.c_int64)]
+
+
+class RelocCandidate(C.Structure):
+    """elm_reloc_candidate: a kept hypothesis (T0) and its ICP result (T), column-major."""
+    _fields_ = [("T0", C.c_double * 16), ("T", C.c_double * 16), ("score", C.c_uint32), ("hyp_index", C.c_int32),
+                ("is_success", C.c_int32), ("iterations", C.c_int32), ("fitness_score", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -140,6 +153,7 @@ EXPORTS = [
     "elm_ini_load", "elm_ini_destroy", "elm_ini_get_string", "elm_ini_get_int", "elm_ini_get_bool", "elm_ini_get_double",
     "elm_ini_get_array", "elm_pcm_node_config_default", "elm_load_pcm_config", "elm_load_ekf_config", "elm_pcd_load_xyz",
     "elm_free", "elm_scan_from_cloud", "elm_pcm_callback_point_cloud",
+    "elm_reloc_config_default", "elm_reloc_make_hypotheses", "elm_map_score_poses", "elm_relocalize",
 ]
 
 
@@ -302,6 +316,12 @@ def lib():
                                       C.c_size_t, szp]
     L.elm_pcm_callback_point_cloud.argtypes = [vp, vp, C.POINTER(PcmNodeConfig), C.POINTER(RegConfig), fp, fp, C.c_size_t, C.c_double,
                                                dp, C.c_size_t, dp, C.c_size_t, C.POINTER(PcmScanOutput), ip]
+    L.elm_reloc_config_default.argtypes = [C.POINTER(RelocConfigC)]
+    L.elm_reloc_config_default.restype = None
+    L.elm_reloc_make_hypotheses.argtypes = [dp, C.POINTER(RelocConfigC), dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_map_score_poses.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RelocConfigC), C.POINTER(C.c_uint32)]
+    L.elm_relocalize.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(RelocConfigC), C.POINTER(RegConfig), dp, C.POINTER(RegResult),
+                                 C.POINTER(RelocCandidate), C.c_int, ip]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

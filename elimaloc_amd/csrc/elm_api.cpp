@@ -101,6 +101,7 @@ struct elm_ctx {
     uint16_t* d_hilbert = nullptr; // Hilbert index of every cell of the ordering grid (kOrderCells^2 entries)
     DevBuf d_order_jobs, d_order_tmp, d_arena, d_raw, d_flagged, d_asym;
     DevBuf d_q0, d_q1, d_q2, d_q3, d_q4, d_q5; // scratch of elm_map_get_correspondences / elm_align_clouds_local (kept between calls)
+    DevBuf d_reloc[5]; // scratch of elm_map_score_poses / elm_relocalize (elm_reloc.cpp; kept between calls)
     bool work_counters = false; // elm_ctx_set_work_counters: the accumulate launches also sum the work counters of
                                 // elm_reg_result (n_cand_total, n_occ_total, n_tested_total, fallback_blocks); off: those fields read 0
     void* h_jobs = nullptr; // pinned: ordering job descriptors
@@ -330,7 +331,8 @@ extern "C" void elm_ctx_destroy(elm_ctx* ctx) {
     if (ctx->d_hilbert) (void)hipFree(ctx->d_hilbert);
     if (ctx->h_jobs) (void)hipHostFree(ctx->h_jobs);
     DevBuf* bufs[] = {&ctx->d_scans, &ctx->d_state, &ctx->d_partials, &ctx->d_sums, &ctx->d_T0, &ctx->d_trace, &ctx->d_stage_pts, &ctx->d_active, &ctx->d_queue, &ctx->d_ds,
-                      &ctx->d_order_jobs, &ctx->d_order_tmp, &ctx->d_arena, &ctx->d_raw, &ctx->d_flagged, &ctx->d_asym, &ctx->d_q0, &ctx->d_q1, &ctx->d_q2, &ctx->d_q3, &ctx->d_q4, &ctx->d_q5};
+                      &ctx->d_order_jobs, &ctx->d_order_tmp, &ctx->d_arena, &ctx->d_raw, &ctx->d_flagged, &ctx->d_asym, &ctx->d_q0, &ctx->d_q1, &ctx->d_q2, &ctx->d_q3, &ctx->d_q4, &ctx->d_q5,
+                      &ctx->d_reloc[0], &ctx->d_reloc[1], &ctx->d_reloc[2], &ctx->d_reloc[3], &ctx->d_reloc[4]};
     if (ctx->h_active) (void)hipHostFree(ctx->h_active);
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -2854,6 +2856,14 @@ elm_ctx* map_ctx(const elm_map* m) { return m->ctx; }
 std::vector<elm_scan*>& scan_shards(elm_scan* s) { return s->shards; }
 elm_ctx* scan_ctx(const elm_scan* s) { return s->ctx; }
 void scan_set_total(elm_scan* s, size_t n_total) { s->n_total = (uint32_t)n_total; }
+// ... and for elm_reloc.cpp
+bool ctx_exchange_attached(const elm_ctx* ctx) { return ctx->comm != nullptr || ctx->hook != nullptr; }
+bool ctx_in_flight(const elm_ctx* ctx) { return ctx->in_flight; }
+void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc) {
+    *rc = dev_reserve(ctx, ctx->d_reloc[which], bytes);
+    return *rc == ELM_OK ? ctx->d_reloc[which].p : nullptr;
+}
+const elm::DevMap& map_dev(const elm_map* m) { return m->dm; }
 } // namespace elm_host
 
 // ------------------------------------------------------------------------------------------------------

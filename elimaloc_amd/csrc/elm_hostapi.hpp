@@ -9,6 +9,7 @@
 
 #include "../../include/elimaloc_hip.h"
 
+namespace elm { struct DevMap; }
 struct elm_group; // a lead context's group of per-device contexts inside one process (elm_multi.cpp)
 
 namespace elm_host {
@@ -27,6 +28,11 @@ elm_ctx* map_ctx(const elm_map* m);
 std::vector<elm_scan*>& scan_shards(elm_scan* s);
 elm_ctx* scan_ctx(const elm_scan* s);
 void scan_set_total(elm_scan* s, size_t n_total);
+// ... for elm_reloc.cpp
+bool ctx_exchange_attached(const elm_ctx* ctx); // a communicator or an all-reduce hook is attached
+bool ctx_in_flight(const elm_ctx* ctx);          // an enqueued batch has not been finished
+void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc); // grow-only device scratch 0..4 of the context (nullptr: *rc)
+const elm::DevMap& map_dev(const elm_map* m);
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

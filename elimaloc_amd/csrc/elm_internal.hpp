@@ -307,6 +307,19 @@ void launch_nbr_fill(hipStream_t s, const DevMap& m, const int32_t* qkeys, uint3
 void launch_voxel_cov(hipStream_t s, const DevMap& m, const uint2* ranges, double* vox_mean, double* vox_cov, double* vox_cinv, double* vox_nk, unsigned* bad);
 void launch_point_cov(hipStream_t s, const DevMap& m, double d2max, double* pt_gicp, double* pt_cov, unsigned* bad); // pt_cov [n_pts][9]: read-backs
 
+// relocalization scores (elm_k_reloc.hip): the key box of the occupancy bitmap, cells (cx * ny + cy) * nz + cz
+struct RelocBox {
+    int32_t x0, y0, z0;
+    uint32_t nx, ny, nz;
+};
+constexpr int kRelocPPL = 8;                    // scan points per lane of k_reloc_score
+constexpr int kRelocChunk = kBlock * kRelocPPL; // points per workgroup
+constexpr int kRelocHyp = 32;                   // hypotheses per workgroup
+void launch_reloc_bitmap(hipStream_t s, const DevMap& m, const RelocBox& b, uint64_t n_cells, unsigned long long* bits);
+// form 0: bitmap in LDS (n_words 32-bit words), 1: bitmap in global memory, 2: hash probes only.  partial: [n_poses][chunks] scratch
+void launch_reloc_score(hipStream_t s, int form, const DevMap& m, const float* pts, uint32_t n, const double* poses, uint32_t n_poses,
+                        const RelocBox& b, const uint32_t* bits, uint32_t n_words, uint32_t* partial, uint32_t* scores);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

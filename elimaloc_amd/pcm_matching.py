@@ -184,8 +184,11 @@ class PcmMatching:
                     fitness=out.fitness_score, time=out.time_scan_end, covariance=np.array(out.covariance).reshape(6, 6),
                     n_source=int(out.n_source))
 
-    def CallbackInitialPose(self, rviz_pose, raw_scan_xyz):
-        """pcm.cpp:356-447: ground height under the clicked pose, then RunRegister on the last RAW scan."""
+    def CallbackInitialPose(self, rviz_pose, raw_scan_xyz, relocalize=None):
+        """pcm.cpp:356-447: ground height under the clicked pose, then RunRegister on the last RAW scan.
+
+        relocalize: a RelocConfig -- the same ground-height step, then Relocalize (occupancy-scored xy x yaw hypotheses around the clicked
+        pose, ICP from the best ones) instead of the single RunRegister; the result also carries the candidates.  None: the reference's call."""
         rviz_pose = np.asarray(rviz_pose, dtype=np.float64)
         found, z_ground = self.local_map_.FindGroundHeight(rviz_pose[:2, 3])
         if not found:
@@ -194,10 +197,15 @@ class PcmMatching:
         ground_pose[2, 3] = z_ground
         init_lidar_pose = ground_pose @ self.cfg_.tf_ego_to_lidar
         src, _ = voxel_downsample(raw_scan_xyz, self.cfg_.d_input_voxel_ds_m)
-        pose, ok, fit, cov = self.registration_.RunRegister(src, self.local_map_, init_lidar_pose)
+        if relocalize is None:
+            pose, ok, fit, cov = self.registration_.RunRegister(src, self.local_map_, init_lidar_pose)
+            extra = {}
+        else:
+            pose, ok, fit, cov, cands = self.registration_.Relocalize(src, self.local_map_, init_lidar_pose, relocalize)
+            extra = dict(candidates=cands)
         self.icp_local_cov_ = cov
         final_pose = pose @ np.linalg.inv(self.cfg_.tf_ego_to_lidar)
         if not ok:
             return None
         self.d_icp_pose_std_m = fit
-        return dict(pose_ego=final_pose, pose_lidar=pose, fitness=fit, ground_z=z_ground)
+        return dict(pose_ego=final_pose, pose_lidar=pose, fitness=fit, ground_z=z_ground, **extra)

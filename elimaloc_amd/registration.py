@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import ElmError, RegConfig, RegResult, IterTrace, MapInfo, check
+from ._lib import ElmError, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC, check
 
 
 class IcpMethod(enum.IntEnum):  # reg.hpp:60
@@ -31,6 +31,34 @@ def RegistrationConfig(**kw):
             raise AttributeError(f"RegistrationConfig has no field {k}")
         setattr(cfg, k, int(v) if k in ("icp_method", "max_iteration", "i_max_thread", "use_radar_cov") else v)
     return cfg
+
+
+def RelocConfig(**kw):
+    """elm_reloc_config with its defaults (5 m / 0.5 m xy window, 180 deg / 2 deg yaw, 50 m score range, 8192 score points, top 16 after
+    non-maximum suppression at 1.0 m / 6 deg, 64 KiB LDS / 64 MiB bitmap budgets)."""
+    cfg = RelocConfigC()
+    _lib.lib().elm_reloc_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(f"RelocConfig has no field {k}")
+        setattr(cfg, k, int(v) if k in ("max_score_points", "top_k", "lds_budget_bytes", "bitmap_max_bytes") else float(v))
+    return cfg
+
+
+def MakeHypotheses(guess, reloc=None):
+    """The relocalization hypotheses around guess (elm_reloc_make_hypotheses) -> [n, 4, 4], index h = (k W + (i + m)) W + (j + m)."""
+    cfg = reloc if reloc is not None else RelocConfig()
+    T = _colmajor16(guess)
+    n = C.c_size_t(0)
+    check(_lib.lib().elm_reloc_make_hypotheses(_dp(T), C.byref(cfg), None, 0, C.byref(n)), None, "elm_reloc_make_hypotheses")
+    out = np.empty((n.value, 16))
+    check(_lib.lib().elm_reloc_make_hypotheses(_dp(T), C.byref(cfg), _dp(out), n.value, C.byref(n)), None, "elm_reloc_make_hypotheses")
+    return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
+
+def _candidate_dict(c):
+    return dict(T0=np.array(c.T0).reshape(4, 4).T.copy(), T=np.array(c.T).reshape(4, 4).T.copy(), score=int(c.score),
+                hyp_index=int(c.hyp_index), is_success=bool(c.is_success), iterations=int(c.iterations), fitness_score=float(c.fitness_score))
 
 
 def _dp(a):
@@ -315,6 +343,18 @@ class VoxelHashMap:
         tc = np.where(ok[:, None, None], cov[np.maximum(tgt, 0)], np.eye(3)) if tgt.size else np.zeros((0, 3, 3))
         return (q[src], tm, tc, src, tgt) if indices else (q[src], tm, tc)
 
+    def ScorePoses(self, scan, poses, cfg=None):
+        """Voxel-occupancy scores (elm_map_score_poses) of poses [n, 4, 4] for a scan (a resident Scan, or (m, 3) points uploaded for the
+        call): per pose the number of scan points within cfg.score_max_range_m whose stored key under the pose is a voxel of the map."""
+        cfg = cfg if cfg is not None else RelocConfig()
+        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        n = P.size // 16
+        out = np.zeros(max(n, 1), np.uint32)
+        check(_lib.lib().elm_map_score_poses(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg),
+                                             out.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx._h, "elm_map_score_poses")
+        return out[:n]
+
     def GetAdjacentVoxels(self, point, search_range):  # vhm.cpp:208-243: keys only, whether or not such voxels exist
         v = self.PointToVoxel(point, self.voxel_size_).astype(np.int64)
         if search_range == 0:
@@ -435,6 +475,28 @@ class Registration:
         if trace:
             return out + (_result_dict(res, tr),)
         return out
+
+    def Relocalize(self, source_local, voxel_map, guess, reloc=None, m_config=None):
+        """Relocalization from a coarse pose (elm_relocalize): occupancy scores of the xy x yaw hypotheses around guess on the device, non-maximum
+        suppression, ICP from the best top_k in one batch.  Returns (pose 4x4, is_success, fitness_score or None, local_cov 6x6, candidates):
+        the winner's result and the kept hypotheses in rank order (dicts: T0, T, score, hyp_index, is_success, iterations, fitness_score).
+        The winner's full result dict is kept in last_relocalize_."""
+        cfg = m_config if m_config is not None else self.config_
+        rc = reloc if reloc is not None else RelocConfig()
+        scan = np.ascontiguousarray(source_local, dtype=np.float32).reshape(-1, 3)
+        T0 = _colmajor16(guess)
+        Tout = np.empty(16)
+        res = RegResult()
+        cap = int(rc.top_k)
+        cands = (RelocCandidate * cap)()
+        nc = C.c_int(0)
+        check(_lib.lib().elm_relocalize(self.ctx._h, voxel_map._handle(), _fp(scan), scan.shape[0], _dp(T0), C.byref(rc), C.byref(cfg),
+                                        _dp(Tout), C.byref(res), cands, cap, C.byref(nc)), self.ctx._h, "elm_relocalize")
+        self.d_fitness_score_ = res.d_fitness
+        self.last_relocalize_ = _result_dict(res)
+        ok = bool(res.is_success)
+        return (Tout.reshape(4, 4).T.copy(), ok, (res.fitness_score if ok else None), np.array(res.local_cov).reshape(6, 6).T.copy(),
+                [_candidate_dict(cands[b]) for b in range(min(nc.value, cap))])
 
     def _align(self, method, source_local, target_xyz, target_cov, last_icp_pose, trans_th, m_config, source_cov=None):
         cfg = m_config if m_config is not None else self.config_

@@ -56,6 +56,11 @@ struct RegistrationConfig {
     }
 };
 
+// elm_reloc_config with its defaults (include/elimaloc_hip.h, relocalization): the search window, score range, top_k and NMS of RunRelocalize
+struct RelocConfig : elm_reloc_config {
+    RelocConfig() { elm_reloc_config_default(this); }
+};
+
 struct Registration {
     Registration() {}
     Registration(RegistrationConfig config) { config_ = config; }
@@ -98,6 +103,32 @@ struct Registration {
                         VoxelHashMap::ctx(), "RunRegister");
         is_success = ok != 0;
         d_fitness_score_ = res.d_fitness;
+        return T;
+    }
+
+    // Relocalization from a coarse pose (not in the reference; a node's CallbackInitialPose can call it where pcm.cpp:412-414 calls RunRegister):
+    // the xy x yaw hypotheses of reloc_config around init_pose are scored by voxel occupancy on the GPU, the best top_k after non-maximum
+    // suppression are refined by ICP in one batch, the best refined one is returned.  Out-parameters as RunRegister's (fitness_score written
+    // only on success); the candidates go to *candidates when it is given.
+    elimaloc::Matrix4d RunRelocalize(const std::vector<PointStruct>& points, const VoxelHashMap& voxel_map, const elimaloc::Matrix4d& init_pose,
+                                     RegistrationConfig reg_config, const RelocConfig& reloc_config, bool& success, double& fitness_score,
+                                     elimaloc::Matrix6d& local_cov, std::vector<elm_reloc_candidate>* candidates = nullptr) {
+        scratch_xyz_.resize(3 * points.size());
+        for (size_t i = 0; i < points.size(); ++i)
+            for (int k = 0; k < 3; ++k) scratch_xyz_[3 * i + k] = (float)points[i].pose(k);
+        const elm_reg_config c = reg_config.c_struct();
+        std::vector<elm_reloc_candidate> cands((size_t)std::max(reloc_config.top_k, 1));
+        int n_cands = 0;
+        elimaloc::Matrix4d T;
+        elm_reg_result res;
+        elimaloc::check(elm_relocalize(VoxelHashMap::ctx(), voxel_map.handle(), scratch_xyz_.data(), points.size(), init_pose.data(), &reloc_config,
+                                       &c, T.data(), &res, cands.data(), (int)cands.size(), &n_cands),
+                        VoxelHashMap::ctx(), "RunRelocalize");
+        success = res.is_success != 0;
+        if (success) fitness_score = res.fitness_score;
+        for (int k = 0; k < 36; ++k) local_cov.data()[k] = res.local_cov[k];
+        d_fitness_score_ = res.d_fitness;
+        if (candidates) candidates->assign(cands.begin(), cands.begin() + std::min<size_t>((size_t)n_cands, cands.size()));
         return T;
     }
 

@@ -318,6 +318,47 @@ int elm_register_batch_enqueue(elm_ctx* ctx, const elm_map* map, elm_scan* const
                                const double* T0, const elm_reg_config* cfg, int want_trace);
 int elm_register_batch_finish(elm_ctx* ctx, elm_reg_result* results, elm_iter_trace* trace);
 
+/* ---------------------------------------------------------------- relocalization ------------------ */
+/* Recovery from a coarse pose (the clicked pose of CallbackInitialPose, pcm.cpp:356-447, metres / tens of degrees off): every pose of an
+ * xy x yaw grid around the guess is scored on the device by voxel occupancy, the best ones after non-maximum suppression are refined by ICP.
+ * score(T) = the number of COUNTED scan points -- ((x*x + y*y) + z*z) <= score_max_range_m^2 in float64 -- whose stored key
+ * (int)(q / voxel_size) (truncation, vhm.cpp:275) under q_r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r (float64, this association) is a voxel of
+ * the map: exact, deterministic and independent of the map's search index (it reads only the voxel set). */
+typedef struct elm_reloc_config {
+    double radius_xy_m, step_xy_m;      /* square xy window around the guess: offsets i * step, |i| <= floor(radius / step + 1e-9) */
+    double yaw_range_deg, step_yaw_deg; /* |dyaw| <= range (k = 0: 0, then +step, -step, +2 step, ...); range >= 180: k * step,
+                                         * k in [0, ceil(360 / step - 1e-9)) */
+    double score_max_range_m;           /* r_max of the score */
+    int32_t max_score_points;           /* elm_relocalize scores every ceil(n / cap)-th point of the caller's order */
+    int32_t top_k;                      /* hypotheses refined by ICP after non-maximum suppression */
+    double nms_xy_m, nms_yaw_deg;       /* a hypothesis within nms_xy_m in xy AND nms_yaw_deg in yaw of a better kept one is suppressed */
+    int64_t lds_budget_bytes, bitmap_max_bytes; /* the occupancy bitmap of the hypotheses' key box goes to LDS when it fits the first (at most
+                                                 * 64 KiB are used), is read from global memory when it fits the second, else every key is a
+                                                 * hash probe; 0 disables the LDS form / both bitmap forms.  The counts are the same in all. */
+} elm_reloc_config;
+typedef struct elm_reloc_candidate {
+    double T0[16], T[16]; /* hypothesis pose and ICP result (column-major) */
+    uint32_t score;
+    int32_t hyp_index, is_success, iterations;
+    double fitness_score;
+} elm_reloc_candidate;
+/* 5 m / 0.5 m, 180 deg / 2 deg, 50 m, 8192, 16, 1.0 m / 6 deg, 64 KiB, 64 MiB */
+void elm_reloc_config_default(elm_reloc_config* c);
+/* Hypotheses around T_guess (lidar frame, column-major): T_h = [Rz(dyaw_k) R0 | t0 + (i step, j step, 0)], h = (k W + (i + m)) W + (j + m),
+ * W = 2 m + 1.  Writes min(cap, count) column-major poses (poses16 may be NULL when cap = 0), *n = count.  Host function, no GPU needed. */
+int elm_reloc_make_hypotheses(const double T_guess[16], const elm_reloc_config* c, double* poses16, size_t cap, size_t* n);
+/* scores[h] = score(poses16[h]) of the resident scan against the map (c: score_max_range_m and the two byte budgets are read).  An empty map
+ * scores 0 everywhere.  ELM_ERR_UNSUPPORTED on a device group's lead or with a communicator / hook attached. */
+int elm_map_score_poses(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses,
+                        const elm_reloc_config* c, uint32_t* scores);
+/* Relocalize from T_guess: uploads the score subsample and the scan, scores every hypothesis, sorts them by (score desc, index asc), keeps
+ * top_k after greedy non-maximum suppression and refines those with ONE elm_register_batch (the scan repeated, T0 = T_h, config reg).  The
+ * winner is the first successful one with the lowest fitness_score (ties: rank); without success, rank 0.  T_out / result = the winner's;
+ * cands (cap entries, may be NULL) = the kept hypotheses in rank order, *n_cands = their count.  Empty map: result.gate = 1. */
+int elm_relocalize(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_guess[16],
+                   const elm_reloc_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
+                   elm_reloc_candidate* cands, int cap, int* n_cands);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {
