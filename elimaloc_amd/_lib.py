@@ -136,6 +136,22 @@ class RelocCandidate(C.Structure):
                 ("is_success", C.c_int32), ("iterations", C.c_int32), ("fitness_score", C.c_double)]
 
 
+class GlobalRelocConfigC(C.Structure):
+    """elm_reloc_global_config (include/elimaloc_hip.h, global relocalization)."""
+    _fields_ = [("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double), ("step_xy_m", C.c_double),
+                ("step_yaw_deg", C.c_double), ("score_max_range_m", C.c_double), ("score_min_height_m", C.c_double),
+                ("max_score_points", C.c_int32), ("top_k", C.c_int32), ("nms_xy_m", C.c_double), ("nms_yaw_deg", C.c_double),
+                ("pool_min", C.c_int32), ("max_kz_span", C.c_int32), ("bitmap_max_bytes", C.c_int64)]
+
+
+class GlobalRelocStats(C.Structure):
+    """elm_reloc_global_stats: lattice size, pruning per level, leaves scored, timings of one elm_relocalize_global."""
+    _fields_ = [("lattice_poses", C.c_int64), ("valid_leaves", C.c_int64), ("nx", C.c_int32), ("ny", C.c_int32), ("n_yaw", C.c_int32),
+                ("levels", C.c_int32), ("n_counted", C.c_int32), ("passes", C.c_int32), ("tau", C.c_uint32), ("_pad", C.c_uint32),
+                ("nodes_bounded", C.c_int64 * 24), ("nodes_kept", C.c_int64 * 24), ("leaves_scored", C.c_int64), ("point_evals", C.c_int64),
+                ("ms_ground", C.c_double), ("ms_search", C.c_double), ("ms_refine", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -154,6 +170,7 @@ EXPORTS = [
     "elm_ini_get_array", "elm_pcm_node_config_default", "elm_load_pcm_config", "elm_load_ekf_config", "elm_pcd_load_xyz",
     "elm_free", "elm_scan_from_cloud", "elm_pcm_callback_point_cloud",
     "elm_reloc_config_default", "elm_reloc_make_hypotheses", "elm_map_score_poses", "elm_relocalize",
+    "elm_reloc_global_config_default", "elm_map_ground_heights", "elm_reloc_global_hypotheses", "elm_relocalize_global",
 ]
 
 
@@ -322,6 +339,13 @@ def lib():
     L.elm_map_score_poses.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RelocConfigC), C.POINTER(C.c_uint32)]
     L.elm_relocalize.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(RelocConfigC), C.POINTER(RegConfig), dp, C.POINTER(RegResult),
                                  C.POINTER(RelocCandidate), C.c_int, ip]
+    L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
+    L.elm_reloc_global_config_default.restype = None
+    L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]
+    L.elm_reloc_global_hypotheses.argtypes = [vp, vp, dp, C.POINTER(GlobalRelocConfigC), dp, C.POINTER(C.c_int32), C.c_size_t,
+                                              C.POINTER(C.c_size_t)]
+    L.elm_relocalize_global.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(GlobalRelocConfigC), C.POINTER(RegConfig), dp,
+                                        C.POINTER(RegResult), C.POINTER(RelocCandidate), C.c_int, ip, C.POINTER(GlobalRelocStats)]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

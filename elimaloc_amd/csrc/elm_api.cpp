@@ -101,7 +101,7 @@ struct elm_ctx {
     uint16_t* d_hilbert = nullptr; // Hilbert index of every cell of the ordering grid (kOrderCells^2 entries)
     DevBuf d_order_jobs, d_order_tmp, d_arena, d_raw, d_flagged, d_asym;
     DevBuf d_q0, d_q1, d_q2, d_q3, d_q4, d_q5; // scratch of elm_map_get_correspondences / elm_align_clouds_local (kept between calls)
-    DevBuf d_reloc[5]; // scratch of elm_map_score_poses / elm_relocalize (elm_reloc.cpp; kept between calls)
+    DevBuf d_reloc[16]; // scratch of elm_map_score_poses / elm_relocalize (0 .. 4) and of elm_relocalize_global (elm_reloc.cpp; kept between calls)
     bool work_counters = false; // elm_ctx_set_work_counters: the accumulate launches also sum the work counters of
                                 // elm_reg_result (n_cand_total, n_occ_total, n_tested_total, fallback_blocks); off: those fields read 0
     void* h_jobs = nullptr; // pinned: ordering job descriptors
@@ -331,11 +331,12 @@ extern "C" void elm_ctx_destroy(elm_ctx* ctx) {
     if (ctx->d_hilbert) (void)hipFree(ctx->d_hilbert);
     if (ctx->h_jobs) (void)hipHostFree(ctx->h_jobs);
     DevBuf* bufs[] = {&ctx->d_scans, &ctx->d_state, &ctx->d_partials, &ctx->d_sums, &ctx->d_T0, &ctx->d_trace, &ctx->d_stage_pts, &ctx->d_active, &ctx->d_queue, &ctx->d_ds,
-                      &ctx->d_order_jobs, &ctx->d_order_tmp, &ctx->d_arena, &ctx->d_raw, &ctx->d_flagged, &ctx->d_asym, &ctx->d_q0, &ctx->d_q1, &ctx->d_q2, &ctx->d_q3, &ctx->d_q4, &ctx->d_q5,
-                      &ctx->d_reloc[0], &ctx->d_reloc[1], &ctx->d_reloc[2], &ctx->d_reloc[3], &ctx->d_reloc[4]};
+                      &ctx->d_order_jobs, &ctx->d_order_tmp, &ctx->d_arena, &ctx->d_raw, &ctx->d_flagged, &ctx->d_asym, &ctx->d_q0, &ctx->d_q1, &ctx->d_q2, &ctx->d_q3, &ctx->d_q4, &ctx->d_q5};
     if (ctx->h_active) (void)hipHostFree(ctx->h_active);
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf& b : ctx->d_reloc)
+        if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->scan_pool) (void)hipFree(b.first);
     for (elm_scan* f : ctx->scan_free) delete f;
     if (ctx->h_state) (void)hipHostFree(ctx->h_state);
@@ -432,6 +433,12 @@ struct elm_map {
     bool has_nbr = false;
     std::vector<int32_t> h_keys;
     std::vector<uint2> h_ranges;
+    // the ground field's 2-D bin index (elm_map_ground_heights; built at its first call) and the xy bounds of the stored points
+    float4* d_gpts = nullptr;
+    uint32_t* d_gstart = nullptr;
+    elm::GroundIndex gidx{};
+    double pt_bounds[4] = {0.0, 0.0, 0.0, 0.0};
+    bool has_gidx = false;
 };
 
 namespace {
@@ -584,7 +591,7 @@ static void map_free(elm_map* m) {
     m->replicas.clear();
     if (ctx_alive(m->ctx, m->ctx_id)) (void)hipSetDevice(m->ctx->device); // a context destroyed first: just release the device memory
     void* ptrs[] = {m->d_grid_tiles, m->d_vox_nk, m->d_bad, m->d_grid_gicp8, m->d_slots, m->d_pts, m->d_ranges, m->d_keys, m->d_vox_mean, m->d_vox_cov, m->d_vox_cinv, m->d_pt_gicp, m->d_pt_cov, m->d_qslots, m->d_nbr_pts, m->d_nbr_idx, m->d_nbr_cell_off, m->d_vqslots, m->d_vq_dense, m->d_vqf_dense, m->d_vface, m->d_vox_rec, m->d_vnbr_blk,
-                    m->d_grid_blk, m->d_grid_idx, m->d_grid_start, m->d_vox_stat, m->d_grid_gicp};
+                    m->d_grid_blk, m->d_grid_idx, m->d_grid_start, m->d_vox_stat, m->d_grid_gicp, m->d_gpts, m->d_gstart};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -2864,6 +2871,52 @@ void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc) {
     return *rc == ELM_OK ? ctx->d_reloc[which].p : nullptr;
 }
 const elm::DevMap& map_dev(const elm_map* m) { return m->dm; }
+const std::vector<int32_t>& map_host_keys(const elm_map* m) { return m->h_keys; }
+int map_ground_index(const elm_map* cm, const elm::GroundIndex** gi, double bounds[4]) {
+    elm_map* m = const_cast<elm_map*>(cm); // the index is a cache of the (immutable) map
+    elm_ctx* ctx = m->ctx;
+    if (!m->has_gidx) {
+        const size_t n = m->dm.n_pts;
+        std::vector<float4> pts(n);
+        if (n) HIPCHK(ctx, hipMemcpy(pts.data(), m->d_pts, n * sizeof(float4), hipMemcpyDeviceToHost));
+        double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
+        for (const float4& p : pts) {
+            lo[0] = std::min(lo[0], (double)p.x); hi[0] = std::max(hi[0], (double)p.x);
+            lo[1] = std::min(lo[1], (double)p.y); hi[1] = std::max(hi[1], (double)p.y);
+        }
+        elm::GroundIndex g{};
+        g.bin = elm::kGroundBin;
+        if (n) {
+            g.x0 = lo[0]; g.y0 = lo[1];
+            g.nbx = (int32_t)floor((hi[0] - lo[0]) / g.bin) + 1;
+            g.nby = (int32_t)floor((hi[1] - lo[1]) / g.bin) + 1;
+        }
+        const size_t nb = (size_t)g.nbx * (size_t)g.nby;
+        std::vector<uint32_t> bin(n), start(nb + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t bx = std::min((int32_t)floor(((double)pts[i].x - g.x0) / g.bin), g.nbx - 1);
+            const int32_t by = std::min((int32_t)floor(((double)pts[i].y - g.y0) / g.bin), g.nby - 1);
+            bin[i] = (uint32_t)bx * (uint32_t)g.nby + (uint32_t)by;
+            ++start[bin[i] + 1];
+        }
+        for (size_t b = 0; b < nb; ++b) start[b + 1] += start[b];
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        std::vector<float4> sorted(n);
+        for (size_t i = 0; i < n; ++i) sorted[fill[bin[i]]++] = pts[i];
+        HIPCHK(ctx, hipMalloc((void**)&m->d_gpts, std::max<size_t>(n * sizeof(float4), 256)));
+        HIPCHK(ctx, hipMalloc((void**)&m->d_gstart, (nb + 1) * sizeof(uint32_t)));
+        if (n) HIPCHK(ctx, hipMemcpy(m->d_gpts, sorted.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(m->d_gstart, start.data(), (nb + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        g.pts = m->d_gpts;
+        g.start = m->d_gstart;
+        m->gidx = g;
+        m->pt_bounds[0] = lo[0]; m->pt_bounds[1] = hi[0]; m->pt_bounds[2] = lo[1]; m->pt_bounds[3] = hi[1];
+        m->has_gidx = true;
+    }
+    *gi = &m->gidx;
+    memcpy(bounds, m->pt_bounds, sizeof(m->pt_bounds));
+    return ELM_OK;
+}
 } // namespace elm_host
 
 // ------------------------------------------------------------------------------------------------------

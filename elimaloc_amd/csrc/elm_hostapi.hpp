@@ -9,7 +9,7 @@
 
 #include "../../include/elimaloc_hip.h"
 
-namespace elm { struct DevMap; }
+namespace elm { struct DevMap; struct GroundIndex; }
 struct elm_group; // a lead context's group of per-device contexts inside one process (elm_multi.cpp)
 
 namespace elm_host {
@@ -31,8 +31,11 @@ void scan_set_total(elm_scan* s, size_t n_total);
 // ... for elm_reloc.cpp
 bool ctx_exchange_attached(const elm_ctx* ctx); // a communicator or an all-reduce hook is attached
 bool ctx_in_flight(const elm_ctx* ctx);          // an enqueued batch has not been finished
-void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc); // grow-only device scratch 0..4 of the context (nullptr: *rc)
+void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc); // grow-only device scratch 0..15 of the context (nullptr: *rc)
 const elm::DevMap& map_dev(const elm_map* m);
+const std::vector<int32_t>& map_host_keys(const elm_map* m); // [n_vox][3] stored keys
+// the map's ground-field bin index (built at the first call, kept with the map) and the xy bounds of its stored points {x_lo, x_hi, y_lo, y_hi}
+int map_ground_index(const elm_map* m, const elm::GroundIndex** gi, double bounds[4]);
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

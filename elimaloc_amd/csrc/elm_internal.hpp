@@ -320,6 +320,33 @@ void launch_reloc_bitmap(hipStream_t s, const DevMap& m, const RelocBox& b, uint
 void launch_reloc_score(hipStream_t s, int form, const DevMap& m, const float* pts, uint32_t n, const double* poses, uint32_t n_poses,
                         const RelocBox& b, const uint32_t* bits, uint32_t n_words, uint32_t* partial, uint32_t* scores);
 
+// global relocalization (elm_k_reloc.hip)
+// 2-D bin index of the map's points for the ground field: bin (bx, by) = (floor((x - x0) / bin), floor((y - y0) / bin)) in float64, points
+// sorted by bin (bx * nby + by), start[b] .. start[b + 1]; 2 bin > 5 m, so a query reads the 5 x 5 bins around its own
+struct GroundIndex {
+    const float4* pts;
+    const uint32_t* start; // [nbx * nby + 1]
+    double x0, y0, bin;
+    int32_t nbx, nby;
+};
+constexpr double kGroundBin = 2.75;
+void launch_ground_heights(hipStream_t s, const GroundIndex& gi, const double* xy, uint32_t n, double* z, int32_t* found);
+// level windows of the occupancy bitmap: columns of nzw 32-bit words (cell (cx, cy) at word (cx * ny + cy) * nzw); out(c) = OR of in over the
+// window [c, c + w) along axis (0: x, 1: y) read as windows of width wp of in (reads past the box are empty)
+void launch_reloc_window_or(hipStream_t s, const uint32_t* in, uint32_t* out, uint32_t nx, uint32_t ny, uint32_t nzw, int axis, uint32_t wp, uint32_t w);
+// a search node: the x / y range of its lattice nodes, the z range of fl(g + h) over its valid leaves, its yaw row
+struct RelocNode {
+    double xlo, xhi, ylo, yhi, zlo, zhi;
+    int32_t k, _pad;
+};
+// bounds[n] = the counted points whose window at the node is occupied (rot: [K][9] row-major Rz(yaw_k) R0; bits: the level's windows of
+// width w over the box b, columns of b.nz / 32 words)
+void launch_reloc_bound(hipStream_t s, const DevMap& m, const float* pts, uint32_t n, const RelocNode* nodes, uint32_t n_nodes, const double* rot,
+                        const RelocBox& b, const uint32_t* bits, uint32_t w, uint32_t kz_cap, uint32_t* partial, uint32_t* bounds);
+// rows[12 l] of lattice pose hyps[l] = (k NX + i) NY + j: rot row k, t = (x_min + i step, y_min + j step, gz[i NY + j])
+void launch_reloc_leaf_rows(hipStream_t s, const uint32_t* hyps, uint32_t n, const double* rot, double x_min, double y_min, double step,
+                            uint32_t NX, uint32_t NY, const double* gz, double* rows);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

@@ -209,3 +209,20 @@ class PcmMatching:
             return None
         self.d_icp_pose_std_m = fit
         return dict(pose_ego=final_pose, pose_lidar=pose, fitness=fit, ground_z=z_ground, **extra)
+
+    def InitializeGlobal(self, raw_scan_xyz, reloc=None):
+        """Start without an initial pose (not in the reference: a cold start, a kidnap): the last RAW scan voxel-downsampled as
+        CallbackInitialPose does, then RelocalizeGlobal over the whole map with T_tilt = [R(tf_ego_to_lidar) | (0, 0, tf_ego_to_lidar z)] --
+        the lidar's mounting tilt and height above the ground.  reloc: a GlobalRelocConfig (None: the defaults).  Returns None when no
+        candidate converges, else dict(pose_ego, pose_lidar, fitness, candidates, stats)."""
+        tf = self.cfg_.tf_ego_to_lidar
+        T_tilt = np.eye(4)
+        T_tilt[:3, :3] = tf[:3, :3]
+        T_tilt[2, 3] = tf[2, 3]
+        src, _ = voxel_downsample(raw_scan_xyz, self.cfg_.d_input_voxel_ds_m)
+        pose, ok, fit, cov, cands, stats = self.registration_.RelocalizeGlobal(src, self.local_map_, T_tilt, reloc)
+        self.icp_local_cov_ = cov
+        if not ok:
+            return None
+        self.d_icp_pose_std_m = fit
+        return dict(pose_ego=pose @ np.linalg.inv(tf), pose_lidar=pose, fitness=fit, candidates=cands, stats=stats)

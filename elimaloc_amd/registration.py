@@ -12,7 +12,8 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import ElmError, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC, check
+from ._lib import (ElmError, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+                   check)
 
 
 class IcpMethod(enum.IntEnum):  # reg.hpp:60
@@ -43,6 +44,27 @@ def RelocConfig(**kw):
             raise AttributeError(f"RelocConfig has no field {k}")
         setattr(cfg, k, int(v) if k in ("max_score_points", "top_k", "lds_budget_bytes", "bitmap_max_bytes") else float(v))
     return cfg
+
+
+def GlobalRelocConfig(**kw):
+    """elm_reloc_global_config with its defaults (the map's xy bounds (NaN rectangle), 0.5 m / 2 deg lattice, 50 m score range, counted points
+    1.0 m or more above the ground, 8192 score points, top 16 after non-maximum suppression at 1.0 m / 6 deg, pool 64, kz span 64, 256 MiB)."""
+    cfg = GlobalRelocConfigC()
+    _lib.lib().elm_reloc_global_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(f"GlobalRelocConfig has no field {k}")
+        setattr(cfg, k, int(v) if k in ("max_score_points", "top_k", "pool_min", "max_kz_span", "bitmap_max_bytes") else float(v))
+    return cfg
+
+
+def _global_stats_dict(st):
+    L = int(st.levels)
+    return dict(lattice_poses=int(st.lattice_poses), valid_leaves=int(st.valid_leaves), nx=int(st.nx), ny=int(st.ny), n_yaw=int(st.n_yaw),
+                levels=L, n_counted=int(st.n_counted), passes=int(st.passes), tau=int(st.tau),
+                nodes_bounded=[int(st.nodes_bounded[l]) for l in range(L + 1)], nodes_kept=[int(st.nodes_kept[l]) for l in range(L + 1)],
+                leaves_scored=int(st.leaves_scored), point_evals=int(st.point_evals), ms_ground=float(st.ms_ground),
+                ms_search=float(st.ms_search), ms_refine=float(st.ms_refine))
 
 
 def MakeHypotheses(guess, reloc=None):
@@ -355,6 +377,35 @@ class VoxelHashMap:
                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx._h, "elm_map_score_poses")
         return out[:n]
 
+    def FindGroundHeights(self, xy):
+        """FindGroundHeight of many xy positions [n, 2] on the device (elm_map_ground_heights, bit for bit the single query) -> (found bool
+        [n], z [n]; 0 where not found)."""
+        q = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+        n = q.shape[0]
+        z = np.zeros(max(n, 1))
+        found = np.zeros(max(n, 1), np.int32)
+        check(_lib.lib().elm_map_ground_heights(self.ctx._h, self._handle(), _dp(q), n, _dp(z), found.ctypes.data_as(C.POINTER(C.c_int32))),
+              self.ctx._h, "elm_map_ground_heights")
+        return found[:n] != 0, z[:n]
+
+    def GlobalHypotheses(self, T_tilt, cfg=None, max_poses=None):
+        """The lattice poses of a global relocalization (elm_reloc_global_hypotheses) -> (poses [n, 4, 4], valid bool [n]), index
+        hyp = (k NX + i) NY + j; a pose without ground under it is not valid.  max_poses: only the first ones."""
+        cfg = cfg if cfg is not None else GlobalRelocConfig()
+        T = _colmajor16(T_tilt)
+        n = C.c_size_t(0)
+        check(_lib.lib().elm_reloc_global_hypotheses(self.ctx._h, self._handle(), _dp(T), C.byref(cfg), None, None, 0, C.byref(n)),
+              self.ctx._h, "elm_reloc_global_hypotheses")
+        if max_poses is not None:
+            n.value = min(n.value, int(max_poses))
+        cnt = C.c_size_t(0)
+        out = np.empty((max(n.value, 1), 16))
+        valid = np.zeros(max(n.value, 1), np.int32)
+        check(_lib.lib().elm_reloc_global_hypotheses(self.ctx._h, self._handle(), _dp(T), C.byref(cfg), _dp(out),
+                                                     valid.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(cnt)),
+              self.ctx._h, "elm_reloc_global_hypotheses")
+        return out[:n.value].reshape(-1, 4, 4).transpose(0, 2, 1).copy(), valid[:n.value] != 0
+
     def GetAdjacentVoxels(self, point, search_range):  # vhm.cpp:208-243: keys only, whether or not such voxels exist
         v = self.PointToVoxel(point, self.voxel_size_).astype(np.int64)
         if search_range == 0:
@@ -497,6 +548,30 @@ class Registration:
         ok = bool(res.is_success)
         return (Tout.reshape(4, 4).T.copy(), ok, (res.fitness_score if ok else None), np.array(res.local_cov).reshape(6, 6).T.copy(),
                 [_candidate_dict(cands[b]) for b in range(min(nc.value, cap))])
+
+    def RelocalizeGlobal(self, source_local, voxel_map, T_tilt=None, reloc=None, m_config=None):
+        """Global relocalization without a guess (elm_relocalize_global): branch-and-bound over an xy lattice of the map x the whole turn of
+        yaw, every pose standing on the map's ground (T_tilt = [R0 | (0, 0, h)]: sensor roll / pitch and height; identity by default), then
+        ICP from the best top_k.  Returns (pose 4x4, is_success, fitness_score or None, local_cov 6x6, candidates, stats); candidates as
+        Relocalize's (hyp_index = the lattice index), stats the search's counters and timings."""
+        cfg = m_config if m_config is not None else self.config_
+        rc = reloc if reloc is not None else GlobalRelocConfig()
+        scan = np.ascontiguousarray(source_local, dtype=np.float32).reshape(-1, 3)
+        T0 = _colmajor16(np.eye(4) if T_tilt is None else T_tilt)
+        Tout = np.empty(16)
+        res = RegResult()
+        cap = int(rc.top_k)
+        cands = (RelocCandidate * cap)()
+        nc = C.c_int(0)
+        st = GlobalRelocStats()
+        check(_lib.lib().elm_relocalize_global(self.ctx._h, voxel_map._handle(), _fp(scan), scan.shape[0], _dp(T0), C.byref(rc), C.byref(cfg),
+                                               _dp(Tout), C.byref(res), cands, cap, C.byref(nc), C.byref(st)), self.ctx._h,
+              "elm_relocalize_global")
+        self.d_fitness_score_ = res.d_fitness
+        self.last_relocalize_ = _result_dict(res)
+        ok = bool(res.is_success)
+        return (Tout.reshape(4, 4).T.copy(), ok, (res.fitness_score if ok else None), np.array(res.local_cov).reshape(6, 6).T.copy(),
+                [_candidate_dict(cands[b]) for b in range(min(nc.value, cap))], _global_stats_dict(st))
 
     def _align(self, method, source_local, target_xyz, target_cov, last_icp_pose, trans_th, m_config, source_cov=None):
         cfg = m_config if m_config is not None else self.config_

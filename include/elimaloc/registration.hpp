@@ -61,6 +61,11 @@ struct RelocConfig : elm_reloc_config {
     RelocConfig() { elm_reloc_config_default(this); }
 };
 
+// elm_reloc_global_config with its defaults (include/elimaloc_hip.h, global relocalization): lattice, score and NMS of RunRelocalizeGlobal
+struct GlobalRelocConfig : elm_reloc_global_config {
+    GlobalRelocConfig() { elm_reloc_global_config_default(this); }
+};
+
 struct Registration {
     Registration() {}
     Registration(RegistrationConfig config) { config_ = config; }
@@ -124,6 +129,32 @@ struct Registration {
         elimaloc::check(elm_relocalize(VoxelHashMap::ctx(), voxel_map.handle(), scratch_xyz_.data(), points.size(), init_pose.data(), &reloc_config,
                                        &c, T.data(), &res, cands.data(), (int)cands.size(), &n_cands),
                         VoxelHashMap::ctx(), "RunRelocalize");
+        success = res.is_success != 0;
+        if (success) fitness_score = res.fitness_score;
+        for (int k = 0; k < 36; ++k) local_cov.data()[k] = res.local_cov[k];
+        d_fitness_score_ = res.d_fitness;
+        if (candidates) candidates->assign(cands.begin(), cands.begin() + std::min<size_t>((size_t)n_cands, cands.size()));
+        return T;
+    }
+
+    // Global relocalization (not in the reference; what a node calls when no initial pose arrives): branch-and-bound over an xy lattice of the
+    // map x the whole turn of yaw, every pose on the map's ground (T_tilt = [R0 | (0, 0, h)]: the sensor's roll / pitch and height), ICP from
+    // the best top_k.  Out-parameters as RunRelocalize's; the search's counters go to *stats when it is given.
+    elimaloc::Matrix4d RunRelocalizeGlobal(const std::vector<PointStruct>& points, const VoxelHashMap& voxel_map, const elimaloc::Matrix4d& T_tilt,
+                                           RegistrationConfig reg_config, const GlobalRelocConfig& reloc_config, bool& success,
+                                           double& fitness_score, elimaloc::Matrix6d& local_cov,
+                                           std::vector<elm_reloc_candidate>* candidates = nullptr, elm_reloc_global_stats* stats = nullptr) {
+        scratch_xyz_.resize(3 * points.size());
+        for (size_t i = 0; i < points.size(); ++i)
+            for (int k = 0; k < 3; ++k) scratch_xyz_[3 * i + k] = (float)points[i].pose(k);
+        const elm_reg_config c = reg_config.c_struct();
+        std::vector<elm_reloc_candidate> cands((size_t)std::max(reloc_config.top_k, 1));
+        int n_cands = 0;
+        elimaloc::Matrix4d T;
+        elm_reg_result res;
+        elimaloc::check(elm_relocalize_global(VoxelHashMap::ctx(), voxel_map.handle(), scratch_xyz_.data(), points.size(), T_tilt.data(),
+                                              &reloc_config, &c, T.data(), &res, cands.data(), (int)cands.size(), &n_cands, stats),
+                        VoxelHashMap::ctx(), "RunRelocalizeGlobal");
         success = res.is_success != 0;
         if (success) fitness_score = res.fitness_score;
         for (int k = 0; k < 36; ++k) local_cov.data()[k] = res.local_cov[k];

@@ -229,6 +229,14 @@ struct VoxelHashMap {
         return found != 0;
     }
 
+    // FindGroundHeight of many xy positions in one device call (elm_map_ground_heights; bit for bit the single query): z = 0 where not found
+    inline void FindGroundHeights(const std::vector<double>& xy, std::vector<double>& ground_z, std::vector<int32_t>& found) const {
+        const size_t n = xy.size() / 2;
+        ground_z.assign(n, 0.0);
+        found.assign(n, 0);
+        elimaloc::check(elm_map_ground_heights(ctx(), handle(), xy.data(), n, ground_z.data(), found.data()), ctx(), "FindGroundHeights");
+    }
+
     void Pairs(int what, const RadarPointVector& vec_points, double max_dist, std::vector<uint32_t>& src, std::vector<int32_t>& tgt) const {
         std::vector<double> xyz(3 * vec_points.size());
         for (size_t i = 0; i < vec_points.size(); ++i)

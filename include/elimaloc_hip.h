@@ -359,6 +359,57 @@ int elm_relocalize(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size
                    const elm_reloc_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
                    elm_reloc_candidate* cands, int cap, int* n_cands);
 
+/* ---------------------------------------------------------------- global relocalization ----------- */
+/* Relocalization without a guess: an xy lattice over the map x the whole turn of yaw, every pose standing on the
+ * map's ground, searched exactly by branch-and-bound on the device; the best ones are refined as elm_relocalize refines its hypotheses.
+ * Lattice: x_i = x_min + i * step_xy (i < NX = floor((x_max - x_min) / step_xy + 1e-9) + 1), y_j likewise; yaw_k = k * step_yaw_deg,
+ * k in [0, ceil(360 / step_yaw_deg - 1e-9)), cos / sin as elm_reloc_make_hypotheses' full-turn mode.  Pose (k, i, j):
+ * T = [Rz(yaw_k) R0 | (x_i, y_j, fl(g(x_i, y_j) + h))] where T_tilt = [R0 | (0, 0, h)] (sensor roll / pitch and height above the ground;
+ * a T_tilt with a non-zero x or y translation is ELM_ERR_INVALID) and g is the ground field of elm_map_ground_heights.  A node without
+ * ground is not a pose.  Index hyp = (k NX + i) NY + j; a lattice above 2^31 - 1 poses is ELM_ERR_INVALID.
+ * Score: elm_map_score_poses' contract, over the counted points that also satisfy (R0 p)_z + h >= score_min_height_m (float64,
+ * ((R0_20 x + R0_21 y) + R0_22 z) + h; -INFINITY counts every point).  Result: the lattice sorted by (score desc, hyp asc), greedy NMS
+ * (xy distance <= nms_xy_m AND wrapped |dyaw| <= nms_yaw_deg of a kept pose suppresses) down to top_k -- identical to scoring every
+ * valid pose of the lattice -- then ONE elm_register_batch and elm_relocalize's winner rule. */
+typedef struct elm_reloc_global_config {
+    double x_min, x_max, y_min, y_max; /* the lattice's rectangle; all four NaN: the xy bounds of the map's stored points */
+    double step_xy_m, step_yaw_deg;
+    double score_max_range_m;   /* r_max of the score */
+    double score_min_height_m;  /* counted points below this height above the ground are not counted (-INFINITY: all are) */
+    int32_t max_score_points;   /* the score subsample: every ceil(n / cap)-th point of the caller's order */
+    int32_t top_k;              /* kept poses, refined by ICP */
+    double nms_xy_m, nms_yaw_deg;
+    int32_t pool_min;           /* the first pruning threshold is the pool_min-th best score of the greedy descent's leaves */
+    int32_t max_kz_span;        /* a bound whose z-key range exceeds this counts the point as a hit */
+    int64_t bitmap_max_bytes;   /* the occupancy bitmap and its level windows together; more: ELM_ERR_UNSUPPORTED */
+} elm_reloc_global_config;
+typedef struct elm_reloc_global_stats {
+    int64_t lattice_poses, valid_leaves;   /* NX NY K; the poses with ground */
+    int32_t nx, ny, n_yaw, levels;         /* lattice dims; the top level of the search */
+    int32_t n_counted, passes;             /* counted score points; search passes (a pass lowers the threshold when NMS keeps < top_k) */
+    uint32_t tau, _pad;                    /* the last pass's pruning threshold */
+    int64_t nodes_bounded[24], nodes_kept[24]; /* per level (index = level, 1 .. levels), summed over passes */
+    int64_t leaves_scored;                 /* exact leaf scores, over passes (the greedy descent's included) */
+    int64_t point_evals;                   /* counted points x (nodes bounded + leaves scored) */
+    double ms_ground, ms_search, ms_refine; /* host wall time: ground field, search (bitmaps included), ICP */
+} elm_reloc_global_stats;
+/* full map rectangle, 0.5 m / 2 deg, 50 m, min height 1.0 m, 8192, 16, 1.0 m / 6 deg, pool 64, kz span 64, 256 MiB */
+void elm_reloc_global_config_default(elm_reloc_global_config* c);
+/* Ground heights of n xy queries (xy[2 q], xy[2 q + 1]) on the device: bit for bit elm_map_find_ground_height -- the mean of the (up to) 5
+ * lowest z among the map points with dx*dx + dy*dy <= 25 (float64), summed in ascending order; found only with more than 3 such points.
+ * z[q] = 0 where not found.  A 2-D bin index of the map's points is built at the first call and kept with the map.  One rank only. */
+int elm_map_ground_heights(elm_ctx* ctx, const elm_map* map, const double* xy, size_t n, double* z, int32_t* found);
+/* The lattice poses of elm_relocalize_global (column-major, min(cap, count) written; poses16 / valid may be NULL when cap = 0), valid[h] =
+ * the node has ground, *n = NX NY K.  Invalid poses carry z = h.  With cap = 0 and an explicit rectangle only *n is computed: ctx and map
+ * may then be NULL (no device needed); the arguments are checked as elm_relocalize_global checks them. */
+int elm_reloc_global_hypotheses(elm_ctx* ctx, const elm_map* map, const double T_tilt[16], const elm_reloc_global_config* c,
+                                double* poses16, int32_t* valid, size_t cap, size_t* n);
+/* Global relocalization of a scan (sensor frame).  Outputs as elm_relocalize's (hyp_index = the lattice index); stats may be NULL.  No valid
+ * pose (an empty map, a rectangle off the map): result.gate = 1, *n_cands = 0, T_out = T_tilt.  One rank only (ELM_ERR_UNSUPPORTED). */
+int elm_relocalize_global(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_tilt[16],
+                          const elm_reloc_global_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
+                          elm_reloc_candidate* cands, int cap, int* n_cands, elm_reloc_global_stats* stats);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {

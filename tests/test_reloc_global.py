@@ -1,0 +1,404 @@
+"""Global relocalization on the GPU (elm_map_ground_heights / elm_reloc_global_hypotheses / elm_relocalize_global): the device ground field
+against FindGroundHeight bit for bit, the lattice against a numpy mirror, the branch-and-bound candidates against scoring every valid lattice
+pose (ScorePoses + numpy greedy NMS), the stats, recovery without a guess, the index forms, the node's InitializeGlobal and the edge cases."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from elimaloc_amd import synth
+from elimaloc_amd._lib import ElmError
+from elimaloc_amd.registration import (Context, GlobalRelocConfig, IcpMethod, Registration, RegistrationConfig, RelocConfig, Scan,
+                                       VoxelHashMap)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def field1m(ctx):
+    world = synth.make_field_world(1_000_000, seed=4242)
+    vm = VoxelHashMap(1.0, 30, ctx)
+    vm.AddPoints(world)
+    return world, vm
+
+
+def _tilt(roll, pitch, h):
+    T = np.eye(4)
+    T[:3, :3] = synth.rot_zyx(roll, pitch, 0.0)
+    T[2, 3] = h
+    return T
+
+
+def _ground_mirror(pts, xy):
+    """elm_map_find_ground_height in numpy: the stored points with dx*dx + dy*dy <= 25 (float64), the (up to) 5 lowest z summed in
+    ascending order from 0.0, divided by N; found with more than 3 points.  The points are binned by 5 m so a query reads 3 x 3 bins."""
+    p = np.asarray(pts, dtype=np.float32)[:, :3]
+    bx = np.floor(p[:, 0].astype(np.float64) / 5.0).astype(np.int64)
+    by = np.floor(p[:, 1].astype(np.float64) / 5.0).astype(np.int64)
+    order = np.lexsort((by, bx))
+    keys = bx[order] * (1 << 32) + (by[order] + (1 << 31))
+    found = np.zeros(xy.shape[0], bool)
+    z = np.zeros(xy.shape[0])
+    for q, (x, y) in enumerate(xy):
+        qx, qy = int(math.floor(x / 5.0)), int(math.floor(y / 5.0))
+        parts = []
+        for ix in (qx - 1, qx, qx + 1):
+            lo = np.searchsorted(keys, ix * (1 << 32) + (qy - 1 + (1 << 31)))
+            hi = np.searchsorted(keys, ix * (1 << 32) + (qy + 1 + (1 << 31)), side="right")
+            parts.append(order[lo:hi])
+        c = p[np.concatenate(parts)]
+        dx, dy = c[:, 0].astype(np.float64) - x, c[:, 1].astype(np.float64) - y
+        zs = np.sort(c[dx * dx + dy * dy <= 25.0, 2].astype(np.float64))
+        if zs.size > 3:
+            s = 0.0
+            for v in zs[:5]:
+                s += float(v)
+            found[q], z[q] = True, s / min(5, zs.size)
+    return found, z
+
+
+def test_ground_heights_match_single_queries(ctx, field1m):
+    world, vm = field1m
+    rng = np.random.default_rng(3)
+    ext = float(np.max(np.abs(world[:, :2])))
+    xy = np.concatenate([rng.uniform(-ext - 8.0, ext + 8.0, size=(5000, 2)),  # inside, at the edges and off the map
+                         [[1e6, -1e6], [float("nan"), 0.0]]])
+    found, z = vm.FindGroundHeights(xy)
+    assert found.shape == (xy.shape[0],) and found[:5000].sum() > 3000 and not found[-2:].any()
+    # every query against a numpy mirror of elm_map_find_ground_height over the map's stored points
+    mf, mz = _ground_mirror(vm.Pointcloud(), xy[:5000])
+    assert np.array_equal(found[:5000], mf)
+    assert np.array_equal(z[:5000][mf], mz[mf])
+    # and a subset against the single-query function itself (each single query reads the whole map)
+    pick = np.concatenate([rng.choice(5000, 300, replace=False), [5000]])
+    for q in pick:
+        f1, z1 = vm.FindGroundHeight(xy[q])
+        assert bool(found[q]) == f1, q
+        if f1:
+            assert z[q] == z1, (q, z[q], z1)
+
+
+def test_ground_heights_exact_radius(ctx):
+    # float32-exact points; the query (400, 395) lies exactly 5 m from the first (dy*dy == 25): all four count, the mean of the 4 lowest
+    pts = np.array([[400.0, 400.0, 1.0], [400.0, 399.5, 1.5], [400.0, 399.0, 2.0], [400.25, 398.0, 0.5], [400.0, 400.5, 9.0]], np.float32)
+    vm = VoxelHashMap(1.0, 30, ctx)
+    vm.AddPoints(pts)
+    xy = np.array([[400.0, 395.0], [400.0, 394.99], [405.0, 400.0], [395.0, 395.0], [400.0, 400.0]])
+    found, z = vm.FindGroundHeights(xy)
+    assert found[0] and z[0] == (((0.5 + 1.0) + 1.5) + 2.0) / 4.0
+    assert not found[1]  # the first point is 5.01 m away: three left
+    assert found[4] and z[4] == ((((0.5 + 1.0) + 1.5) + 2.0) + 9.0) / 5.0
+    for q in range(xy.shape[0]):
+        f1, z1 = vm.FindGroundHeight(xy[q])
+        assert bool(found[q]) == f1 and (not f1 or z[q] == z1), q
+
+
+def test_global_hypotheses_mirror(ctx, field1m):
+    world, vm = field1m
+    cfg = GlobalRelocConfig(x_min=-20.0, x_max=-5.25, y_min=10.0, y_max=22.0, step_xy_m=0.75, step_yaw_deg=50.0)
+    T_tilt = _tilt(0.02, -0.015, 1.8)
+    H, valid = vm.GlobalHypotheses(T_tilt, cfg)
+    xs = -20.0 + np.arange(20) * 0.75
+    ys = 10.0 + np.arange(17) * 0.75
+    K = 8  # ceil(360 / 50)
+    assert H.shape == (K * 20 * 17, 4, 4)
+    gx, gy = np.meshgrid(xs, ys, indexing="ij")
+    found, g = vm.FindGroundHeights(np.column_stack([gx.ravel(), gy.ravel()]))
+    for k in range(K):
+        a = k * 50.0 * (math.pi / 180.0)
+        Rz = np.array([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
+        blk = H[k * 340:(k + 1) * 340]
+        np.testing.assert_allclose(blk[:, :3, :3], np.broadcast_to(Rz @ T_tilt[:3, :3], (340, 3, 3)), rtol=0, atol=1e-12)
+        assert np.array_equal(blk[:, 0, 3], gx.ravel()) and np.array_equal(blk[:, 1, 3], gy.ravel())
+        assert np.array_equal(blk[:, 2, 3], np.where(found, g + 1.8, 1.8))
+        assert np.array_equal(valid[k * 340:(k + 1) * 340], found)
+    assert np.array_equal(H[:, 3], np.broadcast_to([0.0, 0.0, 0.0, 1.0], (H.shape[0], 4)))
+
+
+def _counted(scan, cfg, T_tilt):
+    """the global form's counted points: within r_max, then (R0 p)_z + h >= score_min_height_m (float64, the contract's association)."""
+    p = scan.astype(np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    keep = (x * x + y * y) + z * z <= cfg.score_max_range_m ** 2
+    R = T_tilt[:3, :3]
+    keep &= ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + T_tilt[2, 3] >= cfg.score_min_height_m
+    return scan[keep]
+
+
+def _exhaustive(vm, scan, T_tilt, cfg, ctx):
+    """the reference: ScorePoses over every valid lattice pose, (score desc, hyp asc), numpy greedy NMS."""
+    H, valid = vm.GlobalHypotheses(T_tilt, cfg)
+    hyp = np.flatnonzero(valid)
+    S = _counted(scan, cfg, T_tilt)
+    if S.shape[0]:
+        scores = vm.ScorePoses(Scan(ctx, S), H[hyp], RelocConfig(score_max_range_m=cfg.score_max_range_m)).astype(np.int64)
+    else:
+        scores = np.zeros(hyp.size, np.int64)
+    order = np.lexsort((hyp, -scores))
+    K = int(math.ceil(360.0 / cfg.step_yaw_deg - 1e-9))
+    nxy = H.shape[0] // K
+    kept = []
+    for r in order:
+        h = int(hyp[r])
+        x, y, yaw = H[h][0, 3], H[h][1, 3], (h // nxy) * cfg.step_yaw_deg
+        sup = False
+        for (_, _, kx, ky, kyaw) in kept:
+            d = math.fmod(yaw - kyaw, 360.0)
+            d = d - 360.0 if d > 180.0 else (d + 360.0 if d < -180.0 else d)
+            if math.hypot(x - kx, y - ky) <= cfg.nms_xy_m and abs(d) <= cfg.nms_yaw_deg:
+                sup = True
+                break
+        if not sup:
+            kept.append((h, int(scores[r]), x, y, yaw))
+            if len(kept) == cfg.top_k:
+                break
+    return [(h, s) for (h, s, _, _, _) in kept], H, valid
+
+
+def _scan_case(world, vm, seed, n=6000):
+    """truth at 1.8 m above the ground with its roll / pitch; T_tilt = the truth's tilt and height."""
+    rng = np.random.default_rng(seed)
+    T = synth.make_pose(world, seed)
+    ext = float(np.max(np.abs(world[:, :2])))
+    T[:2, 3] = rng.uniform(-0.4 * ext, 0.4 * ext, 2)
+    found, gz = vm.FindGroundHeight(T[:2, 3])
+    assert found
+    T[2, 3] = gz + 1.8
+    scan, _ = synth.make_scan(world, n, seed=seed + 1, T_true=T)
+    yaw = math.atan2(T[1, 0], T[0, 0])
+    T_tilt = np.eye(4)
+    T_tilt[:3, :3] = synth.rot_zyx(0.0, 0.0, -yaw) @ T[:3, :3]
+    T_tilt[2, 3] = 1.8
+    return T, scan, T_tilt
+
+
+def _check_equal(ctx, vm, scan, T_tilt, cfg, reg=None):
+    ref, H, _ = _exhaustive(vm, scan, T_tilt, cfg, ctx)
+    r = Registration(reg if reg is not None else RegistrationConfig(icp_method=IcpMethod.P2P, max_iteration=2), ctx)
+    pose, ok, fit, cov, cands, st = r.RelocalizeGlobal(scan, vm, T_tilt, cfg)
+    got = [(c["hyp_index"], c["score"]) for c in cands]
+    assert got == ref, (got[:6], ref[:6], st)
+    for c in cands:
+        assert np.array_equal(c["T0"], H[c["hyp_index"]])
+    S = _counted(scan, cfg, T_tilt)
+    if S.shape[0] and cands:
+        again = vm.ScorePoses(Scan(ctx, S), np.array([c["T0"] for c in cands]), RelocConfig(score_max_range_m=cfg.score_max_range_m))
+        assert [int(v) for v in again] == [c["score"] for c in cands]
+    return cands, st
+
+
+@pytest.mark.parametrize("min_h", [None, -math.inf])
+@pytest.mark.parametrize("seed", [11, 12])
+def test_search_equals_exhaustive_field(ctx, field1m, seed, min_h):
+    world, vm = field1m
+    T, scan, T_tilt = _scan_case(world, vm, seed)
+    x0, y0 = T[0, 3], T[1, 3]
+    kw = {} if min_h is None else dict(score_min_height_m=min_h)
+    cfg = GlobalRelocConfig(x_min=x0 - 15.3, x_max=x0 + 16.0, y_min=y0 - 14.0, y_max=y0 + 15.7, step_xy_m=0.5, step_yaw_deg=6.0, **kw)
+    cands, st = _check_equal(ctx, vm, scan, T_tilt, cfg)
+    assert len(cands) == cfg.top_k
+
+
+def test_search_equals_exhaustive_rect_off_map(ctx, field1m):
+    world, vm = field1m
+    ext = float(np.max(np.abs(world[:, :2])))
+    T, scan, T_tilt = _scan_case(world, vm, 13)
+    cfg = GlobalRelocConfig(x_min=ext - 12.0, x_max=ext + 20.0, y_min=-10.0, y_max=14.0, step_xy_m=0.75, step_yaw_deg=10.0, top_k=8)
+    _check_equal(ctx, vm, scan, T_tilt, cfg)
+
+
+def test_search_equals_exhaustive_ties(ctx):
+    world = synth.make_world(300_000, seed=77)
+    vm = VoxelHashMap(0.5, 30, ctx)
+    vm.AddPoints(world)
+    scan, T = synth.make_scan(world, 3000, seed=8, max_range=40.0)
+    T_tilt = _tilt(0.0, 0.0, 1.0)
+    cfg = GlobalRelocConfig(x_min=T[0, 3] - 10.0, x_max=T[0, 3] + 10.0, y_min=T[1, 3] - 10.0, y_max=T[1, 3] + 10.0, step_xy_m=0.5,
+                            step_yaw_deg=90.0, score_min_height_m=-math.inf, top_k=12, nms_xy_m=0.5)
+    _check_equal(ctx, vm, scan, T_tilt, cfg)
+
+
+def test_stats_add_up(ctx, field1m):
+    world, vm = field1m
+    T, scan, T_tilt = _scan_case(world, vm, 21)
+    cfg = GlobalRelocConfig(x_min=T[0, 3] - 40.0, x_max=T[0, 3] + 40.0, y_min=T[1, 3] - 40.0, y_max=T[1, 3] + 40.0)
+    r = Registration(RegistrationConfig(icp_method=IcpMethod.P2P, max_iteration=2), ctx)
+    _, _, _, _, cands, st = r.RelocalizeGlobal(scan, vm, T_tilt, cfg)
+    H, valid = vm.GlobalHypotheses(T_tilt, cfg)
+    assert st["lattice_poses"] == H.shape[0] == st["nx"] * st["ny"] * st["n_yaw"] == 161 * 161 * 180
+    assert st["valid_leaves"] == int(valid.sum())
+    assert st["n_counted"] == _counted(scan[::max(1, -(-scan.shape[0] // cfg.max_score_points))], cfg, T_tilt).shape[0]
+    L = st["levels"]
+    assert L >= 1 and st["passes"] >= 1
+    for l in range(1, L + 1):
+        assert 0 <= st["nodes_kept"][l] <= st["nodes_bounded"][l]
+    assert st["point_evals"] == st["n_counted"] * (sum(st["nodes_bounded"]) + st["leaves_scored"])
+    # pruning: the exact leaf scores are a small part of the lattice (DESIGN.md section 12 gives the measured ratios)
+    # (measured: 6 % of the leaves scored, 29 % of the exhaustive point-evaluations on this 80 m square)
+    assert st["leaves_scored"] < 0.12 * st["valid_leaves"], st
+    assert st["point_evals"] < 0.5 * st["n_counted"] * st["valid_leaves"], st
+    assert all(c["score"] >= st["tau"] for c in cands)
+
+
+# ---------------------------------------------------------------- end to end
+@pytest.fixture(scope="module")
+def field2m(ctx):
+    world = synth.make_field_world(2_000_000, seed=2027)
+    vm = VoxelHashMap(1.0, 30, ctx)
+    vm.AddPoints(world)
+    vm.CalPointCovAll(0.4)
+    return world, vm
+
+
+def test_recovers_without_guess(ctx, field2m):
+    world, vm = field2m
+    reg = Registration(RegistrationConfig(icp_method=IcpMethod.GICP), ctx)
+    for seed in (101, 202, 303):
+        T, scan, T_tilt = _scan_case(world, vm, seed, n=16384)
+        pose, ok, fit, cov, cands, st = reg.RelocalizeGlobal(scan, vm, T_tilt)
+        # premise: the best lattice pose (the exhaustive one: the search equals it) lies within 1 m / 3 deg of the truth
+        dt0, dr0 = synth.pose_error(T, cands[0]["T0"])
+        assert math.hypot(*(T[:2, 3] - cands[0]["T0"][:2, 3])) <= 1.0 and dr0 <= math.radians(3.0), (seed, dt0, dr0, st)
+        ref, ok_ref, _, _ = reg.RunRegister(scan, vm, T)
+        assert ok_ref and ok
+        dt, dr = synth.pose_error(ref, pose)
+        assert dt <= 0.05 and dr <= math.radians(0.2), (seed, dt, dr)
+        win = [c for c in cands if np.array_equal(c["T"], pose)]
+        assert win
+        again = reg.RunRegisterBatch([Scan(ctx, scan)], vm, [win[0]["T0"]])[0]
+        assert np.array_equal(again["T"], pose) and again["fitness_score"] == fit and again["is_success"]
+
+
+@pytest.mark.parametrize("env", [("ELM_KERNEL", "lists"), ("ELM_GRID", "tiled")])
+def test_same_candidates_under_every_index_form(monkeypatch, field1m, env):
+    world, _ = field1m
+    c0 = Context(0)
+    vm0 = VoxelHashMap(1.0, 30, c0)
+    vm0.AddPoints(world)
+    T, scan, T_tilt = _scan_case(world, vm0, 31)
+    cfg = GlobalRelocConfig(x_min=T[0, 3] - 12.0, x_max=T[0, 3] + 12.0, y_min=T[1, 3] - 12.0, y_max=T[1, 3] + 12.0, step_yaw_deg=8.0)
+    reg = RegistrationConfig(icp_method=IcpMethod.P2P, max_iteration=2)
+    a = Registration(reg, c0).RelocalizeGlobal(scan, vm0, T_tilt, cfg)[4]
+    monkeypatch.setenv(*env)
+    c1 = Context(0)
+    vm1 = VoxelHashMap(1.0, 30, c1)
+    vm1.AddPoints(world)
+    b = Registration(reg, c1).RelocalizeGlobal(scan, vm1, T_tilt, cfg)[4]
+    assert [(c["hyp_index"], c["score"]) for c in a] == [(c["hyp_index"], c["score"]) for c in b]
+    assert all(np.array_equal(x["T0"], y["T0"]) for x, y in zip(a, b))
+    # the refinement runs on the index form the switch selects: the same success flags and (to rounding) the same refined poses
+    assert [c["is_success"] for c in a] == [c["is_success"] for c in b]
+    for x, y in zip(a, b):
+        dt, dr = synth.pose_error(x["T"], y["T"])
+        assert dt <= 1e-6 and dr <= 1e-7, (dt, dr)
+    del vm0, vm1
+    c0.close()
+    c1.close()
+
+
+def test_initialize_global_node(ctx, field1m):
+    from elimaloc_amd.pcm_matching import PcmMatching, PcmMatchingConfig
+    world, vm = field1m
+    tf = np.eye(4)
+    tf[2, 3] = 1.8
+    node = PcmMatching(PcmMatchingConfig(tf_ego_to_lidar=tf), ctx)
+    node.Init(world)
+    T, scan, _ = _scan_case(world, vm, 41)
+    cfg = GlobalRelocConfig(x_min=T[0, 3] - 10.0, x_max=T[0, 3] + 10.0, y_min=T[1, 3] - 10.0, y_max=T[1, 3] + 10.0, step_yaw_deg=4.0)
+    out = node.InitializeGlobal(scan, cfg)
+    assert out is not None and out["candidates"] and out["stats"]["valid_leaves"] > 0
+    assert np.allclose(out["pose_ego"], out["pose_lidar"] @ np.linalg.inv(tf))
+
+
+def test_edge_cases(ctx, field1m):
+    world, vm = field1m
+    reg = Registration(RegistrationConfig(icp_method=IcpMethod.P2P, max_iteration=2), ctx)
+    scan, T = synth.make_scan(world, 2048, seed=5)
+    cfg = GlobalRelocConfig(x_min=T[0, 3] - 3.0, x_max=T[0, 3] + 3.0, y_min=T[1, 3] - 3.0, y_max=T[1, 3] + 3.0, step_yaw_deg=30.0, top_k=4)
+    # an empty map: no pose stands on ground, gate 1
+    empty = VoxelHashMap(1.0, 30, ctx)
+    empty.AddPoints(np.zeros((0, 3), np.float32))
+    pose, ok, fit, _, cands, st = reg.RelocalizeGlobal(scan, empty, _tilt(0.0, 0.0, 1.5), GlobalRelocConfig(top_k=4))
+    assert not ok and fit is None and cands == [] and reg.last_relocalize_["gate"] == 1 and st["valid_leaves"] == 0
+    found, z = empty.FindGroundHeights([[0.0, 0.0], [1.0, 2.0]])
+    assert not found.any()
+    # no counted point: every score 0, the kept ones in index order after NMS
+    c0 = GlobalRelocConfig(**{f: getattr(cfg, f) for f in ("x_min", "x_max", "y_min", "y_max", "step_yaw_deg", "top_k")},
+                           score_min_height_m=1e9)
+    cands, st = _check_equal(ctx, vm, scan, _tilt(0.0, 0.0, 1.5), c0)
+    assert st["n_counted"] == 0 and cands and all(c["score"] == 0 for c in cands)
+    # a lattice above 2^31 - 1 poses is refused
+    with pytest.raises(ElmError):
+        reg.RelocalizeGlobal(scan, vm, np.eye(4), GlobalRelocConfig(step_xy_m=0.01, step_yaw_deg=0.1))
+
+
+def test_one_rank_only(ctx):
+    world = synth.make_world(30_000, seed=11)
+    scan, T = synth.make_scan(world, 2048, seed=12)
+    cfg = GlobalRelocConfig(step_xy_m=2.0, step_yaw_deg=90.0, top_k=2)
+    grp = Context.multi([0, 0])
+    gvm = VoxelHashMap(1.0, 30, grp)
+    gvm.AddPoints(world)
+    r = Registration(RegistrationConfig(icp_method=IcpMethod.P2P), grp)
+    for call in (lambda: r.RelocalizeGlobal(scan, gvm, np.eye(4), cfg), lambda: gvm.FindGroundHeights([[0.0, 0.0]]),
+                 lambda: gvm.GlobalHypotheses(np.eye(4), cfg)):
+        with pytest.raises(ElmError) as e:
+            call()
+        assert "one rank" in str(e.value) or "-5" in str(e.value)
+    del gvm
+    grp.close()
+    hc = Context(0)
+    hc.set_allreduce_hook(lambda p, n, s: 0)
+    hvm = VoxelHashMap(1.0, 30, hc)
+    hvm.AddPoints(world)
+    with pytest.raises(ElmError):
+        Registration(RegistrationConfig(icp_method=IcpMethod.P2P), hc).RelocalizeGlobal(scan, hvm, np.eye(4), cfg)
+    hc.set_allreduce_hook(None)
+    out = Registration(RegistrationConfig(icp_method=IcpMethod.P2P), hc).RelocalizeGlobal(scan, hvm, np.eye(4), cfg)
+    assert out[5]["valid_leaves"] > 0
+    del hvm
+    hc.close()
+
+
+def test_argument_errors_with_a_live_context(ctx, field1m):
+    """With a real context and map the only source of ELM_ERR_INVALID is the argument checks: the valid config runs, every bad one is refused."""
+    from elimaloc_amd import _lib
+    L = _lib.lib()
+    world, vm = field1m
+    scan, T = synth.make_scan(world, 2048, seed=5)
+    rect = dict(x_min=T[0, 3] - 2.0, x_max=T[0, 3] + 2.0, y_min=T[1, 3] - 2.0, y_max=T[1, 3] + 2.0, step_yaw_deg=45.0, top_k=2)
+    reg = RegistrationConfig(icp_method=IcpMethod.P2P, max_iteration=2)
+    Tt = _tilt(0.0, 0.0, 1.8)
+    fp = scan.ctypes.data_as(C.POINTER(C.c_float))
+
+    def codes(cfg, T_tilt=Tt):
+        Tc = np.ascontiguousarray(T_tilt.T).ravel()
+        Tout, res, cands, nc, st = np.empty(16), _lib.RegResult(), (_lib.RelocCandidate * 2)(), C.c_int(0), _lib.GlobalRelocStats()
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        a = L.elm_relocalize_global(ctx._h, vm._handle(), fp, scan.shape[0], dp(Tc), C.byref(cfg), C.byref(reg), dp(Tout), C.byref(res),
+                                    cands, 2, C.byref(nc), C.byref(st))
+        n = C.c_size_t(0)
+        b = L.elm_reloc_global_hypotheses(ctx._h, vm._handle(), dp(Tc), C.byref(cfg), None, None, 0, C.byref(n))
+        return a, b
+
+    assert codes(GlobalRelocConfig(**rect)) == (0, 0)
+    assert codes(GlobalRelocConfig(**rect, score_min_height_m=-math.inf)) == (0, 0)
+    nan = float("nan")
+    bad = [dict(step_xy_m=0.0), dict(step_yaw_deg=nan), dict(top_k=0), dict(top_k=1025), dict(score_min_height_m=nan),
+           dict(score_min_height_m=math.inf), dict(score_max_range_m=-1.0), dict(pool_min=0), dict(max_kz_span=0),
+           dict(x_min=nan), dict(y_min=nan, y_max=nan), dict(x_max=rect["x_min"] - 1.0), dict(y_max=math.inf),
+           dict(x_min=0.0, x_max=10000.0, y_min=0.0, y_max=10000.0, step_yaw_deg=2.0)]
+    for kw in bad:
+        assert codes(GlobalRelocConfig(**(rect | kw))) == (-1, -1), kw
+    for idx, v in (((0, 3), 0.5), ((1, 3), -1.0), ((3, 0), 1.0), ((3, 3), 2.0), ((2, 3), nan)):
+        Tb = Tt.copy()
+        Tb[idx] = v
+        assert codes(GlobalRelocConfig(**rect), Tb) == (-1, -1), idx
