@@ -1813,11 +1813,6 @@ static int strict_pairs() { // 1: per-pair kernels always, -1: fast kernels, sid
 }
 static int build_search_index(elm_map* m, bool* use_grid);
 static int build_voxel_neighbourhoods(elm_map* m, bool want_faces);
-// Which kernels one registration call runs.  `radar`: the per-pair kernels (use_radar_cov, or ELM_CHECK=strict_pairs).  Otherwise the search
-// index (built on first use) -- dense / two-level cell grid, neighbourhood lists, voxel-mean lists, or the plain walk -- and `asym`: the
-// map holds a flagged covariance of the method's kind whose stored inverse is not symmetric, and the fast kernels carry the antisymmetric
-// part of J^T M J in side records (RegParams::asym; grid and voxel-list kernels, unfused reduction).  Such a map on one of the fall-back
-// indices (lists / plain walk: maps the grid cannot hold, ELM_KERNEL=...) or under ELM_FUSED_REDUCE still takes the per-pair kernels.
 // pcm.cpp:92-100: the covariance methods need their covariances computed (the index builders read them)
 static int check_covariances(elm_ctx* ctx, const elm_map* map, int method) {
     if (!map || map->dm.n_vox == 0) return ELM_OK;
@@ -1834,6 +1829,12 @@ static int check_covariances(elm_ctx* ctx, const elm_map* map, int method) {
 struct PathChoice {
     bool radar = false, asym = false, use_grid = false, use_cells = false, use_vnbr = false;
 };
+// Which kernels one registration call runs.  `radar`: the per-pair kernels (use_radar_cov, or ELM_CHECK=strict_pairs).  Otherwise the search
+// index (built on first use) -- dense / two-level cell grid, neighbourhood lists, voxel-mean lists, or the plain walk -- and `asym`: the
+// map holds a flagged covariance of the method's kind whose stored inverse is not symmetric, and the fast kernels carry the antisymmetric
+// part of J^T M J in side records (RegParams::asym; grid and voxel-list kernels, unfused reduction).  Such a map on one of the fall-back
+// indices (lists / plain walk: maps the grid cannot hold, ELM_KERNEL=...) still takes the per-pair kernels.  The one check of the
+// covariances every registration driver relies on (check_covariances) runs here.
 static int choose_path(elm_ctx* ctx, const elm_map* map, const elm_reg_config* cfg, PathChoice* pc) {
     *pc = PathChoice();
     const int method = cfg->icp_method;
@@ -2052,28 +2053,79 @@ static int align_clouds_local_impl(elm_ctx* ctx, int method, const double* src_l
     return ELM_OK;
 }
 
-// the side records of a launch of `blocks` workgroups over `n_scans` scans / slots; the scans' reduced side sums sit right behind the
-// packed sums in d_sums (one exchange carries both)
-static int reserve_asym(elm_ctx* ctx, RegParams& rp, uint32_t blocks, int n_scans) {
+// ctx->rp of a registration call: `blocks` workgroups over `n_scans` scans / slots, uniform_blocks > 0 when each owns that many.  The
+// side records of an asymmetric map (pc.asym): the scans' reduced side sums sit right behind the packed sums in d_sums (one exchange
+// carries both).  radar_var is read by k_accumulate_radar alone, which runs only when rp.radar != 0.
+static int set_reg_params(elm_ctx* ctx, const elm_reg_config* cfg, const PathChoice& pc, uint32_t blocks, int n_scans, uint32_t uniform_blocks) {
+    RegParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.th = cfg->max_search_dist;
+    rp.th2 = cfg->max_search_dist * cfg->max_search_dist;
+    rp.lm_lambda = cfg->lm_lambda;
+    rp.term_thr = cfg->icp_termination_threshold_m;
+    rp.min_overlap = cfg->min_overlap_ratio;
+    rp.max_fitness = cfg->max_fitness_score;
+    rp.method = cfg->icp_method;
+    rp.max_iter = cfg->max_iteration;
+    rp.uniform_blocks = uniform_blocks;
+    rp.radar = pc.radar ? (cfg->use_radar_cov != 0 ? 1 : 2) : 0; // 2: the radar kernels without a source covariance (ELM_CHECK=strict_pairs)
+    rp.stats = ctx->work_counters ? 1 : 0;
+    rp.radar_var[0] = cfg->range_variance_m;
+    rp.radar_var[1] = cfg->azimuth_variance_deg;
+    rp.radar_var[2] = cfg->elevation_variance_deg;
+    if (pc.asym) {
+        int rc;
+        if ((rc = dev_reserve(ctx, ctx->d_asym, (size_t)std::max<uint32_t>(blocks, 1) * kAsymRecord * sizeof(double))) != ELM_OK) return rc;
+        rp.asym = (double*)ctx->d_asym.p;
+        rp.asym_sums = (double*)ctx->d_sums.p + (size_t)n_scans * kSums;
+    }
+    rp.rank_check = ((ctx->comm || ctx->hook) && !rp.radar && !rp.stats) ? 1 : 0;
+    ctx->rp = rp;
+    return ELM_OK;
+}
+
+// the misuse every registration driver refuses: a map of another context, an unknown method, a batch still in flight
+static bool reg_args_ok(const elm_ctx* ctx, const elm_map* map, const elm_reg_config* cfg) {
+    return map->ctx == ctx && cfg->icp_method >= ELM_P2P && cfg->icp_method <= ELM_AVGICP && !ctx->in_flight;
+}
+
+// The 64 bytes behind the ScanState array of a lockstep batch (d_state, h_state): one copy reads the states and these together.
+struct StateTail {
+    int32_t active;        // scans still iterating (the early-stop counter)
+    int32_t rank_mismatch; // the ranks iterated different registrations (rank-agreement check of the exchanged sums)
+    int32_t _pad0[2];
+    uint32_t ds_kept;      // downsample_enqueue: the points kept, the size of a one-scan batch on the device (launch_init_pack's n_dev)
+    int32_t ds_overflow;   // downsample_enqueue: a voxel key does not pack
+    int32_t _pad1[10];
+};
+static_assert(sizeof(StateTail) == 64 && offsetof(StateTail, rank_mismatch) == 4 && offsetof(StateTail, ds_kept) == 16 &&
+              offsetof(StateTail, ds_overflow) == 20, "the state tail's layout");
+static StateTail* state_tail(void* states, int n_scans) { return (StateTail*)((char*)states + (size_t)n_scans * sizeof(ScanState)); }
+
+static size_t trace_bytes(int count) { return (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace); }
+// the iteration traces of `count` registrations: device (zeroed on the context stream) and host copies
+static int reserve_trace(elm_ctx* ctx, int count, elm_iter_trace** d_trace) {
+    const size_t tb = trace_bytes(count);
     int rc;
-    if ((rc = dev_reserve(ctx, ctx->d_asym, (size_t)std::max<uint32_t>(blocks, 1) * kAsymRecord * sizeof(double))) != ELM_OK) return rc;
-    rp.asym = (double*)ctx->d_asym.p;
-    rp.asym_sums = (double*)ctx->d_sums.p + (size_t)n_scans * kSums;
+    if ((rc = dev_reserve(ctx, ctx->d_trace, tb)) != ELM_OK) return rc;
+    if ((rc = pinned_reserve(ctx, &ctx->h_trace, &ctx->h_trace_cap, tb)) != ELM_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_trace.p, 0, tb, ctx->stream));
+    *d_trace = (elm_iter_trace*)ctx->d_trace.p;
     return ELM_OK;
 }
 
 // One ICP iteration's correspondence + accumulation launch for `n_scans` scans / slots, bracketed by two profiling marks (the
 // solve span starts at the second).
 static int enqueue_accumulate(elm_ctx* ctx, const elm_map* map, const ScanDesc* dsc, int n_scans, uint32_t blocks, ScanState* st,
-                              const RegParams& rp, bool use_grid, bool use_cells, bool use_vnbr, double* partials = nullptr) {
+                              const RegParams& rp, const PathChoice& pc, double* partials = nullptr) {
     int rc;
     if ((rc = prof_mark(ctx)) != ELM_OK) return rc;
     if (!partials) partials = (double*)ctx->d_partials.p;
     if (blocks) {
         if (rp.radar) launch_accumulate_radar(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
-        else if (use_grid) launch_accumulate_grid(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
-        else if (use_cells) launch_accumulate_cell(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
-        else if (use_vnbr && rp.method == ELM_AVGICP && map->dm.vface_flagged) {
+        else if (pc.use_grid) launch_accumulate_grid(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
+        else if (pc.use_cells) launch_accumulate_cell(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
+        else if (pc.use_vnbr && rp.method == ELM_AVGICP && map->dm.vface_flagged) {
             // the fused walk on a map with flagged voxels: one flag per workgroup (all zero between launches: the fix-up launch clears what
             // the walk sets)
             RegParams rq = rp;
@@ -2085,7 +2137,7 @@ static int enqueue_accumulate(elm_ctx* ctx, const elm_map* map, const ScanDesc* 
             rq.flagged = (need <= ctx->d_flagged.cap) ? (uint32_t*)ctx->d_flagged.p : nullptr;
             launch_accumulate_vnbr(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rq);
         }
-        else if (use_vnbr) launch_accumulate_vnbr(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
+        else if (pc.use_vnbr) launch_accumulate_vnbr(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
         else launch_accumulate_direct(ctx->stream, map->dm, dsc, n_scans, (int)blocks, st, partials, rp);
     }
     return prof_mark(ctx);
@@ -2109,9 +2161,7 @@ static int prof_collect(elm_ctx* ctx) {
 static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const* scans, int batch, const double* T0, const elm_reg_config* cfg,
                               int want_trace, const unsigned* n_dev) {
     if (!ctx || !map || !scans || batch <= 0 || !T0 || !cfg) return ELM_ERR_INVALID;
-    if (map->ctx != ctx) return ELM_ERR_INVALID;
-    if (cfg->icp_method < ELM_P2P || cfg->icp_method > ELM_AVGICP) return ELM_ERR_INVALID;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
+    if (!reg_args_ok(ctx, map, cfg)) return ELM_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int method = cfg->icp_method;
     const bool map_empty = map->dm.n_vox == 0;
@@ -2121,17 +2171,6 @@ static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const*
         ctx->iter_key_map = map; ctx->iter_key_method = method; ctx->iter_key_batch = batch;
         for (int k = 0; k < 8; ++k) ctx->iter_ring[k] = 0;
         ctx->iter_hint = 0;
-    }
-    // (use_radar_cov on several ranks: the all-reduce carries the radar kernel's 64 sums per scan instead of the 32 of the packed layout)
-    if (!map_empty) {
-        if ((method == ELM_VGICP || method == ELM_AVGICP) && !map->info.has_voxel_cov) {
-            ctx->last_error = "VGICP/AVGICP need elm_map_cal_voxel_cov_all() (pcm.cpp:92-95)";
-            return ELM_ERR_INVALID;
-        }
-        if (method == ELM_GICP && !map->info.has_point_cov) {
-            ctx->last_error = "GICP needs elm_map_cal_point_cov_all() (pcm.cpp:97-100)";
-            return ELM_ERR_INVALID;
-        }
     }
     int rc;
     PathChoice pc;
@@ -2157,56 +2196,29 @@ static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const*
         hd[b].blk_end = blocks;
     }
     memcpy(hT, T0, (size_t)batch * 16 * sizeof(double));
-    // the counter of still-iterating scans sits right behind the states: an early-stop check reads both with ONE copy, and when the
-    // counter is zero the final states are already on the host
-    const size_t st_bytes = (size_t)batch * sizeof(ScanState);
+    // the counter of still-iterating scans sits right behind the states (StateTail): an early-stop check reads both with ONE copy, and
+    // when the counter is zero the final states are already on the host
+    const size_t st_bytes = (size_t)batch * sizeof(ScanState) + sizeof(StateTail);
     if ((rc = dev_reserve(ctx, ctx->d_scans, (size_t)batch * sizeof(ScanDesc))) != ELM_OK) return rc;
     if ((rc = dev_reserve(ctx, ctx->d_T0, (size_t)batch * 16 * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_state, st_bytes + 64)) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_state, st_bytes)) != ELM_OK) return rc;
     if ((rc = dev_reserve(ctx, ctx->d_partials, (size_t)std::max<uint32_t>(blocks, 1) * (radar ? kRadarRecord : kSums) * sizeof(double))) != ELM_OK) return rc;
     if ((rc = dev_reserve(ctx, ctx->d_sums, (size_t)batch * (radar ? kRadarRecord : kSums + kAsymRecord) * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = pinned_reserve(ctx, &ctx->h_state, &ctx->h_state_cap, st_bytes + 64)) != ELM_OK) return rc;
+    if ((rc = pinned_reserve(ctx, &ctx->h_state, &ctx->h_state_cap, st_bytes)) != ELM_OK) return rc;
     ctx->results_ready = false;
     elm_iter_trace* d_trace = nullptr;
-    if (want_trace) {
-        const size_t tb = (size_t)batch * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace);
-        if ((rc = dev_reserve(ctx, ctx->d_trace, tb)) != ELM_OK) return rc;
-        if ((rc = pinned_reserve(ctx, &ctx->h_trace, &ctx->h_trace_cap, tb)) != ELM_OK) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_trace.p, 0, tb, ctx->stream));
-        d_trace = (elm_iter_trace*)ctx->d_trace.p;
-    }
+    if (want_trace && (rc = reserve_trace(ctx, batch, &d_trace)) != ELM_OK) return rc;
     const bool packed_init = batch <= kInitPack;
     if (!packed_init) {
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_scans.p, hd, (size_t)batch * sizeof(ScanDesc), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_T0.p, hT, (size_t)batch * 16 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
+    if ((rc = set_reg_params(ctx, cfg, pc, blocks, batch, uniform_blocks)) != ELM_OK) return rc;
+    const RegParams& rp = ctx->rp;
 
-    RegParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.th = cfg->max_search_dist;
-    rp.th2 = cfg->max_search_dist * cfg->max_search_dist;
-    rp.lm_lambda = cfg->lm_lambda;
-    rp.term_thr = cfg->icp_termination_threshold_m;
-    rp.min_overlap = cfg->min_overlap_ratio;
-    rp.max_fitness = cfg->max_fitness_score;
-    rp.method = method;
-    rp.max_iter = cfg->max_iteration;
-    rp.uniform_blocks = uniform_blocks;
-    rp.radar = radar ? (cfg->use_radar_cov != 0 ? 1 : 2) : 0; // 2: the radar kernels without a source covariance (ELM_CHECK=strict_pairs)
-    rp.stats = ctx->work_counters ? 1 : 0;
-    rp.radar_var[0] = cfg->range_variance_m;
-    rp.radar_var[1] = cfg->azimuth_variance_deg;
-    rp.radar_var[2] = cfg->elevation_variance_deg;
-    if (pc.asym && (rc = reserve_asym(ctx, rp, blocks, batch)) != ELM_OK) return rc;
-    rp.rank_check = ((ctx->comm || ctx->hook) && !radar && !rp.stats) ? 1 : 0;
-    ctx->rp = rp;
-
-    // the search index (choose_path built it on first use): dense / two-level cell grid, else the cell-indexed neighbourhood lists, else
-    // the plain walk (maps whose lists cannot be cell-sorted); use_radar_cov: k_accumulate_radar walks the hash map itself
-    const bool use_grid = pc.use_grid, use_cells = pc.use_cells, use_vnbr = pc.use_vnbr;
     ScanState* st = (ScanState*)ctx->d_state.p;
     const ScanDesc* dsc = (const ScanDesc*)ctx->d_scans.p;
-    int* d_active = (int*)((char*)ctx->d_state.p + st_bytes);
+    int* d_active = &state_tail(st, batch)->active;
     (void)hipGetLastError();
     if (packed_init) { // descriptors and guesses as kernel arguments: no H2D copies, no memset
         InitPack pack;
@@ -2224,9 +2236,10 @@ static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const*
     ctx->events_used = 0;
     if (!map_empty) {
         for (int it = 0; it < cfg->max_iteration; ++it) {
-            if ((rc = enqueue_accumulate(ctx, map, dsc, batch, blocks, st, rp, use_grid, use_cells, use_vnbr)) != ELM_OK) return rc;
+            if ((rc = enqueue_accumulate(ctx, map, dsc, batch, blocks, st, rp, pc)) != ELM_OK) return rc;
             if (distributed) {
                 launch_solve(ctx->stream, dsc, batch, st, (const double*)ctx->d_partials.p, (double*)ctx->d_sums.p, rp, d_trace, 1, d_active); // reduce only
+                // (use_radar_cov on several ranks: the all-reduce carries the radar kernel's 64 sums per scan instead of the 32 of the packed layout)
                 if ((rc = exchange(ctx, (double*)ctx->d_sums.p, (size_t)batch * (radar ? kRadarRecord : (rp.asym ? kSums + kAsymRecord : kSums)))) != ELM_OK) return rc;
                 launch_solve(ctx->stream, dsc, batch, st, (const double*)ctx->d_partials.p, (double*)ctx->d_sums.p, rp, d_trace, 2, d_active);
             } else {
@@ -2238,9 +2251,9 @@ static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const*
             const int done_iters = it + 1;
             if (ctx->iter_hint > 0 && done_iters >= ctx->iter_hint && done_iters < cfg->max_iteration &&
                 ((done_iters - ctx->iter_hint) % 2) == 0) {
-                HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, st, st_bytes + 64, hipMemcpyDeviceToHost, ctx->stream)); // states + counter (+ the downsample totals)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, st, st_bytes, hipMemcpyDeviceToHost, ctx->stream)); // states + tail
                 HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                if (*(const int*)((const char*)ctx->h_state + st_bytes) == 0) {
+                if (state_tail(ctx->h_state, batch)->active == 0) {
                     ctx->results_ready = true; // every scan has finished: these ARE the final states
                     break;
                 }
@@ -2249,10 +2262,8 @@ static int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const*
         if ((rc = prof_mark(ctx)) != ELM_OK) return rc;
     }
     HIPCHK(ctx, hipGetLastError());
-    if (!ctx->results_ready) HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, st, st_bytes + 64, hipMemcpyDeviceToHost, ctx->stream));
-    if (want_trace)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, (size_t)batch * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace),
-                                   hipMemcpyDeviceToHost, ctx->stream));
+    if (!ctx->results_ready) HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (want_trace) HIPCHK(ctx, hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, trace_bytes(batch), hipMemcpyDeviceToHost, ctx->stream));
     ctx->batch = batch;
     ctx->want_trace = want_trace != 0;
     ctx->in_flight = true;
@@ -2282,6 +2293,12 @@ static void state_to_result(const ScanState& h, const RegParams& rp, elm_reg_res
     r.n_tested_total = h.tested_total;
     if (rp.max_iter <= 0 && h.gate == 0) r.is_success = 1; // no iteration ran: fitness gate on the initial 0.0 passes
 }
+// the results of the call's `count` registrations from their final states in h_state and, with `trace`, their iteration traces
+static void hand_back(const elm_ctx* ctx, int count, elm_reg_result* results, elm_iter_trace* trace) {
+    const ScanState* hs = (const ScanState*)ctx->h_state;
+    for (int b = 0; results && b < count; ++b) state_to_result(hs[b], ctx->rp, results[b], ctx->path);
+    if (trace) memcpy(trace, ctx->h_trace, trace_bytes(count));
+}
 
 extern "C" int elm_register_batch_finish(elm_ctx* ctx, elm_reg_result* results, elm_iter_trace* trace) {
     if (!ctx || !ctx->in_flight) return ELM_ERR_INVALID;
@@ -2293,11 +2310,11 @@ extern "C" int elm_register_batch_finish(elm_ctx* ctx, elm_reg_result* results, 
         if (prc != ELM_OK) return prc;
     }
     const ScanState* hs = (const ScanState*)ctx->h_state;
-    if (ctx->rp.rank_check && ((const int*)((const char*)ctx->h_state + (size_t)ctx->batch * sizeof(ScanState)))[1] != 0) {
+    if (ctx->rp.rank_check && state_tail(ctx->h_state, ctx->batch)->rank_mismatch != 0) {
         ctx->last_error = "the ranks iterated different registrations in one slot (rank-agreement check of the exchanged sums)";
         return ELM_ERR_COMM;
     }
-    for (int b = 0; results && b < ctx->batch; ++b) state_to_result(hs[b], ctx->rp, results[b], ctx->path);
+    hand_back(ctx, ctx->batch, results, ctx->want_trace ? trace : nullptr);
     {
         int mx = 0;
         for (int b = 0; b < ctx->batch; ++b) mx = std::max(mx, (int)hs[b].iters);
@@ -2310,8 +2327,6 @@ extern "C" int elm_register_batch_finish(elm_ctx* ctx, elm_reg_result* results, 
         for (int k = 0; k < 8; ++k) h = std::max(h, ctx->iter_ring[k]);
         ctx->iter_hint = h;
     }
-    if (trace && ctx->want_trace)
-        memcpy(trace, ctx->h_trace, (size_t)ctx->batch * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace));
     return ELM_OK;
 }
 
@@ -2321,6 +2336,44 @@ extern "C" int elm_register_batch(elm_ctx* ctx, const elm_map* map, elm_scan* co
     int rc = elm_register_batch_enqueue(ctx, map, scans, batch, T0, cfg, trace != nullptr);
     if (rc != ELM_OK) return rc;
     return elm_register_batch_finish(ctx, results, trace);
+}
+
+// The queue of a slot stream in d_queue: the registrations' items, their initial guesses, the control block and, 64-byte aligned, their
+// final states.  h_desc stages the same head [items | guesses | control] -- one copy -- and the slot descriptors at out_off.
+struct SlotQueue {
+    size_t ctrl_off, out_off;
+    QueueItem* d_q; double* d_qT0; StreamCtrl* d_ctrl; ScanState* d_out; // in d_queue
+    QueueItem* hq; double* hT; StreamCtrl* hc; ScanDesc* hd;              // in h_desc
+};
+// what a stream of `count` registrations through S slots of cap_blocks workgroups each reserves: the host staging, the slot descriptors
+// and states, the partial records and sums, the queue, the host copy of the final states and the completion counters
+static int reserve_slot_queue(elm_ctx* ctx, int count, int S, uint32_t cap_blocks, SlotQueue* q) {
+    const size_t t0_off = (size_t)count * sizeof(QueueItem);
+    q->ctrl_off = t0_off + (size_t)count * 16 * sizeof(double);
+    q->out_off = q->ctrl_off + ((sizeof(StreamCtrl) + 63) / 64) * 64;
+    const size_t d_bytes = (size_t)S * sizeof(ScanDesc);
+    const uint32_t blocks = cap_blocks * (uint32_t)S;
+    int rc;
+    if ((rc = pinned_reserve(ctx, &ctx->h_desc, &ctx->h_desc_cap, std::max<size_t>(q->out_off + d_bytes, 4096))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_scans, d_bytes)) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_state, (size_t)S * sizeof(ScanState))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_partials, (size_t)std::max<uint32_t>(blocks, 1) * kSums * sizeof(double))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_sums, (size_t)S * (kSums + kAsymRecord) * sizeof(double))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_queue, q->out_off + (size_t)count * sizeof(ScanState))) != ELM_OK) return rc;
+    if ((rc = pinned_reserve(ctx, &ctx->h_state, &ctx->h_state_cap, (size_t)count * sizeof(ScanState))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_active, 256)) != ELM_OK) return rc;
+    if (!ctx->h_active) HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_active, 64, hipHostMallocDefault));
+    char* d = (char*)ctx->d_queue.p;
+    char* h = (char*)ctx->h_desc;
+    q->d_q = (QueueItem*)d;
+    q->d_qT0 = (double*)(d + t0_off);
+    q->d_ctrl = (StreamCtrl*)(d + q->ctrl_off);
+    q->d_out = (ScanState*)(d + q->out_off);
+    q->hq = (QueueItem*)h;
+    q->hT = (double*)(h + t0_off);
+    q->hc = (StreamCtrl*)(h + q->ctrl_off);
+    q->hd = (ScanDesc*)(h + q->out_off);
+    return ELM_OK;
 }
 
 // Continuous batching: `count` registrations through `slots` slots.  Every ICP iteration is one accumulate launch over the
@@ -2333,9 +2386,7 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
     if (group_call(ctx)) return elm_multi::reg_batch(ctx, map, scans, count, T0, cfg, slots, results, trace);
     if (map->dm.n_vox == 0 || cfg->max_iteration <= 0) // nothing iterates: the lockstep path handles the degenerate cases
         return elm_register_batch(ctx, map, scans, count, T0, cfg, results, trace);
-    if (map->ctx != ctx) return ELM_ERR_INVALID;
-    if (cfg->icp_method < ELM_P2P || cfg->icp_method > ELM_AVGICP) return ELM_ERR_INVALID;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
+    if (!reg_args_ok(ctx, map, cfg)) return ELM_ERR_INVALID;
     int rc;
     PathChoice pc;
     if ((rc = choose_path(ctx, map, cfg, &pc)) != ELM_OK) return rc;
@@ -2352,17 +2403,7 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
         return ELM_OK;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int method = cfg->icp_method;
-    if ((method == ELM_VGICP || method == ELM_AVGICP) && !map->info.has_voxel_cov) {
-        ctx->last_error = "VGICP/AVGICP need elm_map_cal_voxel_cov_all() (pcm.cpp:92-95)";
-        return ELM_ERR_INVALID;
-    }
-    if (method == ELM_GICP && !map->info.has_point_cov) {
-        ctx->last_error = "GICP needs elm_map_cal_point_cov_all() (pcm.cpp:97-100)";
-        return ELM_ERR_INVALID;
-    }
     const int S = std::min(std::min(slots, count), stream_max_slots());
-    // queue (host staging): items, initial guesses; slot descriptors with fixed block ranges sized for the largest scan
     uint32_t max_n = 0;
     for (int b = 0; b < count; ++b) {
         if (!scans[b] || scans[b]->ctx != ctx) return ELM_ERR_INVALID;
@@ -2370,71 +2411,30 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
     }
     const uint32_t cap_blocks = (max_n + kBlock - 1) / kBlock;
     const uint32_t blocks = cap_blocks * (uint32_t)S;
-    const size_t q_bytes = (size_t)count * sizeof(QueueItem), t_bytes = (size_t)count * 16 * sizeof(double), d_bytes = (size_t)S * sizeof(ScanDesc);
-    const size_t stage_bytes = q_bytes + t_bytes + d_bytes + sizeof(StreamCtrl);
-    if ((rc = pinned_reserve(ctx, &ctx->h_desc, &ctx->h_desc_cap, std::max<size_t>(stage_bytes, 4096))) != ELM_OK) return rc;
-    QueueItem* hq = (QueueItem*)ctx->h_desc;
-    double* hT = (double*)((char*)ctx->h_desc + q_bytes);
-    ScanDesc* hd = (ScanDesc*)((char*)ctx->h_desc + q_bytes + t_bytes);
-    StreamCtrl* hc = (StreamCtrl*)((char*)ctx->h_desc + q_bytes + t_bytes + d_bytes);
-    for (int b = 0; b < count; ++b) { hq[b].pts = scans[b]->d_pts; hq[b].n = scans[b]->n; hq[b].n_total = scans[b]->n_total; }
-    memcpy(hT, T0, t_bytes);
+    SlotQueue q;
+    if ((rc = reserve_slot_queue(ctx, count, S, cap_blocks, &q)) != ELM_OK) return rc;
+    for (int b = 0; b < count; ++b) { q.hq[b].pts = scans[b]->d_pts; q.hq[b].n = scans[b]->n; q.hq[b].n_total = scans[b]->n_total; }
+    memcpy(q.hT, T0, (size_t)count * 16 * sizeof(double));
+    *q.hc = StreamCtrl{/*next*/ 0, /*completed*/ 0, /*total*/ count, /*ready*/ count, /*done_iter*/ -1};
+    // slot descriptors with fixed block ranges sized for the largest scan
     for (int s = 0; s < S; ++s) {
-        hd[s].pts = nullptr; hd[s].n = 0; hd[s].n_total = 0;
-        hd[s].blk_begin = cap_blocks * (uint32_t)s; hd[s].blk_end = cap_blocks * (uint32_t)(s + 1);
+        q.hd[s].pts = nullptr; q.hd[s].n = 0; q.hd[s].n_total = 0;
+        q.hd[s].blk_begin = cap_blocks * (uint32_t)s; q.hd[s].blk_end = cap_blocks * (uint32_t)(s + 1);
     }
-    hc->next = 0; hc->completed = 0; hc->total = count; hc->ready = count; hc->done_iter = -1;
-    if ((rc = dev_reserve(ctx, ctx->d_scans, d_bytes)) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_state, (size_t)S * sizeof(ScanState))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_partials, (size_t)std::max<uint32_t>(blocks, 1) * kSums * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_sums, (size_t)S * (kSums + kAsymRecord) * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_queue, q_bytes + t_bytes + sizeof(StreamCtrl) + (size_t)count * sizeof(ScanState) + 64)) != ELM_OK) return rc;
-    if ((rc = pinned_reserve(ctx, &ctx->h_state, &ctx->h_state_cap, (size_t)count * sizeof(ScanState))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_active, 256)) != ELM_OK) return rc;
-    if (!ctx->h_active) HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_active, 64, hipHostMallocDefault));
-    char* qb = (char*)ctx->d_queue.p;
-    QueueItem* d_q = (QueueItem*)qb;
-    double* d_qT0 = (double*)(qb + q_bytes);
-    StreamCtrl* d_ctrl = (StreamCtrl*)(qb + q_bytes + t_bytes);
-    ScanState* d_out = (ScanState*)(qb + q_bytes + t_bytes + ((sizeof(StreamCtrl) + 63) / 64) * 64);
     elm_iter_trace* d_trace = nullptr;
-    if (trace) {
-        const size_t tb = (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace);
-        if ((rc = dev_reserve(ctx, ctx->d_trace, tb)) != ELM_OK) return rc;
-        if ((rc = pinned_reserve(ctx, &ctx->h_trace, &ctx->h_trace_cap, tb)) != ELM_OK) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_trace.p, 0, tb, ctx->stream));
-        d_trace = (elm_iter_trace*)ctx->d_trace.p;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_q, hq, q_bytes + t_bytes, hipMemcpyHostToDevice, ctx->stream)); // items + guesses are contiguous
-    HIPCHK(ctx, hipMemcpyAsync(d_ctrl, hc, sizeof(StreamCtrl), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_scans.p, hd, d_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (trace && (rc = reserve_trace(ctx, count, &d_trace)) != ELM_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(q.d_q, q.hq, q.ctrl_off + sizeof(StreamCtrl), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_scans.p, q.hd, (size_t)S * sizeof(ScanDesc), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_active.p, 0, 2 * sizeof(int), ctx->stream));
-
-    RegParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.th = cfg->max_search_dist;
-    rp.th2 = cfg->max_search_dist * cfg->max_search_dist;
-    rp.lm_lambda = cfg->lm_lambda;
-    rp.term_thr = cfg->icp_termination_threshold_m;
-    rp.min_overlap = cfg->min_overlap_ratio;
-    rp.max_fitness = cfg->max_fitness_score;
-    rp.method = method;
-    rp.max_iter = cfg->max_iteration;
-    rp.uniform_blocks = cap_blocks; // every slot owns cap_blocks workgroups
-    rp.radar = 0;
-    rp.stats = ctx->work_counters ? 1 : 0;
-    rp.radar_var[0] = rp.radar_var[1] = rp.radar_var[2] = 0.0;
-    if (pc.asym && (rc = reserve_asym(ctx, rp, blocks, S)) != ELM_OK) return rc;
-    rp.rank_check = ((ctx->comm || ctx->hook) && !rp.stats) ? 1 : 0;
-    ctx->rp = rp;
-    const bool use_grid = pc.use_grid, use_cells = pc.use_cells, use_vnbr = pc.use_vnbr;
+    if ((rc = set_reg_params(ctx, cfg, pc, blocks, S, cap_blocks)) != ELM_OK) return rc; // every slot owns cap_blocks workgroups
+    const RegParams& rp = ctx->rp;
 
     ScanState* st = (ScanState*)ctx->d_state.p;
     ScanDesc* dsc = (ScanDesc*)ctx->d_scans.p;
     int* d_active = (int*)ctx->d_active.p;
     const bool distributed = (ctx->comm != nullptr) || (ctx->hook != nullptr);
     (void)hipGetLastError();
-    launch_stream_refill(ctx->stream, dsc, st, S, d_q, d_qT0, d_out, d_ctrl, 1);
+    launch_stream_refill(ctx->stream, dsc, st, S, q.d_q, q.d_qT0, q.d_out, q.d_ctrl, 1);
     ctx->events_used = 0;
     // Iterations needed: unknown in advance (it depends on when each registration converges).  The previous call with the
     // same shape is the prediction: enqueue that many without looking, then read the completed counter after every
@@ -2446,7 +2446,7 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
     double* const sums = (double*)ctx->d_sums.p;
     int it = 0;
     for (; it < hard_limit; ++it) {
-        if ((rc = enqueue_accumulate(ctx, map, dsc, S, blocks, st, rp, use_grid, use_cells, use_vnbr, partials)) != ELM_OK) return rc;
+        if ((rc = enqueue_accumulate(ctx, map, dsc, S, blocks, st, rp, pc, partials)) != ELM_OK) return rc;
         if (distributed) {
             // reduce -> all-reduce -> solve -> refill: four launches + one collective per iteration.  (Side sums of a map with an asymmetric
             // covariance sit right behind the packed sums: one exchange carries both.)  The refill launch walks the slots in slot order and
@@ -2454,32 +2454,30 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
             // on every rank (the finished flags derive from the all-reduced sums), so no slot idles while the queue has work.
             launch_solve(ctx->stream, dsc, S, st, partials, sums, rp, d_trace, 1, d_active);
             if ((rc = exchange(ctx, sums, (size_t)S * (rp.asym ? kSums + kAsymRecord : kSums))) != ELM_OK) return rc;
-            const StreamArgs sv = {dsc, d_q, d_qT0, d_out, d_ctrl, 0, /*save_only*/ 1, 0, it}; // the solve saves + counts, the refill assigns
+            const StreamArgs sv = {dsc, q.d_q, q.d_qT0, q.d_out, q.d_ctrl, 0, /*save_only*/ 1, 0, it}; // the solve saves + counts, the refill assigns
             launch_solve(ctx->stream, dsc, S, st, partials, sums, rp, d_trace, 2, d_active, &sv);
-            launch_stream_refill(ctx->stream, dsc, st, S, d_q, d_qT0, d_out, d_ctrl, 0, /*save*/ 0);
+            launch_stream_refill(ctx->stream, dsc, st, S, q.d_q, q.d_qT0, q.d_out, q.d_ctrl, 0, /*save*/ 0);
         } else {
             // single rank: the solve hands finished slots their next registration itself (no refill launch)
-            const StreamArgs sa = {dsc, d_q, d_qT0, d_out, d_ctrl, 0, 0, 0, it};
+            const StreamArgs sa = {dsc, q.d_q, q.d_qT0, q.d_out, q.d_ctrl, 0, 0, 0, it};
             launch_solve(ctx->stream, dsc, S, st, partials, sums, rp, d_trace, 0, d_active, &sa);
         }
         const int done_iters = it + 1;
         const bool look = predicted > 0 ? done_iters >= predicted : (done_iters >= (count + S - 1) / S && (done_iters % 2) == 0);
         if (look) {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_active, &d_ctrl->completed, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_active, &q.d_ctrl->completed, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             if (*ctx->h_active == count) { ++it; break; }
         }
     }
     if ((rc = prof_mark(ctx)) != ELM_OK) return rc;
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, d_out, (size_t)count * sizeof(ScanState), hipMemcpyDeviceToHost, ctx->stream));
-    if (trace)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace),
-                                   hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_state, q.d_out, (size_t)count * sizeof(ScanState), hipMemcpyDeviceToHost, ctx->stream));
+    if (trace) HIPCHK(ctx, hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, trace_bytes(count), hipMemcpyDeviceToHost, ctx->stream));
     ctx->h_active[2] = 0;
     if (rp.rank_check) HIPCHK(ctx, hipMemcpyAsync(ctx->h_active + 2, d_active + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ctx->h_active[3] = -1;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_active + 3, &d_ctrl->done_iter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_active + 3, &q.d_ctrl->done_iter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = prof_collect(ctx)) != ELM_OK) return rc;
     if (ctx->h_active[2] != 0) {
@@ -2492,9 +2490,7 @@ extern "C" int elm_register_stream(elm_ctx* ctx, const elm_map* map, elm_scan* c
     // whose solve finished the last registration) -- not the count at which the host happened to look, which can only grow: a call
     // with poor initial guesses would leave every later call of the shape enqueueing its iteration count in empty launches
     ctx->stream_hint_iters = (ctx->h_active[3] >= 0) ? std::min(it, ctx->h_active[3] + 1) : it;
-    const ScanState* hs = (const ScanState*)ctx->h_state;
-    for (int b = 0; results && b < count; ++b) state_to_result(hs[b], rp, results[b], ctx->path);
-    if (trace) memcpy(trace, ctx->h_trace, (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace));
+    hand_back(ctx, count, results, trace);
     return ELM_OK;
 }
 
@@ -2572,9 +2568,7 @@ static void sync_all_streams(elm_ctx* ctx) {
 extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const float* const* scan_xyz, const uint32_t* n_pts, int count,
                                         const double* T0, const elm_reg_config* cfg, int slots, elm_reg_result* results, elm_iter_trace* trace) {
     if (!ctx || !map || !scan_xyz || !n_pts || count <= 0 || !T0 || !cfg || slots <= 0) return ELM_ERR_INVALID;
-    if (map->ctx != ctx) return ELM_ERR_INVALID;
-    if (cfg->icp_method < ELM_P2P || cfg->icp_method > ELM_AVGICP) return ELM_ERR_INVALID;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
+    if (!reg_args_ok(ctx, map, cfg)) return ELM_ERR_INVALID;
     if (ctx->comm || ctx->hook) {
         ctx->last_error = "host-fed streams run on one rank (slot assignment follows scan arrival, which differs between ranks)";
         return ELM_ERR_UNSUPPORTED;
@@ -2597,15 +2591,6 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
         if (rc == ELM_OK) rc = elm_register_batch(ctx, map, sc.data(), count, T0, cfg, results, trace);
         for (elm_scan* x : sc) elm_scan_destroy(x);
         return rc;
-    }
-    const int method = cfg->icp_method;
-    if ((method == ELM_VGICP || method == ELM_AVGICP) && !map->info.has_voxel_cov) {
-        ctx->last_error = "VGICP/AVGICP need elm_map_cal_voxel_cov_all() (pcm.cpp:92-95)";
-        return ELM_ERR_INVALID;
-    }
-    if (method == ELM_GICP && !map->info.has_point_cov) {
-        ctx->last_error = "GICP needs elm_map_cal_point_cov_all() (pcm.cpp:97-100)";
-        return ELM_ERR_INVALID;
     }
     if ((rc = ensure_side_streams(ctx)) != ELM_OK) return rc;
     if ((rc = ensure_hilbert(ctx)) != ELM_OK) return rc;
@@ -2633,54 +2618,16 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
         hj[b].n = n_pts[b];
         hj[b]._pad = 0;
     }
-    // queue, guesses, control block, result states (the layout of elm_register_stream)
-    const size_t q_bytes = (size_t)count * sizeof(QueueItem), t_bytes = (size_t)count * 16 * sizeof(double), d_bytes = (size_t)S * sizeof(ScanDesc);
-    const size_t stage_bytes = q_bytes + t_bytes + sizeof(StreamCtrl);
-    if ((rc = pinned_reserve(ctx, &ctx->h_desc, &ctx->h_desc_cap, std::max<size_t>(stage_bytes, 4096))) != ELM_OK) return rc;
-    QueueItem* hq = (QueueItem*)ctx->h_desc;
-    double* hT = (double*)((char*)ctx->h_desc + q_bytes);
-    StreamCtrl* hc = (StreamCtrl*)((char*)ctx->h_desc + q_bytes + t_bytes);
-    for (int b = 0; b < count; ++b) { hq[b].pts = hj[b].dst; hq[b].n = n_pts[b]; hq[b].n_total = n_pts[b]; }
-    memcpy(hT, T0, t_bytes);
-    hc->next = 0; hc->completed = 0; hc->total = count; hc->ready = 0; hc->done_iter = -1;
-    if ((rc = dev_reserve(ctx, ctx->d_scans, d_bytes)) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_state, (size_t)S * sizeof(ScanState))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_partials, (size_t)std::max<uint32_t>(blocks, 1) * kSums * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_sums, (size_t)S * (kSums + kAsymRecord) * sizeof(double))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_queue, q_bytes + t_bytes + sizeof(StreamCtrl) + (size_t)count * sizeof(ScanState) + 64)) != ELM_OK) return rc;
-    if ((rc = pinned_reserve(ctx, &ctx->h_state, &ctx->h_state_cap, (size_t)count * sizeof(ScanState))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_active, 256)) != ELM_OK) return rc;
-    if (!ctx->h_active) HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_active, 64, hipHostMallocDefault));
-    char* qb = (char*)ctx->d_queue.p;
-    QueueItem* d_q = (QueueItem*)qb;
-    double* d_qT0 = (double*)(qb + q_bytes);
-    StreamCtrl* d_ctrl = (StreamCtrl*)(qb + q_bytes + t_bytes);
-    ScanState* d_out = (ScanState*)(qb + q_bytes + t_bytes + ((sizeof(StreamCtrl) + 63) / 64) * 64);
+    // queue, guesses, control block, result states (ready = 0: the registrations arrive while the stream runs)
+    SlotQueue q;
+    if ((rc = reserve_slot_queue(ctx, count, S, cap_blocks, &q)) != ELM_OK) return rc;
+    for (int b = 0; b < count; ++b) { q.hq[b].pts = hj[b].dst; q.hq[b].n = n_pts[b]; q.hq[b].n_total = n_pts[b]; }
+    memcpy(q.hT, T0, (size_t)count * 16 * sizeof(double));
+    *q.hc = StreamCtrl{/*next*/ 0, /*completed*/ 0, /*total*/ count, /*ready*/ 0, /*done_iter*/ -1};
     elm_iter_trace* d_trace = nullptr;
-    if (trace) {
-        const size_t tb = (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace);
-        if ((rc = dev_reserve(ctx, ctx->d_trace, tb)) != ELM_OK) return rc;
-        if ((rc = pinned_reserve(ctx, &ctx->h_trace, &ctx->h_trace_cap, tb)) != ELM_OK) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_trace.p, 0, tb, ctx->stream));
-        d_trace = (elm_iter_trace*)ctx->d_trace.p;
-    }
-    RegParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.th = cfg->max_search_dist;
-    rp.th2 = cfg->max_search_dist * cfg->max_search_dist;
-    rp.lm_lambda = cfg->lm_lambda;
-    rp.term_thr = cfg->icp_termination_threshold_m;
-    rp.min_overlap = cfg->min_overlap_ratio;
-    rp.max_fitness = cfg->max_fitness_score;
-    rp.method = method;
-    rp.max_iter = cfg->max_iteration;
-    rp.uniform_blocks = cap_blocks;
-    rp.radar = 0;
-    rp.stats = ctx->work_counters ? 1 : 0;
-    rp.radar_var[0] = rp.radar_var[1] = rp.radar_var[2] = 0.0;
-    if (pc.asym && (rc = reserve_asym(ctx, rp, blocks, S)) != ELM_OK) return rc;
-    ctx->rp = rp;
-    const bool use_grid = pc.use_grid, use_cells = pc.use_cells, use_vnbr = pc.use_vnbr;
+    if (trace && (rc = reserve_trace(ctx, count, &d_trace)) != ELM_OK) return rc;
+    if ((rc = set_reg_params(ctx, cfg, pc, blocks, S, cap_blocks)) != ELM_OK) return rc; // (no comm / hook here: rank_check stays 0)
+    const RegParams& rp = ctx->rp;
 
 #define HF_CHK(call)                                                                                   \
     do {                                                                                               \
@@ -2691,8 +2638,7 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
             return ELM_ERR_DEVICE;                                                                     \
         }                                                                                              \
     } while (0)
-    HF_CHK(hipMemcpyAsync(d_q, hq, q_bytes + t_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HF_CHK(hipMemcpyAsync(d_ctrl, hc, sizeof(StreamCtrl), hipMemcpyHostToDevice, ctx->stream));
+    HF_CHK(hipMemcpyAsync(q.d_q, q.hq, q.ctrl_off + sizeof(StreamCtrl), hipMemcpyHostToDevice, ctx->stream));
     HF_CHK(hipMemcpyAsync(ctx->d_order_jobs.p, hj, (size_t)count * sizeof(OrderJob), hipMemcpyHostToDevice, ctx->stream));
     HF_CHK(hipMemsetAsync(ctx->d_active.p, 0, 2 * sizeof(int), ctx->stream));
     ScanState* st = (ScanState*)ctx->d_state.p;
@@ -2735,7 +2681,7 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
         if (e == hipSuccess) e = hipStreamWaitEvent(order_stream, ev_copied, 0);
         if (e == hipSuccess) {
             launch_scan_order(order_stream, d_jobs + r0, r1 - r0, ctx->d_hilbert);
-            launch_publish_ready(order_stream, d_ctrl, r1);
+            launch_publish_ready(order_stream, q.d_ctrl, r1);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(ev_ordered, order_stream);
@@ -2743,7 +2689,7 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
     };
     // Iterations are enqueued a few ahead of the device (an event per iteration throttles the host); the number of finished
     // registrations is read on a stream of its own, so that looking never waits for the iterations in flight.
-    const StreamArgs sa = {dsc, d_q, d_qT0, d_out, d_ctrl, 1, 0, 0, 0};
+    const StreamArgs sa = {dsc, q.d_q, q.d_qT0, q.d_out, q.d_ctrl, 1, 0, 0, 0};
     int it = 0, done_seen = 0, idle_turns = 0, g_done = 0;
     const int idle_limit = 4000000; // ~ minutes of polling without a single registration finishing: a lost upload, give up
     const int groups_ahead = 2 * kStageSets; // uploads enqueued but not yet ordered: enough to keep the DMA engine fed; a long backlog
@@ -2753,11 +2699,11 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
         (void)hipGetLastError(); // hipErrorNotReady of the query
         for (int k = 0; k < 2 && g_enq < n_groups && g_enq - g_done < groups_ahead; ++k, ++g_enq) HF_CHK(enqueue_group(g_enq));
         if (it >= 4) HF_CHK(hipEventSynchronize(ctx->ev_iter[it & 3]));
-        if ((rc = enqueue_accumulate(ctx, map, dsc, S, blocks, st, rp, use_grid, use_cells, use_vnbr)) != ELM_OK) { sync_all_streams(ctx); return rc; }
+        if ((rc = enqueue_accumulate(ctx, map, dsc, S, blocks, st, rp, pc)) != ELM_OK) { sync_all_streams(ctx); return rc; }
         launch_solve(ctx->stream, dsc, S, st, (const double*)ctx->d_partials.p, (double*)ctx->d_sums.p, rp, d_trace, 0, d_active, &sa);
         HF_CHK(hipEventRecord(ctx->ev_iter[it & 3], ctx->stream));
         ++it;
-        HF_CHK(hipMemcpyAsync(ctx->h_active, &d_ctrl->completed, sizeof(int), hipMemcpyDeviceToHost, ctx->poll_stream));
+        HF_CHK(hipMemcpyAsync(ctx->h_active, &q.d_ctrl->completed, sizeof(int), hipMemcpyDeviceToHost, ctx->poll_stream));
         HF_CHK(hipStreamSynchronize(ctx->poll_stream));
         const int c = *ctx->h_active;
         if (c >= count) break;
@@ -2771,16 +2717,12 @@ extern "C" int elm_register_stream_host(elm_ctx* ctx, const elm_map* map, const 
     }
     if ((rc = prof_mark(ctx)) != ELM_OK) { sync_all_streams(ctx); return rc; }
     HF_CHK(hipGetLastError());
-    HF_CHK(hipMemcpyAsync(ctx->h_state, d_out, (size_t)count * sizeof(ScanState), hipMemcpyDeviceToHost, ctx->stream));
-    if (trace)
-        HF_CHK(hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace),
-                              hipMemcpyDeviceToHost, ctx->stream));
+    HF_CHK(hipMemcpyAsync(ctx->h_state, q.d_out, (size_t)count * sizeof(ScanState), hipMemcpyDeviceToHost, ctx->stream));
+    if (trace) HF_CHK(hipMemcpyAsync(ctx->h_trace, ctx->d_trace.p, trace_bytes(count), hipMemcpyDeviceToHost, ctx->stream));
     HF_CHK(hipStreamSynchronize(ctx->stream));
 #undef HF_CHK
     if ((rc = prof_collect(ctx)) != ELM_OK) return rc;
-    const ScanState* hs = (const ScanState*)ctx->h_state;
-    for (int b = 0; results && b < count; ++b) state_to_result(hs[b], rp, results[b], ctx->path);
-    if (trace) memcpy(trace, ctx->h_trace, (size_t)count * ELM_MAX_ITER_TRACE * sizeof(elm_iter_trace));
+    hand_back(ctx, count, results, trace);
     return ELM_OK;
 }
 
@@ -2922,6 +2864,18 @@ int map_ground_index(const elm_map* cm, const elm::GroundIndex** gi, double boun
 // ------------------------------------------------------------------------------------------------------
 // deskew
 // ------------------------------------------------------------------------------------------------------
+// the deskew kernel's arguments: the scalars of `tab`, its four tables (time, rot_x, rot_y, rot_z) of `rows` doubles each back to back at d_tab
+static DeskewDev deskew_args(const elm_deskew_tables* tab, const double* d_tab, size_t rows) {
+    DeskewDev d;
+    d.time_scan_cur = tab->d_time_scan_cur;
+    d.time_scan_end = tab->d_time_scan_end;
+    d.imu_pointer_cur = tab->i_imu_pointer_cur;
+    d.odom_available = tab->b_is_odom_available;
+    d.incre_x = tab->f_odom_incre_x; d.incre_y = tab->f_odom_incre_y; d.incre_z = tab->f_odom_incre_z;
+    d._pad = 0.f;
+    d.imu_time = d_tab; d.rot_x = d_tab + rows; d.rot_y = d_tab + 2 * rows; d.rot_z = d_tab + 3 * rows;
+    return d;
+}
 // uploads the raw points + tables and runs the deskew kernel; the undistorted points (3 floats each) stay on the device
 static int deskew_enqueue(elm_ctx* ctx, const float* xyz, const float* rel_time, size_t n, const elm_deskew_tables* tab, float** d_out_p) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2948,16 +2902,8 @@ static int deskew_enqueue(elm_ctx* ctx, const float* xyz, const float* rel_time,
     memcpy(ht + 3 * k, tab->vec_d_imu_rot_z, k * sizeof(double));
     HIPCHK(ctx, hipMemcpyAsync(d_tab, ht, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_time, rel_time, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    DeskewDev d;
-    d.time_scan_cur = tab->d_time_scan_cur;
-    d.time_scan_end = tab->d_time_scan_end;
-    d.imu_pointer_cur = tab->i_imu_pointer_cur;
-    d.odom_available = tab->b_is_odom_available;
-    d.incre_x = tab->f_odom_incre_x; d.incre_y = tab->f_odom_incre_y; d.incre_z = tab->f_odom_incre_z;
-    d._pad = 0.f;
-    d.imu_time = d_tab; d.rot_x = d_tab + k; d.rot_y = d_tab + 2 * k; d.rot_z = d_tab + 3 * k;
     (void)hipGetLastError();
-    launch_deskew(ctx->stream, d_xyz, d_time, (uint32_t)n, d, d_out);
+    launch_deskew(ctx->stream, d_xyz, d_time, (uint32_t)n, deskew_args(tab, d_tab, k), d_out);
     HIPCHK(ctx, hipGetLastError());
     *d_out_p = d_out;
     return ELM_OK;
@@ -2993,24 +2939,24 @@ static int downsample_enqueue(elm_ctx* ctx, const float* d_und, size_t n, double
     const size_t bytes = cap * 12 + std::max<size_t>(n, 1) * 4 + (nb + 1) * 4 + 64;
     if (bytes > ctx->d_ds.cap) ctx->ds_clean_ptr = nullptr; // dev_reserve reallocates: fresh memory (even at the same address) is not "all ones"
     if ((rc = dev_reserve(ctx, ctx->d_ds, bytes)) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_state, sizeof(ScanState) + 64)) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_state, sizeof(ScanState) + sizeof(StateTail))) != ELM_OK) return rc;
     char* base = (char*)ctx->d_ds.p;
     unsigned long long* d_table = (unsigned long long*)base;
     unsigned* d_first = (unsigned*)(base + cap * 8);
     unsigned* d_slot = d_first + cap;
     unsigned* d_bcount = d_slot + std::max<size_t>(n, 1);
-    unsigned* d_total = (unsigned*)((char*)ctx->d_state.p + sizeof(ScanState) + 16); // [0] kept points, [1] overflow flag
+    StateTail* tail = state_tail(ctx->d_state.p, 1);
     elm_scan* sc = nullptr;
     if ((rc = scan_alloc(ctx, n, &sc)) != ELM_OK) return rc;
     hipError_t e = hipSuccess;
     const bool clean = ctx->ds_clean_ptr == ctx->d_ds.p && ctx->ds_clean_cap_log2 == cap_log2;
     ctx->ds_clean_ptr = nullptr; // dirty until this pass has cleaned up after itself
     if (!clean) e = hipMemsetAsync(d_table, 0xFF, cap * 12, ctx->stream); // keys and first indices: all ones
-    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, 8, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(&tail->ds_kept, 0, 8, ctx->stream); // kept points, overflow flag
     if (e == hipSuccess && n) {
         (void)hipGetLastError();
-        launch_voxel_downsample(ctx->stream, d_und, (uint32_t)n, voxel_size, d_table, d_first, cap_log2, d_slot, d_bcount, d_total,
-                                (int*)(d_total + 1), sc->d_pts);
+        launch_voxel_downsample(ctx->stream, d_und, (uint32_t)n, voxel_size, d_table, d_first, cap_log2, d_slot, d_bcount, &tail->ds_kept,
+                                &tail->ds_overflow, sc->d_pts);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -3023,7 +2969,7 @@ static int downsample_enqueue(elm_ctx* ctx, const float* d_und, size_t n, double
     sc->n = (uint32_t)n; // upper bound until the host has read the kept count
     sc->n_total = (uint32_t)n;
     *sc_out = sc;
-    *d_total_out = d_total;
+    *d_total_out = &tail->ds_kept;
     return ELM_OK;
 }
 
@@ -3094,16 +3040,8 @@ int callback_register(elm_ctx* ctx, const elm_map* map, const void* stage, const
     const float* d_und = d_xyz; // run_deskew = 0: the cloud as it is (pcm.cpp:513-525)
     if (tab->b_run_deskew) {
         HIPCHK(ctx, hipMemcpyAsync(d_time, rel_time, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        DeskewDev d;
-        d.time_scan_cur = tab->d_time_scan_cur;
-        d.time_scan_end = tab->d_time_scan_end;
-        d.imu_pointer_cur = tab->i_imu_pointer_cur;
-        d.odom_available = tab->b_is_odom_available;
-        d.incre_x = tab->f_odom_incre_x; d.incre_y = tab->f_odom_incre_y; d.incre_z = tab->f_odom_incre_z;
-        d._pad = 0.f;
-        d.imu_time = d_tab; d.rot_x = d_tab + kCbTableRows; d.rot_y = d_tab + 2 * kCbTableRows; d.rot_z = d_tab + 3 * kCbTableRows;
         (void)hipGetLastError();
-        launch_deskew(ctx->stream, d_xyz, d_time, (uint32_t)n, d, d_out);
+        launch_deskew(ctx->stream, d_xyz, d_time, (uint32_t)n, deskew_args(tab, d_tab, kCbTableRows), d_out);
         HIPCHK(ctx, hipGetLastError());
         d_und = d_out;
     }
@@ -3115,9 +3053,9 @@ int callback_register(elm_ctx* ctx, const elm_map* map, const void* stage, const
     else (void)hipStreamSynchronize(ctx->stream);
     elm_scan_destroy(sc);
     if (rc != ELM_OK) return rc;
-    const unsigned* ht = (const unsigned*)((const char*)ctx->h_state + sizeof(ScanState) + 16);
-    *n_source = ht[0];
-    *unpackable = ht[1] ? 1 : 0;
+    const StateTail* ht = state_tail(ctx->h_state, 1);
+    *n_source = ht->ds_kept;
+    *unpackable = ht->ds_overflow ? 1 : 0;
     return ELM_OK;
 }
 } // namespace elm_host

@@ -496,6 +496,17 @@ def results_from_raw(res):
     return [_result_dict(r) for r in res]
 
 
+def _trace_buffer(B, trace):
+    """The iteration-trace array of B registrations the C ABI fills (None without trace)."""
+    return (IterTrace * (_lib.MAX_ITER_TRACE * B))() if trace else None
+
+
+def _result_dicts(res, tr, B):
+    """Result dicts of B registrations, each with its slice of the trace array tr (or none)."""
+    T = _lib.MAX_ITER_TRACE
+    return [_result_dict(res[b], tr[b * T:(b + 1) * T] if tr is not None else None) for b in range(B)]
+
+
 class Registration:
     """reg.hpp:101-230."""
 
@@ -618,9 +629,9 @@ class Registration:
         B = len(scans)
         arr, T0 = self.pack_inputs(scans, initial_guesses)
         res = (RegResult * B)()
-        tr = (IterTrace * (_lib.MAX_ITER_TRACE * B))() if trace else None
+        tr = _trace_buffer(B, trace)
         check(_lib.lib().elm_register_batch(self.ctx._h, voxel_map._handle(), arr, B, _dp(T0), C.byref(cfg), res, tr), self.ctx._h, "elm_register_batch")
-        return [_result_dict(res[b], tr[b * _lib.MAX_ITER_TRACE:(b + 1) * _lib.MAX_ITER_TRACE] if trace else None) for b in range(B)]
+        return _result_dicts(res, tr, B)
 
     @staticmethod
     def pack_inputs(scans, initial_guesses):
@@ -638,12 +649,12 @@ class Registration:
             arr, T0 = self.pack_inputs(scans, initial_guesses)
         B = len(arr)
         res = (RegResult * B)()
-        tr = (IterTrace * (_lib.MAX_ITER_TRACE * B))() if trace else None
+        tr = _trace_buffer(B, trace)
         check(_lib.lib().elm_register_stream(self.ctx._h, voxel_map._handle(), arr, B, _dp(T0), C.byref(cfg), int(slots), res, tr),
               self.ctx._h, "elm_register_stream")
         if raw:  # the elm_reg_result array as the library filled it; results_from_raw() turns it into dicts later
             return res
-        return [_result_dict(res[b], tr[b * _lib.MAX_ITER_TRACE:(b + 1) * _lib.MAX_ITER_TRACE] if trace else None) for b in range(B)]
+        return _result_dicts(res, tr, B)
 
     @staticmethod
     def pack_host_inputs(scans_host, initial_guesses, pinned=None):
@@ -674,18 +685,17 @@ class Registration:
         arr, npts, T0, _keep = packed
         B = len(arr)
         res = (RegResult * B)()
-        tr = (IterTrace * (_lib.MAX_ITER_TRACE * B))() if trace else None
+        tr = _trace_buffer(B, trace)
         check(_lib.lib().elm_register_stream_host(self.ctx._h, voxel_map._handle(), arr, npts, B, _dp(T0), C.byref(cfg), int(slots), res, tr),
               self.ctx._h, "elm_register_stream_host")
         if raw:
             return res
-        return [_result_dict(res[b], tr[b * _lib.MAX_ITER_TRACE:(b + 1) * _lib.MAX_ITER_TRACE] if trace else None) for b in range(B)]
+        return _result_dicts(res, tr, B)
 
     def EnqueueBatch(self, scans, voxel_map, initial_guesses, m_config=None, trace=False):
         cfg = m_config if m_config is not None else self.config_
         B = len(scans)
-        arr = (C.c_void_p * B)(*[s._h for s in scans])
-        T0 = np.concatenate([_colmajor16(T) for T in initial_guesses])
+        arr, T0 = self.pack_inputs(scans, initial_guesses)
         self._pending = (B, trace)
         check(_lib.lib().elm_register_batch_enqueue(self.ctx._h, voxel_map._handle(), arr, B, _dp(T0),
                                                     C.byref(cfg), int(bool(trace))), self.ctx._h,
@@ -694,13 +704,9 @@ class Registration:
     def FinishBatch(self):
         B, trace = self._pending
         res = (RegResult * B)()
-        tr = (IterTrace * (_lib.MAX_ITER_TRACE * B))() if trace else None
+        tr = _trace_buffer(B, trace)
         check(_lib.lib().elm_register_batch_finish(self.ctx._h, res, tr), self.ctx._h, "elm_register_batch_finish")
-        out = []
-        for b in range(B):
-            t = tr[b * _lib.MAX_ITER_TRACE:(b + 1) * _lib.MAX_ITER_TRACE] if trace else None
-            out.append(_result_dict(res[b], t))
-        return out
+        return _result_dicts(res, tr, B)
 
     @staticmethod
     def TransformPoints(T, points):  # reg.hpp:126-148 (host-side convenience, float64)
