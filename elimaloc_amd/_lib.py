@@ -152,6 +152,19 @@ class GlobalRelocStats(C.Structure):
                 ("ms_ground", C.c_double), ("ms_search", C.c_double), ("ms_refine", C.c_double)]
 
 
+class FreeSpaceConfigC(C.Structure):
+    """elm_freespace_config (include/elimaloc_hip.h, free-space check)."""
+    _fields_ = [("sub", C.c_int32), ("min_hits", C.c_int32), ("max_samples", C.c_int32), ("_pad", C.c_int32), ("step_m", C.c_double),
+                ("start_m", C.c_double), ("min_range_m", C.c_double), ("max_range_m", C.c_double), ("end_margin_m", C.c_double),
+                ("end_margin_frac", C.c_double), ("origin", C.c_double * 3)]
+
+
+class FreeSpaceStatsC(C.Structure):
+    """elm_freespace_stats: the counts of one pose."""
+    _fields_ = [("n_counted", C.c_uint32), ("n_pierced", C.c_uint32), ("n_end_occupied", C.c_uint32), ("n_supported", C.c_uint32),
+                ("n_samples", C.c_uint64), ("n_hit_samples", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -171,6 +184,7 @@ EXPORTS = [
     "elm_free", "elm_scan_from_cloud", "elm_pcm_callback_point_cloud",
     "elm_reloc_config_default", "elm_reloc_make_hypotheses", "elm_map_score_poses", "elm_relocalize",
     "elm_reloc_global_config_default", "elm_map_ground_heights", "elm_reloc_global_hypotheses", "elm_relocalize_global",
+    "elm_freespace_config_default", "elm_map_fine_cells", "elm_map_check_free_space",
 ]
 
 
@@ -339,6 +353,11 @@ def lib():
     L.elm_map_score_poses.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RelocConfigC), C.POINTER(C.c_uint32)]
     L.elm_relocalize.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(RelocConfigC), C.POINTER(RegConfig), dp, C.POINTER(RegResult),
                                  C.POINTER(RelocCandidate), C.c_int, ip]
+    L.elm_freespace_config_default.argtypes = [C.POINTER(FreeSpaceConfigC)]
+    L.elm_freespace_config_default.restype = None
+    L.elm_map_fine_cells.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_map_check_free_space.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(FreeSpaceConfigC), C.POINTER(FreeSpaceStatsC),
+                                           C.POINTER(C.c_uint16)]
     L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
     L.elm_reloc_global_config_default.restype = None
     L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]

@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -439,6 +440,12 @@ struct elm_map {
     elm::GroundIndex gidx{};
     double pt_bounds[4] = {0.0, 0.0, 0.0, 0.0};
     bool has_gidx = false;
+    // the fine-occupancy tables of the free-space check (elm_map_check_free_space; built at the first call per sub = 1, 2, 4)
+    int4* d_fine_keys[3] = {nullptr, nullptr, nullptr};
+    unsigned long long* d_fine_masks[3] = {nullptr, nullptr, nullptr};
+    elm::FineTable fine[3]{};
+    double fine_info[3][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}; // build ms, device bytes
+    bool has_fine[3] = {false, false, false};
 };
 
 namespace {
@@ -591,7 +598,8 @@ static void map_free(elm_map* m) {
     m->replicas.clear();
     if (ctx_alive(m->ctx, m->ctx_id)) (void)hipSetDevice(m->ctx->device); // a context destroyed first: just release the device memory
     void* ptrs[] = {m->d_grid_tiles, m->d_vox_nk, m->d_bad, m->d_grid_gicp8, m->d_slots, m->d_pts, m->d_ranges, m->d_keys, m->d_vox_mean, m->d_vox_cov, m->d_vox_cinv, m->d_pt_gicp, m->d_pt_cov, m->d_qslots, m->d_nbr_pts, m->d_nbr_idx, m->d_nbr_cell_off, m->d_vqslots, m->d_vq_dense, m->d_vqf_dense, m->d_vface, m->d_vox_rec, m->d_vnbr_blk,
-                    m->d_grid_blk, m->d_grid_idx, m->d_grid_start, m->d_vox_stat, m->d_grid_gicp, m->d_gpts, m->d_gstart};
+                    m->d_grid_blk, m->d_grid_idx, m->d_grid_start, m->d_vox_stat, m->d_grid_gicp, m->d_gpts, m->d_gstart,
+                    m->d_fine_keys[0], m->d_fine_keys[1], m->d_fine_keys[2], m->d_fine_masks[0], m->d_fine_masks[1], m->d_fine_masks[2]};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -2859,6 +2867,105 @@ int map_ground_index(const elm_map* cm, const elm::GroundIndex** gi, double boun
     memcpy(bounds, m->pt_bounds, sizeof(m->pt_bounds));
     return ELM_OK;
 }
+// the fine cell of every stored point for cell = voxel_size / sub: (int)floor((double)coordinate / cell)
+static int fine_cells_of_points(const elm_map* m, int sub, std::vector<int32_t>& f) {
+    elm_ctx* ctx = m->ctx;
+    const size_t n = m->dm.n_pts;
+    std::vector<float4> pts(n);
+    if (n) HIPCHK(ctx, hipMemcpy(pts.data(), m->d_pts, n * sizeof(float4), hipMemcpyDeviceToHost));
+    const double cell = m->dm.voxel_size / (double)sub;
+    f.resize(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+        f[3 * i] = (int32_t)floor((double)pts[i].x / cell);
+        f[3 * i + 1] = (int32_t)floor((double)pts[i].y / cell);
+        f[3 * i + 2] = (int32_t)floor((double)pts[i].z / cell);
+    }
+    return ELM_OK;
+}
+int map_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3) {
+    std::vector<int32_t> f;
+    int rc = fine_cells_of_points(m, sub, f);
+    if (rc != ELM_OK) return rc;
+    const size_t n = f.size() / 3;
+    std::vector<std::array<int32_t, 3>> c(n);
+    for (size_t i = 0; i < n; ++i) c[i] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]};
+    std::sort(c.begin(), c.end());
+    c.erase(std::unique(c.begin(), c.end()), c.end());
+    cells3.resize(3 * c.size());
+    for (size_t i = 0; i < c.size(); ++i) memcpy(&cells3[3 * i], c[i].data(), 3 * sizeof(int32_t));
+    return ELM_OK;
+}
+int map_fine_table(const elm_map* cm, int sub, const elm::FineTable** ft, double info[2]) {
+    elm_map* m = const_cast<elm_map*>(cm); // the table is a cache of the (immutable) map
+    elm_ctx* ctx = m->ctx;
+    const int s = sub == 1 ? 0 : (sub == 2 ? 1 : 2);
+    if (!m->has_fine[s]) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<int32_t> f;
+        int rc = fine_cells_of_points(m, sub, f);
+        if (rc != ELM_OK) return rc;
+        const size_t n = f.size() / 3;
+        // open addressing over the coarse cells (f >> 2, arithmetic), grown so that the load factor stays <= 0.5
+        uint32_t cap = 1024, used = 0;
+        std::vector<int4> keys(cap, int4{0, 0, 0, 0});
+        std::vector<unsigned long long> masks(cap, 0ull);
+        auto insert = [&](std::vector<int4>& K, std::vector<unsigned long long>& M, uint32_t c, int cx, int cy, int cz, unsigned long long bits) {
+            uint32_t h = hash3(cx, cy, cz) & (c - 1);
+            for (;; h = (h + 1) & (c - 1)) {
+                if (K[h].w == 0) {
+                    K[h] = int4{cx, cy, cz, 1};
+                    M[h] = bits;
+                    return true;
+                }
+                if (K[h].x == cx && K[h].y == cy && K[h].z == cz) {
+                    M[h] |= bits;
+                    return false;
+                }
+            }
+        };
+        for (size_t i = 0; i < n; ++i) {
+            const int fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
+            const unsigned long long bit = 1ull << ((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3));
+            if (insert(keys, masks, cap, fx >> 2, fy >> 2, fz >> 2, bit) && 2 * (uint64_t)++used > cap) {
+                if (cap >= 0x40000000u) {
+                    ctx->last_error = "fine occupancy table: too many cells";
+                    return ELM_ERR_UNSUPPORTED;
+                }
+                const uint32_t cap2 = cap * 2;
+                std::vector<int4> k2(cap2, int4{0, 0, 0, 0});
+                std::vector<unsigned long long> m2(cap2, 0ull);
+                for (uint32_t h = 0; h < cap; ++h)
+                    if (keys[h].w) insert(k2, m2, cap2, keys[h].x, keys[h].y, keys[h].z, masks[h]);
+                keys.swap(k2);
+                masks.swap(m2);
+                cap = cap2;
+            }
+        }
+        HIPCHK(ctx, hipMalloc((void**)&m->d_fine_keys[s], (size_t)cap * sizeof(int4)));
+        HIPCHK(ctx, hipMalloc((void**)&m->d_fine_masks[s], (size_t)cap * sizeof(unsigned long long)));
+        HIPCHK(ctx, hipMemcpy(m->d_fine_keys[s], keys.data(), (size_t)cap * sizeof(int4), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(m->d_fine_masks[s], masks.data(), (size_t)cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        elm::FineTable& t = m->fine[s];
+        t.keys = m->d_fine_keys[s];
+        t.masks = m->d_fine_masks[s];
+        t.mask = cap - 1;
+        t.n_coarse = used;
+        t.cell = m->dm.voxel_size / (double)sub;
+        int e = 0;
+        t.inv_cell_exact = frexp(t.cell, &e) == 0.5 ? 1.0 / t.cell : 0.0; // a power of two: q * (1 / cell) is q / cell bit for bit
+        m->fine_info[s][0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        m->fine_info[s][1] = (double)cap * (sizeof(int4) + sizeof(unsigned long long));
+        m->has_fine[s] = true;
+    }
+    *ft = &m->fine[s];
+    if (info) memcpy(info, m->fine_info[s], sizeof(m->fine_info[s]));
+    return ELM_OK;
+}
+const float* scan_dev_points(const elm_scan* s, size_t* n) {
+    *n = s->n;
+    return (const float*)s->d_pts;
+}
+int free_space_form() { return check_mode("free_wave") ? 1 : 0; }
 } // namespace elm_host
 
 // ------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 
 #include "../../include/elimaloc_hip.h"
 
-namespace elm { struct DevMap; struct GroundIndex; }
+namespace elm { struct DevMap; struct GroundIndex; struct FineTable; }
 struct elm_group; // a lead context's group of per-device contexts inside one process (elm_multi.cpp)
 
 namespace elm_host {
@@ -36,6 +36,14 @@ const elm::DevMap& map_dev(const elm_map* m);
 const std::vector<int32_t>& map_host_keys(const elm_map* m); // [n_vox][3] stored keys
 // the map's ground-field bin index (built at the first call, kept with the map) and the xy bounds of its stored points {x_lo, x_hi, y_lo, y_hi}
 int map_ground_index(const elm_map* m, const elm::GroundIndex** gi, double bounds[4]);
+// ... for elm_free.cpp
+// the map's fine-occupancy table for sub in {1, 2, 4} (built at the first call per sub, kept with the map); info, when given: the host
+// milliseconds and device bytes of that build
+int map_fine_table(const elm_map* m, int sub, const elm::FineTable** ft, double info[2]);
+// the stored points' fine cells for sub, sorted ascending by (x, y, z), duplicates removed
+int map_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
+const float* scan_dev_points(const elm_scan* s, size_t* n); // the resident points of a plain (unsharded) scan, packed xyz
+int free_space_form(); // 0: one ray per lane; 1: ELM_CHECK=free_wave, a wave per ray (the A/B of DESIGN.md section 13)
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

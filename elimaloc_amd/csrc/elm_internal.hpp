@@ -347,6 +347,27 @@ void launch_reloc_bound(hipStream_t s, const DevMap& m, const float* pts, uint32
 void launch_reloc_leaf_rows(hipStream_t s, const uint32_t* hyps, uint32_t n, const double* rot, double x_min, double y_min, double step,
                             uint32_t NX, uint32_t NY, const double* gz, double* rows);
 
+// free-space check (elm_k_free.hip): the fine occupancy of a map as an open-addressing table of coarse cells
+// (fine cell >> 2 per axis, arithmetic), each with the 64-bit mask of its 4 x 4 x 4 fine cells, bit ((f_x & 3) * 4 + (f_y & 3)) * 4 + (f_z & 3)
+struct FineTable {
+    const int4* keys;                // [mask + 1] coarse cell in x, y, z; w = 1 used, 0 empty (load factor <= 0.5: a probe always ends)
+    const unsigned long long* masks; // [mask + 1]
+    uint32_t mask;
+    uint32_t n_coarse;
+    double cell, inv_cell_exact; // voxel_size / sub; 1 / cell where cell is a power of two (q * inv gives q / cell's bits), else 0
+};
+struct FreeParams { // elm_freespace_config resolved for one map
+    double ox, oy, oz, step, min_r2, max_r2, margin_m, margin_frac;
+    int32_t k0, max_samples, min_hits, _pad;
+};
+constexpr int kFreePoses = 16;  // poses per workgroup of k_free_rays
+constexpr int kFreeWords = 6;   // a partial: counted, pierced, end-occupied, supported, samples, hit samples of one (pose, chunk)
+// form 0: one ray per lane, the last coarse cell's mask kept in registers; form 1: a wave walks its 64 rays one after the other, its lanes
+// taking consecutive samples (the A/B of DESIGN.md section 13).  rows: 12 doubles per pose (R_r0, R_r1, R_r2, t_r); partial:
+// [n_poses][chunks][kFreeWords] scratch; hits: [n_poses][n] or nullptr
+void launch_free_space(hipStream_t s, int form, const FineTable& ft, const FreeParams& fp, const float* pts, uint32_t n, const double* rows,
+                       uint32_t n_poses, uint32_t* partial, elm_freespace_stats* stats, uint16_t* hits);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

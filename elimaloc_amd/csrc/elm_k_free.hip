@@ -1,0 +1,211 @@
+// elm_k_free.hip -- free-space check: the rays of one scan tested against the fine occupancy of the map at many poses
+// (elm_map_check_free_space).  Every result is an integer count, so the answer is the same on every run.
+//   K6a k_free_rays   (ray chunk x pose block) partials: per pose the counted / pierced / end-occupied / supported rays and the samples /
+//                     occupied samples of the chunk, and (optionally) every ray's occupied samples
+//   K6b k_free_sum    per pose, the chunk partials summed in chunk order
+#include <hip/hip_runtime.h>
+
+#include "elm_internal.hpp"
+
+namespace elm {
+
+namespace {
+
+// The contract's fine cell of one world coordinate: (int)floor(q / cell), or q * (1 / cell) where that product is exact.
+__device__ __forceinline__ int fine_of(double q, const FineTable& ft) {
+    return (int)floor(ft.inv_cell_exact != 0.0 ? q * ft.inv_cell_exact : q / ft.cell);
+}
+
+// The 64-bit mask of coarse cell (cx, cy, cz); 0 when the map has no point there.
+__device__ __forceinline__ unsigned long long fine_probe(const FineTable& ft, int cx, int cy, int cz) {
+    uint32_t h = hash3(cx, cy, cz) & ft.mask;
+    for (;;) {
+        const int4 k = ft.keys[h];
+        if (k.w == 0) return 0ull;
+        if (k.x == cx && k.y == cy && k.z == cz) return ft.masks[h];
+        h = (h + 1) & ft.mask;
+    }
+}
+
+__device__ __forceinline__ uint32_t fine_bit(int fx, int fy, int fz) { return (uint32_t)((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3)); }
+
+// The local indices 0 .. 3 of coarse cell c (one axis) whose fine cell lies in [f - 1, f + 1], as 4 bits.
+__device__ __forceinline__ uint32_t near_bits(int f, int c) {
+    uint32_t b = 0;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const int d = (c << 2) + l - f;
+        b |= (d >= -1 && d <= 1) ? (1u << l) : 0u;
+    }
+    return b;
+}
+
+// Whether fine cell (fx, fy, fz) or one of its 26 neighbours is occupied: the (up to 2 x 2 x 2) coarse cells they lie in.
+__device__ __forceinline__ bool fine_supported(const FineTable& ft, int fx, int fy, int fz) {
+    for (int cx = (fx - 1) >> 2; cx <= (fx + 1) >> 2; ++cx)
+        for (int cy = (fy - 1) >> 2; cy <= (fy + 1) >> 2; ++cy)
+            for (int cz = (fz - 1) >> 2; cz <= (fz + 1) >> 2; ++cz) {
+                const unsigned long long m = fine_probe(ft, cx, cy, cz);
+                if (!m) continue;
+                const uint32_t xb = near_bits(fx, cx), yb = near_bits(fy, cy), zb = near_bits(fz, cz);
+                uint32_t yz = 0;
+#pragma unroll
+                for (int l = 0; l < 4; ++l) yz |= ((yb >> l) & 1u) ? (zb << (4 * l)) : 0u;
+                unsigned long long nb = 0;
+#pragma unroll
+                for (int l = 0; l < 4; ++l) nb |= ((xb >> l) & 1u) ? ((unsigned long long)yz << (16 * l)) : 0ull;
+                if (m & nb) return true;
+            }
+    return false;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// One sample of a ray: a = o + u (k step), q = R a + t in the contract's association, whether q's fine cell is occupied.  (lcx, lcy, lcz,
+// lmask, have) keep the last coarse cell probed: consecutive samples mostly share it (8 per cell along an axis at the defaults).
+struct PoseRows {
+    double r00, r01, r02, t0, r10, r11, r12, t1, r20, r21, r22, t2;
+};
+__device__ __forceinline__ bool sample_hit(const FineTable& ft, const FreeParams& fp, const PoseRows& P, double ux, double uy, double uz, int k, int& lcx,
+                                           int& lcy, int& lcz, unsigned long long& lmask, bool& have) {
+    const double s = (double)k * fp.step;
+    const double ax = fp.ox + ux * s, ay = fp.oy + uy * s, az = fp.oz + uz * s;
+    const int fx = fine_of(((P.r00 * ax + P.r01 * ay) + P.r02 * az) + P.t0, ft);
+    const int fy = fine_of(((P.r10 * ax + P.r11 * ay) + P.r12 * az) + P.t1, ft);
+    const int fz = fine_of(((P.r20 * ax + P.r21 * ay) + P.r22 * az) + P.t2, ft);
+    const int cx = fx >> 2, cy = fy >> 2, cz = fz >> 2;
+    if (!have || cx != lcx || cy != lcy || cz != lcz) {
+        lmask = fine_probe(ft, cx, cy, cz);
+        lcx = cx; lcy = cy; lcz = cz;
+        have = true;
+    }
+    return (lmask >> fine_bit(fx, fy, fz)) & 1ull;
+}
+
+} // namespace
+
+// K6a.  Workgroup = 256 consecutive rays (one per lane, float64 in registers) x kFreePoses consecutive poses, whose rows are
+// workgroup-uniform.  The ray's length, direction and sample count do not depend on the pose: they are formed once.
+//   FORM 0: a lane walks its own ray; the last coarse cell's mask stays in registers, a probe only when the cell changes.
+//   FORM 1: a wave walks its 64 rays one after the other, lane l taking samples k0 + l, k0 + l + 64, ...: no lane waits for a longer ray,
+//           but neighbouring samples sit in different lanes, so nearly every sample is a probe.
+// Per pose each wave counts with ballot + popcount (and one shuffle sum for the occupied samples); the four waves meet in LDS and one lane
+// per pose stores the workgroup's partial.
+template <int FORM>
+__global__ __launch_bounds__(256) void k_free_rays(const FineTable ft, const FreeParams fp, const float* __restrict__ pts, uint32_t n,
+                                                   const double* __restrict__ rows, uint32_t n_poses, uint32_t n_chunks, uint32_t* __restrict__ partial,
+                                                   uint16_t* __restrict__ hits_out) {
+    __shared__ uint32_t wcnt[kFreePoses][4][4]; // per pose and wave: pierced, end-occupied, supported, occupied samples
+    __shared__ uint32_t wray[4][2];             // per wave: counted rays, samples (the same for every pose)
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t chunk = blockIdx.x % n_chunks, h0 = (blockIdx.x / n_chunks) * kFreePoses;
+    const uint32_t i = chunk * 256u + tid;
+    const bool valid = i < n;
+    const uint32_t j = valid ? i : 0u;
+    const double px = (double)pts[3 * (size_t)j], py = (double)pts[3 * (size_t)j + 1], pz = (double)pts[3 * (size_t)j + 2];
+    const double dx = px - fp.ox, dy = py - fp.oy, dz = pz - fp.oz;
+    const double L2 = (dx * dx + dy * dy) + dz * dz;
+    const bool counted = valid && L2 >= fp.min_r2 && L2 <= fp.max_r2 && L2 > 0.0;
+    const double L = sqrt(L2);
+    const double reach = L - fmax(fp.margin_m, fp.margin_frac * L);
+    int K = 0;
+    if (counted && reach > 0.0) K = (int)fmin(floor(reach / fp.step), (double)fp.max_samples);
+    const double ux = dx / L, uy = dy / L, uz = dz / L;
+    const uint32_t n_s = K >= fp.k0 ? (uint32_t)(K - fp.k0 + 1) : 0u;
+    {
+        const uint32_t c = (uint32_t)__popcll(__ballot(counted)), s = wave_sum(n_s);
+        if (lane == 0) {
+            wray[wave][0] = c;
+            wray[wave][1] = s;
+        }
+    }
+    const uint32_t hn = min((uint32_t)kFreePoses, n_poses - h0);
+    for (uint32_t hl = 0; hl < hn; ++hl) {
+        const double* R = rows + (size_t)(h0 + hl) * 12;
+        const PoseRows P{R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], R[9], R[10], R[11]};
+        uint32_t hits = 0;
+        int lcx = 0, lcy = 0, lcz = 0;
+        unsigned long long lmask = 0;
+        bool have = false;
+        if (FORM == 0) {
+            for (int k = fp.k0; k <= K; ++k) hits += sample_hit(ft, fp, P, ux, uy, uz, k, lcx, lcy, lcz, lmask, have) ? 1u : 0u;
+        } else {
+            for (int r = 0; r < 64; ++r) {
+                const int Kr = __shfl(K, r);
+                if (Kr < fp.k0) continue; // wave-uniform
+                const double rx = __shfl(ux, r), ry = __shfl(uy, r), rz = __shfl(uz, r);
+                uint32_t c = 0;
+                for (int kb = fp.k0; kb <= Kr; kb += 64) {
+                    const int k = kb + (int)lane;
+                    const bool hit = k <= Kr && sample_hit(ft, fp, P, rx, ry, rz, k, lcx, lcy, lcz, lmask, have);
+                    c += (uint32_t)__popcll(__ballot(hit));
+                }
+                if ((int)lane == r) hits = c;
+            }
+        }
+        bool end_occ = false, sup = false;
+        if (counted) {
+            const int fx = fine_of(((P.r00 * px + P.r01 * py) + P.r02 * pz) + P.t0, ft);
+            const int fy = fine_of(((P.r10 * px + P.r11 * py) + P.r12 * pz) + P.t1, ft);
+            const int fz = fine_of(((P.r20 * px + P.r21 * py) + P.r22 * pz) + P.t2, ft);
+            end_occ = (fine_probe(ft, fx >> 2, fy >> 2, fz >> 2) >> fine_bit(fx, fy, fz)) & 1ull;
+            sup = end_occ || fine_supported(ft, fx, fy, fz);
+        }
+        if (hits_out && valid) hits_out[(size_t)(h0 + hl) * n + i] = (uint16_t)min(hits, 65535u);
+        const uint32_t c_p = (uint32_t)__popcll(__ballot(hits >= (uint32_t)fp.min_hits));
+        const uint32_t c_e = (uint32_t)__popcll(__ballot(end_occ)), c_s = (uint32_t)__popcll(__ballot(sup));
+        const uint32_t c_h = wave_sum(hits);
+        if (lane == 0) {
+            wcnt[hl][wave][0] = c_p;
+            wcnt[hl][wave][1] = c_e;
+            wcnt[hl][wave][2] = c_s;
+            wcnt[hl][wave][3] = c_h;
+        }
+    }
+    __syncthreads();
+    if (tid < hn) {
+        uint32_t* out = partial + ((size_t)(h0 + tid) * n_chunks + chunk) * kFreeWords;
+        out[0] = ((wray[0][0] + wray[1][0]) + wray[2][0]) + wray[3][0];
+        out[4] = ((wray[0][1] + wray[1][1]) + wray[2][1]) + wray[3][1];
+        out[1] = ((wcnt[tid][0][0] + wcnt[tid][1][0]) + wcnt[tid][2][0]) + wcnt[tid][3][0];
+        out[2] = ((wcnt[tid][0][1] + wcnt[tid][1][1]) + wcnt[tid][2][1]) + wcnt[tid][3][1];
+        out[3] = ((wcnt[tid][0][2] + wcnt[tid][1][2]) + wcnt[tid][2][2]) + wcnt[tid][3][2];
+        out[5] = ((wcnt[tid][0][3] + wcnt[tid][1][3]) + wcnt[tid][2][3]) + wcnt[tid][3][3];
+    }
+}
+
+// K6b: stats[h] = the chunk partials of pose h, summed in chunk order
+__global__ __launch_bounds__(256) void k_free_sum(const uint32_t* __restrict__ partial, uint32_t n_chunks, uint32_t n_poses,
+                                                  elm_freespace_stats* __restrict__ stats) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= n_poses) return;
+    uint32_t a[4] = {0, 0, 0, 0};
+    uint64_t s = 0, hs = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        const uint32_t* p = partial + ((size_t)h * n_chunks + c) * kFreeWords;
+        a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3];
+        s += p[4];
+        hs += p[5];
+    }
+    elm_freespace_stats o;
+    o.n_counted = a[0]; o.n_pierced = a[1]; o.n_end_occupied = a[2]; o.n_supported = a[3];
+    o.n_samples = s;
+    o.n_hit_samples = hs;
+    stats[h] = o;
+}
+
+void launch_free_space(hipStream_t s, int form, const FineTable& ft, const FreeParams& fp, const float* pts, uint32_t n, const double* rows,
+                       uint32_t n_poses, uint32_t* partial, elm_freespace_stats* stats, uint16_t* hits) {
+    if (!n || !n_poses) return;
+    const uint32_t n_chunks = (n + 255u) / 256u;
+    const uint32_t n_blk = (n_poses + kFreePoses - 1) / kFreePoses;
+    if (form == 0) hipLaunchKernelGGL(k_free_rays<0>, dim3(n_chunks * n_blk), dim3(256), 0, s, ft, fp, pts, n, rows, n_poses, n_chunks, partial, hits);
+    else hipLaunchKernelGGL(k_free_rays<1>, dim3(n_chunks * n_blk), dim3(256), 0, s, ft, fp, pts, n, rows, n_poses, n_chunks, partial, hits);
+    hipLaunchKernelGGL(k_free_sum, dim3((n_poses + 255) / 256), dim3(256), 0, s, partial, n_chunks, n_poses, stats);
+}
+
+} // namespace elm

@@ -111,9 +111,10 @@ class PcmMatching:
         elif m == IcpMethod.GICP:
             self.local_map_.CalPointCovAll(self.cfg_.registration.gicp_cov_search_dist)
 
-    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom):
+    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None):
         """pcm.cpp:198-324.  Returns None when the reference would publish nothing (deskew / pose sync / ICP failure),
-        else dict(pose_ego 4x4 float64, covariance 6x6 row-major, fitness, time)."""
+        else dict(pose_ego 4x4 float64, covariance 6x6 row-major, fitness, time).  free_space: a FreeSpaceConfig -- the result also
+        carries "free_space", the free-space statistics of the registered pose (VoxelHashMap.CheckFreeSpace); nothing else changes."""
         import time
         tm = self.timings_ = {}
         t0 = time.perf_counter()
@@ -150,6 +151,9 @@ class PcmMatching:
         out = dict(pose_ego=icp_ego_pose, pose_lidar=pose, fitness=fit, time=self.d_time_scan_end_,
                    covariance=shape_odom_covariance(cov, icp_ego_pose, fit), n_source=src.shape[0])
         lap("publish_ms")
+        if free_space is not None:
+            out["free_space"] = self.local_map_.CheckFreeSpace(src, pose[None], free_space)[0]
+            lap("free_space_ms")
         return out
 
     def _node_config(self):

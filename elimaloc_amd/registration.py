@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+from ._lib import (ElmError, FreeSpaceConfigC, FreeSpaceStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
                    check)
 
 
@@ -56,6 +56,31 @@ def GlobalRelocConfig(**kw):
             raise AttributeError(f"GlobalRelocConfig has no field {k}")
         setattr(cfg, k, int(v) if k in ("max_score_points", "top_k", "pool_min", "max_kz_span", "bitmap_max_bytes") else float(v))
     return cfg
+
+
+def FreeSpaceConfig(**kw):
+    """elm_freespace_config with its defaults (sub 4, step_m 0 = cell / 2 of the map, start 1 m, range 2 .. 50 m, end margins 1 m / 0.2 L,
+    min_hits 2, max_samples 1024, origin 0)."""
+    cfg = FreeSpaceConfigC()
+    _lib.lib().elm_freespace_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"FreeSpaceConfig has no field {k}")
+        if k == "origin":
+            cfg.origin = (C.c_double * 3)(*[float(x) for x in v])
+        else:
+            setattr(cfg, k, int(v) if k in ("sub", "min_hits", "max_samples") else float(v))
+    return cfg
+
+
+_FREE_FIELDS = ("n_counted", "n_pierced", "n_end_occupied", "n_supported", "n_samples", "n_hit_samples")
+
+
+def FreeSpaceStats(st):
+    """elm_freespace_stats of one pose as a dict (+ pierced_share = n_pierced / n_counted, 0 without counted rays)."""
+    d = {k: int(getattr(st, k)) for k in _FREE_FIELDS}
+    d["pierced_share"] = d["n_pierced"] / d["n_counted"] if d["n_counted"] else 0.0
+    return d
 
 
 def _global_stats_dict(st):
@@ -377,6 +402,42 @@ class VoxelHashMap:
                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx._h, "elm_map_score_poses")
         return out[:n]
 
+    def FineCells(self, sub=4):
+        """The occupied fine cells (elm_map_fine_cells): floor(stored point / (voxel_size / sub)) -> int32 [n, 3], ascending (x, y, z)."""
+        n = C.c_size_t(0)
+        L = _lib.lib()
+        check(L.elm_map_fine_cells(self.ctx._h, self._handle(), int(sub), None, 0, C.byref(n)), self.ctx._h, "elm_map_fine_cells")
+        out = np.zeros((max(n.value, 1), 3), np.int32)
+        check(L.elm_map_fine_cells(self.ctx._h, self._handle(), int(sub), out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
+              self.ctx._h, "elm_map_fine_cells")
+        return out[:n.value]
+
+    def CheckFreeSpace(self, scan, poses, cfg=None, hits=False):
+        """Free-space check (elm_map_check_free_space) of poses [n, 4, 4] for a scan (a resident Scan, or (m, 3) points uploaded for the
+        call): per pose a FreeSpaceStats dict -- the counted rays, those that pass through occupied fine cells of the map before their end
+        point (pierced), the end points in / next to an occupied cell, the samples and the occupied samples.  hits=True: also the occupied
+        samples of every ray, uint16 [n, m]; in the caller's point order for an array, in the resident order (Scan.points()) for a Scan."""
+        cfg = cfg if cfg is not None else FreeSpaceConfig()
+        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        n = P.size // 16
+        st = (FreeSpaceStatsC * max(n, 1))()
+        H = np.zeros((max(n, 1), sc.n), np.uint16) if hits else None
+        check(_lib.lib().elm_map_check_free_space(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st,
+                                                  H.ctypes.data_as(C.POINTER(C.c_uint16)) if hits else None), self.ctx._h,
+              "elm_map_check_free_space")
+        out = [FreeSpaceStats(st[h]) for h in range(n)]
+        if not hits:
+            return out
+        H = H[:n]
+        if not isinstance(scan, Scan):  # back to the caller's order: equal points have equal counts, so match by the points' bytes
+            key = np.dtype((np.void, 12))
+            res = np.ascontiguousarray(sc.points()).view(key).ravel()
+            own = np.ascontiguousarray(scan, dtype=np.float32).reshape(-1, 3).view(key).ravel()
+            order = np.argsort(res, kind="stable")
+            H = H[:, order[np.searchsorted(res[order], own)]] if sc.n else H
+        return out, H
+
     def FindGroundHeights(self, xy):
         """FindGroundHeight of many xy positions [n, 2] on the device (elm_map_ground_heights, bit for bit the single query) -> (found bool
         [n], z [n]; 0 where not found)."""
@@ -440,6 +501,12 @@ class Scan:
         self._h = C.c_void_p()
         check(_lib.lib().elm_scan_upload(ctx._h, _fp(pts), self.n, self.n if n_total is None else int(n_total),
                                          C.byref(self._h)), ctx._h, "elm_scan_upload")
+
+    def points(self):
+        """The resident points in device order (elm_scan_download) -> float32 [n, 3]."""
+        out = np.zeros((max(self.n, 1), 3), np.float32)
+        check(_lib.lib().elm_scan_download(self._h, _fp(out), self.n), self.ctx._h, "elm_scan_download")
+        return out[:self.n]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -538,11 +605,20 @@ class Registration:
             return out + (_result_dict(res, tr),)
         return out
 
-    def Relocalize(self, source_local, voxel_map, guess, reloc=None, m_config=None):
+    @staticmethod
+    def _with_free_space(cands, scan, voxel_map, free_space):
+        """The candidates' refined poses checked in ONE CheckFreeSpace call; each dict gains "free_space" (its FreeSpaceStats)."""
+        if free_space is None or not cands:
+            return cands
+        stats = voxel_map.CheckFreeSpace(scan, np.stack([c["T"] for c in cands]), free_space)
+        return [dict(c, free_space=st) for c, st in zip(cands, stats)]
+
+    def Relocalize(self, source_local, voxel_map, guess, reloc=None, m_config=None, free_space=None):
         """Relocalization from a coarse pose (elm_relocalize): occupancy scores of the xy x yaw hypotheses around guess on the device, non-maximum
         suppression, ICP from the best top_k in one batch.  Returns (pose 4x4, is_success, fitness_score or None, local_cov 6x6, candidates):
         the winner's result and the kept hypotheses in rank order (dicts: T0, T, score, hyp_index, is_success, iterations, fitness_score).
-        The winner's full result dict is kept in last_relocalize_."""
+        The winner's full result dict is kept in last_relocalize_.  free_space: a FreeSpaceConfig -- every candidate also
+        carries "free_space", the free-space statistics of its refined pose (one CheckFreeSpace call); the winner rule does not change."""
         cfg = m_config if m_config is not None else self.config_
         rc = reloc if reloc is not None else RelocConfig()
         scan = np.ascontiguousarray(source_local, dtype=np.float32).reshape(-1, 3)
@@ -558,13 +634,13 @@ class Registration:
         self.last_relocalize_ = _result_dict(res)
         ok = bool(res.is_success)
         return (Tout.reshape(4, 4).T.copy(), ok, (res.fitness_score if ok else None), np.array(res.local_cov).reshape(6, 6).T.copy(),
-                [_candidate_dict(cands[b]) for b in range(min(nc.value, cap))])
+                self._with_free_space([_candidate_dict(cands[b]) for b in range(min(nc.value, cap))], scan, voxel_map, free_space))
 
-    def RelocalizeGlobal(self, source_local, voxel_map, T_tilt=None, reloc=None, m_config=None):
+    def RelocalizeGlobal(self, source_local, voxel_map, T_tilt=None, reloc=None, m_config=None, free_space=None):
         """Global relocalization without a guess (elm_relocalize_global): branch-and-bound over an xy lattice of the map x the whole turn of
         yaw, every pose standing on the map's ground (T_tilt = [R0 | (0, 0, h)]: sensor roll / pitch and height; identity by default), then
         ICP from the best top_k.  Returns (pose 4x4, is_success, fitness_score or None, local_cov 6x6, candidates, stats); candidates as
-        Relocalize's (hyp_index = the lattice index), stats the search's counters and timings."""
+        Relocalize's (hyp_index = the lattice index), stats the search's counters and timings; free_space as Relocalize's."""
         cfg = m_config if m_config is not None else self.config_
         rc = reloc if reloc is not None else GlobalRelocConfig()
         scan = np.ascontiguousarray(source_local, dtype=np.float32).reshape(-1, 3)
@@ -582,7 +658,8 @@ class Registration:
         self.last_relocalize_ = _result_dict(res)
         ok = bool(res.is_success)
         return (Tout.reshape(4, 4).T.copy(), ok, (res.fitness_score if ok else None), np.array(res.local_cov).reshape(6, 6).T.copy(),
-                [_candidate_dict(cands[b]) for b in range(min(nc.value, cap))], _global_stats_dict(st))
+                self._with_free_space([_candidate_dict(cands[b]) for b in range(min(nc.value, cap))], scan, voxel_map, free_space),
+                _global_stats_dict(st))
 
     def _align(self, method, source_local, target_xyz, target_cov, last_icp_pose, trans_th, m_config, source_cov=None):
         cfg = m_config if m_config is not None else self.config_

@@ -86,6 +86,11 @@ struct PointStruct {
 // std::vector<PointStruct> uses the default allocator there as here)
 static_assert(sizeof(CovStruct) == 96 && sizeof(PointStruct) == 168 && alignof(PointStruct) == 8, "PointStruct must keep the reference's layout");
 
+// elm_freespace_config with its defaults (include/elimaloc_hip.h, free-space check): the ray sampling of VoxelHashMap::CheckFreeSpace
+struct FreeSpaceConfig : elm_freespace_config {
+    FreeSpaceConfig() { elm_freespace_config_default(this); }
+};
+
 struct VoxelHashMap {
     using RadarPointVector = std::vector<PointStruct>;
     using RadarPointVectorTuple = std::tuple<RadarPointVector, RadarPointVector>;
@@ -235,6 +240,30 @@ struct VoxelHashMap {
         ground_z.assign(n, 0.0);
         found.assign(n, 0);
         elimaloc::check(elm_map_ground_heights(ctx(), handle(), xy.data(), n, ground_z.data(), found.data()), ctx(), "FindGroundHeights");
+    }
+
+    // Free-space check of a scan (sensor frame, PointStruct::pose) at poses (elm_map_check_free_space): per pose the counted rays, those
+    // that pass through occupied fine cells of the map before their end point, the end points in / next to an occupied cell.  A pose whose
+    // rays pierce the map is a wrong pose -- or, at a trusted pose, a changed map.  hits (optional): the occupied samples of every ray,
+    // [pose][point] in the resident scan's order.
+    inline std::vector<elm_freespace_stats> CheckFreeSpace(const RadarPointVector& scan, const std::vector<elimaloc::Matrix4d>& poses,
+                                                           const FreeSpaceConfig& config = FreeSpaceConfig(),
+                                                           std::vector<uint16_t>* hits = nullptr) const {
+        std::vector<float> xyz(3 * scan.size());
+        for (size_t i = 0; i < scan.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scan[i].pose(k);
+        std::vector<double> T(16 * poses.size());
+        for (size_t h = 0; h < poses.size(); ++h)
+            for (int k = 0; k < 16; ++k) T[16 * h + k] = poses[h].data()[k]; // column-major on both sides
+        std::vector<elm_freespace_stats> stats(poses.size());
+        if (hits) hits->assign(poses.size() * scan.size(), 0);
+        elm_scan* s = nullptr;
+        elimaloc::check(elm_scan_upload(ctx(), xyz.data(), scan.size(), scan.size(), &s), ctx(), "elm_scan_upload");
+        const int rc = elm_map_check_free_space(ctx(), handle(), s, T.data(), (int)poses.size(), &config, stats.data(),
+                                                hits && !hits->empty() ? hits->data() : nullptr);
+        elm_scan_destroy(s);
+        elimaloc::check(rc, ctx(), "CheckFreeSpace");
+        return stats;
     }
 
     void Pairs(int what, const RadarPointVector& vec_points, double max_dist, std::vector<uint32_t>& src, std::vector<int32_t>& tgt) const {

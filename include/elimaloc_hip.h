@@ -159,7 +159,8 @@ typedef struct elm_map_info {
  *                       36 entries of J^T M J, 3x3 products and an inverse per pair), full_records (pairs read the stored 3x3 inverses
  *                       instead of the compact {mean, normal, k} records), pair_nine / avg_nine (nine entries of w C^-1 per pair instead of
  *                       the fused gathers), avg_inline / avg_fixup (AVGICP on maps with flagged voxels: in-line fallback / fix-up launch,
- *                       whatever the map's share of flagged voxels), query_direct (elm_map_get_correspondences by the plain walk).
+ *                       whatever the map's share of flagged voxels), query_direct (elm_map_get_correspondences by the plain walk),
+ *                       free_wave (elm_map_check_free_space: a wave per ray instead of a lane per ray; the same counts).
  *   ELM_SCAN_ORDER      none: elm_scan_upload keeps the caller's point order (default: Hilbert order over 2 m cells, on the device).
  *   ELM_GROUP_EXCHANGE  host | rccl: the exchange of a device group (default: RCCL when every rank has a device of its own).
  *   ELM_DEVICES         (shims) "0,1,2,3": the process-wide context of the C++ shims is a device group over these GPUs.
@@ -409,6 +410,48 @@ int elm_reloc_global_hypotheses(elm_ctx* ctx, const elm_map* map, const double T
 int elm_relocalize_global(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_tilt[16],
                           const elm_reloc_global_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
                           elm_reloc_candidate* cands, int cap, int* n_cands, elm_reloc_global_stats* stats);
+
+/* ---------------------------------------------------------------- free-space check ---------------- */
+/* Ray test of a scan against the map at a pose: the space between the sensor and every end point was empty when the scan was taken, so a
+ * ray that passes through mapped structure before its end point is evidence against the pose (or, at a trusted pose, of a changed map).
+ * Fine occupancy: cell = voxel_size / sub (float64); the fine cell of a STORED map point (elm_map_download_points' float32 coordinates as
+ * float64) is f_r = (int)floor(q_r / cell) per axis -- floor, not the map's truncated keys; the occupancy is the set of these cells.
+ * Per scan point p (float32 -> float64), origin o and pose T = [R | t]:
+ *   d = p - o, L2 = (d_x d_x + d_y d_y) + d_z d_z, L = sqrt(L2); the ray is COUNTED when min_range_m^2 <= L2 <= max_range_m^2 and L2 > 0;
+ *   reach = L - max(end_margin_m, end_margin_frac L); K = (int)floor(reach / step_m) when reach > 0, else 0, capped at max_samples;
+ *   k0 = (int)floor(start_m / step_m) + 1; u = d / L; sample k in [k0, K]: a_r = o_r + u_r (k step_m),
+ *   q_r = ((R_r0 a_x + R_r1 a_y) + R_r2 a_z) + t_r (float64, no contraction), fine cell floor(q_r / cell);
+ *   hits = the samples whose fine cell is occupied; the ray is PIERCED when hits >= min_hits;
+ *   the end point q(p) (the same transform of p itself) is END-OCCUPIED when its fine cell is occupied and SUPPORTED when that cell or one
+ *   of its 26 neighbours is.  Only counted rays enter any field.  All results are integers: the same on every run and every index form. */
+typedef struct elm_freespace_config {
+    int32_t sub;            /* fine cells per voxel edge: 1, 2 or 4 */
+    int32_t min_hits;       /* occupied samples that make a ray pierced (>= 1) */
+    int32_t max_samples;    /* cap of K (1 .. 65536) */
+    int32_t _pad;
+    double step_m;          /* sample spacing along the ray; 0: cell / 2 of the map the call is made on */
+    double start_m;         /* samples start beyond this distance from the origin (>= 0) */
+    double min_range_m, max_range_m; /* counted rays: min^2 <= L2 <= max^2 */
+    double end_margin_m, end_margin_frac; /* samples stop max(end_margin_m, end_margin_frac L) before the end point */
+    double origin[3];       /* the ray origin in the scan frame */
+} elm_freespace_config;
+typedef struct elm_freespace_stats {
+    uint32_t n_counted, n_pierced, n_end_occupied, n_supported;
+    uint64_t n_samples, n_hit_samples;
+} elm_freespace_stats;
+/* sub 4, step_m 0 (= cell / 2), start 1 m, range 2 .. 50 m, margins 1 m / 0.2 L, min_hits 2, max_samples 1024, origin 0.  Why a fractional
+ * margin: from height h over flat ground a ray stays within one cell c of the ground over the last c / h of its length at any range. */
+void elm_freespace_config_default(elm_freespace_config* c);
+/* The occupied fine cells of the map for `sub` as int32 triples in ascending (x, y, z) order: min(cap, count) written, *n = count
+ * (cells3 may be NULL when cap = 0).  sub other than 1, 2, 4: ELM_ERR_INVALID. */
+int elm_map_fine_cells(elm_ctx* ctx, const elm_map* map, int sub, int32_t* cells3, size_t cap, size_t* n);
+/* The free-space statistics of a resident scan at n_poses poses (column-major, 16 doubles each, as elm_map_score_poses): stats[n_poses],
+ * and, when hits is not NULL, hits[n_poses][elm_scan_size(scan)] = the occupied samples of every ray (saturating at 65535; 0 for a ray that
+ * is not counted).  n_poses = 0 is allowed (nothing is written).  The fine occupancy table is built at the first call per (map, sub) and
+ * kept with the map.  An empty map: nothing pierced, nothing supported.  ELM_ERR_UNSUPPORTED on a device group's lead or with a
+ * communicator / hook attached. */
+int elm_map_check_free_space(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses,
+                             const elm_freespace_config* c, elm_freespace_stats* stats, uint16_t* hits);
 
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
