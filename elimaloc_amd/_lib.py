@@ -165,6 +165,20 @@ class FreeSpaceStatsC(C.Structure):
                 ("n_samples", C.c_uint64), ("n_hit_samples", C.c_uint64)]
 
 
+class RayCastConfigC(C.Structure):
+    """elm_raycast_config (include/elimaloc_hip.h, ray casting)."""
+    _fields_ = [("sub", C.c_int32), ("max_steps", C.c_int32), ("min_range_m", C.c_double), ("max_range_m", C.c_double),
+                ("cmp_min_range_m", C.c_double), ("cmp_max_range_m", C.c_double), ("tol_m", C.c_double), ("tol_frac", C.c_double),
+                ("origin", C.c_double * 3)]
+
+
+class RayCastStatsC(C.Structure):
+    """elm_raycast_stats: the counts of one pose."""
+    _fields_ = [("n_cast", C.c_uint32), ("n_hit", C.c_uint32), ("n_miss", C.c_uint32), ("n_truncated", C.c_uint32),
+                ("n_compared", C.c_uint32), ("n_match", C.c_uint32), ("n_through", C.c_uint32), ("n_front", C.c_uint32),
+                ("n_steps", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -185,6 +199,7 @@ EXPORTS = [
     "elm_reloc_config_default", "elm_reloc_make_hypotheses", "elm_map_score_poses", "elm_relocalize",
     "elm_reloc_global_config_default", "elm_map_ground_heights", "elm_reloc_global_hypotheses", "elm_relocalize_global",
     "elm_freespace_config_default", "elm_map_fine_cells", "elm_map_check_free_space",
+    "elm_raycast_config_default", "elm_map_raycast",
 ]
 
 
@@ -358,6 +373,10 @@ def lib():
     L.elm_map_fine_cells.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
     L.elm_map_check_free_space.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(FreeSpaceConfigC), C.POINTER(FreeSpaceStatsC),
                                            C.POINTER(C.c_uint16)]
+    L.elm_raycast_config_default.argtypes = [C.POINTER(RayCastConfigC)]
+    L.elm_raycast_config_default.restype = None
+    L.elm_map_raycast.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RayCastConfigC), C.POINTER(RayCastStatsC), dp, dp,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
     L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
     L.elm_reloc_global_config_default.restype = None
     L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]

@@ -2966,6 +2966,12 @@ const float* scan_dev_points(const elm_scan* s, size_t* n) {
     return (const float*)s->d_pts;
 }
 int free_space_form() { return check_mode("free_wave") ? 1 : 0; }
+int ray_pose_block(int dflt) {
+    const char* v = nullptr;
+    if (!env_token("ELM_CHECK", "ray_poses", &v) || !v) return dflt;
+    const int b = atoi(v);
+    return b >= 1 && b <= elm::kRayMaxPoses ? b : dflt;
+}
 } // namespace elm_host
 
 // ------------------------------------------------------------------------------------------------------

@@ -1,0 +1,39 @@
+// elm_dev_fine.hpp -- device code shared by the kernels that read the fine occupancy table of a map (FineTable, elm_internal.hpp): the
+// free-space check (elm_k_free.hip) and the ray cast (elm_k_ray.hip, section 14).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "elm_internal.hpp"
+
+namespace elm {
+
+// The contract's fine cell of one world coordinate: (int)floor(q / cell), or q * (1 / cell) where that product is exact.
+__device__ __forceinline__ int fine_of(double q, const FineTable& ft) {
+    return (int)floor(ft.inv_cell_exact != 0.0 ? q * ft.inv_cell_exact : q / ft.cell);
+}
+
+// The 64-bit mask of coarse cell (cx, cy, cz); 0 when the map has no point there.
+__device__ __forceinline__ unsigned long long fine_probe(const FineTable& ft, int cx, int cy, int cz) {
+    uint32_t h = hash3(cx, cy, cz) & ft.mask;
+    for (;;) {
+        const int4 k = ft.keys[h];
+        if (k.w == 0) return 0ull;
+        if (k.x == cx && k.y == cy && k.z == cz) return ft.masks[h];
+        h = (h + 1) & ft.mask;
+    }
+}
+
+__device__ __forceinline__ uint32_t fine_bit(int fx, int fy, int fz) { return (uint32_t)((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3)); }
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// The rows of one pose [R | t], workgroup-uniform: 12 doubles (R_r0, R_r1, R_r2, t_r) per row r.
+struct PoseRows {
+    double r00, r01, r02, t0, r10, r11, r12, t1, r20, r21, r22, t2;
+};
+
+} // namespace elm

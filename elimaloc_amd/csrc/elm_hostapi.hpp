@@ -44,6 +44,8 @@ int map_fine_table(const elm_map* m, int sub, const elm::FineTable** ft, double 
 int map_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
 const float* scan_dev_points(const elm_scan* s, size_t* n); // the resident points of a plain (unsharded) scan, packed xyz
 int free_space_form(); // 0: one ray per lane; 1: ELM_CHECK=free_wave, a wave per ray (the A/B of DESIGN.md section 13)
+// ... for elm_ray.cpp
+int ray_pose_block(int dflt); // poses per workgroup of k_ray_cast: dflt, or N of ELM_CHECK=ray_poses=N (1 .. 16; the sweep of DESIGN.md section 14)
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

@@ -368,6 +368,20 @@ constexpr int kFreeWords = 6;   // a partial: counted, pierced, end-occupied, su
 void launch_free_space(hipStream_t s, int form, const FineTable& ft, const FreeParams& fp, const float* pts, uint32_t n, const double* rows,
                        uint32_t n_poses, uint32_t* partial, elm_freespace_stats* stats, uint16_t* hits);
 
+// ray casting (elm_k_ray.hip): exact traversal of the fine cells (FineTable) along every beam of a scan at many poses
+struct RayParams { // elm_raycast_config resolved for one call
+    double ox, oy, oz, t_min, t_max, cmp_min_r2, cmp_max_r2, tol_m, tol_frac;
+    int32_t max_steps, _pad;
+};
+constexpr int kRayMaxPoses = 16;    // the largest pose block of k_ray_cast (its LDS is sized for it)
+constexpr int kRayPosesDefault = 1; // the pose block that measured fastest; ELM_CHECK=ray_poses=N overrides it
+constexpr int kRayWords = 9;        // a partial: cast, hit, miss, truncated, compared, match, through, front, steps of one (pose, chunk)
+constexpr int kRayMaxSteps = 1 << 20; // cap of max_steps: 256 beams x 2^20 steps fit a 32-bit partial
+// rows: 12 doubles per pose (R_r0, R_r1, R_r2, t_r); partial: [n_poses][chunks][kRayWords] scratch; range_in / range_out [n_poses][n],
+// cell [n_poses][n][3], flag [n_poses][n]: each nullptr or a device array; pose_block: 1 .. kRayMaxPoses poses per workgroup
+void launch_ray_cast(hipStream_t s, uint32_t pose_block, const FineTable& ft, const RayParams& rp, const float* pts, uint32_t n, const double* rows,
+                     uint32_t n_poses, uint32_t* partial, elm_raycast_stats* stats, double* range_in, double* range_out, int32_t* cell, uint8_t* flag);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

@@ -5,29 +5,12 @@
 //   K6b k_free_sum    per pose, the chunk partials summed in chunk order
 #include <hip/hip_runtime.h>
 
+#include "elm_dev_fine.hpp"
 #include "elm_internal.hpp"
 
 namespace elm {
 
 namespace {
-
-// The contract's fine cell of one world coordinate: (int)floor(q / cell), or q * (1 / cell) where that product is exact.
-__device__ __forceinline__ int fine_of(double q, const FineTable& ft) {
-    return (int)floor(ft.inv_cell_exact != 0.0 ? q * ft.inv_cell_exact : q / ft.cell);
-}
-
-// The 64-bit mask of coarse cell (cx, cy, cz); 0 when the map has no point there.
-__device__ __forceinline__ unsigned long long fine_probe(const FineTable& ft, int cx, int cy, int cz) {
-    uint32_t h = hash3(cx, cy, cz) & ft.mask;
-    for (;;) {
-        const int4 k = ft.keys[h];
-        if (k.w == 0) return 0ull;
-        if (k.x == cx && k.y == cy && k.z == cz) return ft.masks[h];
-        h = (h + 1) & ft.mask;
-    }
-}
-
-__device__ __forceinline__ uint32_t fine_bit(int fx, int fy, int fz) { return (uint32_t)((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3)); }
 
 // The local indices 0 .. 3 of coarse cell c (one axis) whose fine cell lies in [f - 1, f + 1], as 4 bits.
 __device__ __forceinline__ uint32_t near_bits(int f, int c) {
@@ -59,17 +42,8 @@ __device__ __forceinline__ bool fine_supported(const FineTable& ft, int fx, int 
     return false;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 // One sample of a ray: a = o + u (k step), q = R a + t in the contract's association, whether q's fine cell is occupied.  (lcx, lcy, lcz,
 // lmask, have) keep the last coarse cell probed: consecutive samples mostly share it (8 per cell along an axis at the defaults).
-struct PoseRows {
-    double r00, r01, r02, t0, r10, r11, r12, t1, r20, r21, r22, t2;
-};
 __device__ __forceinline__ bool sample_hit(const FineTable& ft, const FreeParams& fp, const PoseRows& P, double ux, double uy, double uz, int k, int& lcx,
                                            int& lcy, int& lcz, unsigned long long& lmask, bool& have) {
     const double s = (double)k * fp.step;

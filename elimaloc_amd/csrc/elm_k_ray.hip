@@ -1,0 +1,188 @@
+// elm_k_ray.hip -- ray casting: the beams of one scan walked cell by cell through the fine occupancy of the map at many poses
+// (elm_map_raycast; the contract is in include/elimaloc_hip.h, "ray casting").  Every count is an integer and every
+// range one division result, so the answer is the same on every run.
+//   K7a k_ray_cast   (beam chunk x pose block) partials: per pose the cast / hit / missed / truncated / compared / matching / through / front
+//                    beams and the steps of the chunk, and (optionally) every beam's range_in, range_out, hit cell and flag
+//   K7b k_ray_sum    per pose, the chunk partials summed in chunk order
+#include <hip/hip_runtime.h>
+
+#include "elm_dev_fine.hpp"
+#include "elm_internal.hpp"
+
+namespace elm {
+
+namespace {
+
+// The exit parameter of cell c along one axis: the far face in the direction of travel, from the integer cell (never accumulated).
+__device__ __forceinline__ double exit_param(int c, int up, double cell, double s, double w) { return ((double)(c + up) * cell - s) / w; }
+
+} // namespace
+
+// K7a.  Workgroup = 256 consecutive beams (one per lane, float64 in registers) x pose_block consecutive poses, whose rows are
+// workgroup-uniform.  The beam's length, direction, cast / compared state and tolerance do not depend on the pose: they are formed once.
+// Per step a lane takes one 3-way minimum, one integer add, one multiply-subtract-divide for the stepped axis and a bit test of the
+// current coarse cell's mask held in registers; the table is probed only when the coarse cell (c >> 2) changes.  Per pose each wave
+// counts with ballot + popcount (and one shuffle sum for the steps); the four waves meet in LDS and one lane per pose stores the partial.
+__global__ __launch_bounds__(256) void k_ray_cast(const FineTable ft, const RayParams rp, const float* __restrict__ pts, uint32_t n,
+                                                  const double* __restrict__ rows, uint32_t n_poses, uint32_t n_chunks, uint32_t pose_block,
+                                                  uint32_t* __restrict__ partial, double* __restrict__ rin_out, double* __restrict__ rout_out,
+                                                  int32_t* __restrict__ cell_out, uint8_t* __restrict__ flag_out) {
+    __shared__ uint32_t wcnt[kRayMaxPoses][4][7]; // per pose and wave: hit, miss, truncated, match, through, front, steps
+    __shared__ uint32_t wray[4][2];               // per wave: cast, compared beams (the same for every pose)
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t chunk = blockIdx.x % n_chunks, h0 = (blockIdx.x / n_chunks) * pose_block;
+    const uint32_t i = chunk * 256u + tid;
+    const bool valid = i < n;
+    const uint32_t j = valid ? i : 0u;
+    const double dx = (double)pts[3 * (size_t)j] - rp.ox, dy = (double)pts[3 * (size_t)j + 1] - rp.oy, dz = (double)pts[3 * (size_t)j + 2] - rp.oz;
+    const double L2 = (dx * dx + dy * dy) + dz * dz;
+    const bool cast = valid && L2 > 0.0 && L2 < HUGE_VAL; // (a NaN fails both)
+    const bool compared = cast && L2 >= rp.cmp_min_r2 && L2 <= rp.cmp_max_r2;
+    const double L = sqrt(L2);
+    const double ux = dx / L, uy = dy / L, uz = dz / L;
+    const double tol = fmax(rp.tol_m, rp.tol_frac * L);
+    const double cell = ft.cell;
+    {
+        const uint32_t c = (uint32_t)__popcll(__ballot(cast)), m = (uint32_t)__popcll(__ballot(compared));
+        if (lane == 0) {
+            wray[wave][0] = c;
+            wray[wave][1] = m;
+        }
+    }
+    const uint32_t hn = min(pose_block, n_poses - h0);
+    for (uint32_t hl = 0; hl < hn; ++hl) {
+        const double* R = rows + (size_t)(h0 + hl) * 12;
+        const PoseRows P{R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], R[9], R[10], R[11]};
+        uint32_t flag = 0, steps_hit = 0;
+        double rin = -1.0, rout = -1.0;
+        int hx = 0, hy = 0, hz = 0;
+        if (cast) {
+            const double s0 = ((P.r00 * rp.ox + P.r01 * rp.oy) + P.r02 * rp.oz) + P.t0;
+            const double s1 = ((P.r10 * rp.ox + P.r11 * rp.oy) + P.r12 * rp.oz) + P.t1;
+            const double s2 = ((P.r20 * rp.ox + P.r21 * rp.oy) + P.r22 * rp.oz) + P.t2;
+            const double w0 = (P.r00 * ux + P.r01 * uy) + P.r02 * uz;
+            const double w1 = (P.r10 * ux + P.r11 * uy) + P.r12 * uz;
+            const double w2 = (P.r20 * ux + P.r21 * uy) + P.r22 * uz;
+            double t_in = rp.t_min;
+            int c0 = fine_of(s0 + w0 * t_in, ft), c1 = fine_of(s1 + w1 * t_in, ft), c2 = fine_of(s2 + w2 * t_in, ft);
+            const int g0 = w0 > 0.0 ? 1 : (w0 < 0.0 ? -1 : 0), g1 = w1 > 0.0 ? 1 : (w1 < 0.0 ? -1 : 0), g2 = w2 > 0.0 ? 1 : (w2 < 0.0 ? -1 : 0);
+            const int up0 = g0 > 0 ? 1 : 0, up1 = g1 > 0 ? 1 : 0, up2 = g2 > 0 ? 1 : 0;
+            double tx0 = g0 ? exit_param(c0, up0, cell, s0, w0) : HUGE_VAL;
+            double tx1 = g1 ? exit_param(c1, up1, cell, s1, w1) : HUGE_VAL;
+            double tx2 = g2 ? exit_param(c2, up2, cell, s2, w2) : HUGE_VAL;
+            int lcx = 0, lcy = 0, lcz = 0;
+            unsigned long long lmask = 0;
+            bool have = false, in_run = false;
+            uint32_t steps = 0;
+            for (;;) {
+                const int cx = c0 >> 2, cy = c1 >> 2, cz = c2 >> 2;
+                if (!have || cx != lcx || cy != lcy || cz != lcz) {
+                    lmask = fine_probe(ft, cx, cy, cz);
+                    lcx = cx; lcy = cy; lcz = cz;
+                    have = true;
+                }
+                const bool occ = (lmask >> fine_bit(c0, c1, c2)) & 1ull;
+                if (!in_run) {
+                    if (occ) {
+                        in_run = true;
+                        flag = 1;
+                        rin = t_in;
+                        hx = c0; hy = c1; hz = c2;
+                        steps_hit = steps;
+                    }
+                } else if (!occ) {
+                    rout = t_in;
+                    break;
+                }
+                int ax = 0;
+                double tmin = tx0;
+                if (tx1 < tmin) { tmin = tx1; ax = 1; }
+                if (tx2 < tmin) { tmin = tx2; ax = 2; }
+                const double t_next = fmax(t_in, tmin);
+                if (t_next > rp.t_max) { // the walk ends by range
+                    if (in_run) rout = rp.t_max;
+                    else { flag = 2; steps_hit = steps; }
+                    break;
+                }
+                if (steps >= (uint32_t)rp.max_steps) { // ... by steps
+                    if (in_run) rout = t_in;
+                    else { flag = 3; steps_hit = steps; }
+                    break;
+                }
+                t_in = t_next;
+                if (ax == 0) { c0 += g0; tx0 = exit_param(c0, up0, cell, s0, w0); }
+                else if (ax == 1) { c1 += g1; tx1 = exit_param(c1, up1, cell, s1, w1); }
+                else { c2 += g2; tx2 = exit_param(c2, up2, cell, s2, w2); }
+                ++steps;
+            }
+        }
+        const bool hit = flag == 1;
+        const bool match = compared && hit && rin - tol <= L && L <= rout + tol;
+        const bool through = compared && hit && L > rout + tol;
+        const bool front = compared && !match && !through;
+        if (valid) {
+            const size_t o = (size_t)(h0 + hl) * n + i;
+            if (rin_out) rin_out[o] = rin;
+            if (rout_out) rout_out[o] = rout;
+            if (cell_out) {
+                cell_out[3 * o] = hx;
+                cell_out[3 * o + 1] = hy;
+                cell_out[3 * o + 2] = hz;
+            }
+            if (flag_out) flag_out[o] = (uint8_t)flag;
+        }
+        const uint32_t c_h = (uint32_t)__popcll(__ballot(hit)), c_m = (uint32_t)__popcll(__ballot(flag == 2)), c_t = (uint32_t)__popcll(__ballot(flag == 3));
+        const uint32_t c_a = (uint32_t)__popcll(__ballot(match)), c_p = (uint32_t)__popcll(__ballot(through)), c_f = (uint32_t)__popcll(__ballot(front));
+        const uint32_t c_s = wave_sum(steps_hit);
+        if (lane == 0) {
+            uint32_t* w = wcnt[hl][wave];
+            w[0] = c_h; w[1] = c_m; w[2] = c_t; w[3] = c_a; w[4] = c_p; w[5] = c_f; w[6] = c_s;
+        }
+    }
+    __syncthreads();
+    if (tid < hn) {
+        uint32_t* out = partial + ((size_t)(h0 + tid) * n_chunks + chunk) * kRayWords;
+        out[0] = ((wray[0][0] + wray[1][0]) + wray[2][0]) + wray[3][0];
+        out[4] = ((wray[0][1] + wray[1][1]) + wray[2][1]) + wray[3][1];
+        out[1] = ((wcnt[tid][0][0] + wcnt[tid][1][0]) + wcnt[tid][2][0]) + wcnt[tid][3][0];
+        out[2] = ((wcnt[tid][0][1] + wcnt[tid][1][1]) + wcnt[tid][2][1]) + wcnt[tid][3][1];
+        out[3] = ((wcnt[tid][0][2] + wcnt[tid][1][2]) + wcnt[tid][2][2]) + wcnt[tid][3][2];
+        out[5] = ((wcnt[tid][0][3] + wcnt[tid][1][3]) + wcnt[tid][2][3]) + wcnt[tid][3][3];
+        out[6] = ((wcnt[tid][0][4] + wcnt[tid][1][4]) + wcnt[tid][2][4]) + wcnt[tid][3][4];
+        out[7] = ((wcnt[tid][0][5] + wcnt[tid][1][5]) + wcnt[tid][2][5]) + wcnt[tid][3][5];
+        out[8] = ((wcnt[tid][0][6] + wcnt[tid][1][6]) + wcnt[tid][2][6]) + wcnt[tid][3][6];
+    }
+}
+
+// K7b: stats[h] = the chunk partials of pose h, summed in chunk order (the steps in 64 bits)
+__global__ __launch_bounds__(256) void k_ray_sum(const uint32_t* __restrict__ partial, uint32_t n_chunks, uint32_t n_poses,
+                                                 elm_raycast_stats* __restrict__ stats) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= n_poses) return;
+    uint32_t a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t s = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        const uint32_t* p = partial + ((size_t)h * n_chunks + c) * kRayWords;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] += p[k];
+        s += p[8];
+    }
+    elm_raycast_stats o;
+    o.n_cast = a[0]; o.n_hit = a[1]; o.n_miss = a[2]; o.n_truncated = a[3];
+    o.n_compared = a[4]; o.n_match = a[5]; o.n_through = a[6]; o.n_front = a[7];
+    o.n_steps = s;
+    stats[h] = o;
+}
+
+void launch_ray_cast(hipStream_t s, uint32_t pose_block, const FineTable& ft, const RayParams& rp, const float* pts, uint32_t n, const double* rows,
+                     uint32_t n_poses, uint32_t* partial, elm_raycast_stats* stats, double* range_in, double* range_out, int32_t* cell, uint8_t* flag) {
+    if (!n || !n_poses) return;
+    pose_block = pose_block < 1u ? 1u : (pose_block > (uint32_t)kRayMaxPoses ? (uint32_t)kRayMaxPoses : pose_block);
+    const uint32_t n_chunks = (n + 255u) / 256u;
+    const uint32_t n_blk = (n_poses + pose_block - 1) / pose_block;
+    hipLaunchKernelGGL(k_ray_cast, dim3(n_chunks * n_blk), dim3(256), 0, s, ft, rp, pts, n, rows, n_poses, n_chunks, pose_block, partial, range_in,
+                       range_out, cell, flag);
+    hipLaunchKernelGGL(k_ray_sum, dim3((n_poses + 255) / 256), dim3(256), 0, s, partial, n_chunks, n_poses, stats);
+}
+
+} // namespace elm

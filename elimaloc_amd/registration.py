@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, FreeSpaceConfigC, FreeSpaceStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+from ._lib import (ElmError, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
                    check)
 
 
@@ -80,6 +80,32 @@ def FreeSpaceStats(st):
     """elm_freespace_stats of one pose as a dict (+ pierced_share = n_pierced / n_counted, 0 without counted rays)."""
     d = {k: int(getattr(st, k)) for k in _FREE_FIELDS}
     d["pierced_share"] = d["n_pierced"] / d["n_counted"] if d["n_counted"] else 0.0
+    return d
+
+
+def RayCastConfig(**kw):
+    """elm_raycast_config with its defaults (sub 4, max_steps 4096, range 1 .. 100 m, compared 2 .. 50 m, tol_m 0.5, tol_frac 0.02,
+    origin 0)."""
+    cfg = RayCastConfigC()
+    _lib.lib().elm_raycast_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"RayCastConfig has no field {k}")
+        if k == "origin":
+            cfg.origin = (C.c_double * 3)(*[float(x) for x in v])
+        else:
+            setattr(cfg, k, int(v) if k in ("sub", "max_steps") else float(v))
+    return cfg
+
+
+_RAY_FIELDS = ("n_cast", "n_hit", "n_miss", "n_truncated", "n_compared", "n_match", "n_through", "n_front", "n_steps")
+
+
+def RayCastStats(st):
+    """elm_raycast_stats of one pose as a dict (+ match_share / through_share / front_share of the compared beams, 0 without any)."""
+    d = {k: int(getattr(st, k)) for k in _RAY_FIELDS}
+    for k in ("match", "through", "front"):
+        d[k + "_share"] = d["n_" + k] / d["n_compared"] if d["n_compared"] else 0.0
     return d
 
 
@@ -437,6 +463,96 @@ class VoxelHashMap:
             order = np.argsort(res, kind="stable")
             H = H[:, order[np.searchsorted(res[order], own)]] if sc.n else H
         return out, H
+
+    def RayCast(self, beams, poses, cfg=None, ranges=False, cells=False, flags=False):
+        """Ray cast (elm_map_raycast) of beams at poses [n, 4, 4]: beam i runs from cfg.origin through point i of `beams` (a resident Scan,
+        or (m, 3) points uploaded for the call; unit vectors for a sensor model, a real scan to compare its measured ranges).  Per pose a
+        RayCastStats dict: the cast beams, those that hit / miss the map / are truncated, the compared beams and how their measured range
+        lies to the expected one (match / through / front), the steps walked.  With ranges / cells / flags also a dict of the per-beam
+        arrays asked for -- "range_in", "range_out" float64 [n, m] (-1 without a hit), "cell" int32 [n, m, 3] (the hit cell), "flag" uint8
+        [n, m] (0 not cast, 1 hit, 2 miss, 3 truncated) -- in the caller's beam order for an array, in the resident order (Scan.points())
+        for a Scan."""
+        cfg = cfg if cfg is not None else RayCastConfig()
+        sc = beams if isinstance(beams, Scan) else Scan(self.ctx, beams)
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        n = P.size // 16
+        st = (RayCastStatsC * max(n, 1))()
+        rows = max(n, 1)
+        arr = {}
+        if ranges:
+            arr["range_in"] = np.full((rows, sc.n), -1.0)
+            arr["range_out"] = np.full((rows, sc.n), -1.0)
+        if cells:
+            arr["cell"] = np.zeros((rows, sc.n, 3), np.int32)
+        if flags:
+            arr["flag"] = np.zeros((rows, sc.n), np.uint8)
+        check(_lib.lib().elm_map_raycast(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st,
+                                         _dp(arr["range_in"]) if ranges else None, _dp(arr["range_out"]) if ranges else None,
+                                         arr["cell"].ctypes.data_as(C.POINTER(C.c_int32)) if cells else None,
+                                         arr["flag"].ctypes.data_as(C.POINTER(C.c_uint8)) if flags else None), self.ctx._h, "elm_map_raycast")
+        out = [RayCastStats(st[h]) for h in range(n)]
+        if not arr:
+            return out
+        arr = {k: v[:n] for k, v in arr.items()}
+        if not isinstance(beams, Scan) and sc.n:  # back to the caller's order: equal points are equal beams, so match by the points' bytes
+            key = np.dtype((np.void, 12))
+            res = np.ascontiguousarray(sc.points()).view(key).ravel()
+            own = np.ascontiguousarray(beams, dtype=np.float32).reshape(-1, 3).view(key).ravel()
+            order = np.argsort(res, kind="stable")
+            back = order[np.searchsorted(res[order], own)]
+            arr = {k: np.ascontiguousarray(v[:, back]) for k, v in arr.items()}
+        return out, arr
+
+    def RenderScan(self, pose, beams, cfg=None, noise=0.0, seed=None, return_index=False):
+        """The scan a sensor at `pose` [4, 4] would record with the beam model `beams` (an (m, 3) array or a resident Scan): one RayCast,
+        then for every beam that hits the STORED map point of the hit cell that lies nearest to the beam, expressed in the sensor frame
+        (R^T (q - t)), plus N(0, noise) per coordinate (seed) -> float32 [k, 3], k = the beams that hit, in beam order.  The points are
+        real map points (as synth.make_scan's), but one per beam and the first surface only.
+        Nearest: with s / w the beam's world origin / direction of the ray-casting contract, e = q - s, a = (e_x w_x + e_y w_y) + e_z w_z,
+        r = e - w a, the smallest (r_x r_x + r_y r_y) + r_z r_z; the lowest Pointcloud() index on a tie.
+        The cell -> point lookup runs on the host from Pointcloud() (numpy; not a hot path).  On grazing ground the first occupied cell
+        lies before the true surface point, so the rendered ground rings are somewhat tighter than a real sensor's.
+        return_index: also the beam index and the Pointcloud() index of every returned point."""
+        cfg = cfg if cfg is not None else RayCastConfig()
+        T = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+        _, arr = self.RayCast(beams, T[None], cfg, cells=True, flags=True)
+        b = (beams.points() if isinstance(beams, Scan) else np.ascontiguousarray(beams, dtype=np.float32).reshape(-1, 3)).astype(np.float64)
+        hit = np.flatnonzero(arr["flag"][0] == 1)
+        stored = self.Pointcloud() if hit.size else np.zeros((0, 3))
+
+        def codes(k):
+            k = np.asarray(k, dtype=np.int64) + (1 << 20)
+            return (k[:, 0] << 42) | (k[:, 1] << 21) | k[:, 2]
+
+        cell = self.voxel_size_ / float(cfg.sub)
+        pc = codes(np.floor(stored / cell))
+        order = np.argsort(pc, kind="stable")
+        hc = codes(arr["cell"][0][hit])
+        lo, hi = np.searchsorted(pc[order], hc, "left"), np.searchsorted(pc[order], hc, "right")
+        cnt = hi - lo
+        which = np.repeat(np.arange(hit.size), cnt)                                   # the hit a candidate belongs to
+        cand = order[np.repeat(lo, cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))]
+        o = np.array(list(cfg.origin))
+        d = b[hit] - o
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
+        s = np.array([((T[r, 0] * o[0] + T[r, 1] * o[1]) + T[r, 2] * o[2]) + T[r, 3] for r in range(3)])
+        w = np.stack([(T[r, 0] * u[:, 0] + T[r, 1] * u[:, 1]) + T[r, 2] * u[:, 2] for r in range(3)], 1)
+        e = stored[cand] - s
+        wc = w[which]
+        a = (e[:, 0] * wc[:, 0] + e[:, 1] * wc[:, 1]) + e[:, 2] * wc[:, 2]
+        r = e - wc * a[:, None]
+        d2 = (r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2]
+        best = np.lexsort((cand, d2, which))                                          # per hit: smallest d2, then lowest index
+        first = best[np.flatnonzero(np.r_[True, which[best][1:] != which[best][:-1]])] if best.size else best
+        pick = cand[first]
+        q = stored[pick] - T[:3, 3]
+        R = T[:3, :3]
+        local = np.stack([(q[:, 0] * R[0, j] + q[:, 1] * R[1, j]) + q[:, 2] * R[2, j] for j in range(3)], 1)
+        if noise > 0.0:
+            local = local + np.random.default_rng(seed).normal(0.0, noise, local.shape)
+        scan = np.ascontiguousarray(local.astype(np.float32)).reshape(-1, 3)
+        return (scan, hit[which[first]], pick) if return_index else scan
 
     def FindGroundHeights(self, xy):
         """FindGroundHeight of many xy positions [n, 2] on the device (elm_map_ground_heights, bit for bit the single query) -> (found bool

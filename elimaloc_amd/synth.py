@@ -262,6 +262,17 @@ def make_scan(map_xyz, n_scan, seed, T_true=None, max_range=60.0, noise=0.01):
     return np.ascontiguousarray(local.astype(np.float32)), T_true
 
 
+def lidar_beams(rings=32, azimuths=512, elevation_min_deg=-25.0, elevation_max_deg=15.0):
+    """Unit vectors of a spinning LiDAR in the sensor frame: `rings` elevations evenly spaced over [elevation_min_deg, elevation_max_deg]
+    (one ring: their mean) x `azimuths` evenly spaced over the full turn from 0 -> float32 [rings * azimuths, 3], ring-major.  The beam
+    model of VoxelHashMap.RayCast / RenderScan: one return per beam, unlike make_scan's draw of map points."""
+    el = np.deg2rad(np.linspace(elevation_min_deg, elevation_max_deg, rings) if rings > 1 else np.array([0.5 * (elevation_min_deg + elevation_max_deg)]))
+    az = 2.0 * math.pi * np.arange(azimuths, dtype=np.float64) / azimuths
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    v = np.stack([ce * np.cos(az)[None, :], ce * np.sin(az)[None, :], se * np.ones_like(az)[None, :]], 2).reshape(-1, 3)
+    return np.ascontiguousarray(v.astype(np.float32))
+
+
 def perturb(T_true, seed, max_trans=0.15, max_rot_deg=0.5):
     """Initial guess T0 = T_true * delta; delta translation uniform in a ball, rotation angle uniform <= max."""
     rng = np.random.default_rng(seed)

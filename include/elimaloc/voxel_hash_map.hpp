@@ -91,6 +91,11 @@ struct FreeSpaceConfig : elm_freespace_config {
     FreeSpaceConfig() { elm_freespace_config_default(this); }
 };
 
+// elm_raycast_config with its defaults (include/elimaloc_hip.h, ray casting): the traversal and comparison of VoxelHashMap::RayCast
+struct RayCastConfig : elm_raycast_config {
+    RayCastConfig() { elm_raycast_config_default(this); }
+};
+
 struct VoxelHashMap {
     using RadarPointVector = std::vector<PointStruct>;
     using RadarPointVectorTuple = std::tuple<RadarPointVector, RadarPointVector>;
@@ -263,6 +268,43 @@ struct VoxelHashMap {
                                                 hits && !hits->empty() ? hits->data() : nullptr);
         elm_scan_destroy(s);
         elimaloc::check(rc, ctx(), "CheckFreeSpace");
+        return stats;
+    }
+
+    // The per-beam outputs of RayCast, each [pose][beam] in the resident scan's order (see elm_map_raycast)
+    struct RayCastArrays {
+        std::vector<double> range_in, range_out; // -1 for a beam that did not hit
+        std::vector<int32_t> cell;               // x, y, z of the hit fine cell
+        std::vector<uint8_t> flag;               // 0 not cast, 1 hit, 2 miss, 3 truncated
+    };
+
+    // Ray cast of the beams of a scan (sensor frame, PointStruct::pose; beam i runs from config.origin through point i) at poses
+    // (elm_map_raycast): per pose the beams that hit / miss the map and, for a real scan, how its measured ranges lie to the expected
+    // ones (match / through / front).  arrays (optional): the expected range interval, hit cell and flag of every beam.
+    inline std::vector<elm_raycast_stats> RayCast(const RadarPointVector& scan, const std::vector<elimaloc::Matrix4d>& poses,
+                                                  const RayCastConfig& config = RayCastConfig(), RayCastArrays* arrays = nullptr) const {
+        std::vector<float> xyz(3 * scan.size());
+        for (size_t i = 0; i < scan.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scan[i].pose(k);
+        std::vector<double> T(16 * poses.size());
+        for (size_t h = 0; h < poses.size(); ++h)
+            for (int k = 0; k < 16; ++k) T[16 * h + k] = poses[h].data()[k]; // column-major on both sides
+        std::vector<elm_raycast_stats> stats(poses.size());
+        const size_t beams = poses.size() * scan.size();
+        if (arrays) {
+            arrays->range_in.assign(beams, -1.0);
+            arrays->range_out.assign(beams, -1.0);
+            arrays->cell.assign(3 * beams, 0);
+            arrays->flag.assign(beams, 0);
+        }
+        const bool want = arrays && beams;
+        elm_scan* s = nullptr;
+        elimaloc::check(elm_scan_upload(ctx(), xyz.data(), scan.size(), scan.size(), &s), ctx(), "elm_scan_upload");
+        const int rc = elm_map_raycast(ctx(), handle(), s, T.data(), (int)poses.size(), &config, stats.data(), want ? arrays->range_in.data() : nullptr,
+                                       want ? arrays->range_out.data() : nullptr, want ? arrays->cell.data() : nullptr,
+                                       want ? arrays->flag.data() : nullptr);
+        elm_scan_destroy(s);
+        elimaloc::check(rc, ctx(), "RayCast");
         return stats;
     }
 

@@ -160,7 +160,8 @@ typedef struct elm_map_info {
  *                       instead of the compact {mean, normal, k} records), pair_nine / avg_nine (nine entries of w C^-1 per pair instead of
  *                       the fused gathers), avg_inline / avg_fixup (AVGICP on maps with flagged voxels: in-line fallback / fix-up launch,
  *                       whatever the map's share of flagged voxels), query_direct (elm_map_get_correspondences by the plain walk),
- *                       free_wave (elm_map_check_free_space: a wave per ray instead of a lane per ray; the same counts).
+ *                       free_wave (elm_map_check_free_space: a wave per ray instead of a lane per ray; the same counts),
+ *                       ray_poses=N (elm_map_raycast: N = 1 .. 16 poses per workgroup instead of the shipped block; the same outputs).
  *   ELM_SCAN_ORDER      none: elm_scan_upload keeps the caller's point order (default: Hilbert order over 2 m cells, on the device).
  *   ELM_GROUP_EXCHANGE  host | rccl: the exchange of a device group (default: RCCL when every rank has a device of its own).
  *   ELM_DEVICES         (shims) "0,1,2,3": the process-wide context of the C++ shims is a device group over these GPUs.
@@ -452,6 +453,59 @@ int elm_map_fine_cells(elm_ctx* ctx, const elm_map* map, int sub, int32_t* cells
  * communicator / hook attached. */
 int elm_map_check_free_space(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses,
                              const elm_freespace_config* c, elm_freespace_stats* stats, uint16_t* hits);
+
+/* ---------------------------------------------------------------- ray casting --------------------- */
+/* Standing at this pose, what range should this beam return?  An exact traversal of the map's fine cells (the occupancy of the free-space
+ * check: cell = voxel_size / sub, the cells of elm_map_fine_cells) along every beam of a resident scan, at one or many poses.  Beam i starts
+ * at `origin` o (scan frame) and passes through scan point p_i (float32 -> float64): a sensor model is a scan of unit vectors, a real scan
+ * gives its own beams and, with them, its measured ranges L.  All arithmetic float64 without contraction; q / cell below is formed as the
+ * fine occupancy forms it (q * (1 / cell) where cell is a power of two, the same bits).  Per beam and pose T = [R | t]:
+ *   d = p - o, L2 = (d_x d_x + d_y d_y) + d_z d_z, L = sqrt(L2), u = d / L; the beam is CAST when L2 > 0 and finite;
+ *   s_r = ((R_r0 o_x + R_r1 o_y) + R_r2 o_z) + t_r (world origin), w_r = (R_r0 u_x + R_r1 u_y) + R_r2 u_z (world direction);
+ *   start: t_in = min_range_m, a_r = s_r + w_r t_in, cell c_r = (int)floor(a_r / cell);
+ *   per axis sg_r = +1 / -1 / 0 by the sign of w_r and the exit parameter of the current cell
+ *     tx_r = ((double)(c_r + (sg_r > 0 ? 1 : 0)) cell - s_r) / w_r, +inf when sg_r = 0 -- formed from the integer cell every time that axis
+ *     steps, never accumulated;
+ *   the walk: TEST the current cell; then STEP: the axis with the smallest tx (ties: x before y before z), t_next = fmax(t_in, tx_axis);
+ *     if t_next > max_range_m the walk ends BY RANGE; else if max_steps steps were already taken it ends BY STEPS; else t_in = t_next,
+ *     c_axis += sg_axis, tx_axis is formed anew, one step is counted; test, step, ...  (The first cell, at min_range_m, is tested like
+ *     any other; max_steps steps test max_steps + 1 cells.)
+ *   the first occupied cell is the HIT: range_in = its t_in, cell = c.  The walk goes on through the OCCUPIED RUN: range_out = the t_in of
+ *     the first unoccupied cell after the hit, or max_range_m when the walk ends by range inside the run, or the last t_in when it ends
+ *     by steps there.  A walk that ends by range without a hit is a MISS, one that ends by steps without a hit is TRUNCATED.
+ *   n_steps counts the steps up to the hit or the end of the walk (the run's steps are not included: the count does not depend on what
+ *     lies behind a surface).
+ *   comparison with the measurement, for the cast beams with cmp_min_range_m^2 <= L2 <= cmp_max_range_m^2 (the COMPARED beams):
+ *     tol = fmax(tol_m, tol_frac L); MATCH when hit and range_in - tol <= L <= range_out + tol; THROUGH when hit and L > range_out + tol
+ *     (the map has a surface in front of the measurement: the free-space check's "pierced", with a position); FRONT otherwise (a miss,
+ *     a truncation, or L < range_in - tol: the measurement ends before anything mapped).
+ *   Why the run and not the entry alone: from height h over flat ground a beam runs inside the occupied ground layer of cells over the
+ *     last cell / h of its length, so the entry of the first occupied cell lies metres before a return at 40 m; [range_in, range_out] is
+ *     what a voxel map can say about where the return lies.
+ * Every count is an integer and every range one IEEE division result (or a config value): the same on every run and every index form.
+ * The tolerance defaults are a starting point (two fine cells of a 1 m map: a stored point lies up to cell sqrt(3) inside its cell), not
+ * a measured optimum. */
+typedef struct elm_raycast_config {
+    int32_t sub;            /* fine cells per voxel edge: 1, 2 or 4 */
+    int32_t max_steps;      /* cap of the steps of one walk (1 .. 1048576) */
+    double min_range_m, max_range_m;         /* the walk covers [min_range_m, max_range_m] along the beam (0 <= min <= max) */
+    double cmp_min_range_m, cmp_max_range_m; /* compared beams: min^2 <= L2 <= max^2 */
+    double tol_m, tol_frac; /* tol = max(tol_m, tol_frac L) */
+    double origin[3];       /* the beam origin in the scan frame */
+} elm_raycast_config;
+typedef struct elm_raycast_stats {
+    uint32_t n_cast, n_hit, n_miss, n_truncated, n_compared, n_match, n_through, n_front;
+    uint64_t n_steps;
+} elm_raycast_stats;
+/* sub 4, max_steps 4096, range 1 .. 100 m, compared 2 .. 50 m, tol_m 0.5, tol_frac 0.02, origin 0 */
+void elm_raycast_config_default(elm_raycast_config* c);
+/* The ray cast of a resident scan's beams at n_poses poses (column-major, 16 doubles each, as elm_map_score_poses): stats[n_poses] and,
+ * each when not NULL, per-beam arrays [n_poses][elm_scan_size(scan)] in the resident scan's order: range_in, range_out (-1.0 for a beam
+ * that did not hit), cell (int32 x 3, the hit cell; zeros when no hit), flag (0 not cast, 1 hit, 2 miss, 3 truncated).  n_poses = 0 is
+ * allowed (nothing is written).  The fine occupancy table is built at the first call per (map, sub) and kept with the map.  An empty
+ * map: every cast beam misses (or is truncated).  ELM_ERR_UNSUPPORTED on a device group's lead or with a communicator / hook attached. */
+int elm_map_raycast(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses, const elm_raycast_config* c,
+                    elm_raycast_stats* stats, double* range_in, double* range_out, int32_t* cell, uint8_t* flag);
 
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
