@@ -762,14 +762,15 @@ def test_stream_through_exchange_hook(ctx, oracle, world100k):
     assert dt <= POSE_TOL_M and dr <= POSE_TOL_RAD
 
 
-def _randomized_case(ctx, oracle, seed):
+def _randomized_case(ctx, oracle, seed, method=None):
     """Differential sweep of the default kernels against the oracle: random voxel size (also not a power of two, also
     larger than the lattice pitch allows for 30 points), bucket cap, search radius, map offset (negative / far-from-origin
     coordinates), scan partly outside the map, initial errors from tiny to half a voxel (so the share of points that need
     the exact wave-cooperative stage varies from ~0 to most of them)."""
     from elimaloc_amd.registration import Registration, RegistrationConfig, IcpMethod
     rng = np.random.default_rng(9000 + seed)
-    method = IcpMethod(int(rng.integers(0, 3)))
+    drawn = IcpMethod(int(rng.integers(0, 3)))  # (the draw stays: the other parameters of a seed must not move)
+    method = drawn if method is None else IcpMethod(method)
     voxel = float(rng.choice([0.4, 0.5, 0.75, 1.0, 1.3, 2.0]))
     max_pts = int(rng.choice([6, 12, 30, 60]))
     th = float(rng.choice([0.8, 2.0, 5.0]))
@@ -796,6 +797,12 @@ def _randomized_case(ctx, oracle, seed):
 @pytest.mark.parametrize("seed", range(32))
 def test_randomized_configs_default_kernels(ctx, oracle, seed):
     _randomized_case(ctx, oracle, seed)
+
+
+@pytest.mark.parametrize("seed", range(300, 312))
+def test_randomized_configs_avgicp(ctx, oracle, seed):
+    """The sweep draws its method from P2P / GICP / VGICP: the same sweep with AVGICP (up to seven pairs per point), on seeds of its own."""
+    _randomized_case(ctx, oracle, seed, method=3)
 
 
 @pytest.mark.parametrize("seed", range(16))
