@@ -57,7 +57,11 @@ __global__ __launch_bounds__(256) void k_deskew(const float* __restrict__ xyz, c
     const float DE = D * E, DF = D * F;
     const float t00 = A * Cc, t01 = A * DF - B * E, t02 = B * F + A * DE;
     const float t10 = B * Cc, t11 = A * E + B * DF, t12 = B * DE - A * F;
-    const float t20 = -D, t21 = Cc * F, t22 = Cc * E;
+    float t20 = -D; // (pcl stores -sin(pitch) as a matrix entry of its own)
+    // keeps that entry a value: free to move the negation, the compiler negates the PRODUCT t20 * x instead, which flips the sign bit of the
+    // NaN a NaN coordinate gives -- the reference's arithmetic hands the coordinate's NaN through unchanged (tests/test_scan_kernels.py)
+    asm volatile("" : "+v"(t20));
+    const float t21 = Cc * F, t22 = Cc * E;
     out[3 * i] = t00 * x + t01 * y + t02 * z + tx;
     out[3 * i + 1] = t10 * x + t11 * y + t12 * z + ty;
     out[3 * i + 2] = t20 * x + t21 * y + t22 * z + tz;
