@@ -179,6 +179,24 @@ class RayCastStatsC(C.Structure):
                 ("n_steps", C.c_uint64)]
 
 
+class EvidenceConfigC(C.Structure):
+    """elm_evidence_config (include/elimaloc_hip.h, map evidence)."""
+    _fields_ = [("sub", C.c_int32), ("max_steps", C.c_int32), ("min_range_m", C.c_double), ("obs_min_range_m", C.c_double),
+                ("obs_max_range_m", C.c_double), ("end_margin_m", C.c_double), ("end_margin_frac", C.c_double), ("origin", C.c_double * 3)]
+
+
+class EvidenceStatsC(C.Structure):
+    """elm_evidence_stats: the counts of one observation."""
+    _fields_ = [("n_cast", C.c_uint32), ("n_observing", C.c_uint32), ("n_walked", C.c_uint32), ("n_truncated", C.c_uint32),
+                ("n_through_beams", C.c_uint32), ("n_end_hit", C.c_uint32), ("n_end_free", C.c_uint32), ("_pad", C.c_uint32),
+                ("n_through_events", C.c_uint64), ("n_steps", C.c_uint64)]
+
+
+class EvidenceRuleC(C.Structure):
+    """elm_evidence_rule: when a cell's counters make it stale."""
+    _fields_ = [("min_through", C.c_uint32), ("through_per_hit", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -200,6 +218,8 @@ EXPORTS = [
     "elm_reloc_global_config_default", "elm_map_ground_heights", "elm_reloc_global_hypotheses", "elm_relocalize_global",
     "elm_freespace_config_default", "elm_map_fine_cells", "elm_map_check_free_space",
     "elm_raycast_config_default", "elm_map_raycast",
+    "elm_evidence_config_default", "elm_evidence_rule_default", "elm_evidence_create", "elm_evidence_destroy", "elm_evidence_reset",
+    "elm_evidence_accumulate", "elm_evidence_accumulate_batch", "elm_evidence_counts", "elm_evidence_stale_points",
 ]
 
 
@@ -377,6 +397,18 @@ def lib():
     L.elm_raycast_config_default.restype = None
     L.elm_map_raycast.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RayCastConfigC), C.POINTER(RayCastStatsC), dp, dp,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
+    L.elm_evidence_config_default.argtypes = [C.POINTER(EvidenceConfigC)]
+    L.elm_evidence_config_default.restype = None
+    L.elm_evidence_rule_default.argtypes = [C.POINTER(EvidenceRuleC)]
+    L.elm_evidence_rule_default.restype = None
+    L.elm_evidence_create.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.elm_evidence_destroy.argtypes = [vp]
+    L.elm_evidence_destroy.restype = None
+    L.elm_evidence_reset.argtypes = [vp, vp]
+    L.elm_evidence_accumulate.argtypes = [vp, vp, vp, dp, C.POINTER(EvidenceConfigC), C.POINTER(EvidenceStatsC), C.POINTER(C.c_uint16)]
+    L.elm_evidence_accumulate_batch.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(EvidenceConfigC), C.POINTER(EvidenceStatsC)]
+    L.elm_evidence_counts.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_evidence_stale_points.argtypes = [vp, vp, C.POINTER(EvidenceRuleC), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]
     L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
     L.elm_reloc_global_config_default.restype = None
     L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]

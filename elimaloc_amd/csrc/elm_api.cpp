@@ -2961,6 +2961,9 @@ int map_fine_table(const elm_map* cm, int sub, const elm::FineTable** ft, double
     if (info) memcpy(info, m->fine_info[s], sizeof(m->fine_info[s]));
     return ELM_OK;
 }
+bool ctx_is_alive(const elm_ctx* ctx, uint64_t id) { return ctx_alive(ctx, id); }
+uint64_t ctx_unique_id(const elm_ctx* ctx) { return ctx->id; }
+int map_point_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3) { return fine_cells_of_points(m, sub, cells3); }
 const float* scan_dev_points(const elm_scan* s, size_t* n) {
     *n = s->n;
     return (const float*)s->d_pts;

@@ -1,5 +1,6 @@
 // elm_dev_fine.hpp -- device code shared by the kernels that read the fine occupancy table of a map (FineTable, elm_internal.hpp): the
-// free-space check (elm_k_free.hip) and the ray cast (elm_k_ray.hip, section 14).
+// free-space check (elm_k_free.hip), the ray cast (elm_k_ray.hip, section 14) and the map evidence (elm_k_evid.hip,
+// section 15).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,7 +24,26 @@ __device__ __forceinline__ unsigned long long fine_probe(const FineTable& ft, in
     }
 }
 
+// The same probe, also giving the table slot of the coarse cell (left alone when the cell is absent): the map evidence addresses its
+// counters by slot.
+__device__ __forceinline__ unsigned long long fine_probe_slot(const FineTable& ft, int cx, int cy, int cz, uint32_t& slot) {
+    uint32_t h = hash3(cx, cy, cz) & ft.mask;
+    for (;;) {
+        const int4 k = ft.keys[h];
+        if (k.w == 0) return 0ull;
+        if (k.x == cx && k.y == cy && k.z == cz) {
+            slot = h;
+            return ft.masks[h];
+        }
+        h = (h + 1) & ft.mask;
+    }
+}
+
 __device__ __forceinline__ uint32_t fine_bit(int fx, int fy, int fz) { return (uint32_t)((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3)); }
+
+// The exit parameter of cell c along one axis of a cell walk: the far face in the direction of travel, from the integer cell (never
+// accumulated).
+__device__ __forceinline__ double exit_param(int c, int up, double cell, double s, double w) { return ((double)(c + up) * cell - s) / w; }
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll

@@ -46,6 +46,11 @@ const float* scan_dev_points(const elm_scan* s, size_t* n); // the resident poin
 int free_space_form(); // 0: one ray per lane; 1: ELM_CHECK=free_wave, a wave per ray (the A/B of DESIGN.md section 13)
 // ... for elm_ray.cpp
 int ray_pose_block(int dflt); // poses per workgroup of k_ray_cast: dflt, or N of ELM_CHECK=ray_poses=N (1 .. 16; the sweep of DESIGN.md section 14)
+// ... for elm_evid.cpp
+bool ctx_is_alive(const elm_ctx* ctx, uint64_t id); // the context with this unique id still exists (a child may outlive its context)
+uint64_t ctx_unique_id(const elm_ctx* ctx);
+// the fine cell of every stored point for sub, in elm_map_download_points order: [n_points][3]
+int map_point_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

@@ -382,6 +382,26 @@ constexpr int kRayMaxSteps = 1 << 20; // cap of max_steps: 256 beams x 2^20 step
 void launch_ray_cast(hipStream_t s, uint32_t pose_block, const FineTable& ft, const RayParams& rp, const float* pts, uint32_t n, const double* rows,
                      uint32_t n_poses, uint32_t* partial, elm_raycast_stats* stats, double* range_in, double* range_out, int32_t* cell, uint8_t* flag);
 
+// map evidence (elm_k_evid.hip): the ray cast's walk stopped before the measured end point, counting per occupied
+// fine cell the beams that passed through it and the beams that ended in it
+struct EvidParams { // elm_evidence_config resolved for one call
+    double ox, oy, oz, t_min, obs_min_r2, obs_max_r2, margin_m, margin_frac;
+    int32_t max_steps, _pad;
+};
+struct EvidJob { // one observation: a resident scan at a pose
+    const float* pts; // packed xyz
+    uint32_t n;       // beams
+    uint32_t chunk0;  // the job's first 256-beam chunk among all chunks of the launch
+    double rows[12];  // (R_r0, R_r1, R_r2, t_r) per row r
+};
+constexpr int kEvidMaxJobs = 4096;
+constexpr int kEvidWords = 9; // a partial: cast, observing, walked, truncated, through beams, end hit, end free, through events, steps of a chunk
+// jobs [n_jobs] with ascending chunk0, n_chunks = all chunks of the launch (> 0); base [ft.mask + 1]: the first counter of every table slot
+// (prefix of the masks' popcounts in slot order); through / hit: the counters; partial [n_chunks][kEvidWords] scratch; stats [n_jobs];
+// events [jobs[0].n] or nullptr (one job only)
+void launch_evid_walk(hipStream_t s, const FineTable& ft, const EvidParams& ep, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks,
+                      const uint32_t* base, uint32_t* through, uint32_t* hit, uint32_t* partial, elm_evidence_stats* stats, uint16_t* events);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

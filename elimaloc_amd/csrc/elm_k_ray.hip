@@ -11,13 +11,6 @@
 
 namespace elm {
 
-namespace {
-
-// The exit parameter of cell c along one axis: the far face in the direction of travel, from the integer cell (never accumulated).
-__device__ __forceinline__ double exit_param(int c, int up, double cell, double s, double w) { return ((double)(c + up) * cell - s) / w; }
-
-} // namespace
-
 // K7a.  Workgroup = 256 consecutive beams (one per lane, float64 in registers) x pose_block consecutive poses, whose rows are
 // workgroup-uniform.  The beam's length, direction, cast / compared state and tolerance do not depend on the pose: they are formed once.
 // Per step a lane takes one 3-way minimum, one integer add, one multiply-subtract-divide for the stepped axis and a bit test of the

@@ -111,10 +111,13 @@ class PcmMatching:
         elif m == IcpMethod.GICP:
             self.local_map_.CalPointCovAll(self.cfg_.registration.gicp_cov_search_dist)
 
-    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None):
+    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None, evidence=None, evidence_cfg=None):
         """pcm.cpp:198-324.  Returns None when the reference would publish nothing (deskew / pose sync / ICP failure),
         else dict(pose_ego 4x4 float64, covariance 6x6 row-major, fitness, time).  free_space: a FreeSpaceConfig -- the result also
-        carries "free_space", the free-space statistics of the registered pose (VoxelHashMap.CheckFreeSpace); nothing else changes."""
+        carries "free_space", the free-space statistics of the registered pose (VoxelHashMap.CheckFreeSpace); nothing else changes.
+        evidence: a MapEvidence of the local map -- after a successful registration the source scan is accumulated into it at the
+        registered pose (evidence_cfg: an EvidenceConfig, default its defaults) and the result carries "evidence", that observation's
+        statistics; nothing else changes."""
         import time
         tm = self.timings_ = {}
         t0 = time.perf_counter()
@@ -154,6 +157,9 @@ class PcmMatching:
         if free_space is not None:
             out["free_space"] = self.local_map_.CheckFreeSpace(src, pose[None], free_space)[0]
             lap("free_space_ms")
+        if evidence is not None:
+            out["evidence"] = evidence.Accumulate(src, pose, evidence_cfg)
+            lap("evidence_ms")
         return out
 
     def _node_config(self):

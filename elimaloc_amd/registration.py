@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+from ._lib import (ElmError, EvidenceConfigC, EvidenceRuleC, EvidenceStatsC, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
                    check)
 
 
@@ -107,6 +107,40 @@ def RayCastStats(st):
     for k in ("match", "through", "front"):
         d[k + "_share"] = d["n_" + k] / d["n_compared"] if d["n_compared"] else 0.0
     return d
+
+
+def EvidenceConfig(**kw):
+    """elm_evidence_config with its defaults (sub 4, max_steps 4096, walk from 1 m, observing 2 .. 50 m, end margins 1 m / 0.2 L, origin 0)."""
+    cfg = EvidenceConfigC()
+    _lib.lib().elm_evidence_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"EvidenceConfig has no field {k}")
+        if k == "origin":
+            cfg.origin = (C.c_double * 3)(*[float(x) for x in v])
+        else:
+            setattr(cfg, k, int(v) if k in ("sub", "max_steps") else float(v))
+    return cfg
+
+
+def EvidenceRule(**kw):
+    """elm_evidence_rule with its defaults (min_through 3, through_per_hit 4): a cell is stale when through >= min_through and
+    through >= through_per_hit * hit.  A starting point, not a measured optimum."""
+    rule = EvidenceRuleC()
+    _lib.lib().elm_evidence_rule_default(C.byref(rule))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(rule, k):
+            raise AttributeError(f"EvidenceRule has no field {k}")
+        setattr(rule, k, int(v))
+    return rule
+
+
+_EVID_FIELDS = ("n_cast", "n_observing", "n_walked", "n_truncated", "n_through_beams", "n_end_hit", "n_end_free", "n_through_events", "n_steps")
+
+
+def EvidenceStats(st):
+    """elm_evidence_stats of one observation as a dict."""
+    return {k: int(getattr(st, k)) for k in _EVID_FIELDS}
 
 
 def _global_stats_dict(st):
@@ -554,6 +588,22 @@ class VoxelHashMap:
         scan = np.ascontiguousarray(local.astype(np.float32)).reshape(-1, 3)
         return (scan, hit[which[first]], pick) if return_index else scan
 
+    def Evidence(self, sub=4):
+        """A MapEvidence of this map: per occupied fine cell (FineCells(sub)) the beams seen through it and the beams that ended in it,
+        kept on the device and fed by Accumulate.  It belongs to the map as built now: AddPoints / Clear afterwards invalidate it."""
+        return MapEvidence(self, sub)
+
+    def WithoutStale(self, evidence, rule=None):
+        """A new map (same voxel size and cap, same context) built by the usual build from the stored points that evidence.StalePoints(rule)
+        does not flag."""
+        if evidence.map is not self:
+            raise ElmError("WithoutStale: the evidence belongs to another map")
+        flags = evidence.StalePoints(rule)
+        keep = self.Pointcloud()[~flags] if flags.size else np.zeros((0, 3))
+        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx)
+        out.AddPoints(keep.astype(np.float32))  # stored coordinates are float32 values: the conversion is exact
+        return out
+
     def FindGroundHeights(self, xy):
         """FindGroundHeight of many xy positions [n, 2] on the device (elm_map_ground_heights, bit for bit the single query) -> (found bool
         [n], z [n]; 0 where not found)."""
@@ -627,6 +677,100 @@ class Scan:
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().elm_scan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MapEvidence:
+    """Map change evidence (elm_evidence, include/elimaloc_hip.h "map evidence"): two uint32 counters per occupied fine cell of a map,
+    resident on the device.  Made by VoxelHashMap.Evidence(sub)."""
+
+    def __init__(self, voxel_map, sub=4):
+        self.map, self.ctx, self.sub = voxel_map, voxel_map.ctx, int(sub)
+        self._map_h = voxel_map._handle()
+        self._h = C.c_void_p()
+        check(_lib.lib().elm_evidence_create(self.ctx._h, self._map_h, self.sub, C.byref(self._h)), self.ctx._h, "elm_evidence_create")
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ElmError("MapEvidence: closed")
+        if self.map._h is not self._map_h:
+            raise ElmError("MapEvidence: its map was rebuilt or cleared")
+        return self._h
+
+    def Accumulate(self, scans, poses, cfg=None, events=False):
+        """Accumulate observations (elm_evidence_accumulate / _batch).  scans: one scan (a resident Scan, or (m, 3) points uploaded for the
+        call) with one pose [4, 4] -> its EvidenceStats dict; or a list of scans with poses [n, 4, 4] -> a list of dicts, all jobs in one
+        launch (the same Scan may appear several times).  events=True (one scan only): also the through events of every beam, uint16 [m],
+        in the resident order (Scan.points()) for a Scan, in the caller's order for an array."""
+        cfg = cfg if cfg is not None else EvidenceConfig(sub=self.sub)
+        h = self._handle()
+        L = _lib.lib()
+        single = isinstance(scans, Scan) or (isinstance(scans, np.ndarray) and scans.ndim == 2)
+        if single:
+            sc = scans if isinstance(scans, Scan) else Scan(self.ctx, scans)
+            T = _colmajor16(poses)
+            st = EvidenceStatsC()
+            ev = np.zeros(max(sc.n, 1), np.uint16) if events else None
+            check(L.elm_evidence_accumulate(self.ctx._h, h, sc._h, _dp(T), C.byref(cfg), C.byref(st),
+                                            ev.ctypes.data_as(C.POINTER(C.c_uint16)) if events else None), self.ctx._h, "elm_evidence_accumulate")
+            if not events:
+                return EvidenceStats(st)
+            ev = ev[:sc.n]
+            if not isinstance(scans, Scan) and sc.n:  # back to the caller's order: equal points are equal beams
+                key = np.dtype((np.void, 12))
+                res = np.ascontiguousarray(sc.points()).view(key).ravel()
+                own = np.ascontiguousarray(scans, dtype=np.float32).reshape(-1, 3).view(key).ravel()
+                order = np.argsort(res, kind="stable")
+                ev = np.ascontiguousarray(ev[order[np.searchsorted(res[order], own)]])
+            return EvidenceStats(st), ev
+        if events:
+            raise ElmError("MapEvidence.Accumulate: events are returned for a single scan only")
+        scs = [s if isinstance(s, Scan) else Scan(self.ctx, s) for s in scans]
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        if P.size // 16 != len(scs):
+            raise ElmError("MapEvidence.Accumulate: one pose per scan")
+        n = len(scs)
+        hs = (C.c_void_p * max(n, 1))(*[s._h.value for s in scs])
+        st = (EvidenceStatsC * max(n, 1))()
+        check(L.elm_evidence_accumulate_batch(self.ctx._h, h, hs, _dp(P), n, C.byref(cfg), st), self.ctx._h, "elm_evidence_accumulate_batch")
+        return [EvidenceStats(st[j]) for j in range(n)]
+
+    def Counts(self):
+        """(through, hit): uint32 [n_cells] each, entry for entry with map.FineCells(sub)."""
+        n = C.c_size_t(0)
+        L = _lib.lib()
+        h = self._handle()
+        check(L.elm_evidence_counts(self.ctx._h, h, None, None, 0, C.byref(n)), self.ctx._h, "elm_evidence_counts")
+        t, hit = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        check(L.elm_evidence_counts(self.ctx._h, h, t.ctypes.data_as(u32), hit.ctypes.data_as(u32), n.value, C.byref(n)), self.ctx._h,
+              "elm_evidence_counts")
+        return t[:n.value], hit[:n.value]
+
+    def Reset(self):
+        check(_lib.lib().elm_evidence_reset(self.ctx._h, self._handle()), self.ctx._h, "elm_evidence_reset")
+
+    def StalePoints(self, rule=None):
+        """bool [n_points] in map.Pointcloud() order: the stored points whose fine cell is stale by `rule` (EvidenceRule())."""
+        rule = rule if rule is not None else EvidenceRule()
+        n = C.c_size_t(0)
+        L = _lib.lib()
+        h = self._handle()
+        check(L.elm_evidence_stale_points(self.ctx._h, h, C.byref(rule), None, 0, C.byref(n)), self.ctx._h, "elm_evidence_stale_points")
+        f = np.zeros(max(n.value, 1), np.uint8)
+        check(L.elm_evidence_stale_points(self.ctx._h, h, C.byref(rule), f.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n)),
+              self.ctx._h, "elm_evidence_stale_points")
+        return f[:n.value].astype(bool)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().elm_evidence_destroy(self._h)
             self._h = None
 
     def __del__(self):

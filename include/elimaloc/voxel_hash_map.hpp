@@ -96,6 +96,16 @@ struct RayCastConfig : elm_raycast_config {
     RayCastConfig() { elm_raycast_config_default(this); }
 };
 
+// elm_evidence_config with its defaults (include/elimaloc_hip.h, map evidence): the walk of MapEvidence::Accumulate
+struct EvidenceConfig : elm_evidence_config {
+    EvidenceConfig() { elm_evidence_config_default(this); }
+};
+
+// elm_evidence_rule with its defaults: when a cell's counters make it stale (a starting point, not a measured optimum)
+struct EvidenceRule : elm_evidence_rule {
+    EvidenceRule() { elm_evidence_rule_default(this); }
+};
+
 struct VoxelHashMap {
     using RadarPointVector = std::vector<PointStruct>;
     using RadarPointVectorTuple = std::tuple<RadarPointVector, RadarPointVector>;
@@ -367,4 +377,73 @@ private:
     mutable elm_map* map_ = nullptr;
     bool want_voxel_cov_ = false;
     double want_point_cov_ = -1.0;
+};
+
+// Map change evidence (include/elimaloc_hip.h, map evidence): per occupied fine cell of a map the beams seen through it and the beams that
+// ended in it, kept on the device and fed with scans at trusted poses.  It is bound to the map as built when it is made: destroy it
+// before the map, and do not use it after the map has taken more points.
+class MapEvidence {
+public:
+    using RadarPointVector = VoxelHashMap::RadarPointVector;
+    explicit MapEvidence(const VoxelHashMap& map, int sub = 4) : sub_(sub) {
+        elimaloc::check(elm_evidence_create(VoxelHashMap::ctx(), map.handle(), sub, &ev_), VoxelHashMap::ctx(), "elm_evidence_create");
+    }
+    MapEvidence(const MapEvidence&) = delete; // owns device memory
+    MapEvidence& operator=(const MapEvidence&) = delete;
+    ~MapEvidence() { elm_evidence_destroy(ev_); }
+
+    // One observation per scan (sensor frame, PointStruct::pose) at its pose, all in one launch (elm_evidence_accumulate_batch): the
+    // statistics of every observation.  config.sub is set to this object's.
+    inline std::vector<elm_evidence_stats> Accumulate(const std::vector<RadarPointVector>& scans, const std::vector<elimaloc::Matrix4d>& poses,
+                                                      EvidenceConfig config = EvidenceConfig()) {
+        config.sub = sub_;
+        std::vector<elm_evidence_stats> stats(scans.size());
+        if (scans.empty() || scans.size() != poses.size()) {
+            elimaloc::check(scans.empty() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "MapEvidence::Accumulate");
+            return stats;
+        }
+        std::vector<double> T(16 * poses.size());
+        for (size_t h = 0; h < poses.size(); ++h)
+            for (int k = 0; k < 16; ++k) T[16 * h + k] = poses[h].data()[k]; // column-major on both sides
+        std::vector<elm_scan*> res(scans.size(), nullptr);
+        int rc = ELM_OK;
+        for (size_t j = 0; j < scans.size() && rc == ELM_OK; ++j) {
+            std::vector<float> xyz(3 * scans[j].size());
+            for (size_t i = 0; i < scans[j].size(); ++i)
+                for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scans[j][i].pose(k);
+            rc = elm_scan_upload(VoxelHashMap::ctx(), xyz.data(), scans[j].size(), scans[j].size(), &res[j]);
+        }
+        if (rc == ELM_OK) rc = elm_evidence_accumulate_batch(VoxelHashMap::ctx(), ev_, res.data(), T.data(), (int)scans.size(), &config, stats.data());
+        for (elm_scan* s : res)
+            if (s) elm_scan_destroy(s);
+        elimaloc::check(rc, VoxelHashMap::ctx(), "MapEvidence::Accumulate");
+        return stats;
+    }
+    inline elm_evidence_stats Accumulate(const RadarPointVector& scan, const elimaloc::Matrix4d& pose, const EvidenceConfig& config = EvidenceConfig()) {
+        return Accumulate(std::vector<RadarPointVector>(1, scan), std::vector<elimaloc::Matrix4d>(1, pose), config)[0];
+    }
+
+    // The counters, entry for entry with elm_map_fine_cells(map, sub)
+    inline void Counts(std::vector<uint32_t>& through, std::vector<uint32_t>& hit) const {
+        size_t n = 0;
+        elimaloc::check(elm_evidence_counts(VoxelHashMap::ctx(), ev_, nullptr, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_evidence_counts");
+        through.assign(n, 0);
+        hit.assign(n, 0);
+        if (n) elimaloc::check(elm_evidence_counts(VoxelHashMap::ctx(), ev_, through.data(), hit.data(), n, &n), VoxelHashMap::ctx(), "elm_evidence_counts");
+    }
+
+    // One flag per stored point (elm_map_download_points order): 1 when its fine cell is stale by the rule
+    inline std::vector<uint8_t> StalePoints(const EvidenceRule& rule = EvidenceRule()) const {
+        size_t n = 0;
+        elimaloc::check(elm_evidence_stale_points(VoxelHashMap::ctx(), ev_, &rule, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_evidence_stale_points");
+        std::vector<uint8_t> flags(n, 0);
+        if (n) elimaloc::check(elm_evidence_stale_points(VoxelHashMap::ctx(), ev_, &rule, flags.data(), n, &n), VoxelHashMap::ctx(), "elm_evidence_stale_points");
+        return flags;
+    }
+
+    inline void Reset() { elimaloc::check(elm_evidence_reset(VoxelHashMap::ctx(), ev_), VoxelHashMap::ctx(), "elm_evidence_reset"); }
+
+private:
+    elm_evidence* ev_ = nullptr;
+    int sub_ = 4;
 };

@@ -507,6 +507,87 @@ void elm_raycast_config_default(elm_raycast_config* c);
 int elm_map_raycast(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses, const elm_raycast_config* c,
                     elm_raycast_stats* stats, double* range_in, double* range_out, int32_t* cell, uint8_t* flag);
 
+/* ---------------------------------------------------------------- map evidence -------------------- */
+/* Given poses we trust, which parts of the map are no longer there?  An evidence object holds two uint32 counters per occupied fine cell
+ * of a map (the cells of elm_map_fine_cells(map, sub)): THROUGH, the beams that passed through the cell on the way to a farther end point,
+ * and HIT, the beams that ended in it.  It lives on the device between calls and is fed by many (scan, pose) observations in one launch.
+ * The walk is the ray cast's (see "ray casting"), stopped a margin before the measured end point, as the free-space check stops its samples.
+ * All arithmetic float64 without contraction; q / cell below is formed as the fine occupancy forms it (q * (1 / cell) where cell is a power
+ * of two, the same bits).  One OBSERVATION is one resident scan at one pose T = [R | t].  Per beam i (scan point p, float32 -> float64,
+ * origin o):
+ *   d = p - o, L2 = (d_x d_x + d_y d_y) + d_z d_z, L = sqrt(L2), u = d / L;
+ *   the beam is CAST when L2 > 0 and finite;
+ *   it is OBSERVING when cast and obs_min_range_m^2 <= L2 <= obs_max_range_m^2; only observing beams touch any counter;
+ *   end point: q_r = ((R_r0 p_x + R_r1 p_y) + R_r2 p_z) + t_r, e_r = (int)floor(q_r / cell);
+ *     if e is an occupied cell then hit[e] += 1 and the beam is END-HIT, else it is END-FREE;
+ *   reach = L - fmax(end_margin_m, end_margin_frac L); the beam WALKS when reach > min_range_m;
+ *   the walk is the ray cast's with reach in the place of max_range_m:
+ *     s_r = ((R_r0 o_x + R_r1 o_y) + R_r2 o_z) + t_r, w_r = (R_r0 u_x + R_r1 u_y) + R_r2 u_z;
+ *     t_in = min_range_m, start cell c_r = (int)floor((s_r + w_r t_in) / cell);
+ *     sg_r = +1 / -1 / 0 by the sign of w_r, tx_r = ((double)(c_r + (sg_r > 0 ? 1 : 0)) cell - s_r) / w_r, +inf when sg_r = 0, formed from
+ *       the integer cell every time that axis steps;
+ *     STEP: the axis with the smallest tx (ties: x before y before z), t_next = fmax(t_in, tx_axis);
+ *     if t_next > reach the walk ends BY REACH; else if max_steps steps were already taken it ends BY STEPS (the beam is TRUNCATED);
+ *     else the current cell is LEFT: t_in = t_next, c_axis += sg_axis, tx_axis is formed anew, one step is counted; step again;
+ *   every occupied cell that the walk leaves by a step is SEEN THROUGH: through[c] += 1, one through EVENT of the beam;
+ *     the cell in which the walk ends is not counted;
+ *   a beam visits a cell at most once (the walk is monotone on every axis), so one beam adds at most 1 to any one counter.
+ * Why the margins: from height h over flat ground a beam stays within one cell c of the ground over the last c / h of its length at any
+ * range (the free-space check's grazing argument); without a fractional margin every ground return would see through the ground before it.
+ * Every result is an integer and integer addition commutes: the counters and stats are the same on every run, for every job order and
+ * every search-index form. */
+typedef struct elm_evidence elm_evidence;
+typedef struct elm_evidence_config {
+    int32_t sub;            /* fine cells per voxel edge: 1, 2 or 4; must equal the evidence object's */
+    int32_t max_steps;      /* cap of the steps of one walk (1 .. 1048576) */
+    double min_range_m;     /* the walk starts here along the beam (>= 0) */
+    double obs_min_range_m, obs_max_range_m; /* observing beams: min^2 <= L2 <= max^2 */
+    double end_margin_m, end_margin_frac;    /* the walk stops max(end_margin_m, end_margin_frac L) before the end point */
+    double origin[3];       /* the beam origin in the scan frame */
+} elm_evidence_config;
+typedef struct elm_evidence_stats {
+    uint32_t n_cast, n_observing, n_walked, n_truncated;
+    uint32_t n_through_beams;    /* observing beams with at least one through event */
+    uint32_t n_end_hit, n_end_free, _pad;
+    uint64_t n_through_events, n_steps;
+} elm_evidence_stats;
+/* The rule that turns counters into "stale": a cell is stale when through >= min_through and through >= through_per_hit * hit (the product
+ * in 64 bits).  The defaults are a starting point, not a measured optimum. */
+typedef struct elm_evidence_rule {
+    uint32_t min_through;       /* default 3 */
+    uint32_t through_per_hit;   /* default 4 */
+} elm_evidence_rule;
+/* sub 4, max_steps 4096, min_range 1 m, observing 2 .. 50 m, margins 1 m / 0.2 L, origin 0 */
+void elm_evidence_config_default(elm_evidence_config* c);
+/* min_through 3, through_per_hit 4 */
+void elm_evidence_rule_default(elm_evidence_rule* r);
+/* An evidence object bound to (map, sub), sub in {1, 2, 4}, all counters zero.  The map's fine occupancy table is built when it is not there
+ * yet.  The object is destroyed before its map (it is not used after elm_map_destroy of that map; destroying it later only releases its
+ * own memory, as a map or scan destroyed after its context does).  An empty map gives zero cells: accumulation runs and counts nothing.
+ * ELM_ERR_UNSUPPORTED on a device group's lead or with a communicator / hook attached, here and in every call below that takes ctx. */
+int elm_evidence_create(elm_ctx* ctx, const elm_map* map, int sub, elm_evidence** out);
+void elm_evidence_destroy(elm_evidence* ev);
+/* All counters and the object's beam total back to zero. */
+int elm_evidence_reset(elm_ctx* ctx, elm_evidence* ev);
+/* One observation: the resident scan at pose T16 (column-major).  stats (may be NULL): the observation's counts.  events (may be NULL):
+ * events[elm_scan_size(scan)], the through events of every beam in the resident scan's order, saturating at 65535, 0 for a beam that does
+ * not observe.  ELM_ERR_INVALID: cfg.sub differs from the object's, a non-finite pose entry, a scan or evidence of another context, a
+ * batch in flight.  The object keeps a 64-bit total of the beams accumulated; a call that would carry it beyond 2^32 - 1 is refused with
+ * ELM_ERR_UNSUPPORTED before anything is launched, so no counter can wrap. */
+int elm_evidence_accumulate(elm_ctx* ctx, elm_evidence* ev, const elm_scan* scan, const double T16[16], const elm_evidence_config* cfg,
+                            elm_evidence_stats* stats, uint16_t* events);
+/* n_jobs (1 .. 4096) observations in one launch: scans[j] at poses16 + 16 j.  Jobs may have any sizes, 0 included; the same scan may appear
+ * several times.  stats (may be NULL): stats[n_jobs].  The counters afterwards are those of the same jobs accumulated one by one, in any
+ * order. */
+int elm_evidence_accumulate_batch(elm_ctx* ctx, elm_evidence* ev, const elm_scan* const* scans, const double* poses16, int n_jobs,
+                                  const elm_evidence_config* cfg, elm_evidence_stats* stats);
+/* The counters, entry for entry in elm_map_fine_cells' ascending (x, y, z) order: min(cap, count) written, *n = count (through / hit may
+ * each be NULL). */
+int elm_evidence_counts(elm_ctx* ctx, const elm_evidence* ev, uint32_t* through, uint32_t* hit, size_t cap, size_t* n);
+/* flags: one uint8 per stored point in elm_map_download_points order, 1 when the point's fine cell is stale by `rule`; min(cap, count)
+ * written, *n = count (flags may be NULL when cap = 0). */
+int elm_evidence_stale_points(elm_ctx* ctx, const elm_evidence* ev, const elm_evidence_rule* rule, uint8_t* flags, size_t cap, size_t* n);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {
