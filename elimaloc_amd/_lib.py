@@ -197,6 +197,25 @@ class EvidenceRuleC(C.Structure):
     _fields_ = [("min_through", C.c_uint32), ("through_per_hit", C.c_uint32)]
 
 
+class GrowthConfigC(C.Structure):
+    """elm_growth_config (include/elimaloc_hip.h, map growth): the evidence config's fields plus clearance_cells."""
+    _fields_ = [("sub", C.c_int32), ("max_steps", C.c_int32), ("min_range_m", C.c_double), ("obs_min_range_m", C.c_double),
+                ("obs_max_range_m", C.c_double), ("end_margin_m", C.c_double), ("end_margin_frac", C.c_double), ("origin", C.c_double * 3),
+                ("clearance_cells", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GrowthStatsC(C.Structure):
+    """elm_growth_stats: the counts of one observation."""
+    _fields_ = [("n_cast", C.c_uint32), ("n_observing", C.c_uint32), ("n_walked", C.c_uint32), ("n_truncated", C.c_uint32),
+                ("n_end_hit", C.c_uint32), ("n_end_near", C.c_uint32), ("n_end_new", C.c_uint32), ("n_end_out", C.c_uint32),
+                ("n_through_beams", C.c_uint32), ("n_dropped", C.c_uint32), ("n_through_events", C.c_uint64), ("n_steps", C.c_uint64)]
+
+
+class GrowthRuleC(C.Structure):
+    """elm_growth_rule: when a candidate cell's counters make it appeared."""
+    _fields_ = [("min_hit", C.c_uint32), ("hit_per_through", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -220,6 +239,8 @@ EXPORTS = [
     "elm_raycast_config_default", "elm_map_raycast",
     "elm_evidence_config_default", "elm_evidence_rule_default", "elm_evidence_create", "elm_evidence_destroy", "elm_evidence_reset",
     "elm_evidence_accumulate", "elm_evidence_accumulate_batch", "elm_evidence_counts", "elm_evidence_stale_points",
+    "elm_growth_config_default", "elm_growth_rule_default", "elm_growth_create", "elm_growth_destroy", "elm_growth_reset",
+    "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
 ]
 
 
@@ -409,6 +430,19 @@ def lib():
     L.elm_evidence_accumulate_batch.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(EvidenceConfigC), C.POINTER(EvidenceStatsC)]
     L.elm_evidence_counts.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
     L.elm_evidence_stale_points.argtypes = [vp, vp, C.POINTER(EvidenceRuleC), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_growth_config_default.argtypes = [C.POINTER(GrowthConfigC)]
+    L.elm_growth_config_default.restype = None
+    L.elm_growth_rule_default.argtypes = [C.POINTER(GrowthRuleC)]
+    L.elm_growth_rule_default.restype = None
+    L.elm_growth_create.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.elm_growth_destroy.argtypes = [vp]
+    L.elm_growth_destroy.restype = None
+    L.elm_growth_reset.argtypes = [vp, vp]
+    L.elm_growth_accumulate.argtypes = [vp, vp, vp, dp, C.POINTER(GrowthConfigC), C.POINTER(GrowthStatsC), C.POINTER(C.c_uint16)]
+    L.elm_growth_accumulate_batch.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(GrowthConfigC), C.POINTER(GrowthStatsC)]
+    L.elm_growth_cells.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t,
+                                   C.POINTER(C.c_size_t)]
+    L.elm_growth_appeared_points.argtypes = [vp, vp, C.POINTER(GrowthRuleC), dp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
     L.elm_reloc_global_config_default.restype = None
     L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]

@@ -1,6 +1,6 @@
 // elm_dev_fine.hpp -- device code shared by the kernels that read the fine occupancy table of a map (FineTable, elm_internal.hpp): the
-// free-space check (elm_k_free.hip), the ray cast (elm_k_ray.hip, section 14) and the map evidence (elm_k_evid.hip,
-// section 15).
+// free-space check (elm_k_free.hip), the ray cast (elm_k_ray.hip, section 14), the map evidence (elm_k_evid.hip,
+// section 15) and the map growth (elm_k_grow.hip, section 16), with the tables that the growth kernels fill themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +40,53 @@ __device__ __forceinline__ unsigned long long fine_probe_slot(const FineTable& f
 }
 
 __device__ __forceinline__ uint32_t fine_bit(int fx, int fy, int fz) { return (uint32_t)((((fx & 3) << 2) | (fy & 3)) << 2 | (fz & 3)); }
+
+// ---- the tables a kernel fills itself (map growth, elm_k_grow.hip): open addressing over packed 64-bit keys
+// A cell with every |c_r| < 2^20 as one key: 21 bits per axis, biased by 2^20, the top bit set so that 0 is "empty".  Ascending keys are
+// ascending (x, y, z).
+__host__ __device__ __forceinline__ bool grow_in_range(int x, int y, int z) {
+    return x > -kGrowLim && x < kGrowLim && y > -kGrowLim && y < kGrowLim && z > -kGrowLim && z < kGrowLim;
+}
+__host__ __device__ __forceinline__ unsigned long long grow_key(int x, int y, int z) {
+    return (1ull << 63) | ((unsigned long long)(uint32_t)(x + kGrowLim) << 42) | ((unsigned long long)(uint32_t)(y + kGrowLim) << 21) |
+           (unsigned long long)(uint32_t)(z + kGrowLim);
+}
+
+// The slot of `key` in a table that is stable during the launch (plain loads), or false when the key is absent.  The table is at most
+// half full, so an empty slot ends every probe; the loop is bounded by the slot count all the same.
+__device__ __forceinline__ bool grow_find(const unsigned long long* __restrict__ keys, uint32_t mask, uint32_t h, unsigned long long key,
+                                          uint32_t& slot) {
+    h &= mask;
+    for (uint32_t tries = 0; tries <= mask; ++tries) {
+        const unsigned long long k = keys[h];
+        if (k == key) {
+            slot = h;
+            return true;
+        }
+        if (k == 0ull) return false;
+        h = (h + 1) & mask;
+    }
+    return false;
+}
+
+// The slot of `key` in a table that other lanes fill at the same time: one 64-bit compare-and-swap per slot tried.  It returns empty (the
+// slot is now this key's), this key (the slot is shared: lanes of one wave insert the same key together) or another key (the next slot).
+// No lock, and no lane ever waits for another lane.  false when the bounded loop runs out (a full table: the host's capacity guard
+// excludes it).
+__device__ __forceinline__ bool grow_claim(unsigned long long* __restrict__ keys, uint32_t mask, uint32_t h, unsigned long long key,
+                                           uint32_t& slot, bool& fresh) {
+    h &= mask;
+    for (uint32_t tries = 0; tries <= mask; ++tries) {
+        const unsigned long long was = atomicCAS(keys + h, 0ull, key);
+        if (was == 0ull || was == key) {
+            slot = h;
+            fresh = was == 0ull;
+            return true;
+        }
+        h = (h + 1) & mask;
+    }
+    return false;
+}
 
 // The exit parameter of cell c along one axis of a cell walk: the far face in the direction of travel, from the integer cell (never
 // accumulated).

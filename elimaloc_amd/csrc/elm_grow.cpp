@@ -1,0 +1,354 @@
+// elm_grow.cpp -- map growth (include/elimaloc_hip.h, "map growth"): the growth object (two open-addressing tables
+// on the device that the kernels of elm_k_grow.hip fill: candidate fine cells with their counters, and the coarse cells' masks), the
+// argument checks and the capacity guard, the job table, the launches, the downloads and the rule.  Host-side C++17.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "elm_hostapi.hpp"
+#include "elm_internal.hpp"
+
+using namespace elm;
+
+struct elm_growth {
+    elm_ctx* ctx = nullptr;
+    uint64_t ctx_id = 0; // the owning context's unique id (as maps and scans keep it)
+    const elm_map* map = nullptr;
+    int sub = 0;
+    size_t capacity = 0;
+    size_t slots = 0;          // a power of two >= 2 * capacity
+    GrowTables t{};            // device arrays of `slots` entries each (sums: 3 per slot), and the candidate count
+    uint64_t count = 0;        // the candidates, exact after every call
+    uint64_t total_beams = 0;  // beams handed to accumulate calls since creation / reset
+};
+
+extern "C" void elm_growth_config_default(elm_growth_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->sub = 4;
+    c->max_steps = 4096;
+    c->min_range_m = 1.0;
+    c->obs_min_range_m = 2.0;
+    c->obs_max_range_m = 50.0;
+    c->end_margin_m = 1.0;
+    c->end_margin_frac = 0.2;
+    c->clearance_cells = 1;
+}
+
+extern "C" void elm_growth_rule_default(elm_growth_rule* r) {
+    if (!r) return;
+    r->min_hit = 3;
+    r->hit_per_through = 4;
+}
+
+namespace {
+
+constexpr size_t kGrowMaxCapacity = (size_t)1 << 30;
+
+bool fin_ge0(double v) { return isfinite(v) && v >= 0.0; }
+
+bool config_ok(const elm_growth_config* c) {
+    if (!c || !(c->sub == 1 || c->sub == 2 || c->sub == 4) || c->max_steps < 1 || c->max_steps > kRayMaxSteps) return false;
+    if (c->clearance_cells < 0 || c->clearance_cells > 2) return false;
+    if (!fin_ge0(c->min_range_m) || !fin_ge0(c->obs_min_range_m) || !(isfinite(c->obs_max_range_m) && c->obs_max_range_m >= c->obs_min_range_m)) return false;
+    if (!fin_ge0(c->end_margin_m) || !fin_ge0(c->end_margin_frac)) return false;
+    return isfinite(c->origin[0]) && isfinite(c->origin[1]) && isfinite(c->origin[2]);
+}
+
+// one rank, no exchange (as the other map queries)
+int check_plain(elm_ctx* ctx, const char* what) {
+    if ((elm_host::ctx_group(ctx) && !elm_multi::in_worker()) || elm_host::ctx_exchange_attached(ctx)) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    return ELM_OK;
+}
+
+// the checks every call on an existing object shares
+int check_object(elm_ctx* ctx, const elm_growth* g, const char* what) {
+    if (!ctx || !g) return ELM_ERR_INVALID;
+    int rc = check_plain(ctx, what);
+    if (rc != ELM_OK) return rc;
+    if (g->ctx != ctx || g->ctx_id != elm_host::ctx_unique_id(ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    return ELM_OK;
+}
+
+int dev_error(elm_ctx* ctx, const char* what, hipError_t e) {
+    elm_host::ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
+    return ELM_ERR_DEVICE;
+}
+
+void growth_free(elm_growth* g) {
+    if (!g) return;
+    if (elm_host::ctx_is_alive(g->ctx, g->ctx_id)) (void)hipSetDevice(elm_host::ctx_device(g->ctx)); // a context destroyed first: just release
+    void* arrays[] = {g->t.ckeys, g->t.cmasks, g->t.fkeys, g->t.hit, g->t.through, g->t.sums, g->t.count};
+    for (void* p : arrays)
+        if (p) (void)hipFree(p);
+    delete g;
+}
+
+// every table entry and the candidate count to zero, in stream order
+hipError_t clear_tables(const elm_growth* g, hipStream_t st) {
+    const size_t s = g->slots;
+    hipError_t e = hipMemsetAsync(g->t.ckeys, 0, s * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.cmasks, 0, s * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.fkeys, 0, s * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.hit, 0, s * sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.through, 0, s * sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.sums, 0, 3 * s * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(g->t.count, 0, sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+
+int create_impl(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    const FineTable* ft = nullptr;
+    int rc = elm_host::map_fine_table(map, sub, &ft, nullptr); // built now when it is not there yet
+    if (rc != ELM_OK) return rc;
+    elm_growth* g = new elm_growth();
+    g->ctx = ctx;
+    g->ctx_id = elm_host::ctx_unique_id(ctx);
+    g->map = map;
+    g->sub = sub;
+    g->capacity = capacity;
+    g->slots = 2;
+    while (g->slots < 2 * capacity) g->slots <<= 1;
+    g->t.mask = (uint32_t)(g->slots - 1);
+    const size_t s = g->slots;
+    hipError_t e = hipMalloc((void**)&g->t.ckeys, s * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.cmasks, s * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.fkeys, s * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.hit, s * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.through, s * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.sums, 3 * s * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->t.count, 256);
+    if (e == hipSuccess) e = clear_tables(g, (hipStream_t)elm_ctx_stream(ctx));
+    if (e != hipSuccess) {
+        growth_free(g);
+        return dev_error(ctx, "elm_growth_create", e);
+    }
+    *out = g;
+    return ELM_OK;
+}
+
+int accumulate_impl(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, uint32_t n_jobs,
+                    const elm_growth_config* c, elm_growth_stats* stats, uint16_t* events) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    const FineTable* ft = nullptr;
+    int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
+    if (rc != ELM_OK) return rc;
+    std::vector<EvidJob> jobs(n_jobs);
+    uint64_t beams = 0, chunks = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        size_t n = 0;
+        jobs[j].pts = elm_host::scan_dev_points(scans[j], &n);
+        jobs[j].n = (uint32_t)n;
+        jobs[j].chunk0 = (uint32_t)chunks;
+        for (int r = 0; r < 3; ++r)
+            for (int q = 0; q < 4; ++q) jobs[j].rows[r * 4 + q] = poses16[16 * (size_t)j + q * 4 + r];
+        beams += n;
+        chunks += (n + 255) / 256;
+    }
+    // the table can never fill: one beam makes at most one candidate
+    if (g->count + beams > (uint64_t)g->capacity) {
+        elm_host::ctx_set_error(ctx, "map growth: candidates + beams of the call exceed the capacity; download the cells and reset, or create a larger object");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    // no counter can wrap: one beam adds at most 1 to any counter (and less than 2^16 to a sum of 64 bits)
+    if (g->total_beams + beams > 0xFFFFFFFFull) {
+        elm_host::ctx_set_error(ctx, "map growth: more than 2^32 - 1 beams accumulated; download the cells and reset");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    if (stats) memset(stats, 0, (size_t)n_jobs * sizeof(*stats));
+    if (chunks == 0) return ELM_OK;
+    EvidParams ep{};
+    ep.ox = c->origin[0]; ep.oy = c->origin[1]; ep.oz = c->origin[2];
+    ep.t_min = c->min_range_m;
+    ep.obs_min_r2 = c->obs_min_range_m * c->obs_min_range_m;
+    ep.obs_max_r2 = c->obs_max_range_m * c->obs_max_range_m;
+    ep.margin_m = c->end_margin_m;
+    ep.margin_frac = c->end_margin_frac;
+    ep.max_steps = c->max_steps;
+    GrowTables gt = g->t;
+    gt.clearance = c->clearance_cells;
+    const size_t n_ev = events ? jobs[0].n : 0;
+    EvidJob* d_jobs = (EvidJob*)elm_host::ctx_reloc_scratch(ctx, 1, jobs.size() * sizeof(EvidJob), &rc);
+    uint32_t* d_part = d_jobs ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)chunks * kGrowWords * sizeof(uint32_t), &rc) : nullptr;
+    elm_growth_stats* d_stats = d_part ? (elm_growth_stats*)elm_host::ctx_reloc_scratch(ctx, 4, (size_t)n_jobs * sizeof(elm_growth_stats), &rc) : nullptr;
+    uint16_t* d_ev = d_stats && n_ev ? (uint16_t*)elm_host::ctx_reloc_scratch(ctx, 13, n_ev * sizeof(uint16_t), &rc) : nullptr;
+    if (!d_stats || (n_ev && !d_ev)) return rc;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    uint32_t count = 0;
+    hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(EvidJob), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();
+        launch_grow(st, *ft, ep, gt, d_jobs, n_jobs, (uint32_t)chunks, d_part, d_stats, d_ev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) g->total_beams += beams; // the launch is queued: the counters will take these beams
+    if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, (size_t)n_jobs * sizeof(elm_growth_stats), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, g->t.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st); // the count comes back with the stats
+    if (e == hipSuccess && n_ev) e = hipMemcpyAsync(events, d_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st); // the job table on the host is read by the copy until here
+    if (e != hipSuccess) return dev_error(ctx, "map growth", e);
+    g->count = count;
+    return ELM_OK;
+}
+
+int accumulate_checked(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, int n_jobs,
+                       const elm_growth_config* c, elm_growth_stats* stats, uint16_t* events, const char* what) {
+    if (!ctx || !g || !scans || !poses16 || n_jobs < 1 || n_jobs > kEvidMaxJobs || !config_ok(c)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, g, what);
+    if (rc != ELM_OK) return rc;
+    if (c->sub != g->sub) return ELM_ERR_INVALID;
+    for (int j = 0; j < n_jobs; ++j)
+        if (!scans[j] || elm_host::scan_ctx(scans[j]) != ctx) return ELM_ERR_INVALID;
+    for (size_t i = 0; i < 16 * (size_t)n_jobs; ++i)
+        if (!isfinite(poses16[i])) return ELM_ERR_INVALID;
+    try {
+        return accumulate_impl(ctx, g, scans, poses16, (uint32_t)n_jobs, c, stats, events);
+    } catch (const std::bad_alloc&) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": host allocation failed");
+        return ELM_ERR_ALLOC;
+    }
+}
+
+// the candidates in ascending (x, y, z) order, which is the ascending order of their keys
+struct Cells {
+    std::vector<int32_t> cells3;
+    std::vector<uint32_t> hit, through;
+    std::vector<uint64_t> sums3;
+};
+
+int download_cells(elm_ctx* ctx, const elm_growth* g, Cells& out) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (!g->count) return ELM_OK;
+    const size_t s = g->slots;
+    std::vector<unsigned long long> keys(s), sums(3 * s);
+    std::vector<uint32_t> hit(s), through(s);
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    hipError_t e = hipMemcpyAsync(keys.data(), g->t.fkeys, s * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hit.data(), g->t.hit, s * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(through.data(), g->t.through, s * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), g->t.sums, 3 * s * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev_error(ctx, "map growth: download", e);
+    std::vector<uint32_t> order;
+    order.reserve((size_t)g->count);
+    for (size_t h = 0; h < s; ++h)
+        if (keys[h]) order.push_back((uint32_t)h);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    const size_t n = order.size();
+    out.cells3.resize(3 * n);
+    out.hit.resize(n);
+    out.through.resize(n);
+    out.sums3.resize(3 * n);
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t h = order[k];
+        for (int r = 0; r < 3; ++r) {
+            out.cells3[3 * k + r] = (int32_t)((keys[h] >> (21 * (2 - r))) & 0x1FFFFFull) - kGrowLim;
+            out.sums3[3 * k + r] = sums[3 * (size_t)h + r];
+        }
+        out.hit[k] = hit[h];
+        out.through[k] = through[h];
+    }
+    return ELM_OK;
+}
+
+} // namespace
+
+extern "C" int elm_growth_create(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out) {
+    if (!ctx || !map || !out || !(sub == 1 || sub == 2 || sub == 4) || capacity < 1 || capacity > kGrowMaxCapacity) return ELM_ERR_INVALID;
+    *out = nullptr;
+    int rc = check_plain(ctx, "elm_growth_create");
+    if (rc != ELM_OK) return rc;
+    if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    try {
+        return create_impl(ctx, map, sub, capacity, out);
+    } catch (const std::bad_alloc&) {
+        elm_host::ctx_set_error(ctx, "elm_growth_create: host allocation failed");
+        return ELM_ERR_ALLOC;
+    }
+}
+
+extern "C" void elm_growth_destroy(elm_growth* g) { growth_free(g); }
+
+extern "C" int elm_growth_reset(elm_ctx* ctx, elm_growth* g) {
+    int rc = check_object(ctx, g, "elm_growth_reset");
+    if (rc != ELM_OK) return rc;
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    const hipError_t e = clear_tables(g, (hipStream_t)elm_ctx_stream(ctx));
+    if (e != hipSuccess) return dev_error(ctx, "elm_growth_reset", e);
+    g->count = 0;
+    g->total_beams = 0;
+    return ELM_OK;
+}
+
+extern "C" int elm_growth_accumulate(elm_ctx* ctx, elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* cfg,
+                                     elm_growth_stats* stats, uint16_t* events) {
+    if (!scan) return ELM_ERR_INVALID;
+    return accumulate_checked(ctx, g, &scan, T16, 1, cfg, stats, events, "elm_growth_accumulate");
+}
+
+extern "C" int elm_growth_accumulate_batch(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, int n_jobs,
+                                           const elm_growth_config* cfg, elm_growth_stats* stats) {
+    return accumulate_checked(ctx, g, scans, poses16, n_jobs, cfg, stats, nullptr, "elm_growth_accumulate_batch");
+}
+
+extern "C" int elm_growth_cells(elm_ctx* ctx, const elm_growth* g, int32_t* cells3, uint32_t* hit, uint32_t* through, uint64_t* sums3, size_t cap,
+                                size_t* n) {
+    if (!n) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, g, "elm_growth_cells");
+    if (rc != ELM_OK) return rc;
+    *n = (size_t)g->count;
+    const size_t k = std::min<size_t>(cap, (size_t)g->count);
+    if (!k || (!cells3 && !hit && !through && !sums3)) return ELM_OK;
+    try {
+        Cells c;
+        rc = download_cells(ctx, g, c);
+        if (rc != ELM_OK) return rc;
+        if (cells3) memcpy(cells3, c.cells3.data(), 3 * k * sizeof(int32_t));
+        if (hit) memcpy(hit, c.hit.data(), k * sizeof(uint32_t));
+        if (through) memcpy(through, c.through.data(), k * sizeof(uint32_t));
+        if (sums3) memcpy(sums3, c.sums3.data(), 3 * k * sizeof(uint64_t));
+        return ELM_OK;
+    } catch (const std::bad_alloc&) {
+        elm_host::ctx_set_error(ctx, "elm_growth_cells: host allocation failed");
+        return ELM_ERR_ALLOC;
+    }
+}
+
+extern "C" int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, const elm_growth_rule* rule, double* xyz64, size_t cap, size_t* n) {
+    if (!n || !rule || (!xyz64 && cap)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, g, "elm_growth_appeared_points");
+    if (rc != ELM_OK) return rc;
+    try {
+        const FineTable* ft = nullptr;
+        rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
+        if (rc != ELM_OK) return rc;
+        const double cell = ft->cell;
+        Cells c;
+        rc = download_cells(ctx, g, c);
+        if (rc != ELM_OK) return rc;
+        size_t m = 0;
+        for (size_t k = 0; k < c.hit.size(); ++k) {
+            const uint32_t h = c.hit[k], t = c.through[k];
+            if (!(h >= rule->min_hit && (uint64_t)h >= (uint64_t)rule->hit_per_through * (uint64_t)t)) continue;
+            if (m < cap)
+                for (int r = 0; r < 3; ++r)
+                    xyz64[3 * m + r] = ((double)c.cells3[3 * k + r] + ((double)c.sums3[3 * k + r] / (double)h + 0.5) / 65536.0) * cell;
+            ++m;
+        }
+        *n = m;
+        return ELM_OK;
+    } catch (const std::bad_alloc&) {
+        elm_host::ctx_set_error(ctx, "elm_growth_appeared_points: host allocation failed");
+        return ELM_ERR_ALLOC;
+    }
+}

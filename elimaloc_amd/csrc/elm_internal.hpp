@@ -402,6 +402,29 @@ constexpr int kEvidWords = 9; // a partial: cast, observing, walked, truncated, 
 void launch_evid_walk(hipStream_t s, const FineTable& ft, const EvidParams& ep, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks,
                       const uint32_t* base, uint32_t* through, uint32_t* hit, uint32_t* partial, elm_evidence_stats* stats, uint16_t* events);
 
+// map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
+// call fill -- cells the map does not occupy and in which beams ended
+struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end
+    unsigned long long* ckeys;  // coarse cell (fine cell >> 2 per axis)
+    unsigned long long* cmasks; // the 64-bit mask of its candidate fine cells (fine_bit), as FineTable's
+    unsigned long long* fkeys;  // candidate fine cell
+    uint32_t* hit;              // [slots]
+    uint32_t* through;          // [slots]
+    unsigned long long* sums;   // [slots][3] fixed-point sums of the end points' fractions
+    uint32_t* count;            // [1] the candidates
+    uint32_t mask;
+    int32_t clearance;          // elm_growth_config::clearance_cells
+};
+constexpr int kGrowLim = 1 << 20; // a cell packs into one 64-bit key when every |c_r| < 2^20 (grow_key, elm_dev_fine.hpp)
+constexpr int kGrowEndWords = 7;  // k_grow_end's partial of a chunk: cast, observing, end hit, near, new, out, dropped
+constexpr int kGrowWalkWords = 5; // k_grow_walk's: walked, truncated, through beams, through events, steps
+constexpr int kGrowWords = kGrowEndWords + kGrowWalkWords;
+// jobs / n_chunks as launch_evid_walk; partial [n_chunks][kGrowWords] scratch; stats [n_jobs]; events [jobs[0].n] or nullptr (one job only).
+// Three launches on the stream: the end points of all jobs, the walks, the sums -- the kernel boundary is what makes every walk see
+// every candidate of its call.
+void launch_grow(hipStream_t s, const FineTable& ft, const EvidParams& ep, const GrowTables& gt, const EvidJob* jobs, uint32_t n_jobs,
+                 uint32_t n_chunks, uint32_t* partial, elm_growth_stats* stats, uint16_t* events);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

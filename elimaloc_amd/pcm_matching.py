@@ -111,13 +111,16 @@ class PcmMatching:
         elif m == IcpMethod.GICP:
             self.local_map_.CalPointCovAll(self.cfg_.registration.gicp_cov_search_dist)
 
-    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None, evidence=None, evidence_cfg=None):
+    def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None, evidence=None, evidence_cfg=None, growth=None,
+                           growth_cfg=None):
         """pcm.cpp:198-324.  Returns None when the reference would publish nothing (deskew / pose sync / ICP failure),
         else dict(pose_ego 4x4 float64, covariance 6x6 row-major, fitness, time).  free_space: a FreeSpaceConfig -- the result also
         carries "free_space", the free-space statistics of the registered pose (VoxelHashMap.CheckFreeSpace); nothing else changes.
         evidence: a MapEvidence of the local map -- after a successful registration the source scan is accumulated into it at the
         registered pose (evidence_cfg: an EvidenceConfig, default its defaults) and the result carries "evidence", that observation's
-        statistics; nothing else changes."""
+        statistics; nothing else changes.
+        growth: a MapGrowth of the local map -- likewise, the source scan is accumulated into it at the registered pose (growth_cfg: a
+        GrowthConfig, default its defaults) and the result carries "growth"; nothing else changes."""
         import time
         tm = self.timings_ = {}
         t0 = time.perf_counter()
@@ -160,6 +163,9 @@ class PcmMatching:
         if evidence is not None:
             out["evidence"] = evidence.Accumulate(src, pose, evidence_cfg)
             lap("evidence_ms")
+        if growth is not None:
+            out["growth"] = growth.Accumulate(src, pose, growth_cfg)
+            lap("growth_ms")
         return out
 
     def _node_config(self):

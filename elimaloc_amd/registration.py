@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, EvidenceConfigC, EvidenceRuleC, EvidenceStatsC, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+from ._lib import (ElmError, EvidenceConfigC, EvidenceRuleC, EvidenceStatsC, GrowthConfigC, GrowthRuleC, GrowthStatsC, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
                    check)
 
 
@@ -141,6 +141,42 @@ _EVID_FIELDS = ("n_cast", "n_observing", "n_walked", "n_truncated", "n_through_b
 def EvidenceStats(st):
     """elm_evidence_stats of one observation as a dict."""
     return {k: int(getattr(st, k)) for k in _EVID_FIELDS}
+
+
+def GrowthConfig(**kw):
+    """elm_growth_config with its defaults: the EvidenceConfig defaults and clearance_cells 1 (an end point within that many cells of an
+    occupied cell is the old surface, not new structure; 0, 1 or 2 -- a starting point, not a measured optimum)."""
+    cfg = GrowthConfigC()
+    _lib.lib().elm_growth_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"GrowthConfig has no field {k}")
+        if k == "origin":
+            cfg.origin = (C.c_double * 3)(*[float(x) for x in v])
+        else:
+            setattr(cfg, k, int(v) if k in ("sub", "max_steps", "clearance_cells") else float(v))
+    return cfg
+
+
+def GrowthRule(**kw):
+    """elm_growth_rule with its defaults (min_hit 3, hit_per_through 4): a candidate cell has appeared when hit >= min_hit and
+    hit >= hit_per_through * through.  A starting point, not a measured optimum."""
+    rule = GrowthRuleC()
+    _lib.lib().elm_growth_rule_default(C.byref(rule))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(rule, k):
+            raise AttributeError(f"GrowthRule has no field {k}")
+        setattr(rule, k, int(v))
+    return rule
+
+
+_GROWTH_FIELDS = ("n_cast", "n_observing", "n_walked", "n_truncated", "n_end_hit", "n_end_near", "n_end_new", "n_end_out", "n_through_beams",
+                  "n_dropped", "n_through_events", "n_steps")
+
+
+def GrowthStats(st):
+    """elm_growth_stats of one observation as a dict."""
+    return {k: int(getattr(st, k)) for k in _GROWTH_FIELDS}
 
 
 def _global_stats_dict(st):
@@ -604,6 +640,24 @@ class VoxelHashMap:
         out.AddPoints(keep.astype(np.float32))  # stored coordinates are float32 values: the conversion is exact
         return out
 
+    def Growth(self, capacity, sub=4):
+        """A MapGrowth of this map: per candidate fine cell -- a cell the map does not occupy and in which beams ended -- the beams that
+        ended in it, the beams that later passed through it and where in it the end points lay, kept on the device and fed by Accumulate.
+        capacity: the most candidate cells it can hold (a call needs room for one candidate per beam).  It belongs to the map as built now:
+        AddPoints / Clear afterwards invalidate it."""
+        return MapGrowth(self, capacity, sub)
+
+    def WithAppeared(self, growth, rule=None):
+        """A new map (same voxel size and cap, same context) built by the usual build from this map's stored points followed by
+        growth.AppearedPoints(rule) in cell order: the spacing rule and the voxel cap apply to the new points as to any others."""
+        if growth.map is not self:
+            raise ElmError("WithAppeared: the growth object belongs to another map")
+        new = growth.AppearedPoints(rule)
+        old = self.Pointcloud() if not self.Empty() else np.zeros((0, 3))
+        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx)
+        out.AddPoints(np.concatenate([old, new]).astype(np.float32))  # stored coordinates are float32 values: their conversion is exact
+        return out
+
     def FindGroundHeights(self, xy):
         """FindGroundHeight of many xy positions [n, 2] on the device (elm_map_ground_heights, bit for bit the single query) -> (found bool
         [n], z [n]; 0 where not found)."""
@@ -771,6 +825,106 @@ class MapEvidence:
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().elm_evidence_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MapGrowth:
+    """Map growth (elm_growth, include/elimaloc_hip.h "map growth"): a device-resident table of candidate fine cells that the map does not
+    hold, filled by the observations themselves.  Made by VoxelHashMap.Growth(capacity, sub)."""
+
+    def __init__(self, voxel_map, capacity, sub=4):
+        self.map, self.ctx, self.sub, self.capacity = voxel_map, voxel_map.ctx, int(sub), int(capacity)
+        self._map_h = voxel_map._handle()
+        self._h = C.c_void_p()
+        check(_lib.lib().elm_growth_create(self.ctx._h, self._map_h, self.sub, self.capacity, C.byref(self._h)), self.ctx._h, "elm_growth_create")
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ElmError("MapGrowth: closed")
+        if self.map._h is not self._map_h:
+            raise ElmError("MapGrowth: its map was rebuilt or cleared")
+        return self._h
+
+    def Accumulate(self, scans, poses, cfg=None, events=False):
+        """One accumulate call (elm_growth_accumulate / _batch).  scans: one scan (a resident Scan, or (m, 3) points uploaded for the call)
+        with one pose [4, 4] -> its GrowthStats dict; or a list of scans with poses [n, 4, 4] -> a list of dicts, all jobs in ONE call: the
+        end points of all jobs are recorded before any beam walks (the same Scan may appear several times).  events=True (one scan only):
+        also the through events of every beam, uint16 [m], in the resident order (Scan.points()) for a Scan, in the caller's order for an
+        array."""
+        cfg = cfg if cfg is not None else GrowthConfig(sub=self.sub)
+        h = self._handle()
+        L = _lib.lib()
+        single = isinstance(scans, Scan) or (isinstance(scans, np.ndarray) and scans.ndim == 2)
+        if single:
+            sc = scans if isinstance(scans, Scan) else Scan(self.ctx, scans)
+            T = _colmajor16(poses)
+            st = GrowthStatsC()
+            ev = np.zeros(max(sc.n, 1), np.uint16) if events else None
+            check(L.elm_growth_accumulate(self.ctx._h, h, sc._h, _dp(T), C.byref(cfg), C.byref(st),
+                                          ev.ctypes.data_as(C.POINTER(C.c_uint16)) if events else None), self.ctx._h, "elm_growth_accumulate")
+            if not events:
+                return GrowthStats(st)
+            ev = ev[:sc.n]
+            if not isinstance(scans, Scan) and sc.n:  # back to the caller's order: equal points are equal beams
+                key = np.dtype((np.void, 12))
+                res = np.ascontiguousarray(sc.points()).view(key).ravel()
+                own = np.ascontiguousarray(scans, dtype=np.float32).reshape(-1, 3).view(key).ravel()
+                order = np.argsort(res, kind="stable")
+                ev = np.ascontiguousarray(ev[order[np.searchsorted(res[order], own)]])
+            return GrowthStats(st), ev
+        if events:
+            raise ElmError("MapGrowth.Accumulate: events are returned for a single scan only")
+        scs = [s if isinstance(s, Scan) else Scan(self.ctx, s) for s in scans]
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        if P.size // 16 != len(scs):
+            raise ElmError("MapGrowth.Accumulate: one pose per scan")
+        n = len(scs)
+        hs = (C.c_void_p * max(n, 1))(*[s._h.value for s in scs])
+        st = (GrowthStatsC * max(n, 1))()
+        check(L.elm_growth_accumulate_batch(self.ctx._h, h, hs, _dp(P), n, C.byref(cfg), st), self.ctx._h, "elm_growth_accumulate_batch")
+        return [GrowthStats(st[j]) for j in range(n)]
+
+    def Count(self):
+        """The candidate cells held now (known on the host after every call: no download)."""
+        n = C.c_size_t(0)
+        check(_lib.lib().elm_growth_cells(self.ctx._h, self._handle(), None, None, None, None, 0, C.byref(n)), self.ctx._h, "elm_growth_cells")
+        return int(n.value)
+
+    def Cells(self):
+        """(cells int32 [m, 3] ascending (x, y, z), hit uint32 [m], through uint32 [m], sums uint64 [m, 3]) of the candidate cells."""
+        m = self.Count()
+        cells, hit, through = np.zeros((max(m, 1), 3), np.int32), np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint32)
+        sums = np.zeros((max(m, 1), 3), np.uint64)
+        n = C.c_size_t(0)
+        u32 = C.POINTER(C.c_uint32)
+        check(_lib.lib().elm_growth_cells(self.ctx._h, self._handle(), cells.ctypes.data_as(C.POINTER(C.c_int32)), hit.ctypes.data_as(u32),
+                                          through.ctypes.data_as(u32), sums.ctypes.data_as(C.POINTER(C.c_uint64)), m, C.byref(n)), self.ctx._h,
+              "elm_growth_cells")
+        return cells[:m], hit[:m], through[:m], sums[:m]
+
+    def AppearedPoints(self, rule=None):
+        """float64 [k, 3]: the mean end point of every candidate cell that `rule` (GrowthRule()) calls appeared, in cell order."""
+        rule = rule if rule is not None else GrowthRule()
+        n = C.c_size_t(0)
+        L = _lib.lib()
+        h = self._handle()
+        check(L.elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), None, 0, C.byref(n)), self.ctx._h, "elm_growth_appeared_points")
+        out = np.zeros((max(n.value, 1), 3))
+        check(L.elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), _dp(out), n.value, C.byref(n)), self.ctx._h, "elm_growth_appeared_points")
+        return out[:n.value]
+
+    def Reset(self):
+        check(_lib.lib().elm_growth_reset(self.ctx._h, self._handle()), self.ctx._h, "elm_growth_reset")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().elm_growth_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -106,6 +106,18 @@ struct EvidenceRule : elm_evidence_rule {
     EvidenceRule() { elm_evidence_rule_default(this); }
 };
 
+// elm_growth_config with its defaults (include/elimaloc_hip.h, map growth): the evidence walk plus the clearance of MapGrowth::Accumulate
+struct GrowthConfig : elm_growth_config {
+    GrowthConfig() { elm_growth_config_default(this); }
+};
+
+// elm_growth_rule with its defaults: when a candidate cell's counters make it appeared (a starting point, not a measured optimum)
+struct GrowthRule : elm_growth_rule {
+    GrowthRule() { elm_growth_rule_default(this); }
+};
+
+class MapGrowth;
+
 struct VoxelHashMap {
     using RadarPointVector = std::vector<PointStruct>;
     using RadarPointVectorTuple = std::tuple<RadarPointVector, RadarPointVector>;
@@ -243,6 +255,11 @@ struct VoxelHashMap {
                 for (int k = vz - 1; k < vz + 2; ++k) voxels.emplace_back(i, j, k);
         return voxels;
     }
+    // `out` becomes a map of this map's voxel size and cap, built by the usual build from this map's stored points followed by the points
+    // of the cells that `growth` (a MapGrowth of this map) calls appeared, in cell order: the spacing rule and the voxel cap apply to them.
+    // (Filled in place: a map owns device memory and is not copied.)
+    inline void WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule = GrowthRule()) const;
+
     inline bool FindGroundHeight(const elimaloc::Vector2d& position, double& ground_z) const { // vhm.hpp:285-322
         int found = 0;
         elimaloc::check(elm_map_find_ground_height(handle(), position(0), position(1), &ground_z, &found), ctx(), "FindGroundHeight");
@@ -447,3 +464,91 @@ private:
     elm_evidence* ev_ = nullptr;
     int sub_ = 4;
 };
+
+// Map growth (include/elimaloc_hip.h, map growth): per candidate fine cell -- a cell the map does not occupy and in which beams ended --
+// the beams that ended in it, the beams that later passed through it and where in it the end points lay, kept on the device and fed with
+// scans at trusted poses.  It is bound to the map as built when it is made: destroy it before the map, and do not use it after the map
+// has taken more points.  capacity: the most candidate cells it holds; a call needs room for one candidate per beam.
+class MapGrowth {
+public:
+    using RadarPointVector = VoxelHashMap::RadarPointVector;
+    MapGrowth(const VoxelHashMap& map, size_t capacity, int sub = 4) : sub_(sub) {
+        elimaloc::check(elm_growth_create(VoxelHashMap::ctx(), map.handle(), sub, capacity, &g_), VoxelHashMap::ctx(), "elm_growth_create");
+    }
+    MapGrowth(const MapGrowth&) = delete; // owns device memory
+    MapGrowth& operator=(const MapGrowth&) = delete;
+    ~MapGrowth() { elm_growth_destroy(g_); }
+
+    // One observation per scan (sensor frame, PointStruct::pose) at its pose, all in ONE call (elm_growth_accumulate_batch): the end points
+    // of all scans are recorded before any beam walks.  The statistics of every observation.  config.sub is set to this object's.
+    inline std::vector<elm_growth_stats> Accumulate(const std::vector<RadarPointVector>& scans, const std::vector<elimaloc::Matrix4d>& poses,
+                                                    GrowthConfig config = GrowthConfig()) {
+        config.sub = sub_;
+        std::vector<elm_growth_stats> stats(scans.size());
+        if (scans.empty() || scans.size() != poses.size()) {
+            elimaloc::check(scans.empty() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "MapGrowth::Accumulate");
+            return stats;
+        }
+        std::vector<double> T(16 * poses.size());
+        for (size_t h = 0; h < poses.size(); ++h)
+            for (int k = 0; k < 16; ++k) T[16 * h + k] = poses[h].data()[k]; // column-major on both sides
+        std::vector<elm_scan*> res(scans.size(), nullptr);
+        int rc = ELM_OK;
+        for (size_t j = 0; j < scans.size() && rc == ELM_OK; ++j) {
+            std::vector<float> xyz(3 * scans[j].size());
+            for (size_t i = 0; i < scans[j].size(); ++i)
+                for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scans[j][i].pose(k);
+            rc = elm_scan_upload(VoxelHashMap::ctx(), xyz.data(), scans[j].size(), scans[j].size(), &res[j]);
+        }
+        if (rc == ELM_OK) rc = elm_growth_accumulate_batch(VoxelHashMap::ctx(), g_, res.data(), T.data(), (int)scans.size(), &config, stats.data());
+        for (elm_scan* s : res)
+            if (s) elm_scan_destroy(s);
+        elimaloc::check(rc, VoxelHashMap::ctx(), "MapGrowth::Accumulate");
+        return stats;
+    }
+    inline elm_growth_stats Accumulate(const RadarPointVector& scan, const elimaloc::Matrix4d& pose, const GrowthConfig& config = GrowthConfig()) {
+        return Accumulate(std::vector<RadarPointVector>(1, scan), std::vector<elimaloc::Matrix4d>(1, pose), config)[0];
+    }
+
+    // The candidate cells in ascending (x, y, z) order: cells3 [n][3], hit [n], through [n], sums3 [n][3]
+    inline void Cells(std::vector<int32_t>& cells3, std::vector<uint32_t>& hit, std::vector<uint32_t>& through, std::vector<uint64_t>& sums3) const {
+        size_t n = 0;
+        elimaloc::check(elm_growth_cells(VoxelHashMap::ctx(), g_, nullptr, nullptr, nullptr, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_growth_cells");
+        cells3.assign(3 * n, 0);
+        hit.assign(n, 0);
+        through.assign(n, 0);
+        sums3.assign(3 * n, 0);
+        if (n)
+            elimaloc::check(elm_growth_cells(VoxelHashMap::ctx(), g_, cells3.data(), hit.data(), through.data(), sums3.data(), n, &n),
+                            VoxelHashMap::ctx(), "elm_growth_cells");
+    }
+
+    // The mean end point (x, y, z, float64) of every cell that the rule calls appeared, in cell order
+    inline std::vector<double> AppearedPoints(const GrowthRule& rule = GrowthRule()) const {
+        size_t n = 0;
+        elimaloc::check(elm_growth_appeared_points(VoxelHashMap::ctx(), g_, &rule, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_growth_appeared_points");
+        std::vector<double> xyz(3 * n, 0.0);
+        if (n) elimaloc::check(elm_growth_appeared_points(VoxelHashMap::ctx(), g_, &rule, xyz.data(), n, &n), VoxelHashMap::ctx(), "elm_growth_appeared_points");
+        return xyz;
+    }
+
+    inline void Reset() { elimaloc::check(elm_growth_reset(VoxelHashMap::ctx(), g_), VoxelHashMap::ctx(), "elm_growth_reset"); }
+
+private:
+    elm_growth* g_ = nullptr;
+    int sub_ = 4;
+};
+
+inline void VoxelHashMap::WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule) const {
+    const std::vector<double> fresh = growth.AppearedPoints(rule);
+    elm_map_info mi;
+    elimaloc::check(elm_map_get_info(handle(), &mi), ctx(), "elm_map_get_info");
+    std::vector<double> xyz(3 * mi.n_points), cov(9 * mi.n_points), mean(3 * mi.n_points);
+    if (mi.n_points) elimaloc::check(elm_map_download_points(handle(), xyz.data(), cov.data(), mean.data(), mi.n_points), ctx(), "WithAppeared");
+    xyz.insert(xyz.end(), fresh.begin(), fresh.end());
+    std::vector<float> f(xyz.size());
+    for (size_t i = 0; i < xyz.size(); ++i) f[i] = (float)xyz[i]; // stored coordinates are float32 values: their conversion is exact
+    out.Clear();
+    out.Init(voxel_size_, max_points_per_voxel_);
+    out.AddPoints(f.data(), f.size() / 3);
+}

@@ -588,6 +588,92 @@ int elm_evidence_counts(elm_ctx* ctx, const elm_evidence* ev, uint32_t* through,
  * written, *n = count (flags may be NULL when cap = 0). */
 int elm_evidence_stale_points(elm_ctx* ctx, const elm_evidence* ev, const elm_evidence_rule* rule, uint8_t* flags, size_t cap, size_t* n);
 
+/* ---------------------------------------------------------------- map growth ---------------------- */
+/* Given poses we trust, what stands there that the map does not hold?  The other half of "map evidence": a growth object holds, per
+ * CANDIDATE fine cell -- a cell the map does not occupy and in which beams ended -- HIT, the beams that ended in it, THROUGH, the beams
+ * that later passed through it, and a fixed-point sum of where in the cell the end points lay.  The candidate cells are not known in
+ * advance: the object owns a table on the device that the accumulate calls fill.  It is fed by many (scan, pose) observations per call.
+ * Beam, CAST, OBSERVING, the end point q and its cell e, reach, and the walk with its tie rule, t_next, BY REACH and BY STEPS are exactly
+ * those of "map evidence", in the same float64 arithmetic without contraction; they are not restated here.
+ * END CLASS of an observing beam, the first that applies:
+ *   END-HIT   e is an occupied cell of the map;
+ *   END-OUT   some |e_r| >= 2^20 (what lets a cell pack into one 64-bit key);
+ *   END-NEAR  clearance_cells > 0 and some occupied cell e' has max_r |e'_r - e_r| <= clearance_cells (clearance_cells is 0, 1 or 2;
+ *             0: never NEAR);
+ *   END-NEW   every other observing beam.
+ *   HIT, OUT and NEAR beams enter the stats only.  Why a clearance: without it the sensor noise next to every mapped surface would fill
+ *   the table with cells that are the old surface.  The default of 1 is a starting point, not a measured optimum.
+ * One CALL (elm_growth_accumulate is a batch of one job) has two phases.
+ * RECORD (phase 1), for every END-NEW beam of every job of the call: e becomes a candidate if it is not one yet; hit[e] += 1; per axis
+ *   sum_r[e] += k_r (uint64), with v_r = q_r / cell formed as the fine occupancy forms it and
+ *   k_r = min(65535, (uint32)floor((v_r - floor(v_r)) * 65536.0)).  The clamp is part of the contract: a tiny negative v_r gives a
+ *   fraction of exactly 1.0.
+ * WALK (phase 2), after the end points of ALL jobs of the call are recorded: every walking beam walks the evidence walk; every candidate
+ *   cell that the walk leaves by a step gets through[c] += 1, one through EVENT of the beam.  A beam never leaves its own end cell before
+ *   reach: the walk is monotone and stands at a parameter <= reach < L, the parameter of the end point (in exact arithmetic; the counters
+ *   are those of the walk as computed).  A beam visits a cell at most once, so it adds at most 1 to any one counter.
+ * ORDER.  Inside one call the counters do not depend on the order of the jobs.  Across calls they do, by definition: a beam counts against
+ *   the candidates that exist after phase 1 of its own call, not against cells created by later calls.
+ * RULE.  A cell has APPEARED when hit >= min_hit and hit >= hit_per_through * through (the product in 64 bits).
+ * POINT of a cell: m_r = ((double)e_r + ((double)sum_r / (double)hit + 0.5) / 65536.0) * cell, float64, formed on the host: the mean end
+ *   point to half a fixed-point step.
+ * Every stored quantity is an integer fed by integer atomics: the result is the same on every run, for every job order inside a call and
+ * every search-index form. */
+typedef struct elm_growth elm_growth;
+typedef struct elm_growth_config {
+    int32_t sub;            /* fine cells per voxel edge: 1, 2 or 4; must equal the growth object's */
+    int32_t max_steps;      /* cap of the steps of one walk (1 .. 1048576) */
+    double min_range_m;     /* the walk starts here along the beam (>= 0) */
+    double obs_min_range_m, obs_max_range_m; /* observing beams: min^2 <= L2 <= max^2 */
+    double end_margin_m, end_margin_frac;    /* the walk stops max(end_margin_m, end_margin_frac L) before the end point */
+    double origin[3];       /* the beam origin in the scan frame */
+    int32_t clearance_cells; /* END-NEAR: an occupied cell within this Chebyshev distance of e (0, 1 or 2) */
+    int32_t _pad;
+} elm_growth_config;
+typedef struct elm_growth_stats {
+    uint32_t n_cast, n_observing, n_walked, n_truncated;
+    uint32_t n_end_hit, n_end_near, n_end_new, n_end_out;   /* they add up to n_observing */
+    uint32_t n_through_beams;    /* observing beams with at least one through event */
+    uint32_t n_dropped;          /* END-NEW beams that found no slot: always 0 (the capacity guard below) */
+    uint64_t n_through_events, n_steps;
+} elm_growth_stats;
+/* The rule that turns counters into "appeared".  The defaults are a starting point, not a measured optimum. */
+typedef struct elm_growth_rule {
+    uint32_t min_hit;           /* default 3 */
+    uint32_t hit_per_through;   /* default 4 */
+} elm_growth_rule;
+/* the evidence defaults (sub 4, max_steps 4096, min_range 1 m, observing 2 .. 50 m, margins 1 m / 0.2 L, origin 0), clearance_cells 1 */
+void elm_growth_config_default(elm_growth_config* c);
+/* min_hit 3, hit_per_through 4 */
+void elm_growth_rule_default(elm_growth_rule* r);
+/* A growth object bound to (map, sub), sub in {1, 2, 4}, without candidates.  capacity (1 .. 2^30): the most candidate cells it can hold;
+ * its tables are sized once, a power of two >= 2 * capacity slots.  The map's fine occupancy table is built when it is not there yet.  The
+ * object is destroyed before its map (destroying it later only releases its own memory).  ELM_ERR_UNSUPPORTED on a device group's lead or
+ * with a communicator / hook attached, here and in every call below that takes ctx. */
+int elm_growth_create(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out);
+void elm_growth_destroy(elm_growth* g);
+/* No candidates, all counters and the object's beam total back to zero. */
+int elm_growth_reset(elm_ctx* ctx, elm_growth* g);
+/* One observation (a call of one job): the resident scan at pose T16 (column-major).  stats (may be NULL): the observation's counts.
+ * events (may be NULL): events[elm_scan_size(scan)], the through events of every beam in the resident scan's order, saturating at 65535.
+ * ELM_ERR_INVALID: cfg.sub differs from the object's, a non-finite pose entry, a scan or object of another context, a batch in flight.
+ * The object knows its exact candidate count after every call (elm_growth_cells with cap 0 returns it without a download).  A call with
+ * count + (beams of the call) > capacity is refused with ELM_ERR_UNSUPPORTED before anything is launched, and so is a call that would
+ * carry the 64-bit total of beams accumulated beyond 2^32 - 1: the table can never fill and no counter can wrap. */
+int elm_growth_accumulate(elm_ctx* ctx, elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* cfg,
+                          elm_growth_stats* stats, uint16_t* events);
+/* One call of n_jobs (1 .. 4096) observations: scans[j] at poses16 + 16 j.  Jobs may have any sizes, 0 included; the same scan may appear
+ * several times.  stats (may be NULL): stats[n_jobs].  The counters afterwards do not depend on the order of the jobs. */
+int elm_growth_accumulate_batch(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, int n_jobs,
+                                const elm_growth_config* cfg, elm_growth_stats* stats);
+/* The candidate cells in ascending (x, y, z) order (sorted on the host after the download): cells3 int32 [.][3], hit, through, sums3
+ * uint64 [.][3]; min(cap, count) written, *n = count; each array may be NULL. */
+int elm_growth_cells(elm_ctx* ctx, const elm_growth* g, int32_t* cells3, uint32_t* hit, uint32_t* through, uint64_t* sums3, size_t cap,
+                     size_t* n);
+/* The POINT of every appeared cell by `rule`, in the same order: xyz64 float64 [.][3]; min(cap, count) written, *n = count (xyz64 may be
+ * NULL when cap = 0). */
+int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, const elm_growth_rule* rule, double* xyz64, size_t cap, size_t* n);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {
