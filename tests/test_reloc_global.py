@@ -11,6 +11,7 @@ from elimaloc_amd import synth
 from elimaloc_amd._lib import ElmError
 from elimaloc_amd.registration import (Context, GlobalRelocConfig, IcpMethod, Registration, RegistrationConfig, RelocConfig, Scan,
                                        VoxelHashMap)
+from reloc_ref import counted as _counted, greedy_nms
 
 pytestmark = pytest.mark.gpu
 
@@ -123,16 +124,6 @@ def test_global_hypotheses_mirror(ctx, field1m):
     assert np.array_equal(H[:, 3], np.broadcast_to([0.0, 0.0, 0.0, 1.0], (H.shape[0], 4)))
 
 
-def _counted(scan, cfg, T_tilt):
-    """the global form's counted points: within r_max, then (R0 p)_z + h >= score_min_height_m (float64, the contract's association)."""
-    p = scan.astype(np.float64)
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    keep = (x * x + y * y) + z * z <= cfg.score_max_range_m ** 2
-    R = T_tilt[:3, :3]
-    keep &= ((R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z) + T_tilt[2, 3] >= cfg.score_min_height_m
-    return scan[keep]
-
-
 def _exhaustive(vm, scan, T_tilt, cfg, ctx):
     """the reference: ScorePoses over every valid lattice pose, (score desc, hyp asc), numpy greedy NMS."""
     H, valid = vm.GlobalHypotheses(T_tilt, cfg)
@@ -145,22 +136,9 @@ def _exhaustive(vm, scan, T_tilt, cfg, ctx):
     order = np.lexsort((hyp, -scores))
     K = int(math.ceil(360.0 / cfg.step_yaw_deg - 1e-9))
     nxy = H.shape[0] // K
-    kept = []
-    for r in order:
-        h = int(hyp[r])
-        x, y, yaw = H[h][0, 3], H[h][1, 3], (h // nxy) * cfg.step_yaw_deg
-        sup = False
-        for (_, _, kx, ky, kyaw) in kept:
-            d = math.fmod(yaw - kyaw, 360.0)
-            d = d - 360.0 if d > 180.0 else (d + 360.0 if d < -180.0 else d)
-            if math.hypot(x - kx, y - ky) <= cfg.nms_xy_m and abs(d) <= cfg.nms_yaw_deg:
-                sup = True
-                break
-        if not sup:
-            kept.append((h, int(scores[r]), x, y, yaw))
-            if len(kept) == cfg.top_k:
-                break
-    return [(h, s) for (h, s, _, _, _) in kept], H, valid
+    kept = greedy_nms(hyp[order], lambda h: (H[h][0, 3], H[h][1, 3], (h // nxy) * cfg.step_yaw_deg), cfg.top_k, cfg.nms_xy_m, cfg.nms_yaw_deg)
+    by = dict(zip(hyp.tolist(), scores.tolist()))
+    return [(h, int(by[h])) for h in kept], H, valid
 
 
 def _scan_case(world, vm, seed, n=6000):

@@ -11,6 +11,7 @@ from elimaloc_amd import _lib, synth
 from elimaloc_amd.registration import (Context, IcpMethod, MakeHypotheses, Registration, RegistrationConfig, RelocConfig, Scan,
                                        VoxelHashMap)
 from elimaloc_amd._lib import ElmError
+from reloc_ref import _codes, mirror_scores  # noqa: F401  (the numpy mirror of the score contract)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,28 +24,6 @@ def ctx():
     c = Context(0)
     yield c
     c.close()
-
-
-def _codes(k):
-    k = np.asarray(k, dtype=np.int64) + (1 << 20)
-    return (k[:, 0] << 42) | (k[:, 1] << 21) | k[:, 2]
-
-
-def mirror_scores(map_xyz, vs, scan, poses, r_max):
-    """score(T) by the contract: the voxel set = unique truncated keys of ALL map points; counted points within r_max (float64); the
-    transform in the contract's association; truncated keys by division."""
-    vox = np.unique(_codes(np.trunc(map_xyz.astype(np.float64) / vs)))
-    p = scan.astype(np.float64)
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    keep = (x * x + y * y) + z * z <= r_max * r_max
-    x, y, z = x[keep], y[keep], z[keep]
-    out = np.zeros(len(poses), np.uint32)
-    for h, T in enumerate(np.asarray(poses, dtype=np.float64)):
-        q = np.stack([((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)], 1)
-        c = _codes(np.trunc(q / vs))
-        i = np.searchsorted(vox, c)
-        out[h] = np.count_nonzero(vox[np.minimum(i, vox.size - 1)] == c)
-    return out
 
 
 def _small_hyps(T, **kw):
