@@ -1,20 +1,19 @@
 // elm_evid.cpp -- map evidence (include/elimaloc_hip.h, "map evidence"): the evidence object (two device counters
 // per occupied fine cell of a map, addressed through a per-slot prefix of the fine table's mask popcounts), the argument checks, the job
-// table, the launches of elm_k_evid.hip and the downloads.  Host-side C++17.
+// table and the launches of elm_k_evid.hip through the call of many jobs that elm_query.hpp shares with the map growth, and the downloads.
+// Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <array>
-#include <new>
-#include <string>
 #include <vector>
 
-#include "elm_hostapi.hpp"
-#include "elm_internal.hpp"
+#include "elm_query.hpp"
 
 using namespace elm;
+using namespace elm_query;
 
 struct elm_evidence {
     elm_ctx* ctx = nullptr;
@@ -49,38 +48,6 @@ extern "C" void elm_evidence_rule_default(elm_evidence_rule* r) {
 }
 
 namespace {
-
-bool fin_ge0(double v) { return isfinite(v) && v >= 0.0; }
-
-bool config_ok(const elm_evidence_config* c) {
-    if (!c || !(c->sub == 1 || c->sub == 2 || c->sub == 4) || c->max_steps < 1 || c->max_steps > kRayMaxSteps) return false;
-    if (!fin_ge0(c->min_range_m) || !fin_ge0(c->obs_min_range_m) || !(isfinite(c->obs_max_range_m) && c->obs_max_range_m >= c->obs_min_range_m)) return false;
-    if (!fin_ge0(c->end_margin_m) || !fin_ge0(c->end_margin_frac)) return false;
-    return isfinite(c->origin[0]) && isfinite(c->origin[1]) && isfinite(c->origin[2]);
-}
-
-// one rank, no exchange (as the other map queries)
-int check_plain(elm_ctx* ctx, const char* what) {
-    if ((elm_host::ctx_group(ctx) && !elm_multi::in_worker()) || elm_host::ctx_exchange_attached(ctx)) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    return ELM_OK;
-}
-
-// the checks every call on an existing object shares
-int check_object(elm_ctx* ctx, const elm_evidence* ev, const char* what) {
-    if (!ctx || !ev) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, what);
-    if (rc != ELM_OK) return rc;
-    if (ev->ctx != ctx || ev->ctx_id != elm_host::ctx_unique_id(ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    return ELM_OK;
-}
-
-int dev_error(elm_ctx* ctx, const char* what, hipError_t e) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
-    return ELM_ERR_DEVICE;
-}
 
 void evidence_free(elm_evidence* ev) {
     if (!ev) return;
@@ -159,86 +126,32 @@ int accumulate_impl(elm_ctx* ctx, elm_evidence* ev, const elm_scan* const* scans
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(ev->map, ev->sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
-    std::vector<EvidJob> jobs(n_jobs);
-    uint64_t beams = 0, chunks = 0;
-    for (uint32_t j = 0; j < n_jobs; ++j) {
-        size_t n = 0;
-        jobs[j].pts = elm_host::scan_dev_points(scans[j], &n);
-        jobs[j].n = (uint32_t)n;
-        jobs[j].chunk0 = (uint32_t)chunks;
-        for (int r = 0; r < 3; ++r)
-            for (int q = 0; q < 4; ++q) jobs[j].rows[r * 4 + q] = poses16[16 * (size_t)j + q * 4 + r];
-        beams += n;
-        chunks += (n + 255) / 256;
-    }
-    // no counter can wrap: one beam adds at most 1 to any counter, and the object never takes more than 2^32 - 1 beams
-    if (ev->total_beams + beams > 0xFFFFFFFFull) {
-        elm_host::ctx_set_error(ctx, "map evidence: more than 2^32 - 1 beams accumulated; download the counters and reset");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    if (stats) memset(stats, 0, (size_t)n_jobs * sizeof(*stats));
-    if (chunks == 0) return ELM_OK;
-    EvidParams ep{};
-    ep.ox = c->origin[0]; ep.oy = c->origin[1]; ep.oz = c->origin[2];
-    ep.t_min = c->min_range_m;
-    ep.obs_min_r2 = c->obs_min_range_m * c->obs_min_range_m;
-    ep.obs_max_r2 = c->obs_max_range_m * c->obs_max_range_m;
-    ep.margin_m = c->end_margin_m;
-    ep.margin_frac = c->end_margin_frac;
-    ep.max_steps = c->max_steps;
-    const size_t n_ev = events ? jobs[0].n : 0;
-    EvidJob* d_jobs = (EvidJob*)elm_host::ctx_reloc_scratch(ctx, 1, jobs.size() * sizeof(EvidJob), &rc);
-    uint32_t* d_part = d_jobs ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)chunks * kEvidWords * sizeof(uint32_t), &rc) : nullptr;
-    elm_evidence_stats* d_stats = d_part ? (elm_evidence_stats*)elm_host::ctx_reloc_scratch(ctx, 4, (size_t)n_jobs * sizeof(elm_evidence_stats), &rc) : nullptr;
-    uint16_t* d_ev = d_stats && n_ev ? (uint16_t*)elm_host::ctx_reloc_scratch(ctx, 13, n_ev * sizeof(uint16_t), &rc) : nullptr;
-    if (!d_stats || (n_ev && !d_ev)) return rc;
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
-    hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(EvidJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch_evid_walk(st, *ft, ep, d_jobs, n_jobs, (uint32_t)chunks, ev->d_base, ev->d_through, ev->d_hit, d_part, d_stats, d_ev);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) ev->total_beams += beams; // the launch is queued: the counters will take these beams
-    if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, (size_t)n_jobs * sizeof(elm_evidence_stats), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_ev) e = hipMemcpyAsync(events, d_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st); // the job table on the host is read by the copy until here
-    if (e != hipSuccess) return dev_error(ctx, "map evidence", e);
-    return ELM_OK;
+    const JobTable jobs = build_jobs(scans, poses16, n_jobs);
+    const EvidParams ep = walk_params(*c);
+    return run_jobs(
+        ctx, jobs, ev->total_beams, "map evidence", "counters", kEvidWords, stats, events,
+        [&](hipStream_t st, const EvidJob* d_jobs, uint32_t n_chunks, uint32_t* d_part, elm_evidence_stats* d_stats, uint16_t* d_ev) {
+            launch_evid_walk(st, *ft, ep, d_jobs, n_jobs, n_chunks, ev->d_base, ev->d_through, ev->d_hit, d_part, d_stats, d_ev);
+        },
+        [](hipStream_t) { return hipSuccess; });
 }
 
 int accumulate_checked(elm_ctx* ctx, elm_evidence* ev, const elm_scan* const* scans, const double* poses16, int n_jobs,
                        const elm_evidence_config* c, elm_evidence_stats* stats, uint16_t* events, const char* what) {
-    if (!ctx || !ev || !scans || !poses16 || n_jobs < 1 || n_jobs > kEvidMaxJobs || !config_ok(c)) return ELM_ERR_INVALID;
-    int rc = check_object(ctx, ev, what);
+    int rc = check_accumulate(ctx, ev, scans, poses16, n_jobs, c, walk_config_ok(c), what);
     if (rc != ELM_OK) return rc;
-    if (c->sub != ev->sub) return ELM_ERR_INVALID;
-    for (int j = 0; j < n_jobs; ++j)
-        if (!scans[j] || elm_host::scan_ctx(scans[j]) != ctx) return ELM_ERR_INVALID;
-    for (size_t i = 0; i < 16 * (size_t)n_jobs; ++i)
-        if (!isfinite(poses16[i])) return ELM_ERR_INVALID;
-    try {
-        return accumulate_impl(ctx, ev, scans, poses16, (uint32_t)n_jobs, c, stats, events);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, what, [&] { return accumulate_impl(ctx, ev, scans, poses16, (uint32_t)n_jobs, c, stats, events); });
 }
 
 } // namespace
 
 extern "C" int elm_evidence_create(elm_ctx* ctx, const elm_map* map, int sub, elm_evidence** out) {
-    if (!ctx || !map || !out || !(sub == 1 || sub == 2 || sub == 4)) return ELM_ERR_INVALID;
+    if (!ctx || !map || !out || !sub_ok(sub)) return ELM_ERR_INVALID;
     *out = nullptr;
     int rc = check_plain(ctx, "elm_evidence_create");
     if (rc != ELM_OK) return rc;
     if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    try {
-        return create_impl(ctx, map, sub, out);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_evidence_create: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, "elm_evidence_create", [&] { return create_impl(ctx, map, sub, out); });
 }
 
 extern "C" void elm_evidence_destroy(elm_evidence* ev) { evidence_free(ev); }
@@ -301,31 +214,28 @@ extern "C" int elm_evidence_counts(elm_ctx* ctx, const elm_evidence* ev, uint32_
     *n = ev->n_cells;
     const size_t k = std::min<size_t>(cap, ev->n_cells);
     if (!k || (!through && !hit)) return ELM_OK;
-    try {
+    return guard_alloc(ctx, "elm_evidence_counts", [&] {
         std::vector<uint32_t> t, h;
-        rc = download_counts(ctx, ev, t, h);
+        int rc = download_counts(ctx, ev, t, h);
         if (rc != ELM_OK) return rc;
         if (through) memcpy(through, t.data(), k * sizeof(uint32_t));
         if (hit) memcpy(hit, h.data(), k * sizeof(uint32_t));
-        return ELM_OK;
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_evidence_counts: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+        return (int)ELM_OK;
+    });
 }
 
 extern "C" int elm_evidence_stale_points(elm_ctx* ctx, const elm_evidence* ev, const elm_evidence_rule* rule, uint8_t* flags, size_t cap, size_t* n) {
     if (!n || !rule || (!flags && cap)) return ELM_ERR_INVALID;
     int rc = check_object(ctx, ev, "elm_evidence_stale_points");
     if (rc != ELM_OK) return rc;
-    try {
+    return guard_alloc(ctx, "elm_evidence_stale_points", [&] {
         std::vector<int32_t> f;
-        rc = elm_host::map_point_fine_cells(ev->map, ev->sub, f);
+        int rc = elm_host::map_point_fine_cells(ev->map, ev->sub, f);
         if (rc != ELM_OK) return rc;
         const size_t n_pts = f.size() / 3;
         *n = n_pts;
         const size_t k = std::min(cap, n_pts);
-        if (!k) return ELM_OK;
+        if (!k) return (int)ELM_OK;
         std::vector<uint32_t> t, h;
         rc = download_counts(ctx, ev, t, h);
         if (rc != ELM_OK) return rc;
@@ -338,9 +248,6 @@ extern "C" int elm_evidence_stale_points(elm_ctx* ctx, const elm_evidence* ev, c
             const std::array<int32_t, 3>* it = std::lower_bound(cells, cells + ev->n_cells, c);
             flags[i] = (it != cells + ev->n_cells && *it == c) ? stale[it - cells] : 0; // (every stored point's cell is in the table)
         }
-        return ELM_OK;
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_evidence_stale_points: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+        return (int)ELM_OK;
+    });
 }

@@ -1,19 +1,18 @@
 // elm_grow.cpp -- map growth (include/elimaloc_hip.h, "map growth"): the growth object (two open-addressing tables
 // on the device that the kernels of elm_k_grow.hip fill: candidate fine cells with their counters, and the coarse cells' masks), the
-// argument checks and the capacity guard, the job table, the launches, the downloads and the rule.  Host-side C++17.
+// capacity guard, the job table and the launches through the call of many jobs that elm_query.hpp shares with the map evidence, the
+// downloads and the rule.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
-#include <new>
-#include <string>
 #include <vector>
 
-#include "elm_hostapi.hpp"
-#include "elm_internal.hpp"
+#include "elm_query.hpp"
 
 using namespace elm;
+using namespace elm_query;
 
 struct elm_growth {
     elm_ctx* ctx = nullptr;
@@ -50,38 +49,7 @@ namespace {
 
 constexpr size_t kGrowMaxCapacity = (size_t)1 << 30;
 
-bool fin_ge0(double v) { return isfinite(v) && v >= 0.0; }
-
-bool config_ok(const elm_growth_config* c) {
-    if (!c || !(c->sub == 1 || c->sub == 2 || c->sub == 4) || c->max_steps < 1 || c->max_steps > kRayMaxSteps) return false;
-    if (c->clearance_cells < 0 || c->clearance_cells > 2) return false;
-    if (!fin_ge0(c->min_range_m) || !fin_ge0(c->obs_min_range_m) || !(isfinite(c->obs_max_range_m) && c->obs_max_range_m >= c->obs_min_range_m)) return false;
-    if (!fin_ge0(c->end_margin_m) || !fin_ge0(c->end_margin_frac)) return false;
-    return isfinite(c->origin[0]) && isfinite(c->origin[1]) && isfinite(c->origin[2]);
-}
-
-// one rank, no exchange (as the other map queries)
-int check_plain(elm_ctx* ctx, const char* what) {
-    if ((elm_host::ctx_group(ctx) && !elm_multi::in_worker()) || elm_host::ctx_exchange_attached(ctx)) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    return ELM_OK;
-}
-
-// the checks every call on an existing object shares
-int check_object(elm_ctx* ctx, const elm_growth* g, const char* what) {
-    if (!ctx || !g) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, what);
-    if (rc != ELM_OK) return rc;
-    if (g->ctx != ctx || g->ctx_id != elm_host::ctx_unique_id(ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    return ELM_OK;
-}
-
-int dev_error(elm_ctx* ctx, const char* what, hipError_t e) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
-    return ELM_ERR_DEVICE;
-}
+bool config_ok(const elm_growth_config* c) { return walk_config_ok(c) && c->clearance_cells >= 0 && c->clearance_cells <= 2; }
 
 void growth_free(elm_growth* g) {
     if (!g) return;
@@ -143,80 +111,32 @@ int accumulate_impl(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, c
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
-    std::vector<EvidJob> jobs(n_jobs);
-    uint64_t beams = 0, chunks = 0;
-    for (uint32_t j = 0; j < n_jobs; ++j) {
-        size_t n = 0;
-        jobs[j].pts = elm_host::scan_dev_points(scans[j], &n);
-        jobs[j].n = (uint32_t)n;
-        jobs[j].chunk0 = (uint32_t)chunks;
-        for (int r = 0; r < 3; ++r)
-            for (int q = 0; q < 4; ++q) jobs[j].rows[r * 4 + q] = poses16[16 * (size_t)j + q * 4 + r];
-        beams += n;
-        chunks += (n + 255) / 256;
-    }
+    const JobTable jobs = build_jobs(scans, poses16, n_jobs);
     // the table can never fill: one beam makes at most one candidate
-    if (g->count + beams > (uint64_t)g->capacity) {
+    if (g->count + jobs.beams > (uint64_t)g->capacity) {
         elm_host::ctx_set_error(ctx, "map growth: candidates + beams of the call exceed the capacity; download the cells and reset, or create a larger object");
         return ELM_ERR_UNSUPPORTED;
     }
-    // no counter can wrap: one beam adds at most 1 to any counter (and less than 2^16 to a sum of 64 bits)
-    if (g->total_beams + beams > 0xFFFFFFFFull) {
-        elm_host::ctx_set_error(ctx, "map growth: more than 2^32 - 1 beams accumulated; download the cells and reset");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    if (stats) memset(stats, 0, (size_t)n_jobs * sizeof(*stats));
-    if (chunks == 0) return ELM_OK;
-    EvidParams ep{};
-    ep.ox = c->origin[0]; ep.oy = c->origin[1]; ep.oz = c->origin[2];
-    ep.t_min = c->min_range_m;
-    ep.obs_min_r2 = c->obs_min_range_m * c->obs_min_range_m;
-    ep.obs_max_r2 = c->obs_max_range_m * c->obs_max_range_m;
-    ep.margin_m = c->end_margin_m;
-    ep.margin_frac = c->end_margin_frac;
-    ep.max_steps = c->max_steps;
+    const EvidParams ep = walk_params(*c);
     GrowTables gt = g->t;
     gt.clearance = c->clearance_cells;
-    const size_t n_ev = events ? jobs[0].n : 0;
-    EvidJob* d_jobs = (EvidJob*)elm_host::ctx_reloc_scratch(ctx, 1, jobs.size() * sizeof(EvidJob), &rc);
-    uint32_t* d_part = d_jobs ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)chunks * kGrowWords * sizeof(uint32_t), &rc) : nullptr;
-    elm_growth_stats* d_stats = d_part ? (elm_growth_stats*)elm_host::ctx_reloc_scratch(ctx, 4, (size_t)n_jobs * sizeof(elm_growth_stats), &rc) : nullptr;
-    uint16_t* d_ev = d_stats && n_ev ? (uint16_t*)elm_host::ctx_reloc_scratch(ctx, 13, n_ev * sizeof(uint16_t), &rc) : nullptr;
-    if (!d_stats || (n_ev && !d_ev)) return rc;
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     uint32_t count = 0;
-    hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(EvidJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch_grow(st, *ft, ep, gt, d_jobs, n_jobs, (uint32_t)chunks, d_part, d_stats, d_ev);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) g->total_beams += beams; // the launch is queued: the counters will take these beams
-    if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, (size_t)n_jobs * sizeof(elm_growth_stats), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&count, g->t.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st); // the count comes back with the stats
-    if (e == hipSuccess && n_ev) e = hipMemcpyAsync(events, d_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st); // the job table on the host is read by the copy until here
-    if (e != hipSuccess) return dev_error(ctx, "map growth", e);
-    g->count = count;
-    return ELM_OK;
+    rc = run_jobs(
+        ctx, jobs, g->total_beams, "map growth", "cells", kGrowWords, stats, events,
+        [&](hipStream_t st, const EvidJob* d_jobs, uint32_t n_chunks, uint32_t* d_part, elm_growth_stats* d_stats, uint16_t* d_ev) {
+            launch_grow(st, *ft, ep, gt, d_jobs, n_jobs, n_chunks, d_part, d_stats, d_ev);
+        },
+        // the count comes back with the stats
+        [&](hipStream_t st) { return hipMemcpyAsync(&count, g->t.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st); });
+    if (rc == ELM_OK && jobs.chunks) g->count = count;
+    return rc;
 }
 
 int accumulate_checked(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, int n_jobs,
                        const elm_growth_config* c, elm_growth_stats* stats, uint16_t* events, const char* what) {
-    if (!ctx || !g || !scans || !poses16 || n_jobs < 1 || n_jobs > kEvidMaxJobs || !config_ok(c)) return ELM_ERR_INVALID;
-    int rc = check_object(ctx, g, what);
+    int rc = check_accumulate(ctx, g, scans, poses16, n_jobs, c, config_ok(c), what);
     if (rc != ELM_OK) return rc;
-    if (c->sub != g->sub) return ELM_ERR_INVALID;
-    for (int j = 0; j < n_jobs; ++j)
-        if (!scans[j] || elm_host::scan_ctx(scans[j]) != ctx) return ELM_ERR_INVALID;
-    for (size_t i = 0; i < 16 * (size_t)n_jobs; ++i)
-        if (!isfinite(poses16[i])) return ELM_ERR_INVALID;
-    try {
-        return accumulate_impl(ctx, g, scans, poses16, (uint32_t)n_jobs, c, stats, events);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, what, [&] { return accumulate_impl(ctx, g, scans, poses16, (uint32_t)n_jobs, c, stats, events); });
 }
 
 // the candidates in ascending (x, y, z) order, which is the ascending order of their keys
@@ -264,17 +184,12 @@ int download_cells(elm_ctx* ctx, const elm_growth* g, Cells& out) {
 } // namespace
 
 extern "C" int elm_growth_create(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out) {
-    if (!ctx || !map || !out || !(sub == 1 || sub == 2 || sub == 4) || capacity < 1 || capacity > kGrowMaxCapacity) return ELM_ERR_INVALID;
+    if (!ctx || !map || !out || !sub_ok(sub) || capacity < 1 || capacity > kGrowMaxCapacity) return ELM_ERR_INVALID;
     *out = nullptr;
     int rc = check_plain(ctx, "elm_growth_create");
     if (rc != ELM_OK) return rc;
     if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    try {
-        return create_impl(ctx, map, sub, capacity, out);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_growth_create: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, "elm_growth_create", [&] { return create_impl(ctx, map, sub, capacity, out); });
 }
 
 extern "C" void elm_growth_destroy(elm_growth* g) { growth_free(g); }
@@ -309,28 +224,25 @@ extern "C" int elm_growth_cells(elm_ctx* ctx, const elm_growth* g, int32_t* cell
     *n = (size_t)g->count;
     const size_t k = std::min<size_t>(cap, (size_t)g->count);
     if (!k || (!cells3 && !hit && !through && !sums3)) return ELM_OK;
-    try {
+    return guard_alloc(ctx, "elm_growth_cells", [&] {
         Cells c;
-        rc = download_cells(ctx, g, c);
+        int rc = download_cells(ctx, g, c);
         if (rc != ELM_OK) return rc;
         if (cells3) memcpy(cells3, c.cells3.data(), 3 * k * sizeof(int32_t));
         if (hit) memcpy(hit, c.hit.data(), k * sizeof(uint32_t));
         if (through) memcpy(through, c.through.data(), k * sizeof(uint32_t));
         if (sums3) memcpy(sums3, c.sums3.data(), 3 * k * sizeof(uint64_t));
-        return ELM_OK;
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_growth_cells: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+        return (int)ELM_OK;
+    });
 }
 
 extern "C" int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, const elm_growth_rule* rule, double* xyz64, size_t cap, size_t* n) {
     if (!n || !rule || (!xyz64 && cap)) return ELM_ERR_INVALID;
     int rc = check_object(ctx, g, "elm_growth_appeared_points");
     if (rc != ELM_OK) return rc;
-    try {
+    return guard_alloc(ctx, "elm_growth_appeared_points", [&] {
         const FineTable* ft = nullptr;
-        rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
+        int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
         if (rc != ELM_OK) return rc;
         const double cell = ft->cell;
         Cells c;
@@ -346,9 +258,6 @@ extern "C" int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, con
             ++m;
         }
         *n = m;
-        return ELM_OK;
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_growth_appeared_points: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+        return (int)ELM_OK;
+    });
 }

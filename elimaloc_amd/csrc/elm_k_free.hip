@@ -12,59 +12,21 @@ namespace elm {
 
 namespace {
 
-// The local indices 0 .. 3 of coarse cell c (one axis) whose fine cell lies in [f - 1, f + 1], as 4 bits.
-__device__ __forceinline__ uint32_t near_bits(int f, int c) {
-    uint32_t b = 0;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const int d = (c << 2) + l - f;
-        b |= (d >= -1 && d <= 1) ? (1u << l) : 0u;
-    }
-    return b;
-}
-
-// Whether fine cell (fx, fy, fz) or one of its 26 neighbours is occupied: the (up to 2 x 2 x 2) coarse cells they lie in.
-__device__ __forceinline__ bool fine_supported(const FineTable& ft, int fx, int fy, int fz) {
-    for (int cx = (fx - 1) >> 2; cx <= (fx + 1) >> 2; ++cx)
-        for (int cy = (fy - 1) >> 2; cy <= (fy + 1) >> 2; ++cy)
-            for (int cz = (fz - 1) >> 2; cz <= (fz + 1) >> 2; ++cz) {
-                const unsigned long long m = fine_probe(ft, cx, cy, cz);
-                if (!m) continue;
-                const uint32_t xb = near_bits(fx, cx), yb = near_bits(fy, cy), zb = near_bits(fz, cz);
-                uint32_t yz = 0;
-#pragma unroll
-                for (int l = 0; l < 4; ++l) yz |= ((yb >> l) & 1u) ? (zb << (4 * l)) : 0u;
-                unsigned long long nb = 0;
-#pragma unroll
-                for (int l = 0; l < 4; ++l) nb |= ((xb >> l) & 1u) ? ((unsigned long long)yz << (16 * l)) : 0ull;
-                if (m & nb) return true;
-            }
-    return false;
-}
-
-// One sample of a ray: a = o + u (k step), q = R a + t in the contract's association, whether q's fine cell is occupied.  (lcx, lcy, lcz,
-// lmask, have) keep the last coarse cell probed: consecutive samples mostly share it (8 per cell along an axis at the defaults).
-__device__ __forceinline__ bool sample_hit(const FineTable& ft, const FreeParams& fp, const PoseRows& P, double ux, double uy, double uz, int k, int& lcx,
-                                           int& lcy, int& lcz, unsigned long long& lmask, bool& have) {
+// One sample of a ray: a = o + u (k step), q = R a + t, whether q's fine cell is occupied.  mc keeps the last coarse cell probed:
+// consecutive samples mostly share it (8 per cell along an axis at the defaults).
+__device__ __forceinline__ bool sample_hit(const FineTable& ft, const FreeParams& fp, const PoseRows& P, double ux, double uy, double uz, int k,
+                                           MaskCache& mc) {
     const double s = (double)k * fp.step;
-    const double ax = fp.ox + ux * s, ay = fp.oy + uy * s, az = fp.oz + uz * s;
-    const int fx = fine_of(((P.r00 * ax + P.r01 * ay) + P.r02 * az) + P.t0, ft);
-    const int fy = fine_of(((P.r10 * ax + P.r11 * ay) + P.r12 * az) + P.t1, ft);
-    const int fz = fine_of(((P.r20 * ax + P.r21 * ay) + P.r22 * az) + P.t2, ft);
-    const int cx = fx >> 2, cy = fy >> 2, cz = fz >> 2;
-    if (!have || cx != lcx || cy != lcy || cz != lcz) {
-        lmask = fine_probe(ft, cx, cy, cz);
-        lcx = cx; lcy = cy; lcz = cz;
-        have = true;
-    }
-    return (lmask >> fine_bit(fx, fy, fz)) & 1ull;
+    double q0, q1, q2;
+    pose_apply(P, fp.ox + ux * s, fp.oy + uy * s, fp.oz + uz * s, q0, q1, q2);
+    return mc.test(fine_of(q0, ft), fine_of(q1, ft), fine_of(q2, ft), FineProbe{ft});
 }
 
 } // namespace
 
 // K6a.  Workgroup = 256 consecutive rays (one per lane, float64 in registers) x kFreePoses consecutive poses, whose rows are
 // workgroup-uniform.  The ray's length, direction and sample count do not depend on the pose: they are formed once.
-//   FORM 0: a lane walks its own ray; the last coarse cell's mask stays in registers, a probe only when the cell changes.
+//   FORM 0: a lane walks its own ray; the last coarse cell's mask stays in registers (MaskCache), a probe only when the cell changes.
 //   FORM 1: a wave walks its 64 rays one after the other, lane l taking samples k0 + l, k0 + l + 64, ...: no lane waits for a longer ray,
 //           but neighbouring samples sit in different lanes, so nearly every sample is a probe.
 // Per pose each wave counts with ballot + popcount (and one shuffle sum for the occupied samples); the four waves meet in LDS and one lane
@@ -78,20 +40,17 @@ __global__ __launch_bounds__(256) void k_free_rays(const FineTable ft, const Fre
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t chunk = blockIdx.x % n_chunks, h0 = (blockIdx.x / n_chunks) * kFreePoses;
     const uint32_t i = chunk * 256u + tid;
-    const bool valid = i < n;
-    const uint32_t j = valid ? i : 0u;
-    const double px = (double)pts[3 * (size_t)j], py = (double)pts[3 * (size_t)j + 1], pz = (double)pts[3 * (size_t)j + 2];
-    const double dx = px - fp.ox, dy = py - fp.oy, dz = pz - fp.oz;
-    const double L2 = (dx * dx + dy * dy) + dz * dz;
-    const bool counted = valid && L2 >= fp.min_r2 && L2 <= fp.max_r2 && L2 > 0.0;
-    const double L = sqrt(L2);
+    const Beam b = load_beam(pts, i, n, fp.ox, fp.oy, fp.oz);
+    const bool valid = b.valid;
+    const bool counted = valid && in_window(b.L2, fp.min_r2, fp.max_r2) && b.L2 > 0.0; // (not b.cast: max_r2 may be infinite)
+    const double L = sqrt(b.L2);
     const double reach = L - fmax(fp.margin_m, fp.margin_frac * L);
     int K = 0;
     if (counted && reach > 0.0) K = (int)fmin(floor(reach / fp.step), (double)fp.max_samples);
-    const double ux = dx / L, uy = dy / L, uz = dz / L;
+    const double ux = b.dx / L, uy = b.dy / L, uz = b.dz / L;
     const uint32_t n_s = K >= fp.k0 ? (uint32_t)(K - fp.k0 + 1) : 0u;
     {
-        const uint32_t c = (uint32_t)__popcll(__ballot(counted)), s = wave_sum(n_s);
+        const uint32_t c = wave_count(counted), s = wave_sum(n_s);
         if (lane == 0) {
             wray[wave][0] = c;
             wray[wave][1] = s;
@@ -99,14 +58,11 @@ __global__ __launch_bounds__(256) void k_free_rays(const FineTable ft, const Fre
     }
     const uint32_t hn = min((uint32_t)kFreePoses, n_poses - h0);
     for (uint32_t hl = 0; hl < hn; ++hl) {
-        const double* R = rows + (size_t)(h0 + hl) * 12;
-        const PoseRows P{R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], R[9], R[10], R[11]};
+        const PoseRows P = load_pose_rows(rows + (size_t)(h0 + hl) * 12);
         uint32_t hits = 0;
-        int lcx = 0, lcy = 0, lcz = 0;
-        unsigned long long lmask = 0;
-        bool have = false;
+        MaskCache mc;
         if (FORM == 0) {
-            for (int k = fp.k0; k <= K; ++k) hits += sample_hit(ft, fp, P, ux, uy, uz, k, lcx, lcy, lcz, lmask, have) ? 1u : 0u;
+            for (int k = fp.k0; k <= K; ++k) hits += sample_hit(ft, fp, P, ux, uy, uz, k, mc) ? 1u : 0u;
         } else {
             for (int r = 0; r < 64; ++r) {
                 const int Kr = __shfl(K, r);
@@ -115,23 +71,22 @@ __global__ __launch_bounds__(256) void k_free_rays(const FineTable ft, const Fre
                 uint32_t c = 0;
                 for (int kb = fp.k0; kb <= Kr; kb += 64) {
                     const int k = kb + (int)lane;
-                    const bool hit = k <= Kr && sample_hit(ft, fp, P, rx, ry, rz, k, lcx, lcy, lcz, lmask, have);
-                    c += (uint32_t)__popcll(__ballot(hit));
+                    const bool hit = k <= Kr && sample_hit(ft, fp, P, rx, ry, rz, k, mc);
+                    c += wave_count(hit);
                 }
                 if ((int)lane == r) hits = c;
             }
         }
         bool end_occ = false, sup = false;
         if (counted) {
-            const int fx = fine_of(((P.r00 * px + P.r01 * py) + P.r02 * pz) + P.t0, ft);
-            const int fy = fine_of(((P.r10 * px + P.r11 * py) + P.r12 * pz) + P.t1, ft);
-            const int fz = fine_of(((P.r20 * px + P.r21 * py) + P.r22 * pz) + P.t2, ft);
+            double q0, q1, q2;
+            pose_apply(P, b.px, b.py, b.pz, q0, q1, q2);
+            const int fx = fine_of(q0, ft), fy = fine_of(q1, ft), fz = fine_of(q2, ft);
             end_occ = (fine_probe(ft, fx >> 2, fy >> 2, fz >> 2) >> fine_bit(fx, fy, fz)) & 1ull;
-            sup = end_occ || fine_supported(ft, fx, fy, fz);
+            sup = end_occ || near_occupied(ft, fx, fy, fz, 1); // the cell or one of its 26 neighbours
         }
         if (hits_out && valid) hits_out[(size_t)(h0 + hl) * n + i] = (uint16_t)min(hits, 65535u);
-        const uint32_t c_p = (uint32_t)__popcll(__ballot(hits >= (uint32_t)fp.min_hits));
-        const uint32_t c_e = (uint32_t)__popcll(__ballot(end_occ)), c_s = (uint32_t)__popcll(__ballot(sup));
+        const uint32_t c_p = wave_count(hits >= (uint32_t)fp.min_hits), c_e = wave_count(end_occ), c_s = wave_count(sup);
         const uint32_t c_h = wave_sum(hits);
         if (lane == 0) {
             wcnt[hl][wave][0] = c_p;

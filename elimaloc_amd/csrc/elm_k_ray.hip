@@ -13,8 +13,8 @@ namespace elm {
 
 // K7a.  Workgroup = 256 consecutive beams (one per lane, float64 in registers) x pose_block consecutive poses, whose rows are
 // workgroup-uniform.  The beam's length, direction, cast / compared state and tolerance do not depend on the pose: they are formed once.
-// Per step a lane takes one 3-way minimum, one integer add, one multiply-subtract-divide for the stepped axis and a bit test of the
-// current coarse cell's mask held in registers; the table is probed only when the coarse cell (c >> 2) changes.  Per pose each wave
+// The walk is CellWalk and the coarse cell's mask MaskCache (elm_dev_fine.hpp); this kernel's own part is the decision at each cell: a
+// beam enters its first run of occupied cells (range_in) and leaves it (range_out), or ends by range or by steps.  Per pose each wave
 // counts with ballot + popcount (and one shuffle sum for the steps); the four waves meet in LDS and one lane per pose stores the partial.
 __global__ __launch_bounds__(256) void k_ray_cast(const FineTable ft, const RayParams rp, const float* __restrict__ pts, uint32_t n,
                                                   const double* __restrict__ rows, uint32_t n_poses, uint32_t n_chunks, uint32_t pose_block,
@@ -25,18 +25,14 @@ __global__ __launch_bounds__(256) void k_ray_cast(const FineTable ft, const RayP
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t chunk = blockIdx.x % n_chunks, h0 = (blockIdx.x / n_chunks) * pose_block;
     const uint32_t i = chunk * 256u + tid;
-    const bool valid = i < n;
-    const uint32_t j = valid ? i : 0u;
-    const double dx = (double)pts[3 * (size_t)j] - rp.ox, dy = (double)pts[3 * (size_t)j + 1] - rp.oy, dz = (double)pts[3 * (size_t)j + 2] - rp.oz;
-    const double L2 = (dx * dx + dy * dy) + dz * dz;
-    const bool cast = valid && L2 > 0.0 && L2 < HUGE_VAL; // (a NaN fails both)
-    const bool compared = cast && L2 >= rp.cmp_min_r2 && L2 <= rp.cmp_max_r2;
-    const double L = sqrt(L2);
-    const double ux = dx / L, uy = dy / L, uz = dz / L;
+    const Beam b = load_beam(pts, i, n, rp.ox, rp.oy, rp.oz);
+    const bool valid = b.valid, cast = b.cast;
+    const bool compared = cast && in_window(b.L2, rp.cmp_min_r2, rp.cmp_max_r2);
+    const double L = sqrt(b.L2);
+    const double ux = b.dx / L, uy = b.dy / L, uz = b.dz / L;
     const double tol = fmax(rp.tol_m, rp.tol_frac * L);
-    const double cell = ft.cell;
     {
-        const uint32_t c = (uint32_t)__popcll(__ballot(cast)), m = (uint32_t)__popcll(__ballot(compared));
+        const uint32_t c = wave_count(cast), m = wave_count(compared);
         if (lane == 0) {
             wray[wave][0] = c;
             wray[wave][1] = m;
@@ -44,69 +40,42 @@ __global__ __launch_bounds__(256) void k_ray_cast(const FineTable ft, const RayP
     }
     const uint32_t hn = min(pose_block, n_poses - h0);
     for (uint32_t hl = 0; hl < hn; ++hl) {
-        const double* R = rows + (size_t)(h0 + hl) * 12;
-        const PoseRows P{R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], R[9], R[10], R[11]};
+        const PoseRows P = load_pose_rows(rows + (size_t)(h0 + hl) * 12);
         uint32_t flag = 0, steps_hit = 0;
         double rin = -1.0, rout = -1.0;
         int hx = 0, hy = 0, hz = 0;
         if (cast) {
-            const double s0 = ((P.r00 * rp.ox + P.r01 * rp.oy) + P.r02 * rp.oz) + P.t0;
-            const double s1 = ((P.r10 * rp.ox + P.r11 * rp.oy) + P.r12 * rp.oz) + P.t1;
-            const double s2 = ((P.r20 * rp.ox + P.r21 * rp.oy) + P.r22 * rp.oz) + P.t2;
-            const double w0 = (P.r00 * ux + P.r01 * uy) + P.r02 * uz;
-            const double w1 = (P.r10 * ux + P.r11 * uy) + P.r12 * uz;
-            const double w2 = (P.r20 * ux + P.r21 * uy) + P.r22 * uz;
-            double t_in = rp.t_min;
-            int c0 = fine_of(s0 + w0 * t_in, ft), c1 = fine_of(s1 + w1 * t_in, ft), c2 = fine_of(s2 + w2 * t_in, ft);
-            const int g0 = w0 > 0.0 ? 1 : (w0 < 0.0 ? -1 : 0), g1 = w1 > 0.0 ? 1 : (w1 < 0.0 ? -1 : 0), g2 = w2 > 0.0 ? 1 : (w2 < 0.0 ? -1 : 0);
-            const int up0 = g0 > 0 ? 1 : 0, up1 = g1 > 0 ? 1 : 0, up2 = g2 > 0 ? 1 : 0;
-            double tx0 = g0 ? exit_param(c0, up0, cell, s0, w0) : HUGE_VAL;
-            double tx1 = g1 ? exit_param(c1, up1, cell, s1, w1) : HUGE_VAL;
-            double tx2 = g2 ? exit_param(c2, up2, cell, s2, w2) : HUGE_VAL;
-            int lcx = 0, lcy = 0, lcz = 0;
-            unsigned long long lmask = 0;
-            bool have = false, in_run = false;
-            uint32_t steps = 0;
+            CellWalk w;
+            w.start(P, rp.ox, rp.oy, rp.oz, ux, uy, uz, rp.t_min, ft);
+            MaskCache mc;
+            bool in_run = false;
             for (;;) {
-                const int cx = c0 >> 2, cy = c1 >> 2, cz = c2 >> 2;
-                if (!have || cx != lcx || cy != lcy || cz != lcz) {
-                    lmask = fine_probe(ft, cx, cy, cz);
-                    lcx = cx; lcy = cy; lcz = cz;
-                    have = true;
-                }
-                const bool occ = (lmask >> fine_bit(c0, c1, c2)) & 1ull;
+                const bool occ = mc.test(w.c0, w.c1, w.c2, FineProbe{ft});
                 if (!in_run) {
                     if (occ) {
                         in_run = true;
                         flag = 1;
-                        rin = t_in;
-                        hx = c0; hy = c1; hz = c2;
-                        steps_hit = steps;
+                        rin = w.t_in;
+                        hx = w.c0; hy = w.c1; hz = w.c2;
+                        steps_hit = w.steps;
                     }
                 } else if (!occ) {
-                    rout = t_in;
+                    rout = w.t_in;
                     break;
                 }
-                int ax = 0;
-                double tmin = tx0;
-                if (tx1 < tmin) { tmin = tx1; ax = 1; }
-                if (tx2 < tmin) { tmin = tx2; ax = 2; }
-                const double t_next = fmax(t_in, tmin);
+                double t_next;
+                const int ax = w.peek(t_next);
                 if (t_next > rp.t_max) { // the walk ends by range
                     if (in_run) rout = rp.t_max;
-                    else { flag = 2; steps_hit = steps; }
+                    else { flag = 2; steps_hit = w.steps; }
                     break;
                 }
-                if (steps >= (uint32_t)rp.max_steps) { // ... by steps
-                    if (in_run) rout = t_in;
-                    else { flag = 3; steps_hit = steps; }
+                if (w.steps >= (uint32_t)rp.max_steps) { // ... by steps
+                    if (in_run) rout = w.t_in;
+                    else { flag = 3; steps_hit = w.steps; }
                     break;
                 }
-                t_in = t_next;
-                if (ax == 0) { c0 += g0; tx0 = exit_param(c0, up0, cell, s0, w0); }
-                else if (ax == 1) { c1 += g1; tx1 = exit_param(c1, up1, cell, s1, w1); }
-                else { c2 += g2; tx2 = exit_param(c2, up2, cell, s2, w2); }
-                ++steps;
+                w.advance(ax, t_next);
             }
         }
         const bool hit = flag == 1;
@@ -124,12 +93,12 @@ __global__ __launch_bounds__(256) void k_ray_cast(const FineTable ft, const RayP
             }
             if (flag_out) flag_out[o] = (uint8_t)flag;
         }
-        const uint32_t c_h = (uint32_t)__popcll(__ballot(hit)), c_m = (uint32_t)__popcll(__ballot(flag == 2)), c_t = (uint32_t)__popcll(__ballot(flag == 3));
-        const uint32_t c_a = (uint32_t)__popcll(__ballot(match)), c_p = (uint32_t)__popcll(__ballot(through)), c_f = (uint32_t)__popcll(__ballot(front));
+        const uint32_t c_h = wave_count(hit), c_m = wave_count(flag == 2), c_t = wave_count(flag == 3);
+        const uint32_t c_a = wave_count(match), c_p = wave_count(through), c_f = wave_count(front);
         const uint32_t c_s = wave_sum(steps_hit);
         if (lane == 0) {
-            uint32_t* w = wcnt[hl][wave];
-            w[0] = c_h; w[1] = c_m; w[2] = c_t; w[3] = c_a; w[4] = c_p; w[5] = c_f; w[6] = c_s;
+            uint32_t* wc = wcnt[hl][wave];
+            wc[0] = c_h; wc[1] = c_m; wc[2] = c_t; wc[3] = c_a; wc[4] = c_p; wc[5] = c_f; wc[6] = c_s;
         }
     }
     __syncthreads();

@@ -11,10 +11,10 @@
 #include <string>
 #include <vector>
 
-#include "elm_hostapi.hpp"
-#include "elm_internal.hpp"
+#include "elm_query.hpp"
 
 using namespace elm;
+using elm_query::check_plain;
 
 extern "C" void elm_reloc_config_default(elm_reloc_config* c) {
     if (!c) return;
@@ -205,15 +205,6 @@ void counted_points(const float* xyz, size_t n, size_t stride, double r_max, std
         const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
         if ((x * x + y * y) + z * z <= r2) S.insert(S.end(), {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]});
     }
-}
-
-// one rank, no exchange: a device group's lead or a context with a communicator / hook attached is refused
-int check_plain(elm_ctx* ctx, const char* what) {
-    if ((elm_host::ctx_group(ctx) && !elm_multi::in_worker()) || elm_host::ctx_exchange_attached(ctx)) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    return ELM_OK;
 }
 
 double wrap_deg(double d) {

@@ -1,6 +1,7 @@
 """Map growth on the GPU (elm_growth_*): the candidate cells, hit, through, the fixed-point sums, every per-beam event count and every stats
 field against the numpy mirror of the contract (tests/growth_ref.py), exactly and call by call; job order inside a call; contended
-inserts and counters; long probe chains and the capacity guard; the stats against MapEvidence's; every search index form; misuse; and on
+inserts and counters; long probe chains and the capacity guard; the stats against MapEvidence's and the end classes against the free-space
+check's; every search index form; misuse; and on
 a world with a box that the map does not hold, that the box is what appears and that the grown map explains the scans."""
 import ctypes as C
 import math
@@ -12,8 +13,8 @@ import growth_ref
 import ray_ref  # tests/ is on sys.path via conftest
 from elimaloc_amd import _lib, synth
 from elimaloc_amd._lib import ElmError
-from elimaloc_amd.registration import (Context, EvidenceConfig, GrowthConfig, GrowthRule, IcpMethod, Registration, RegistrationConfig, Scan,
-                                        VoxelHashMap)
+from elimaloc_amd.registration import (Context, EvidenceConfig, FreeSpaceConfig, GrowthConfig, GrowthRule, IcpMethod, Registration,
+                                        RegistrationConfig, Scan, VoxelHashMap)
 
 pytestmark = pytest.mark.gpu
 
@@ -280,6 +281,29 @@ def test_stats_agree_with_map_evidence(ctx, field300k, field_map):
         assert all(x[k] == y[k] for k in ("n_cast", "n_observing", "n_walked", "n_truncated", "n_steps", "n_end_hit"))
         assert y["n_end_near"] + y["n_end_new"] + y["n_end_out"] == x["n_end_free"] and y["n_truncated"] > 0 and y["n_end_new"] > 0
     ev.close()
+    g.close()
+
+
+def test_end_classes_agree_with_the_free_space_check(ctx, lattice300k):
+    """The end point's neighbourhood test is one function for both calls: with a clearance of one cell and the same range window and origin,
+    the free-space check's supported end points are growth's END-HIT and END-NEAR ones, at every pose.  (Chosen on the mirrors,
+    growth_ref and test_free_space.mirror, with the first 20 world points of every voxel as the stored points: 98 hit / 81 near / 75
+    neither of 254 observing beams at the first pose, 7 / 14 / 233 at the second, none out of range, the three equalities holding.  On
+    the map itself the classes are 93 / 86 / 75 and 6 / 15 / 233.)"""
+    vm = VoxelHashMap(1.0, 20, ctx)
+    vm.AddPoints(lattice300k)
+    scan, T = synth.make_scan(lattice300k, 300, seed=21)  # one full 256-beam chunk and a tail of 44
+    sc = Scan(ctx, _noisy(scan, seed=22))
+    poses = _random_poses(T, 2, seed=23, spread=0.5)
+    poses[0] = T
+    fcfg = FreeSpaceConfig()
+    gcfg = GrowthConfig(sub=fcfg.sub, origin=fcfg.origin, clearance_cells=1, obs_min_range_m=fcfg.min_range_m, obs_max_range_m=fcfg.max_range_m)
+    g = vm.Growth(1024, fcfg.sub)
+    free, grow = vm.CheckFreeSpace(sc, poses, fcfg), g.Accumulate([sc, sc], poses, gcfg)
+    for f, y in zip(free, grow):
+        assert y["n_end_out"] == 0 and y["n_end_hit"] > 0 and y["n_end_near"] > 0 and y["n_end_new"] > 0, y  # hit, near and neither all occur
+        assert f["n_supported"] == y["n_end_hit"] + y["n_end_near"], (f, y)
+        assert f["n_counted"] == y["n_observing"] and f["n_end_occupied"] == y["n_end_hit"], (f, y)
     g.close()
 
 
