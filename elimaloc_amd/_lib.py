@@ -216,6 +216,23 @@ class GrowthRuleC(C.Structure):
     _fields_ = [("min_hit", C.c_uint32), ("hit_per_through", C.c_uint32)]
 
 
+class GrowthObjectRuleC(C.Structure):
+    """elm_growth_object_rule (include/elimaloc_hip.h, map growth: objects): the member rule, the connectivity, the smallest object."""
+    _fields_ = [("min_hit", C.c_uint32), ("hit_per_through", C.c_uint32), ("connectivity", C.c_uint32), ("min_cells", C.c_uint32)]
+
+
+class GrowthObjectC(C.Structure):
+    """elm_growth_object: one listed component."""
+    _fields_ = [("label", C.c_int32 * 3), ("n_cells", C.c_uint32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("hit", C.c_uint64),
+                ("through", C.c_uint64), ("cell_sum", C.c_uint64 * 3)]
+
+
+class GrowthObjectStatsC(C.Structure):
+    """elm_growth_object_stats: the counts of one labelling."""
+    _fields_ = [("n_members", C.c_uint32), ("n_objects", C.c_uint32), ("n_small", C.c_uint32), ("n_small_cells", C.c_uint32),
+                ("max_cells", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -241,6 +258,7 @@ EXPORTS = [
     "elm_evidence_accumulate", "elm_evidence_accumulate_batch", "elm_evidence_counts", "elm_evidence_stale_points",
     "elm_growth_config_default", "elm_growth_rule_default", "elm_growth_create", "elm_growth_destroy", "elm_growth_reset",
     "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
+    "elm_growth_object_rule_default", "elm_growth_find_objects", "elm_growth_objects", "elm_growth_cell_objects", "elm_growth_beam_objects",
 ]
 
 
@@ -443,6 +461,12 @@ def lib():
     L.elm_growth_cells.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t,
                                    C.POINTER(C.c_size_t)]
     L.elm_growth_appeared_points.argtypes = [vp, vp, C.POINTER(GrowthRuleC), dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_growth_object_rule_default.argtypes = [C.POINTER(GrowthObjectRuleC)]
+    L.elm_growth_object_rule_default.restype = None
+    L.elm_growth_find_objects.argtypes = [vp, vp, C.POINTER(GrowthObjectRuleC), C.POINTER(GrowthObjectStatsC)]
+    L.elm_growth_objects.argtypes = [vp, vp, C.POINTER(GrowthObjectC), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_growth_cell_objects.argtypes = [vp, vp, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.elm_growth_beam_objects.argtypes = [vp, vp, vp, dp, C.POINTER(GrowthConfigC), C.POINTER(C.c_int32)]
     L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
     L.elm_reloc_global_config_default.restype = None
     L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]

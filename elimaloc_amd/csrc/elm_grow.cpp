@@ -1,7 +1,9 @@
 // elm_grow.cpp -- map growth (include/elimaloc_hip.h, "map growth"): the growth object (two open-addressing tables
 // on the device that the kernels of elm_k_grow.hip fill: candidate fine cells with their counters, and the coarse cells' masks), the
 // capacity guard, the job table and the launches through the call of many jobs that elm_query.hpp shares with the map evidence, the
-// downloads and the rule.  Host-side C++17.
+// downloads and the rule; and the objects of the appeared cells ("map growth: objects"): the union-find state
+// that the kernels of elm_k_obj.hip work on, allocated when objects are first asked for, the sorted object list and the two ways back
+// from a cell and from a beam to its object.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -24,6 +26,14 @@ struct elm_growth {
     GrowTables t{};            // device arrays of `slots` entries each (sums: 3 per slot), and the candidate count
     uint64_t count = 0;        // the candidates, exact after every call
     uint64_t total_beams = 0;  // beams handed to accumulate calls since creation / reset
+    // the objects (elm_growth_find_objects): nothing is allocated before the first call
+    ObjTables o{};                 // device state: parent / root_id per slot, records / list / rank per candidate
+    ObjRecord* o_out = nullptr;    // the listed records side by side, for the download
+    size_t o_out_cap = 0;
+    bool o_held = false;           // a result is held: from a find until the next accumulate, reset or find
+    std::vector<elm_growth_object> objects; // ascending label
+    std::vector<int32_t> rank;     // per record: the object's index, or -2 (the host's copy of o.rank)
+    elm_growth_object_stats o_stats{};
 };
 
 extern "C" void elm_growth_config_default(elm_growth_config* c) {
@@ -54,7 +64,8 @@ bool config_ok(const elm_growth_config* c) { return walk_config_ok(c) && c->clea
 void growth_free(elm_growth* g) {
     if (!g) return;
     if (elm_host::ctx_is_alive(g->ctx, g->ctx_id)) (void)hipSetDevice(elm_host::ctx_device(g->ctx)); // a context destroyed first: just release
-    void* arrays[] = {g->t.ckeys, g->t.cmasks, g->t.fkeys, g->t.hit, g->t.through, g->t.sums, g->t.count};
+    void* arrays[] = {g->t.ckeys, g->t.cmasks, g->t.fkeys, g->t.hit, g->t.through, g->t.sums, g->t.count, g->o.parent, g->o.root_id,
+                      g->o.rec, g->o.listed, g->o.rank, g->o.counters, g->o_out};
     for (void* p : arrays)
         if (p) (void)hipFree(p);
     delete g;
@@ -120,6 +131,7 @@ int accumulate_impl(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, c
     const EvidParams ep = walk_params(*c);
     GrowTables gt = g->t;
     gt.clearance = c->clearance_cells;
+    g->o_held = false; // the counters move: the objects held are those of the table as it was
     uint32_t count = 0;
     rc = run_jobs(
         ctx, jobs, g->total_beams, "map growth", "cells", kGrowWords, stats, events,
@@ -181,6 +193,180 @@ int download_cells(elm_ctx* ctx, const elm_growth* g, Cells& out) {
     return ELM_OK;
 }
 
+
+// ---- objects
+void key_to_cell(unsigned long long key, int32_t* c3) {
+    for (int r = 0; r < 3; ++r) c3[r] = (int32_t)((key >> (21 * (2 - r))) & 0x1FFFFFull) - kGrowLim;
+}
+
+// the per-slot state once, the per-candidate state for at least `count` records (grown, never shrunk)
+hipError_t obj_reserve(elm_growth* g) {
+    hipError_t e = hipSuccess;
+    if (!g->o.parent) {
+        e = hipMalloc((void**)&g->o.parent, g->slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->o.root_id, g->slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->o.counters, 256);
+    }
+    const size_t want = std::max<size_t>((size_t)g->count, 1);
+    if (e == hipSuccess && g->o.rec_cap < want) {
+        void* old[] = {g->o.rec, g->o.listed, g->o.rank};
+        for (void* p : old)
+            if (p) (void)hipFree(p);
+        g->o.rec = nullptr; g->o.listed = nullptr; g->o.rank = nullptr;
+        g->o.rec_cap = 0;
+        e = hipMalloc((void**)&g->o.rec, want * sizeof(ObjRecord));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->o.listed, want * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->o.rank, want * sizeof(int32_t));
+        if (e == hipSuccess) g->o.rec_cap = (uint32_t)want;
+    }
+    return e;
+}
+
+int find_objects_impl(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule* rule, elm_growth_object_stats* stats) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    const char* what = "elm_growth_find_objects";
+    g->o_held = false;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    hipError_t e = obj_reserve(g);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    uint32_t cnt[kObjCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
+    e = hipMemsetAsync(g->o.counters, 0, kObjCounters * sizeof(uint32_t), st);
+    if (e == hipSuccess) {
+        (void)hipGetLastError();
+        launch_obj_find(st, g->t, g->o, rule->min_hit, rule->hit_per_through, rule->connectivity, rule->min_cells, (uint32_t)g->count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, g->o.counters, sizeof(cnt), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    const uint32_t n_roots = cnt[1], n_listed = cnt[2];
+    if (cnt[6] || n_roots > g->count || n_listed > n_roots) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": more components than candidate cells (the object's count is stale after a failed call; reset it)");
+        return ELM_ERR_DEVICE;
+    }
+    // the listed records come down, are sorted by label, and every record's rank goes up for the beam call
+    if (g->o_out_cap < n_listed) {
+        if (g->o_out) (void)hipFree(g->o_out);
+        g->o_out = nullptr;
+        g->o_out_cap = 0;
+        e = hipMalloc((void**)&g->o_out, (size_t)n_listed * sizeof(ObjRecord));
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        g->o_out_cap = n_listed;
+    }
+    std::vector<ObjRecord> rec(n_listed);
+    std::vector<uint32_t> listed(n_listed);
+    if (n_listed) {
+        (void)hipGetLastError();
+        launch_obj_gather(st, g->o, n_listed, g->o_out);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(rec.data(), g->o_out, (size_t)n_listed * sizeof(ObjRecord), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(listed.data(), g->o.listed, (size_t)n_listed * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+    }
+    std::vector<uint32_t> order(n_listed);
+    for (uint32_t j = 0; j < n_listed; ++j) order[j] = j;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rec[a].label < rec[b].label; });
+    g->objects.assign(n_listed, elm_growth_object{});
+    g->rank.assign(n_roots, -2);
+    for (uint32_t k = 0; k < n_listed; ++k) {
+        const ObjRecord& r = rec[order[k]];
+        elm_growth_object& ob = g->objects[k];
+        key_to_cell(r.label, ob.label);
+        ob.n_cells = r.n_cells;
+        for (int q = 0; q < 3; ++q) {
+            ob.lo[q] = r.lo[q];
+            ob.hi[q] = r.hi[q];
+            ob.cell_sum[q] = r.cell_sum[q];
+        }
+        ob.hit = r.hit;
+        ob.through = r.through;
+        if (listed[order[k]] >= n_roots) return dev_error(ctx, what, hipErrorUnknown);
+        g->rank[listed[order[k]]] = (int32_t)k;
+    }
+    if (n_roots) {
+        e = hipMemcpyAsync(g->o.rank, g->rank.data(), (size_t)n_roots * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+    }
+    elm_growth_object_stats s{};
+    s.n_members = cnt[0];
+    s.n_objects = n_listed;
+    s.n_small = cnt[3];
+    s.n_small_cells = cnt[4];
+    s.max_cells = cnt[5];
+    g->o_stats = s;
+    g->o_held = true;
+    if (stats) *stats = s;
+    return ELM_OK;
+}
+
+// a read call on the objects: the object checks, and a result must be held
+int check_objects_held(elm_ctx* ctx, const elm_growth* g, const char* what) {
+    int rc = check_object(ctx, g, what);
+    if (rc != ELM_OK) return rc;
+    if (!g->o_held) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": no objects are held (elm_growth_find_objects first; an accumulate or reset drops them)");
+        return ELM_ERR_INVALID;
+    }
+    return ELM_OK;
+}
+
+// one value per candidate cell in elm_growth_cells' order
+int cell_objects_impl(elm_ctx* ctx, const elm_growth* g, std::vector<int32_t>& out) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (!g->count) return ELM_OK;
+    const size_t s = g->slots;
+    std::vector<unsigned long long> keys(s);
+    std::vector<uint32_t> parent(s), root_id(s);
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    hipError_t e = hipMemcpyAsync(keys.data(), g->t.fkeys, s * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(parent.data(), g->o.parent, s * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(root_id.data(), g->o.root_id, s * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev_error(ctx, "map growth: objects: download", e);
+    std::vector<uint32_t> order;
+    order.reserve((size_t)g->count);
+    for (size_t h = 0; h < s; ++h)
+        if (keys[h]) order.push_back((uint32_t)h);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    out.resize(order.size());
+    for (size_t k = 0; k < order.size(); ++k) {
+        const uint32_t root = parent[order[k]];
+        int32_t v = -1;
+        if (root != kObjNone) {
+            const uint32_t id = root < s ? root_id[root] : 0xFFFFFFFFu;
+            if (id >= g->rank.size()) return dev_error(ctx, "map growth: objects: download", hipErrorUnknown);
+            v = g->rank[id];
+        }
+        out[k] = v;
+    }
+    return ELM_OK;
+}
+
+int beam_objects_impl(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* c, int32_t* obj) {
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    const char* what = "elm_growth_beam_objects";
+    const FineTable* ft = nullptr;
+    int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
+    if (rc != ELM_OK) return rc;
+    EvidJob job{};
+    size_t n = 0;
+    job.pts = elm_host::scan_dev_points(scan, &n);
+    job.n = (uint32_t)n;
+    pose_rows12(T16, job.rows);
+    if (!n) return ELM_OK;
+    int32_t* d_out = (int32_t*)elm_host::ctx_reloc_scratch(ctx, 13, n * sizeof(int32_t), &rc);
+    if (!d_out) return rc;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    (void)hipGetLastError();
+    launch_obj_beams(st, *ft, walk_params(*c), g->t, g->o, job, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(obj, d_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? ELM_OK : dev_error(ctx, what, e);
+}
+
 } // namespace
 
 extern "C" int elm_growth_create(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out) {
@@ -202,6 +388,7 @@ extern "C" int elm_growth_reset(elm_ctx* ctx, elm_growth* g) {
     if (e != hipSuccess) return dev_error(ctx, "elm_growth_reset", e);
     g->count = 0;
     g->total_beams = 0;
+    g->o_held = false;
     return ELM_OK;
 }
 
@@ -260,4 +447,55 @@ extern "C" int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, con
         *n = m;
         return (int)ELM_OK;
     });
+}
+
+extern "C" void elm_growth_object_rule_default(elm_growth_object_rule* r) {
+    if (!r) return;
+    r->min_hit = 3;
+    r->hit_per_through = 4;
+    r->connectivity = 26;
+    r->min_cells = 1;
+}
+
+extern "C" int elm_growth_find_objects(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule* rule, elm_growth_object_stats* stats) {
+    if (!rule || (rule->connectivity != 6 && rule->connectivity != 18 && rule->connectivity != 26) || rule->min_cells < 1) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, g, "elm_growth_find_objects");
+    if (rc != ELM_OK) return rc;
+    return guard_alloc(ctx, "elm_growth_find_objects", [&] { return find_objects_impl(ctx, g, rule, stats); });
+}
+
+extern "C" int elm_growth_objects(elm_ctx* ctx, const elm_growth* g, elm_growth_object* objs, size_t cap, size_t* n) {
+    if (!n || (!objs && cap)) return ELM_ERR_INVALID;
+    int rc = check_objects_held(ctx, g, "elm_growth_objects");
+    if (rc != ELM_OK) return rc;
+    *n = g->objects.size();
+    const size_t k = std::min(cap, g->objects.size());
+    if (k) memcpy(objs, g->objects.data(), k * sizeof(elm_growth_object));
+    return ELM_OK;
+}
+
+extern "C" int elm_growth_cell_objects(elm_ctx* ctx, const elm_growth* g, int32_t* obj, size_t cap, size_t* n) {
+    if (!n || (!obj && cap)) return ELM_ERR_INVALID;
+    int rc = check_objects_held(ctx, g, "elm_growth_cell_objects");
+    if (rc != ELM_OK) return rc;
+    *n = (size_t)g->count;
+    const size_t k = std::min<size_t>(cap, (size_t)g->count);
+    if (!k) return ELM_OK;
+    return guard_alloc(ctx, "elm_growth_cell_objects", [&] {
+        std::vector<int32_t> v;
+        int rc = cell_objects_impl(ctx, g, v);
+        if (rc != ELM_OK) return rc;
+        memcpy(obj, v.data(), std::min(k, v.size()) * sizeof(int32_t));
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_growth_beam_objects(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* cfg,
+                                       int32_t* obj) {
+    if (!scan || !obj) return ELM_ERR_INVALID;
+    int rc = check_accumulate(ctx, g, &scan, T16, 1, cfg, config_ok(cfg), "elm_growth_beam_objects");
+    if (rc != ELM_OK) return rc;
+    rc = check_objects_held(ctx, g, "elm_growth_beam_objects");
+    if (rc != ELM_OK) return rc;
+    return guard_alloc(ctx, "elm_growth_beam_objects", [&] { return beam_objects_impl(ctx, g, scan, T16, cfg, obj); });
 }

@@ -425,6 +425,37 @@ constexpr int kGrowWords = kGrowEndWords + kGrowWalkWords;
 void launch_grow(hipStream_t s, const FineTable& ft, const EvidParams& ep, const GrowTables& gt, const EvidJob* jobs, uint32_t n_jobs,
                  uint32_t n_chunks, uint32_t* partial, elm_growth_stats* stats, uint16_t* events);
 
+// map growth: objects (elm_k_obj.hip): the member cells of a growth object's fine table grouped into connected
+// components by a lock-free union-find over its slots, one record per component, and the way back from a slot to its object
+struct ObjRecord { // one component while it is on the device; the host turns the listed ones into elm_growth_object
+    unsigned long long label;     // the smallest grow_key of the component
+    uint32_t n_cells, _pad;
+    int32_t lo[3], hi[3];
+    unsigned long long hit, through, cell_sum[3];
+};
+constexpr uint32_t kObjNone = 0xFFFFFFFFu; // parent of a slot that holds no member
+constexpr int kObjCounters = 8; // members, roots, listed, small, small cells, max cells, roots beyond the records (always 0), spare
+struct ObjTables {
+    uint32_t* parent;   // [slots] kObjNone, or a slot of the same component with a smaller index (itself: the root)
+    uint32_t* root_id;  // [slots] of a root slot: its record
+    ObjRecord* rec;     // [rec_cap] one per root, in the order the roots were met
+    uint32_t* listed;   // [rec_cap] the records with n_cells >= min_cells, in the order they were met
+    int32_t* rank;      // [rec_cap] of a record: the index of its object in ascending label order, -2 for a small component (host-made)
+    uint32_t* counters; // [kObjCounters], zero before launch_obj_find
+    uint32_t rec_cap;
+};
+// The launches of one labelling on the stream: the members by the rule, the unions along the forward half of the neighbourhood
+// (connectivity 6, 18 or 26), every member's parent set to its root and the roots numbered, the records reduced, the objects listed.
+// max_roots: the candidate count, which bounds the roots (<= rec_cap).
+void launch_obj_find(hipStream_t s, const GrowTables& gt, const ObjTables& ot, uint32_t min_hit, uint32_t hit_per_through, uint32_t connectivity,
+                     uint32_t min_cells, uint32_t max_roots);
+// out[j] = rec[listed[j]], j < n_listed
+void launch_obj_gather(hipStream_t s, const ObjTables& ot, uint32_t n_listed, ObjRecord* out);
+// out[i] for every beam i < job.n of the scan at the job's pose: the rank of the object its end cell is a member of, -2 in a small
+// component, -1 otherwise (ft: the cell size only)
+void launch_obj_beams(hipStream_t s, const FineTable& ft, const EvidParams& ep, const GrowTables& gt, const ObjTables& ot, const EvidJob& job,
+                      int32_t* out);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

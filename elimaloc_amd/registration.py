@@ -12,7 +12,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, EvidenceConfigC, EvidenceRuleC, EvidenceStatsC, GrowthConfigC, GrowthRuleC, GrowthStatsC, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
+from ._lib import (ElmError, EvidenceConfigC, EvidenceRuleC, EvidenceStatsC, GrowthConfigC, GrowthObjectC, GrowthObjectRuleC, GrowthObjectStatsC, GrowthRuleC, GrowthStatsC, FreeSpaceConfigC, FreeSpaceStatsC, RayCastConfigC, RayCastStatsC, GlobalRelocConfigC, GlobalRelocStats, RegConfig, RegResult, IterTrace, MapInfo, RelocCandidate, RelocConfigC,
                    check)
 
 
@@ -177,6 +177,22 @@ _GROWTH_FIELDS = ("n_cast", "n_observing", "n_walked", "n_truncated", "n_end_hit
 def GrowthStats(st):
     """elm_growth_stats of one observation as a dict."""
     return {k: int(getattr(st, k)) for k in _GROWTH_FIELDS}
+
+
+def GrowthObjectRule(**kw):
+    """elm_growth_object_rule with its defaults (min_hit 3, hit_per_through 4, connectivity 26, min_cells 1): which candidate cells are
+    members (GrowthRule's rule), which of them are adjacent (6, 18 or 26) and how many cells make an object.  Starting points, not
+    measured optima."""
+    rule = GrowthObjectRuleC()
+    _lib.lib().elm_growth_object_rule_default(C.byref(rule))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(rule, k):
+            raise AttributeError(f"GrowthObjectRule has no field {k}")
+        setattr(rule, k, int(v))
+    return rule
+
+
+_GROWTH_OBJECT_FIELDS = ("n_members", "n_objects", "n_small", "n_small_cells", "max_cells")
 
 
 def _global_stats_dict(st):
@@ -918,6 +934,53 @@ class MapGrowth:
         out = np.zeros((max(n.value, 1), 3))
         check(L.elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), _dp(out), n.value, C.byref(n)), self.ctx._h, "elm_growth_appeared_points")
         return out[:n.value]
+
+    def FindObjects(self, rule=None):
+        """The appeared cells grouped into objects on the device (elm_growth_find_objects; `rule`: GrowthObjectRule()) -> the stats dict
+        (n_members, n_objects, n_small, n_small_cells, max_cells).  The result is held until the next Accumulate, Reset or FindObjects;
+        Objects, CellObjects and BeamObjects read it."""
+        rule = rule if rule is not None else GrowthObjectRule()
+        st = GrowthObjectStatsC()
+        check(_lib.lib().elm_growth_find_objects(self.ctx._h, self._handle(), C.byref(rule), C.byref(st)), self.ctx._h, "elm_growth_find_objects")
+        return {k: int(getattr(st, k)) for k in _GROWTH_OBJECT_FIELDS}
+
+    def Objects(self):
+        """The objects in ascending label order, as a dict of arrays: label int32 [m, 3], n_cells uint32 [m], lo / hi int32 [m, 3] (the
+        bounding box in cells, inclusive), hit / through uint64 [m], cell_sum uint64 [m, 3] (the sum of e + 2^20 over the member cells)."""
+        L = _lib.lib()
+        h = self._handle()
+        n = C.c_size_t(0)
+        check(L.elm_growth_objects(self.ctx._h, h, None, 0, C.byref(n)), self.ctx._h, "elm_growth_objects")
+        m = n.value
+        buf = (GrowthObjectC * max(m, 1))()
+        check(L.elm_growth_objects(self.ctx._h, h, buf, m, C.byref(n)), self.ctx._h, "elm_growth_objects")
+        a = np.frombuffer(buf, dtype=np.dtype([("label", np.int32, 3), ("n_cells", np.uint32), ("lo", np.int32, 3), ("hi", np.int32, 3),
+                                               ("hit", np.uint64), ("through", np.uint64), ("cell_sum", np.uint64, 3)]))[:m]
+        return {k: np.ascontiguousarray(a[k]) for k in a.dtype.names}
+
+    def CellObjects(self):
+        """int32 [count], one value per candidate cell in Cells()' order: the index of its object, -2 for a member of a small component,
+        -1 for a cell that is not a member."""
+        L = _lib.lib()
+        h = self._handle()
+        n = C.c_size_t(0)
+        check(L.elm_growth_cell_objects(self.ctx._h, h, None, 0, C.byref(n)), self.ctx._h, "elm_growth_cell_objects")
+        m = n.value
+        out = np.full(max(m, 1), -1, np.int32)
+        check(L.elm_growth_cell_objects(self.ctx._h, h, out.ctypes.data_as(C.POINTER(C.c_int32)), m, C.byref(n)), self.ctx._h, "elm_growth_cell_objects")
+        return out[:m]
+
+    def BeamObjects(self, scan, pose, cfg=None):
+        """int32 [n], one value per beam of the scan (a resident Scan: its resident order, Scan.points(); (m, 3) points are uploaded for the
+        call and answered in the resident order of that upload) at the pose [4, 4]: the index of the object the beam ends on, -2 for a
+        small component, -1 for anything else (elm_growth_beam_objects)."""
+        cfg = cfg if cfg is not None else GrowthConfig(sub=self.sub)
+        h = self._handle()
+        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
+        out = np.full(max(sc.n, 1), -1, np.int32)
+        check(_lib.lib().elm_growth_beam_objects(self.ctx._h, h, sc._h, _dp(_colmajor16(pose)), C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_int32))),
+              self.ctx._h, "elm_growth_beam_objects")
+        return out[:sc.n]
 
     def Reset(self):
         check(_lib.lib().elm_growth_reset(self.ctx._h, self._handle()), self.ctx._h, "elm_growth_reset")

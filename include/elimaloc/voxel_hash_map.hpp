@@ -116,6 +116,12 @@ struct GrowthRule : elm_growth_rule {
     GrowthRule() { elm_growth_rule_default(this); }
 };
 
+// elm_growth_object_rule with its defaults: the member rule, the connectivity (6, 18 or 26) and the smallest object (starting points, not
+// measured optima)
+struct GrowthObjectRule : elm_growth_object_rule {
+    GrowthObjectRule() { elm_growth_object_rule_default(this); }
+};
+
 class MapGrowth;
 
 struct VoxelHashMap {
@@ -533,6 +539,50 @@ public:
     }
 
     inline void Reset() { elimaloc::check(elm_growth_reset(VoxelHashMap::ctx(), g_), VoxelHashMap::ctx(), "elm_growth_reset"); }
+
+    // The appeared cells grouped into objects on the device (include/elimaloc_hip.h, map growth: objects).  The result is held until the
+    // next Accumulate, Reset or FindObjects; Objects, CellObjects and BeamObjects read it.
+    inline elm_growth_object_stats FindObjects(const GrowthObjectRule& rule = GrowthObjectRule()) {
+        elm_growth_object_stats st;
+        elimaloc::check(elm_growth_find_objects(VoxelHashMap::ctx(), g_, &rule, &st), VoxelHashMap::ctx(), "elm_growth_find_objects");
+        return st;
+    }
+    // The objects in ascending label order
+    inline std::vector<elm_growth_object> Objects() const {
+        size_t n = 0;
+        elimaloc::check(elm_growth_objects(VoxelHashMap::ctx(), g_, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_growth_objects");
+        std::vector<elm_growth_object> objs(n);
+        if (n) elimaloc::check(elm_growth_objects(VoxelHashMap::ctx(), g_, objs.data(), n, &n), VoxelHashMap::ctx(), "elm_growth_objects");
+        return objs;
+    }
+    // One value per candidate cell in Cells' order: the object's index, -2 in a small component, -1 for a cell that is not a member
+    inline std::vector<int32_t> CellObjects() const {
+        size_t n = 0;
+        elimaloc::check(elm_growth_cell_objects(VoxelHashMap::ctx(), g_, nullptr, 0, &n), VoxelHashMap::ctx(), "elm_growth_cell_objects");
+        std::vector<int32_t> obj(n, -1);
+        if (n) elimaloc::check(elm_growth_cell_objects(VoxelHashMap::ctx(), g_, obj.data(), n, &n), VoxelHashMap::ctx(), "elm_growth_cell_objects");
+        return obj;
+    }
+    // One value per beam of the scan (sensor frame, PointStruct::pose) at its pose, in the resident scan's order (the upload orders the
+    // points; resident_xyz, optional, receives them in that order, packed x, y, z): the index of the object the beam ends on, -2 for a
+    // small component, -1 for anything else.  config.sub is set to this object's.
+    inline std::vector<int32_t> BeamObjects(const RadarPointVector& scan, const elimaloc::Matrix4d& pose, GrowthConfig config = GrowthConfig(),
+                                            std::vector<float>* resident_xyz = nullptr) const {
+        config.sub = sub_;
+        std::vector<int32_t> obj(scan.size(), -1);
+        if (resident_xyz) resident_xyz->assign(3 * scan.size(), 0.0f);
+        if (scan.empty()) return obj;
+        std::vector<float> xyz(3 * scan.size());
+        for (size_t i = 0; i < scan.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scan[i].pose(k);
+        elm_scan* res = nullptr;
+        int rc = elm_scan_upload(VoxelHashMap::ctx(), xyz.data(), scan.size(), scan.size(), &res);
+        if (rc == ELM_OK) rc = elm_growth_beam_objects(VoxelHashMap::ctx(), g_, res, pose.data(), &config, obj.data());
+        if (rc == ELM_OK && resident_xyz) rc = elm_scan_download(res, resident_xyz->data(), scan.size());
+        if (res) elm_scan_destroy(res);
+        elimaloc::check(rc, VoxelHashMap::ctx(), "MapGrowth::BeamObjects");
+        return obj;
+    }
 
 private:
     elm_growth* g_ = nullptr;

@@ -674,6 +674,62 @@ int elm_growth_cells(elm_ctx* ctx, const elm_growth* g, int32_t* cells3, uint32_
  * NULL when cap = 0). */
 int elm_growth_appeared_points(elm_ctx* ctx, const elm_growth* g, const elm_growth_rule* rule, double* xyz64, size_t cap, size_t* n);
 
+/* ---------------------------------------------------------------- map growth: objects ------------- */
+/* Which of the appeared cells belong together?  "map growth" ends at a bag of cells; here the cells are grouped into objects on the
+ * device, against the growth object's own tables, and two maps lead back to the objects: candidate cell -> object and beam -> object.
+ * Fed one scan into a fresh growth object and asked with the rule {1, 0, 26, 1}, the objects are the clusters of that scan's returns that
+ * the map does not explain, and the beam map is the segmentation of the scan.
+ *   MEMBER     a candidate cell with hit >= min_hit and hit >= hit_per_through * through (the product in 64 bits): elm_growth_rule's rule.
+ *   ADJACENT   two cells a != b with d = b - a and max_r |d_r| <= 1 are adjacent under connectivity 6 when |d_x| + |d_y| + |d_z| <= 1,
+ *              under 18 when that sum is <= 2, under 26 when it is <= 3.
+ *   COMPONENT  an equivalence class of the member cells under the transitive closure of ADJACENT.  A cell that is not a member connects
+ *              nothing.
+ *   LABEL      of a component: its smallest member cell in (x, y, z) order.
+ *   OBJECT     a component with n_cells >= min_cells.  A component below min_cells is SMALL: counted, not listed.
+ *   ORDER      the objects are listed in ascending label order; an object's INDEX is its place in that list.
+ * Every result is an integer and depends only on the set of candidate cells and their counters: not on the slot a cell occupies in the
+ * table (which varies from run to run), the capacity, the order of the jobs that filled the table, or the search-index form. */
+typedef struct elm_growth_object_rule {
+    uint32_t min_hit, hit_per_through; /* which candidates are members: elm_growth_rule's rule */
+    uint32_t connectivity;             /* 6, 18 or 26 */
+    uint32_t min_cells;                /* >= 1; smaller components are SMALL */
+} elm_growth_object_rule;
+typedef struct elm_growth_object {     /* 80 bytes */
+    int32_t  label[3];                 /* smallest member cell */
+    uint32_t n_cells;
+    int32_t  lo[3], hi[3];             /* bounding box in cells, inclusive */
+    uint64_t hit, through;             /* sums over the member cells */
+    uint64_t cell_sum[3];              /* sum over the member cells of (e_r + 2^20): the cell centroid, exactly */
+} elm_growth_object;
+typedef struct elm_growth_object_stats {
+    uint32_t n_members;                /* member cells */
+    uint32_t n_objects;                /* components listed */
+    uint32_t n_small, n_small_cells;   /* small components and their cells: the objects' n_cells and n_small_cells add up to n_members */
+    uint32_t max_cells;                /* n_cells of the largest component, listed or small; 0 without members */
+    uint32_t _pad;
+} elm_growth_object_stats;
+/* min_hit 3, hit_per_through 4, connectivity 26, min_cells 1 -- starting points, not measured optima; with min_cells 1 the objects
+ * partition the appeared cells */
+void elm_growth_object_rule_default(elm_growth_object_rule* r);
+/* Labels the member cells on the device and keeps the result with the growth object until the next elm_growth_accumulate,
+ * elm_growth_accumulate_batch, elm_growth_reset or elm_growth_find_objects on it; while no result is held the three read calls below
+ * return ELM_ERR_INVALID with a last_error text.  stats may be NULL.  The state it needs is allocated at the first call and freed by
+ * elm_growth_destroy: a growth object that never asks pays nothing.  An object without candidates gives zero members and zero objects.
+ * ELM_ERR_INVALID: a connectivity outside {6, 18, 26}, min_cells = 0, an object of another context, a batch in flight. */
+int elm_growth_find_objects(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule* rule, elm_growth_object_stats* stats);
+/* The objects in ascending label order: min(cap, count) written, *n = count (objs may be NULL when cap = 0). */
+int elm_growth_objects(elm_ctx* ctx, const elm_growth* g, elm_growth_object* objs, size_t cap, size_t* n);
+/* One value per candidate cell, in elm_growth_cells' order: the index of the object the cell is a member of, -2 for a member of a small
+ * component, -1 for a cell that is not a member; min(cap, count) written, *n = count (obj may be NULL when cap = 0). */
+int elm_growth_cell_objects(elm_ctx* ctx, const elm_growth* g, int32_t* obj, size_t cap, size_t* n);
+/* One value per beam of the resident scan at pose T16, in the resident scan's order: obj[elm_scan_size(scan)].  The beam's end cell e is
+ * formed exactly as "map growth" forms it.  If the beam is OBSERVING (cfg's window and origin, as in "map evidence"), every |e_r| < 2^20
+ * and e is a member of a listed object, the value is that object's index; if e is a member of a small component, -2; otherwise -1.  The
+ * map's table is not read.  ELM_ERR_INVALID: cfg.sub differs from the object's, a non-finite pose entry, a scan or object of another
+ * context, a batch in flight. */
+int elm_growth_beam_objects(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* cfg,
+                            int32_t* obj);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {
