@@ -259,6 +259,7 @@ EXPORTS = [
     "elm_growth_config_default", "elm_growth_rule_default", "elm_growth_create", "elm_growth_destroy", "elm_growth_reset",
     "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
     "elm_growth_object_rule_default", "elm_growth_find_objects", "elm_growth_objects", "elm_growth_cell_objects", "elm_growth_beam_objects",
+    "elm_map_build_device", "elm_map_build_device_stages",
 ]
 
 
@@ -345,6 +346,8 @@ def lib():
     L.elm_ctx_set_work_counters.argtypes = [vp, C.c_int]
     L.elm_ctx_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.elm_map_build.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
+    L.elm_map_build_device.argtypes = [vp, vp, C.POINTER(C.c_uint8), fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
+    L.elm_map_build_device_stages.argtypes = [vp, dp]
     L.elm_map_destroy.argtypes = [vp]
     L.elm_map_destroy.restype = None
     L.elm_map_cal_voxel_cov_all.argtypes = [vp]

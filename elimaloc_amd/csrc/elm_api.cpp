@@ -605,6 +605,10 @@ static void map_free(elm_map* m) {
     delete m;
 }
 
+// bytes of a map array of `count` entries (never an empty allocation)
+static size_t map_array_bytes(size_t count, size_t size) { return std::max<size_t>(count * size, 256); }
+static int map_finish(elm_ctx* ctx, elm_map* m, uint32_t n_pts, size_t n_input, double voxel_size, int max_points_per_voxel, elm_map** out);
+
 extern "C" int elm_map_build(elm_ctx* ctx, const float* xyz, size_t n, double voxel_size, int max_points_per_voxel,
                              elm_map** out) {
     if (!ctx || !out || (!xyz && n) || !(voxel_size > 0.0) || max_points_per_voxel <= 0 || n > 0xFFFFFFF0ull) return ELM_ERR_INVALID;
@@ -618,40 +622,15 @@ extern "C" int elm_map_build(elm_ctx* ctx, const float* xyz, size_t n, double vo
     m->ctx_id = ctx->id;
     const uint32_t n_vox = (uint32_t)hb.ranges.size();
     const uint32_t n_pts = (uint32_t)hb.pts.size();
-    // load factor <= 0.25: a probe for an absent key (most of a workgroup's box cells are empty) ends after ~1.4 slots
-    const uint32_t cap = next_pow2((uint64_t)n_vox * 4);
-    std::vector<HashSlot> slots(cap);
-    for (auto& s : slots) {
-        s.kx = s.ky = s.kz = 0;
-        s.vid = -1;
-        s.start = s.cnt = s.pad0 = s.pad1 = 0;
+    hipError_t e = hipMalloc((void**)&m->d_pts, map_array_bytes(n_pts, sizeof(float4)));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->d_ranges, map_array_bytes(n_vox, sizeof(uint2)));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->d_keys, map_array_bytes((size_t)n_vox * 3, sizeof(int32_t)));
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMalloc(map): ") + hipGetErrorString(e);
+        map_free(m);
+        return ELM_ERR_DEVICE;
     }
-    for (uint32_t v = 0; v < n_vox; ++v) {
-        uint32_t h = hash3(hb.keys[3 * v], hb.keys[3 * v + 1], hb.keys[3 * v + 2]) & (cap - 1);
-        while (slots[h].vid >= 0) h = (h + 1) & (cap - 1);
-        slots[h].kx = hb.keys[3 * v]; slots[h].ky = hb.keys[3 * v + 1]; slots[h].kz = hb.keys[3 * v + 2];
-        slots[h].vid = (int32_t)v;
-        slots[h].start = hb.ranges[v].x;
-        slots[h].cnt = hb.ranges[v].y;
-    }
-    size_t bytes = 0;
-#define MAP_ALLOC(ptr, count, T)                                                        \
-    do {                                                                                \
-        size_t b_ = std::max<size_t>((size_t)(count) * sizeof(T), 256);                 \
-        hipError_t e_ = hipMalloc((void**)&(ptr), b_);                                  \
-        if (e_ != hipSuccess) {                                                         \
-            ctx->last_error = std::string("hipMalloc(map): ") + hipGetErrorString(e_);  \
-            map_free(m);                                                                \
-            return ELM_ERR_DEVICE;                                                      \
-        }                                                                               \
-        bytes += b_;                                                                    \
-    } while (0)
-    MAP_ALLOC(m->d_slots, cap, HashSlot);
-    MAP_ALLOC(m->d_pts, n_pts, float4);
-    MAP_ALLOC(m->d_ranges, n_vox, uint2);
-    MAP_ALLOC(m->d_keys, (size_t)n_vox * 3, int32_t);
-    hipError_t e = hipMemcpy(m->d_slots, slots.data(), (size_t)cap * sizeof(HashSlot), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_pts) e = hipMemcpy(m->d_pts, hb.pts.data(), (size_t)n_pts * sizeof(float4), hipMemcpyHostToDevice);
+    if (n_pts) e = hipMemcpy(m->d_pts, hb.pts.data(), (size_t)n_pts * sizeof(float4), hipMemcpyHostToDevice);
     if (e == hipSuccess && n_vox) e = hipMemcpy(m->d_ranges, hb.ranges.data(), (size_t)n_vox * sizeof(uint2), hipMemcpyHostToDevice);
     if (e == hipSuccess && n_vox) e = hipMemcpy(m->d_keys, hb.keys.data(), (size_t)n_vox * 3 * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -661,6 +640,46 @@ extern "C" int elm_map_build(elm_ctx* ctx, const float* xyz, size_t n, double vo
     }
     m->h_keys = std::move(hb.keys);
     m->h_ranges = std::move(hb.ranges);
+    return map_finish(ctx, m, n_pts, n, voxel_size, max_points_per_voxel, out);
+}
+
+// The end of both map builds (elm_map_build above, elm_map_build_device in elm_build.cpp): m holds d_pts, d_ranges and d_keys on the
+// device and h_keys and h_ranges on the host.  The slot table is filled here, on the host and in voxel-id order, and the handle gets
+// its device view and its info.  m is released on failure.
+static int map_finish(elm_ctx* ctx, elm_map* m, uint32_t n_pts, size_t n_input, double voxel_size, int max_points_per_voxel, elm_map** out) {
+    const uint32_t n_vox = (uint32_t)m->h_ranges.size();
+    const std::vector<int32_t>& keys = m->h_keys;
+    // load factor <= 0.25: a probe for an absent key (most of a workgroup's box cells are empty) ends after ~1.4 slots
+    const uint32_t cap = next_pow2((uint64_t)n_vox * 4);
+    std::vector<HashSlot> slots;
+    try {
+        slots.resize(cap);
+    } catch (const std::bad_alloc&) {
+        map_free(m);
+        throw;
+    }
+    for (auto& s : slots) {
+        s.kx = s.ky = s.kz = 0;
+        s.vid = -1;
+        s.start = s.cnt = s.pad0 = s.pad1 = 0;
+    }
+    for (uint32_t v = 0; v < n_vox; ++v) {
+        uint32_t h = hash3(keys[3 * v], keys[3 * v + 1], keys[3 * v + 2]) & (cap - 1);
+        while (slots[h].vid >= 0) h = (h + 1) & (cap - 1);
+        slots[h].kx = keys[3 * v]; slots[h].ky = keys[3 * v + 1]; slots[h].kz = keys[3 * v + 2];
+        slots[h].vid = (int32_t)v;
+        slots[h].start = m->h_ranges[v].x;
+        slots[h].cnt = m->h_ranges[v].y;
+    }
+    hipError_t e = hipMalloc((void**)&m->d_slots, map_array_bytes(cap, sizeof(HashSlot)));
+    if (e == hipSuccess) e = hipMemcpy(m->d_slots, slots.data(), (size_t)cap * sizeof(HashSlot), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("map slots: ") + hipGetErrorString(e);
+        map_free(m);
+        return ELM_ERR_DEVICE;
+    }
+    const size_t bytes = map_array_bytes(cap, sizeof(HashSlot)) + map_array_bytes(n_pts, sizeof(float4)) + map_array_bytes(n_vox, sizeof(uint2)) +
+                         map_array_bytes((size_t)n_vox * 3, sizeof(int32_t));
     m->dm.slots = m->d_slots;
     m->dm.mask = cap - 1;
     m->dm.n_vox = n_vox;
@@ -671,7 +690,7 @@ extern "C" int elm_map_build(elm_ctx* ctx, const float* xyz, size_t n, double vo
         int e2 = 0;
         m->dm.inv_vs_exact = (frexp(voxel_size, &e2) == 0.5) ? 1.0 / voxel_size : 0.0;
     }
-    m->info.n_input_points = n;
+    m->info.n_input_points = n_input;
     m->info.n_points = n_pts;
     m->info.n_voxels = n_vox;
     m->info.hash_capacity = cap;
@@ -2822,6 +2841,34 @@ void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc) {
 }
 const elm::DevMap& map_dev(const elm_map* m) { return m->dm; }
 const std::vector<int32_t>& map_host_keys(const elm_map* m) { return m->h_keys; }
+int map_adopt(elm_ctx* ctx, void* d_pts, void* d_ranges, void* d_keys, size_t n_pts, size_t n_vox, size_t n_input, double voxel_size,
+              int max_points_per_voxel, elm_map** out) {
+    elm_map* m = new (std::nothrow) elm_map();
+    if (!m) {
+        (void)hipFree(d_pts); (void)hipFree(d_ranges); (void)hipFree(d_keys);
+        throw std::bad_alloc();
+    }
+    m->ctx = ctx;
+    m->ctx_id = ctx->id;
+    m->d_pts = (float4*)d_pts;
+    m->d_ranges = (uint2*)d_ranges;
+    m->d_keys = (int32_t*)d_keys;
+    try {
+        m->h_keys.resize(n_vox * 3);
+        m->h_ranges.resize(n_vox);
+    } catch (const std::bad_alloc&) {
+        map_free(m);
+        throw;
+    }
+    hipError_t e = n_vox ? hipMemcpy(m->h_keys.data(), d_keys, n_vox * 3 * sizeof(int32_t), hipMemcpyDeviceToHost) : hipSuccess;
+    if (e == hipSuccess && n_vox) e = hipMemcpy(m->h_ranges.data(), d_ranges, n_vox * sizeof(uint2), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("hipMemcpy(map keys): ") + hipGetErrorString(e);
+        map_free(m);
+        return ELM_ERR_DEVICE;
+    }
+    return map_finish(ctx, m, (uint32_t)n_pts, n_input, voxel_size, max_points_per_voxel, out);
+}
 int map_ground_index(const elm_map* cm, const elm::GroundIndex** gi, double bounds[4]) {
     elm_map* m = const_cast<elm_map*>(cm); // the index is a cache of the (immutable) map
     elm_ctx* ctx = m->ctx;

@@ -1,0 +1,242 @@
+// elm_build.cpp -- the device map build (include/elimaloc_hip.h, "device map build"): the argument checks, the
+// scratch arrays, the stages of elm_k_build.hip queued on the context's stream with the few read-backs that size what follows (kept base
+// points, voxels, kept points), and the hand-over of the finished arrays to a map handle (elm_host::map_adopt).  Host-side C++17.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "elm_query.hpp"
+
+using namespace elm;
+using namespace elm_query;
+
+namespace {
+
+constexpr uint64_t kBuildMaxPoints = 0x7FFFFFFFull; // 32-bit indices with all ones as "no point"
+
+// device arrays of one call: released at its end unless handed on
+struct Scratch {
+    std::vector<void*> ptrs;
+    Scratch() { ptrs.reserve(32); }
+    ~Scratch() {
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t get(T** p, size_t count) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256));
+        if (e == hipSuccess) ptrs.push_back(q); // (room reserved: no allocation here)
+        *p = (T*)q;
+        return e;
+    }
+    void* hand_on(void* p) { // the array leaves with its new owner
+        for (void*& q : ptrs)
+            if (q == p) q = nullptr;
+        return p;
+    }
+};
+
+struct Events {
+    hipEvent_t ev[ELM_BUILD_STAGES + 1] = {};
+    int made = 0, used = 0;
+    ~Events() {
+        for (int k = 0; k < made; ++k) (void)hipEventDestroy(ev[k]);
+    }
+    hipError_t create() {
+        for (; made <= ELM_BUILD_STAGES; ++made) {
+            const hipError_t e = hipEventCreate(&ev[made]);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t mark(hipStream_t st) { return hipEventRecord(ev[used++], st); }
+};
+
+// the stage times of this thread's last successful build
+thread_local uint64_t t_stage_ctx = 0;
+thread_local bool t_stage_valid = false;
+thread_local double t_stage_ms[ELM_BUILD_STAGES];
+
+// what was queued has run: the first error of the launches or of the stream
+hipError_t join(hipStream_t st) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+}
+hipError_t read_word(hipStream_t st, const unsigned* d_word, unsigned* out) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_word, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+}
+
+int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double vs, int cap, elm_map** out) {
+    const char* what = "elm_map_build_device";
+    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    (void)hipGetLastError(); // drop stale errors of other libraries
+    Scratch sc;
+    Events evs;
+    hipError_t e = evs.create();
+    unsigned* d_total = nullptr; // [0] a scan's sum, [1] the kernels' flags
+    if (e == hipSuccess) e = sc.get(&d_total, 2);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    unsigned* d_flags = d_total + 1;
+
+    // ---- the input: base's kept points in bucket order, then xyz
+    const unsigned n_base = base ? elm_host::map_dev(base).n_pts : 0u;
+    unsigned K = n_base;
+    unsigned* d_pos = nullptr;
+    uint8_t* d_drop = nullptr;
+    e = evs.mark(st);
+    if (e == hipSuccess && drop && n_base) {
+        unsigned* d_blk = nullptr;
+        e = sc.get(&d_drop, n_base);
+        if (e == hipSuccess) e = sc.get(&d_pos, n_base);
+        if (e == hipSuccess) e = sc.get(&d_blk, (size_t)n_base / 1024 + 1);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_drop, drop, n_base, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            launch_bd_keep(st, d_drop, n_base, d_pos);
+            launch_bd_scan(st, d_pos, n_base, d_blk, d_total);
+            e = read_word(st, d_total, &K);
+        }
+    }
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    if ((uint64_t)K + n > kBuildMaxPoints) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": more than 2^31 - 1 input points");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    const unsigned N = K + (unsigned)n;
+    Pt3* d_in = nullptr;
+    e = sc.get(&d_in, N);
+    if (e == hipSuccess && K) launch_bd_compact(st, elm_host::map_dev(base).pts, d_drop, d_pos, n_base, d_in);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_in + K, xyz, n * sizeof(Pt3), hipMemcpyHostToDevice, st); // (Pt3 is three packed floats)
+    if (e == hipSuccess) e = evs.mark(st);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+
+    // ---- stage 1: keys into a scratch table sized for one voxel per point at load <= 0.5
+    unsigned cap_log2 = 1;
+    while (((uint64_t)1 << cap_log2) < 2 * (uint64_t)N) ++cap_log2;
+    const size_t T = (size_t)1 << cap_log2;
+    unsigned long long* d_table = nullptr;
+    unsigned *d_first = nullptr, *d_slot_vid = nullptr, *d_slot = nullptr, *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr},
+             *d_blk = nullptr, *d_hist = nullptr;
+    const size_t hist_words = bd_rx_hist_words(N);
+    e = sc.get(&d_table, T);
+    if (e == hipSuccess) e = sc.get(&d_first, T);
+    if (e == hipSuccess) e = sc.get(&d_slot_vid, T);
+    if (e == hipSuccess) e = sc.get(&d_slot, N);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = sc.get(&d_key[k], N);
+        if (e == hipSuccess) e = sc.get(&d_val[k], N);
+    }
+    if (e == hipSuccess) e = sc.get(&d_blk, std::max<size_t>(N, hist_words) / 1024 + 1); // the longest array scanned below
+    if (e == hipSuccess) e = sc.get(&d_hist, hist_words);
+    if (e == hipSuccess) e = hipMemsetAsync(d_table, 0xFF, T * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_first, 0xFF, T * sizeof(unsigned), st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, 2 * sizeof(unsigned), st);
+    unsigned flags = 0;
+    if (e == hipSuccess && N) {
+        launch_bd_insert(st, d_in, N, vs, d_table, d_first, cap_log2, d_slot, d_flags);
+        e = read_word(st, d_flags, &flags);
+    }
+    if (e == hipSuccess) e = evs.mark(st);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    if (flags & kBdBadInput) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": an input coordinate is not finite, or |x / voxel_size| >= 2^20 (the packed key has 21 bits per axis)");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    if (flags & kBdTableFull) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": the scratch key table is full");
+        return ELM_ERR_DEVICE;
+    }
+
+    // ---- stage 2: voxel ids in first-seen order
+    unsigned n_vox = 0;
+    if (N) {
+        launch_bd_opens(st, d_first, d_slot, N, d_key[1]);
+        launch_bd_scan(st, d_key[1], N, d_blk, d_total);
+        e = read_word(st, d_total, &n_vox);
+    }
+    if (e == hipSuccess) e = evs.mark(st);
+    // ---- stage 3: the sort's input, raw counts and group starts
+    int32_t* d_keys = nullptr; // (the map's)
+    unsigned *d_off = nullptr, *d_kcnt = nullptr, *d_kstart = nullptr;
+    if (e == hipSuccess) e = sc.get(&d_keys, (size_t)n_vox * 3);
+    if (e == hipSuccess) e = sc.get(&d_off, n_vox);
+    if (e == hipSuccess) e = sc.get(&d_kcnt, n_vox);
+    if (e == hipSuccess) e = sc.get(&d_kstart, n_vox);
+    if (e == hipSuccess && n_vox) e = hipMemsetAsync(d_off, 0, (size_t)n_vox * sizeof(unsigned), st);
+    if (e == hipSuccess && N) {
+        launch_bd_vid(st, d_first, d_slot, N, d_key[1], d_table, d_slot_vid, d_keys, d_key[0], d_val[0], d_off);
+        launch_bd_scan(st, d_off, n_vox, d_blk, d_total);
+    }
+    if (e == hipSuccess) e = evs.mark(st);
+    // ---- stage 4: the indices grouped by voxel id, input order inside a group: as many 8-bit passes as the ids have digits
+    int cur = 0;
+    if (e == hipSuccess && n_vox > 1) {
+        unsigned bits = 0;
+        while (bits < 32 && ((uint64_t)1 << bits) < n_vox) ++bits;
+        for (unsigned shift = 0; shift < bits; shift += 8, cur ^= 1) {
+            launch_bd_rx_hist(st, d_key[cur], N, shift, d_hist);
+            launch_bd_scan(st, d_hist, (unsigned)hist_words, d_blk, d_total);
+            launch_bd_rx_scatter(st, d_key[cur], d_val[cur], N, shift, d_hist, d_key[cur ^ 1], d_val[cur ^ 1]);
+        }
+    }
+    if (e == hipSuccess) e = evs.mark(st);
+    // ---- stage 5: the replay
+    unsigned n_pts = 0;
+    if (e == hipSuccess && n_vox) {
+        const double map_resolution = sqrt(vs * vs / cap); // as build_host
+        launch_bd_replay(st, d_in, d_val[cur], d_off, n_vox, N, (unsigned)cap, map_resolution, d_kcnt, d_kstart);
+        launch_bd_scan(st, d_kstart, n_vox, d_blk, d_total);
+        e = read_word(st, d_total, &n_pts);
+    }
+    if (e == hipSuccess) e = evs.mark(st);
+    // ---- stage 6: the map's arrays
+    float4* d_pts = nullptr;
+    uint2* d_ranges = nullptr;
+    if (e == hipSuccess) e = sc.get(&d_pts, n_pts);
+    if (e == hipSuccess) e = sc.get(&d_ranges, n_vox);
+    if (e == hipSuccess && n_vox) launch_bd_emit(st, d_in, d_val[cur], d_key[cur], d_off, d_kcnt, d_kstart, n_vox, N, d_pts, d_ranges);
+    if (e == hipSuccess) e = evs.mark(st);
+    if (e == hipSuccess) e = join(st);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    double ms[ELM_BUILD_STAGES];
+    for (int k = 0; k < ELM_BUILD_STAGES; ++k) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, evs.ev[k], evs.ev[k + 1]) != hipSuccess) f = 0.f;
+        ms[k] = f;
+    }
+    const int rc = elm_host::map_adopt(ctx, sc.hand_on(d_pts), sc.hand_on(d_ranges), sc.hand_on(d_keys), n_pts, n_vox, N, vs, cap, out);
+    if (rc == ELM_OK) {
+        std::copy(ms, ms + ELM_BUILD_STAGES, t_stage_ms);
+        t_stage_ctx = elm_host::ctx_unique_id(ctx);
+        t_stage_valid = true;
+    }
+    return rc;
+}
+
+} // namespace
+
+extern "C" int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double voxel_size,
+                                    int max_points_per_voxel, elm_map** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!xyz && n) || !(voxel_size > 0.0) || max_points_per_voxel <= 0 || (drop && !base)) return ELM_ERR_INVALID;
+    const int rc = check_plain(ctx, "elm_map_build_device");
+    if (rc != ELM_OK) return rc;
+    if ((base && elm_host::map_ctx(base) != ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (n > kBuildMaxPoints) {
+        elm_host::ctx_set_error(ctx, "elm_map_build_device: more than 2^31 - 1 input points");
+        return ELM_ERR_UNSUPPORTED;
+    }
+    return guard_alloc(ctx, "elm_map_build_device", [&] { return build_impl(ctx, base, drop, xyz, n, voxel_size, max_points_per_voxel, out); });
+}
+
+extern "C" int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]) {
+    if (!ctx || !ms || !t_stage_valid || t_stage_ctx != elm_host::ctx_unique_id(ctx)) return ELM_ERR_INVALID;
+    std::copy(t_stage_ms, t_stage_ms + ELM_BUILD_STAGES, ms);
+    return ELM_OK;
+}

@@ -51,6 +51,12 @@ bool ctx_is_alive(const elm_ctx* ctx, uint64_t id); // the context with this uni
 uint64_t ctx_unique_id(const elm_ctx* ctx);
 // the fine cell of every stored point for sub, in elm_map_download_points order: [n_points][3]
 int map_point_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
+// ... for elm_build.cpp
+// A map handle around arrays that a device build left in HBM: d_pts float4[n_pts] (w = 0), d_ranges uint2[n_vox], d_keys int32[n_vox][3],
+// each allocated with at least 256 bytes.  Keys and ranges come down, the slot table is filled on the host as elm_map_build fills it.
+// The arrays are the map's from the call on, released with it or on failure (a failed host allocation throws std::bad_alloc).
+int map_adopt(elm_ctx* ctx, void* d_pts, void* d_ranges, void* d_keys, size_t n_pts, size_t n_vox, size_t n_input, double voxel_size,
+              int max_points_per_voxel, elm_map** out);
 } // namespace elm_host
 
 // Device groups: N per-device contexts inside ONE process behind one lead context (elm_ctx_create_multi; SURVEY 8(b): the reference node is

@@ -456,6 +456,35 @@ void launch_obj_gather(hipStream_t s, const ObjTables& ot, uint32_t n_listed, Ob
 void launch_obj_beams(hipStream_t s, const FineTable& ft, const EvidParams& ep, const GrowTables& gt, const ObjTables& ot, const EvidJob& job,
                       int32_t* out);
 
+// device map build (elm_k_build.hip): the stages elm_build.cpp queues.  All indices are 32-bit (at most 2^31 - 1
+// points); every array is the caller's scratch.
+constexpr unsigned kBdBadInput = 1u;  // flags: a coordinate is not finite, or its quotient by the voxel size is outside (-2^20, 2^20)
+constexpr unsigned kBdTableFull = 2u; // flags: the scratch table took no more keys (cannot happen at its load <= 0.5)
+// in-place exclusive scan of a[0 .. n); blk: ceil(n / 1024) words of scratch; *total = the sum
+void launch_bd_scan(hipStream_t s, unsigned* a, unsigned n, unsigned* blk, unsigned* total);
+// pos[i] = 1 where drop[i] == 0 (scan it); then out[pos[i]] = pts[i] for those points (drop == nullptr: out[i] = pts[i])
+void launch_bd_keep(hipStream_t s, const uint8_t* drop, unsigned n, unsigned* pos);
+void launch_bd_compact(hipStream_t s, const float4* pts, const uint8_t* drop, const unsigned* pos, unsigned n, Pt3* out);
+// table / first: 2^cap_log2 >= 2 n entries, all ones before the call; slot: n entries; flags: zero before the call
+void launch_bd_insert(hipStream_t s, const Pt3* in, unsigned n, double vs, unsigned long long* table, unsigned* first, unsigned cap_log2,
+                      unsigned* slot, unsigned* flags);
+// opens[i] = 1 for the first point of every voxel (scan it: the voxel ids in first-seen order, the sum = n_vox)
+void launch_bd_opens(hipStream_t s, const unsigned* first, const unsigned* slot, unsigned n, unsigned* opens);
+// keys[n_vox][3]; key[i] = voxel id of point i, val[i] = i; raw_cnt[n_vox] (zero before the call) = points per voxel
+void launch_bd_vid(hipStream_t s, const unsigned* first, const unsigned* slot, unsigned n, const unsigned* opens, const unsigned long long* table,
+                   unsigned* slot_vid, int32_t* keys, unsigned* key, unsigned* val, unsigned* raw_cnt);
+// one stable 8-bit pass of the sort by key: histogram (bd_rx_hist_words(n) words), its scan by launch_bd_scan, scatter
+size_t bd_rx_hist_words(unsigned n);
+void launch_bd_rx_hist(hipStream_t s, const unsigned* key, unsigned n, unsigned shift, unsigned* hist);
+void launch_bd_rx_scatter(hipStream_t s, const unsigned* key, const unsigned* val, unsigned n, unsigned shift, const unsigned* start,
+                          unsigned* key_out, unsigned* val_out);
+// order: the indices grouped by voxel (kept ones compacted to the front of every group on return); off: start of every group;
+// kcnt = kstart = kept points per voxel (scan kstart)
+void launch_bd_replay(hipStream_t s, const Pt3* in, unsigned* order, const unsigned* off, unsigned n_vox, unsigned n, unsigned cap, double res,
+                      unsigned* kcnt, unsigned* kstart);
+void launch_bd_emit(hipStream_t s, const Pt3* in, const unsigned* order, const unsigned* vid, const unsigned* off, const unsigned* kcnt,
+                    const unsigned* kstart, unsigned n_vox, unsigned n, float4* out, uint2* ranges);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

@@ -7,6 +7,7 @@
 #include "elm_internal.hpp"
 #include "elm_la.hpp"
 #include "elm_dev_pairs.hpp"
+#include "elm_dev_scan.hpp"
 
 namespace elm {
 
@@ -114,24 +115,7 @@ __global__ __launch_bounds__(kDsBlock) void k_ds_count(const unsigned* __restric
 }
 __global__ __launch_bounds__(1024) void k_ds_offsets(unsigned* block_count, unsigned n_blocks, unsigned* total) { // in-place exclusive scan
     __shared__ unsigned s[1024];
-    unsigned carry = 0;
-    for (unsigned base = 0; base < n_blocks; base += 1024) {
-        const unsigned j = base + threadIdx.x;
-        const unsigned v = j < n_blocks ? block_count[j] : 0u;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (unsigned off = 1; off < 1024; off <<= 1) {
-            const unsigned t = threadIdx.x >= off ? s[threadIdx.x - off] : 0u;
-            __syncthreads();
-            s[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (j < n_blocks) block_count[j] = carry + s[threadIdx.x] - v;
-        const unsigned chunk_total = s[1023];
-        __syncthreads();
-        carry += chunk_total;
-    }
-    if (threadIdx.x == 0) *total = carry;
+    chunk_scan_1024(block_count, n_blocks, total, s);
 }
 __global__ __launch_bounds__(kDsBlock) void k_ds_scatter(const float* __restrict__ xyz, const unsigned* __restrict__ first,
                                                          const unsigned* __restrict__ slot, unsigned n,

@@ -349,11 +349,14 @@ def default_context():
 class VoxelHashMap:
     """vhm.hpp:89-335.  Points are (n,3) float32 arrays (the PCD map and the LiDAR are float32, pcm.hpp:205-215)."""
 
-    def __init__(self, voxel_size=1.0, max_points_per_voxel=30, ctx=None):
+    def __init__(self, voxel_size=1.0, max_points_per_voxel=30, ctx=None, device_build=False):
+        """device_build: the map is built by elm_map_build_device (the same map, byte for byte) instead of the host build."""
         self.ctx = ctx or default_context()
         self.voxel_size_ = float(voxel_size)
         self.max_points_per_voxel_ = int(max_points_per_voxel)
+        self.device_build_ = bool(device_build)
         self._pending = []
+        self._derived = False  # made from a base map on the device: _pending is filled from a download when it is first needed
         self._h = None
         self._want_voxel_cov = False
         self._want_point_cov = None
@@ -365,6 +368,7 @@ class VoxelHashMap:
     def Clear(self):  # vhm.hpp:324
         self._release()
         self._pending = []
+        self._derived = False
 
     def _release(self):
         if self._h is not None:
@@ -381,6 +385,9 @@ class VoxelHashMap:
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         if pts.shape[0] == 0:
             return
+        if self._derived:  # stored points replay to themselves: stored ++ points builds what AddPoints(points) makes of this map
+            self._pending = [self.Pointcloud().astype(np.float32)] if not self.Empty() else []
+            self._derived = False
         self._pending.append(pts)
         self._release()  # rebuilt on next use; sequential AddPoints == one AddPoints of the concatenation
 
@@ -393,8 +400,12 @@ class VoxelHashMap:
                     (self._pending[0] if self._pending else np.zeros((0, 3), np.float32)))
             self._pending = [allp] if allp.shape[0] else []
             h = C.c_void_p()
-            check(_lib.lib().elm_map_build(self.ctx._h, _fp(allp), allp.shape[0], self.voxel_size_,
-                                           self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build")
+            if self.device_build_:
+                check(_lib.lib().elm_map_build_device(self.ctx._h, None, None, _fp(allp), allp.shape[0], self.voxel_size_,
+                                                      self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build_device")
+            else:
+                check(_lib.lib().elm_map_build(self.ctx._h, _fp(allp), allp.shape[0], self.voxel_size_,
+                                               self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build")
             self._h = h
             if self._want_voxel_cov:
                 check(_lib.lib().elm_map_cal_voxel_cov_all(self._h), self.ctx._h, "elm_map_cal_voxel_cov_all")
@@ -402,6 +413,29 @@ class VoxelHashMap:
                 check(_lib.lib().elm_map_cal_point_cov_all(self._h, self._want_point_cov), self.ctx._h,
                       "elm_map_cal_point_cov_all")
         return self._h
+
+    def _derive(self, drop, extra):
+        """A new map (same voxel size, cap, context and build path) built on the device from this map's stored points without those that
+        drop (uint8 [n_points], None: none) marks, followed by extra [k, 3]: the stored points stay in HBM."""
+        extra = np.ascontiguousarray(extra, dtype=np.float32).reshape(-1, 3)
+        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx, self.device_build_)
+        dptr = None
+        if drop is not None:
+            drop = np.ascontiguousarray(drop, dtype=np.uint8)
+            if drop.shape != (int(self.info().n_points),):
+                raise ElmError("one drop flag per stored point")
+            dptr = drop.ctypes.data_as(C.POINTER(C.c_uint8))
+        h = C.c_void_p()
+        check(_lib.lib().elm_map_build_device(self.ctx._h, self._handle(), dptr, _fp(extra), extra.shape[0], self.voxel_size_,
+                                              self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build_device")
+        out._h = h
+        out._derived = True
+        return out
+
+    def Updated(self, points):
+        """A new map equal to this one after AddPoints(points) (the reference's Update, vhm.cpp:268), built on the device: this map stays
+        as it is and resident, and only `points` cross the bus."""
+        return self._derive(None, points)
 
     def CalVoxelCovAll(self):  # vhm.hpp:183-193
         self._want_voxel_cov = True
@@ -645,12 +679,14 @@ class VoxelHashMap:
         kept on the device and fed by Accumulate.  It belongs to the map as built now: AddPoints / Clear afterwards invalidate it."""
         return MapEvidence(self, sub)
 
-    def WithoutStale(self, evidence, rule=None):
+    def WithoutStale(self, evidence, rule=None, device=False):
         """A new map (same voxel size and cap, same context) built by the usual build from the stored points that evidence.StalePoints(rule)
-        does not flag."""
+        does not flag.  device: the same map by the device build; only the flags cross the bus."""
         if evidence.map is not self:
             raise ElmError("WithoutStale: the evidence belongs to another map")
         flags = evidence.StalePoints(rule)
+        if device:
+            return self._derive(flags.astype(np.uint8), np.zeros((0, 3), np.float32))
         keep = self.Pointcloud()[~flags] if flags.size else np.zeros((0, 3))
         out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx)
         out.AddPoints(keep.astype(np.float32))  # stored coordinates are float32 values: the conversion is exact
@@ -663,12 +699,15 @@ class VoxelHashMap:
         AddPoints / Clear afterwards invalidate it."""
         return MapGrowth(self, capacity, sub)
 
-    def WithAppeared(self, growth, rule=None):
+    def WithAppeared(self, growth, rule=None, device=False):
         """A new map (same voxel size and cap, same context) built by the usual build from this map's stored points followed by
-        growth.AppearedPoints(rule) in cell order: the spacing rule and the voxel cap apply to the new points as to any others."""
+        growth.AppearedPoints(rule) in cell order: the spacing rule and the voxel cap apply to the new points as to any others.
+        device: the same map by the device build; only the appeared points cross the bus."""
         if growth.map is not self:
             raise ElmError("WithAppeared: the growth object belongs to another map")
         new = growth.AppearedPoints(rule)
+        if device:
+            return self._derive(None, new.astype(np.float32))
         old = self.Pointcloud() if not self.Empty() else np.zeros((0, 3))
         out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx)
         out.AddPoints(np.concatenate([old, new]).astype(np.float32))  # stored coordinates are float32 values: their conversion is exact

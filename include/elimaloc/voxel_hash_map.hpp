@@ -122,6 +122,7 @@ struct GrowthObjectRule : elm_growth_object_rule {
     GrowthObjectRule() { elm_growth_object_rule_default(this); }
 };
 
+class MapEvidence;
 class MapGrowth;
 
 struct VoxelHashMap {
@@ -141,7 +142,10 @@ struct VoxelHashMap {
     }
     // vhm.cpp:270-285.  Repeated calls append (the device map is rebuilt from the concatenation, which is what
     // sequential AddPoints calls produce in the reference).
+    // true: the map is built by elm_map_build_device (the same map, byte for byte) instead of the host build
+    void BuildOnDevice(bool on) { device_build_ = on; }
     void AddPoints(const RadarPointVector& points) {
+        Materialize();
         xyz_.reserve(xyz_.size() + 3 * points.size());
         for (const auto& p : points) {
             xyz_.push_back((float)p.pose(0));
@@ -151,10 +155,19 @@ struct VoxelHashMap {
         Release();
     }
     void AddPoints(const float* xyz, size_t n) { // float32 fast path for callers that hold the PCD's own arrays
+        Materialize();
         xyz_.insert(xyz_.end(), xyz, xyz + 3 * n);
         Release();
     }
     void Update(const RadarPointVector& points, const elimaloc::Vector3d&) { AddPoints(points); } // vhm.cpp:268
+    // `out` becomes this map after AddPoints(points), built on the device (elm_map_build_device): this map stays as it is and resident,
+    // and only `points` cross the bus.  (Filled in place: a map owns device memory and is not copied.)
+    void Updated(const RadarPointVector& points, VoxelHashMap& out) const {
+        std::vector<float> xyz(3 * points.size());
+        for (size_t i = 0; i < points.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)points[i].pose(k);
+        Derive(nullptr, xyz.data(), points.size(), out);
+    }
     void CalVoxelCovAll() { // vhm.hpp:183-193
         want_voxel_cov_ = true;
         elimaloc::check(elm_map_cal_voxel_cov_all(handle()), ctx(), "CalVoxelCovAll");
@@ -185,6 +198,7 @@ struct VoxelHashMap {
     inline void Clear() { // vhm.hpp:324
         Release();
         xyz_.clear();
+        derived_ = false;
     }
     std::vector<PointStruct> Pointcloud() const { // vhm.cpp:245-255
         elm_map_info mi;
@@ -263,8 +277,12 @@ struct VoxelHashMap {
     }
     // `out` becomes a map of this map's voxel size and cap, built by the usual build from this map's stored points followed by the points
     // of the cells that `growth` (a MapGrowth of this map) calls appeared, in cell order: the spacing rule and the voxel cap apply to them.
-    // (Filled in place: a map owns device memory and is not copied.)
-    inline void WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule = GrowthRule()) const;
+    // (Filled in place: a map owns device memory and is not copied.)  device: the same map by the device build; only the appeared points
+    // cross the bus.
+    inline void WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule = GrowthRule(), bool device = false) const;
+    // `out` becomes a map of this map's voxel size and cap, built by the usual build from the stored points that `evidence` (a MapEvidence
+    // of this map) does not call stale.  device: the same map by the device build; only the flags cross the bus.
+    inline void WithoutStale(const MapEvidence& evidence, VoxelHashMap& out, const EvidenceRule& rule = EvidenceRule(), bool device = false) const;
 
     inline bool FindGroundHeight(const elimaloc::Vector2d& position, double& ground_z) const { // vhm.hpp:285-322
         int found = 0;
@@ -380,7 +398,11 @@ struct VoxelHashMap {
     // the device-resident map (built lazily from the accumulated points on first use; const like the reference's read paths)
     elm_map* handle() const {
         if (!map_) {
-            elimaloc::check(elm_map_build(ctx(), xyz_.data(), xyz_.size() / 3, voxel_size_, max_points_per_voxel_, &map_), ctx(), "elm_map_build");
+            if (device_build_)
+                elimaloc::check(elm_map_build_device(ctx(), nullptr, nullptr, xyz_.data(), xyz_.size() / 3, voxel_size_, max_points_per_voxel_, &map_), ctx(),
+                                "elm_map_build_device");
+            else
+                elimaloc::check(elm_map_build(ctx(), xyz_.data(), xyz_.size() / 3, voxel_size_, max_points_per_voxel_, &map_), ctx(), "elm_map_build");
             if (want_voxel_cov_) elimaloc::check(elm_map_cal_voxel_cov_all(map_), ctx(), "CalVoxelCovAll");
             if (want_point_cov_ > 0) elimaloc::check(elm_map_cal_point_cov_all(map_, want_point_cov_), ctx(), "CalPointCovAll");
         }
@@ -396,8 +418,31 @@ private:
         if (map_) elm_map_destroy(map_);
         map_ = nullptr;
     }
+    // `out` becomes the device build of this map's stored points without those that drop (one byte per stored point, nullptr: none)
+    // marks, followed by the n points of xyz
+    void Derive(const uint8_t* drop, const float* xyz, size_t n, VoxelHashMap& out) const {
+        elm_map* m = nullptr;
+        elimaloc::check(elm_map_build_device(ctx(), handle(), drop, xyz, n, voxel_size_, max_points_per_voxel_, &m), ctx(), "elm_map_build_device");
+        out.Clear();
+        out.Init(voxel_size_, max_points_per_voxel_);
+        out.device_build_ = device_build_;
+        out.map_ = m;
+        out.derived_ = true;
+    }
+    // a map made by Derive holds no input points: before it takes more, its stored points (which replay to themselves) become its input
+    void Materialize() {
+        if (!derived_) return;
+        elm_map_info mi;
+        elimaloc::check(elm_map_get_info(map_, &mi), ctx(), "elm_map_get_info");
+        std::vector<double> xyz(3 * mi.n_points);
+        if (mi.n_points) elimaloc::check(elm_map_download_points(map_, xyz.data(), nullptr, nullptr, mi.n_points), ctx(), "elm_map_download_points");
+        xyz_.assign(xyz.begin(), xyz.end()); // stored coordinates are float32 values: the conversion is exact
+        derived_ = false;
+    }
     std::vector<float> xyz_;
     mutable elm_map* map_ = nullptr;
+    bool device_build_ = false;
+    bool derived_ = false;
     bool want_voxel_cov_ = false;
     double want_point_cov_ = -1.0;
 };
@@ -589,8 +634,30 @@ private:
     int sub_ = 4;
 };
 
-inline void VoxelHashMap::WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule) const {
+inline void VoxelHashMap::WithoutStale(const MapEvidence& evidence, VoxelHashMap& out, const EvidenceRule& rule, bool device) const {
+    const std::vector<uint8_t> flags = evidence.StalePoints(rule);
+    if (device) {
+        Derive(flags.data(), nullptr, 0, out);
+        return;
+    }
+    std::vector<double> xyz(3 * flags.size());
+    if (!flags.empty()) elimaloc::check(elm_map_download_points(handle(), xyz.data(), nullptr, nullptr, flags.size()), ctx(), "WithoutStale");
+    std::vector<float> f;
+    for (size_t i = 0; i < flags.size(); ++i)
+        if (!flags[i])
+            for (int k = 0; k < 3; ++k) f.push_back((float)xyz[3 * i + k]); // stored coordinates are float32 values: their conversion is exact
+    out.Clear();
+    out.Init(voxel_size_, max_points_per_voxel_);
+    out.AddPoints(f.data(), f.size() / 3);
+}
+
+inline void VoxelHashMap::WithAppeared(const MapGrowth& growth, VoxelHashMap& out, const GrowthRule& rule, bool device) const {
     const std::vector<double> fresh = growth.AppearedPoints(rule);
+    if (device) {
+        const std::vector<float> f(fresh.begin(), fresh.end());
+        Derive(nullptr, f.data(), f.size() / 3, out);
+        return;
+    }
     elm_map_info mi;
     elimaloc::check(elm_map_get_info(handle(), &mi), ctx(), "elm_map_get_info");
     std::vector<double> xyz(3 * mi.n_points), cov(9 * mi.n_points), mean(3 * mi.n_points);

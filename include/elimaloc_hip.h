@@ -730,6 +730,33 @@ int elm_growth_cell_objects(elm_ctx* ctx, const elm_growth* g, int32_t* obj, siz
 int elm_growth_beam_objects(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* cfg,
                             int32_t* obj);
 
+/* ---------------------------------------------------------------- device map build ---------------- */
+/* AddPoints, a prune and an incremental add as ONE build on the device.  The result is the map that
+ *   elm_map_build(ctx, P, |P|, voxel_size, max_points_per_voxel, out)
+ * returns, where P = the stored points of `base` with drop[i] == 0, in bucket order (voxels in first-seen order, insertion order inside a
+ * voxel: the order of elm_map_download_points), followed by the n points of xyz -- the same elm_map_get_info, elm_map_download_points and
+ * elm_map_download_voxels, byte for byte and in the same order, hence the same covariances, search indices and registrations afterwards.
+ * The stored points of a map survive their own replay (all of them are kept, in their order, and so is any subset), and
+ * AddPoints(A); AddPoints(B) equals one AddPoints(stored(A) ++ B): base and no drop is the reference's Update(points), base and drop a
+ * prune.  base's points are read from HBM and never downloaded; base is not modified; voxel_size and the cap need not be base's.
+ *   base   may be NULL (a build from xyz alone)
+ *   drop   host, one byte per stored point of base in elm_map_download_points order; NULL: keep all; must be NULL when base is NULL
+ *   xyz    host, packed float32, n points (may be NULL when n = 0)
+ * The build's scratch memory (about 100 bytes per point of P) is released before return and is not part of device_bytes.
+ * ELM_ERR_INVALID: ctx or out NULL, voxel_size <= 0 or NaN, max_points_per_voxel <= 0, drop without base, a base of another context,
+ * a batch in flight.  ELM_ERR_UNSUPPORTED with a text in elm_last_error: a coordinate of P that is not finite or whose quotient by
+ * voxel_size is not inside (-2^20, 2^20) (three 21-bit key fields; elm_map_build's cast of such a quotient is undefined or beyond any
+ * map in use), more than 2^31 - 1 points in P, the lead of a device group, a context with a communicator or hook attached.  After any
+ * refusal *out is NULL, nothing stays allocated and the context is usable. */
+int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double voxel_size,
+                         int max_points_per_voxel, elm_map** out);
+/* Device milliseconds (hipEvents on the context's stream) of the stages of the last successful elm_map_build_device of this thread on
+ * ctx: ms[0] base points compacted and xyz uploaded, [1] key and insert, [2] voxel ids, [3] raw counts, [4] grouping (the sort), [5]
+ * replay, [6] kept points and ranges written; the host's share (slot table, transfers of keys and ranges) is the call's wall clock less
+ * their sum.  ELM_ERR_INVALID: no such build. */
+#define ELM_BUILD_STAGES 7
+int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]);
+
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
 typedef struct elm_deskew_tables {
