@@ -65,7 +65,7 @@ __device__ __forceinline__ void grid_lean(const GridAxis& a, int& blo, int& bhi,
 struct GridHardRec {
     double gx, gy, gz;
     float r2; // upper bound of the squared nearest-neighbour distance (inf: nothing found yet)
-    float _pad;
+    int win;  // stage 2 writes the point's winner here (block * 4 + slot, -1: none): the queue record carries its own result
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));

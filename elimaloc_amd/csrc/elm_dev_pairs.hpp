@@ -516,11 +516,14 @@ __device__ __forceinline__ void publish_and_reduce(double value, unsigned L, int
     if (threadIdx.x < (unsigned)kSums) partials[(size_t)L * kSums + threadIdx.x] = value;
 }
 
-// DPP row operations (quad permutes, row rotations / mirrors) instead of ds_bpermute (__shfl), which goes through the LDS pipeline
+// DPP row operations (quad permutes, row rotations / mirrors) instead of ds_bpermute (__shfl), which goes through the LDS pipeline.
+// The move form WITHOUT an old value: every control used here reads a lane of the same row and row_mask / bank_mask are 0xf, so every
+// lane is written and the old value never shows -- tying it to the source (update_dpp(x, x, ..)) only made the compiler copy both
+// halves in front of every step (5 instead of 3 VALU instructions).  Callers run it with whole rows of 16 lanes active.
 template <int CTRL>
 __device__ __forceinline__ double dpp_move(double v) {
     const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
+    return __hiloint2double(__builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false));
 }
 
 // slot `slot` of the voxel-mean lists: its word (voxel id | position code << kVidBits; -1: padding) / its voxel id

@@ -305,36 +305,49 @@ __device__ __forceinline__ void pair_p2p(double* v, const double* Rinv, double p
     v[16] = sqrt_dist2(d2);
     v[17] = 1.0;
 }
-// slot k of the packed 32-sum record (21 upper JTJ, 6 JTr, residual, count, 3 counters) from the 21 reduced P2P values
-__device__ __forceinline__ double p2p_expand(const double* s, int k) {
-    switch (k) {
-    case tri(0, 0): case tri(1, 1): case tri(2, 2): return s[0];
-    case tri(0, 4): return s[3];       // -w [p]x, translation x rotation block
-    case tri(0, 5): return -s[2];
-    case tri(1, 3): return -s[3];
-    case tri(1, 5): return s[1];
-    case tri(2, 3): return s[2];
-    case tri(2, 4): return -s[1];
-    case tri(3, 3): return s[7] + s[9]; // w (|p|^2 I - p p^T), rotation block
-    case tri(3, 4): return -s[5];
-    case tri(3, 5): return -s[6];
-    case tri(4, 4): return s[4] + s[9];
-    case tri(4, 5): return -s[8];
-    case tri(5, 5): return s[4] + s[7];
-    case 21: return s[10];
-    case 22: return s[11];
-    case 23: return s[12];
-    case 24: return s[13];
-    case 25: return s[14];
-    case 26: return s[15];
-    case 27: return s[16];
-    case 28: return s[17];
-    case 29: return s[18];
-    case 30: return s[19];
-    case 31: return s[20];
-    default: return 0.0; // tri(0,1), tri(0,2), tri(1,2), tri(0,3), tri(1,4), tri(2,5)
-    }
+// slot k of the packed 32-sum record (21 upper JTJ, 6 JTr, residual, count, 3 counters) from the 21 reduced P2P values: one code word
+// per slot -- first source, second source (the same as the first unless the slot is a sum), add / negate / zero bits -- so the
+// expansion is straight-line code with ONE LDS round trip (both reads issued together) instead of a switch on the lane, which
+// compiles to a tree of exec-mask regions with one dependent LDS read per leaf, walked by the workgroup's last wavefront alone.
+constexpr unsigned kP2PAdd = 1u << 10, kP2PNeg = 1u << 11, kP2PZero = 1u << 12;
+struct P2PCodes {
+    unsigned w[kSums];
+};
+constexpr unsigned p2p_code(int a, int b = -1, bool neg = false) {
+    return (unsigned)a | ((unsigned)(b < 0 ? a : b) << 5) | (b < 0 ? 0u : kP2PAdd) | (neg ? kP2PNeg : 0u);
 }
+constexpr P2PCodes p2p_codes() {
+    P2PCodes t{};
+    for (int k = 0; k < kSums; ++k) t.w[k] = kP2PZero; // tri(0,1), tri(0,2), tri(1,2), tri(0,3), tri(1,4), tri(2,5): structural zeros
+    t.w[tri(0, 0)] = t.w[tri(1, 1)] = t.w[tri(2, 2)] = p2p_code(0);
+    t.w[tri(0, 4)] = p2p_code(3);               // -w [p]x, translation x rotation block
+    t.w[tri(0, 5)] = p2p_code(2, -1, true);
+    t.w[tri(1, 3)] = p2p_code(3, -1, true);
+    t.w[tri(1, 5)] = p2p_code(1);
+    t.w[tri(2, 3)] = p2p_code(2);
+    t.w[tri(2, 4)] = p2p_code(1, -1, true);
+    t.w[tri(3, 3)] = p2p_code(7, 9);            // w (|p|^2 I - p p^T), rotation block
+    t.w[tri(3, 4)] = p2p_code(5, -1, true);
+    t.w[tri(3, 5)] = p2p_code(6, -1, true);
+    t.w[tri(4, 4)] = p2p_code(4, 9);
+    t.w[tri(4, 5)] = p2p_code(8, -1, true);
+    t.w[tri(5, 5)] = p2p_code(4, 7);
+    for (int k = 21; k < kSums; ++k) t.w[k] = p2p_code(k - 11); // JTr, residual, count, the three counters: values 10..20
+    return t;
+}
+// the code word of slot k (k < kSums): a load from a constant table, to be issued BEFORE the block reduction so that it is back by the tail
+__device__ __forceinline__ unsigned p2p_expand_code(int k) {
+    static constexpr P2PCodes codes = p2p_codes();
+    static_assert((kSums & (kSums - 1)) == 0, "the index is masked into the table");
+    return codes.w[k & (kSums - 1)];
+}
+__device__ __forceinline__ double p2p_expand_coded(const double* s, unsigned code) {
+    const double a = s[code & 31u], b = s[(code >> 5) & 31u];
+    const double r = (code & kP2PAdd) ? a + b : a;
+    const int hi = __double2hiint(r) ^ (int)((code & kP2PNeg) << 20); // -x as a flip of the sign bit: a zero sum becomes -0.0 as with -s[k]
+    return (code & kP2PZero) ? 0.0 : __hiloint2double(hi, __double2loint(r));
+}
+__device__ __forceinline__ double p2p_expand(const double* s, int k) { return p2p_expand_coded(s, p2p_expand_code(k)); } // (k < kSums)
 
 // query-voxel probe of the neighbourhood-list table: linear probing, two slots per round trip (load <= 0.5)
 struct QProbe {

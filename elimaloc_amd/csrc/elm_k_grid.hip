@@ -25,7 +25,6 @@ __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWave
     constexpr int NV = (METHOD == ELM_P2P) ? (kStats ? kP2PVals : kP2PVals - 3) : kSums;
     __shared__ double s_buf[kRedPass * kBlock]; // stage 2: the queue of undecided points; afterwards the reduction's transpose buffer
     __shared__ double s_red[kSums];
-    __shared__ int s_res[kBlock];
     __shared__ int s_tst[kStats ? kBlock : 1];
     __shared__ float s_pz[METHOD == ELM_P2P ? kBlock : 1];  // P2P: the point's z (x and y ride in the stash's spare 8 bytes)
     __shared__ unsigned s_st[kStats ? kBlock : 1];           // instrumented builds: the walk statistics of the query voxel
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWave
             GridHardRec r;
             float pxf_, pyf_;
             load_g(r.gx, r.gy, r.gz, pxf_, pyf_);
-            r.r2 = hr2; r._pad = 0.f;
+            r.r2 = hr2; r.win = -1;
             s_rec[my_slot] = r;
         }
         __syncthreads();
@@ -271,13 +270,13 @@ __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWave
             grid_ball_walk<TILED, LPI>(m, lp, R, live, rl, lane, win, walked);
             if (kStats) walked = group_sum_int<LPI>(walked);
             if (rl == 0 && live) {
-                s_res[it] = win;
+                s_rec[it].win = win; // into the record's spare word: no group but this one reads the record
                 if (kStats) s_tst[it] = walked;
             }
         }
         __syncthreads();
         if (hard) {
-            bj = s_res[my_slot];
+            bj = s_rec[my_slot].win;
             if (kStats) n_tested += s_tst[my_slot];
         }
         __syncthreads(); // the queue is dead: the reduction may overwrite it
@@ -386,13 +385,19 @@ __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWave
     __shared__ double s_asym[(METHOD != ELM_P2P && COMPACT != 2) ? kAsymSums : 1];
     __shared__ unsigned s_hitw[kBlock / 64];
     if (METHOD != ELM_P2P && COMPACT != 2) asym_mark(P.A, rp, s_hitw);
+    const int tk = (int)threadIdx.x;
+    unsigned code = 0;
+    if (METHOD == ELM_P2P && tk < kSums) code = p2p_expand_code(tk); // (requested here: back long before the tail needs it)
     if (METHOD == ELM_P2P) block_reduce_to_lds<NV, kRedPass>(v, s_buf, s_red);
     else
         block_reduce_pair_sum<kRedPass, kStats ? kSums : kSums - 3>(P, s_buf, s_red);
     if (METHOD != ELM_P2P && COMPACT != 2) asym_side_store(P.A, P.ax, P.ay, P.az, L, rp, s_buf, s_asym, s_hitw);
-    const int tk = (int)threadIdx.x;
-    publish_and_reduce((tk < kSums && (kStats || tk < kSums - 3)) ? ((METHOD == ELM_P2P) ? p2p_expand(s_red, tk) : s_red[tk]) : 0.0, L, s, sd.blk_begin,
-                       sd.blk_end, partials, rp, s_buf);
+    double out = 0.0;
+    if (tk < kSums) {
+        out = (METHOD == ELM_P2P) ? p2p_expand_coded(s_red, code) : s_red[tk];
+        out = (kStats || tk < kSums - 3) ? out : 0.0;
+    }
+    publish_and_reduce(out, L, s, sd.blk_begin, sd.blk_end, partials, rp, s_buf);
 }
 
 void launch_accumulate_grid(hipStream_t s, const DevMap& m, const ScanDesc* scans, int batch, int total_blocks,
