@@ -74,7 +74,7 @@ hipError_t read_word(hipStream_t st, const unsigned* d_word, unsigned* out) {
 
 int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double vs, int cap, elm_map** out) {
     const char* what = "elm_map_build_device";
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     (void)hipGetLastError(); // drop stale errors of other libraries
     Scratch sc;
@@ -86,7 +86,7 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
     unsigned* d_flags = d_total + 1;
 
     // ---- the input: base's kept points in bucket order, then xyz
-    const unsigned n_base = base ? elm_host::map_dev(base).n_pts : 0u;
+    const unsigned n_base = base ? base->dm.n_pts : 0u;
     unsigned K = n_base;
     unsigned* d_pos = nullptr;
     uint8_t* d_drop = nullptr;
@@ -111,7 +111,7 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
     const unsigned N = K + (unsigned)n;
     Pt3* d_in = nullptr;
     e = sc.get(&d_in, N);
-    if (e == hipSuccess && K) launch_bd_compact(st, elm_host::map_dev(base).pts, d_drop, d_pos, n_base, d_in);
+    if (e == hipSuccess && K) launch_bd_compact(st, base->dm.pts, d_drop, d_pos, n_base, d_in);
     if (e == hipSuccess && n) e = hipMemcpyAsync(d_in + K, xyz, n * sizeof(Pt3), hipMemcpyHostToDevice, st); // (Pt3 is three packed floats)
     if (e == hipSuccess) e = evs.mark(st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
@@ -213,7 +213,7 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
     const int rc = elm_host::map_adopt(ctx, sc.hand_on(d_pts), sc.hand_on(d_ranges), sc.hand_on(d_keys), n_pts, n_vox, N, vs, cap, out);
     if (rc == ELM_OK) {
         std::copy(ms, ms + ELM_BUILD_STAGES, t_stage_ms);
-        t_stage_ctx = elm_host::ctx_unique_id(ctx);
+        t_stage_ctx = ctx->id;
         t_stage_valid = true;
     }
     return rc;
@@ -227,7 +227,7 @@ extern "C" int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uin
     if (!ctx || !out || (!xyz && n) || !(voxel_size > 0.0) || max_points_per_voxel <= 0 || (drop && !base)) return ELM_ERR_INVALID;
     const int rc = check_plain(ctx, "elm_map_build_device");
     if (rc != ELM_OK) return rc;
-    if ((base && elm_host::map_ctx(base) != ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if ((base && base->ctx != ctx) || ctx->in_flight) return ELM_ERR_INVALID;
     if (n > kBuildMaxPoints) {
         elm_host::ctx_set_error(ctx, "elm_map_build_device: more than 2^31 - 1 input points");
         return ELM_ERR_UNSUPPORTED;
@@ -236,7 +236,7 @@ extern "C" int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uin
 }
 
 extern "C" int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]) {
-    if (!ctx || !ms || !t_stage_valid || t_stage_ctx != elm_host::ctx_unique_id(ctx)) return ELM_ERR_INVALID;
+    if (!ctx || !ms || !t_stage_valid || t_stage_ctx != ctx->id) return ELM_ERR_INVALID;
     std::copy(t_stage_ms, t_stage_ms + ELM_BUILD_STAGES, ms);
     return ELM_OK;
 }

@@ -51,7 +51,7 @@ namespace {
 
 void evidence_free(elm_evidence* ev) {
     if (!ev) return;
-    if (elm_host::ctx_is_alive(ev->ctx, ev->ctx_id)) (void)hipSetDevice(elm_host::ctx_device(ev->ctx)); // a context destroyed first: just release
+    if (elm_host::ctx_is_alive(ev->ctx, ev->ctx_id)) (void)hipSetDevice(ev->ctx->device); // a context destroyed first: just release
     if (ev->d_base) (void)hipFree(ev->d_base);
     if (ev->d_through) (void)hipFree(ev->d_through);
     if (ev->d_hit) (void)hipFree(ev->d_hit);
@@ -59,7 +59,7 @@ void evidence_free(elm_evidence* ev) {
 }
 
 int create_impl(elm_ctx* ctx, const elm_map* map, int sub, elm_evidence** out) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(map, sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
@@ -82,7 +82,7 @@ int create_impl(elm_ctx* ctx, const elm_map* map, int sub, elm_evidence** out) {
     }
     elm_evidence* ev = new elm_evidence();
     ev->ctx = ctx;
-    ev->ctx_id = elm_host::ctx_unique_id(ctx);
+    ev->ctx_id = ctx->id;
     ev->map = map;
     ev->sub = sub;
     ev->n_cells = (uint32_t)total;
@@ -122,7 +122,7 @@ int create_impl(elm_ctx* ctx, const elm_map* map, int sub, elm_evidence** out) {
 
 int accumulate_impl(elm_ctx* ctx, elm_evidence* ev, const elm_scan* const* scans, const double* poses16, uint32_t n_jobs,
                     const elm_evidence_config* c, elm_evidence_stats* stats, uint16_t* events) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(ev->map, ev->sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
@@ -150,7 +150,7 @@ extern "C" int elm_evidence_create(elm_ctx* ctx, const elm_map* map, int sub, el
     *out = nullptr;
     int rc = check_plain(ctx, "elm_evidence_create");
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (map->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
     return guard_alloc(ctx, "elm_evidence_create", [&] { return create_impl(ctx, map, sub, out); });
 }
 
@@ -159,7 +159,7 @@ extern "C" void elm_evidence_destroy(elm_evidence* ev) { evidence_free(ev); }
 extern "C" int elm_evidence_reset(elm_ctx* ctx, elm_evidence* ev) {
     int rc = check_object(ctx, ev, "elm_evidence_reset");
     if (rc != ELM_OK) return rc;
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     hipError_t e = hipSuccess;
     if (ev->n_cells) {
@@ -187,7 +187,7 @@ namespace {
 
 // the counters in elm_map_fine_cells' order
 int download_counts(elm_ctx* ctx, const elm_evidence* ev, std::vector<uint32_t>& through, std::vector<uint32_t>& hit) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const size_t n = ev->n_cells;
     std::vector<uint32_t> t(n), h(n);
     through.resize(n);

@@ -1,5 +1,5 @@
 // elm_free.cpp -- free-space check (include/elimaloc_hip.h, "free-space check"): the argument checks, the fine
-// occupancy table of the map (built and cached by elm_api.cpp), the launches of elm_k_free.hip and the download, through the call of one
+// occupancy table of the map (built and cached by elm_map.cpp), the launches of elm_k_free.hip and the download, through the call of one
 // scan at many poses that elm_query.hpp shares with the ray cast.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -65,9 +65,9 @@ int check_impl(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const dou
 
 extern "C" int elm_map_fine_cells(elm_ctx* ctx, const elm_map* map, int sub, int32_t* cells3, size_t cap, size_t* n) {
     if (!ctx || !map || !sub_ok(sub) || !n || (cap && !cells3)) return ELM_ERR_INVALID;
-    if (elm_host::map_ctx(map) != ctx) return ELM_ERR_INVALID;
+    if (map->ctx != ctx) return ELM_ERR_INVALID;
     return guard_alloc(ctx, "elm_map_fine_cells", [&] {
-        if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
         std::vector<int32_t> cells;
         int rc = elm_host::map_fine_cells(map, sub, cells);
         if (rc != ELM_OK) return rc;

@@ -63,7 +63,7 @@ bool config_ok(const elm_growth_config* c) { return walk_config_ok(c) && c->clea
 
 void growth_free(elm_growth* g) {
     if (!g) return;
-    if (elm_host::ctx_is_alive(g->ctx, g->ctx_id)) (void)hipSetDevice(elm_host::ctx_device(g->ctx)); // a context destroyed first: just release
+    if (elm_host::ctx_is_alive(g->ctx, g->ctx_id)) (void)hipSetDevice(g->ctx->device); // a context destroyed first: just release
     void* arrays[] = {g->t.ckeys, g->t.cmasks, g->t.fkeys, g->t.hit, g->t.through, g->t.sums, g->t.count, g->o.parent, g->o.root_id,
                       g->o.rec, g->o.listed, g->o.rank, g->o.counters, g->o_out};
     for (void* p : arrays)
@@ -86,13 +86,13 @@ hipError_t clear_tables(const elm_growth* g, hipStream_t st) {
 }
 
 int create_impl(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_growth** out) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(map, sub, &ft, nullptr); // built now when it is not there yet
     if (rc != ELM_OK) return rc;
     elm_growth* g = new elm_growth();
     g->ctx = ctx;
-    g->ctx_id = elm_host::ctx_unique_id(ctx);
+    g->ctx_id = ctx->id;
     g->map = map;
     g->sub = sub;
     g->capacity = capacity;
@@ -118,7 +118,7 @@ int create_impl(elm_ctx* ctx, const elm_map* map, int sub, size_t capacity, elm_
 
 int accumulate_impl(elm_ctx* ctx, elm_growth* g, const elm_scan* const* scans, const double* poses16, uint32_t n_jobs,
                     const elm_growth_config* c, elm_growth_stats* stats, uint16_t* events) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
@@ -159,7 +159,7 @@ struct Cells {
 };
 
 int download_cells(elm_ctx* ctx, const elm_growth* g, Cells& out) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     if (!g->count) return ELM_OK;
     const size_t s = g->slots;
     std::vector<unsigned long long> keys(s), sums(3 * s);
@@ -223,7 +223,7 @@ hipError_t obj_reserve(elm_growth* g) {
 }
 
 int find_objects_impl(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule* rule, elm_growth_object_stats* stats) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const char* what = "elm_growth_find_objects";
     g->o_held = false;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
@@ -314,7 +314,7 @@ int check_objects_held(elm_ctx* ctx, const elm_growth* g, const char* what) {
 
 // one value per candidate cell in elm_growth_cells' order
 int cell_objects_impl(elm_ctx* ctx, const elm_growth* g, std::vector<int32_t>& out) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     if (!g->count) return ELM_OK;
     const size_t s = g->slots;
     std::vector<unsigned long long> keys(s);
@@ -345,15 +345,15 @@ int cell_objects_impl(elm_ctx* ctx, const elm_growth* g, std::vector<int32_t>& o
 }
 
 int beam_objects_impl(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, const double T16[16], const elm_growth_config* c, int32_t* obj) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const char* what = "elm_growth_beam_objects";
     const FineTable* ft = nullptr;
     int rc = elm_host::map_fine_table(g->map, g->sub, &ft, nullptr);
     if (rc != ELM_OK) return rc;
     EvidJob job{};
-    size_t n = 0;
-    job.pts = elm_host::scan_dev_points(scan, &n);
-    job.n = (uint32_t)n;
+    const size_t n = scan->n;
+    job.pts = (const float*)scan->d_pts;
+    job.n = scan->n;
     pose_rows12(T16, job.rows);
     if (!n) return ELM_OK;
     int32_t* d_out = (int32_t*)elm_host::ctx_reloc_scratch(ctx, 13, n * sizeof(int32_t), &rc);
@@ -374,7 +374,7 @@ extern "C" int elm_growth_create(elm_ctx* ctx, const elm_map* map, int sub, size
     *out = nullptr;
     int rc = check_plain(ctx, "elm_growth_create");
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (map->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
     return guard_alloc(ctx, "elm_growth_create", [&] { return create_impl(ctx, map, sub, capacity, out); });
 }
 
@@ -383,7 +383,7 @@ extern "C" void elm_growth_destroy(elm_growth* g) { growth_free(g); }
 extern "C" int elm_growth_reset(elm_ctx* ctx, elm_growth* g) {
     int rc = check_object(ctx, g, "elm_growth_reset");
     if (rc != ELM_OK) return rc;
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     const hipError_t e = clear_tables(g, (hipStream_t)elm_ctx_stream(ctx));
     if (e != hipSuccess) return dev_error(ctx, "elm_growth_reset", e);
     g->count = 0;

@@ -19,21 +19,11 @@ void* callback_staging(elm_ctx* ctx, size_t bytes);
 int callback_register(elm_ctx* ctx, const elm_map* map, const void* stage, const float* rel_time, size_t n, const elm_deskew_tables* tab,
                       double voxel_size, const double T0[16], const elm_reg_config* cfg, elm_reg_result* result, uint64_t* n_source,
                       int* unpackable);
-// members of the structs elm_api.cpp defines, for elm_multi.cpp
-elm_group*& ctx_group(elm_ctx* ctx);
-int ctx_device(const elm_ctx* ctx);
+// (the structs behind the handles are in elm_host_types.hpp, which needs HIP; what follows DOES something and stays a function)
+// ... for elm_multi.cpp
 void ctx_set_error(elm_ctx* ctx, const std::string& text);
-std::vector<elm_map*>& map_replicas(elm_map* m);
-elm_ctx* map_ctx(const elm_map* m);
-std::vector<elm_scan*>& scan_shards(elm_scan* s);
-elm_ctx* scan_ctx(const elm_scan* s);
-void scan_set_total(elm_scan* s, size_t n_total);
 // ... for elm_reloc.cpp
-bool ctx_exchange_attached(const elm_ctx* ctx); // a communicator or an all-reduce hook is attached
-bool ctx_in_flight(const elm_ctx* ctx);          // an enqueued batch has not been finished
 void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc); // grow-only device scratch 0..15 of the context (nullptr: *rc)
-const elm::DevMap& map_dev(const elm_map* m);
-const std::vector<int32_t>& map_host_keys(const elm_map* m); // [n_vox][3] stored keys
 // the map's ground-field bin index (built at the first call, kept with the map) and the xy bounds of its stored points {x_lo, x_hi, y_lo, y_hi}
 int map_ground_index(const elm_map* m, const elm::GroundIndex** gi, double bounds[4]);
 // ... for elm_free.cpp
@@ -42,13 +32,11 @@ int map_ground_index(const elm_map* m, const elm::GroundIndex** gi, double bound
 int map_fine_table(const elm_map* m, int sub, const elm::FineTable** ft, double info[2]);
 // the stored points' fine cells for sub, sorted ascending by (x, y, z), duplicates removed
 int map_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
-const float* scan_dev_points(const elm_scan* s, size_t* n); // the resident points of a plain (unsharded) scan, packed xyz
 int free_space_form(); // 0: one ray per lane; 1: ELM_CHECK=free_wave, a wave per ray (the A/B of DESIGN.md section 13)
 // ... for elm_ray.cpp
 int ray_pose_block(int dflt); // poses per workgroup of k_ray_cast: dflt, or N of ELM_CHECK=ray_poses=N (1 .. 16; the sweep of DESIGN.md section 14)
 // ... for elm_evid.cpp
 bool ctx_is_alive(const elm_ctx* ctx, uint64_t id); // the context with this unique id still exists (a child may outlive its context)
-uint64_t ctx_unique_id(const elm_ctx* ctx);
 // the fine cell of every stored point for sub, in elm_map_download_points order: [n_points][3]
 int map_point_fine_cells(const elm_map* m, int sub, std::vector<int32_t>& cells3);
 // ... for elm_build.cpp

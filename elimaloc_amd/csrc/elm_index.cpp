@@ -1,0 +1,686 @@
+// elm_index.cpp -- the search indices of a map: the dense and the two-level (tiled) cell grid, the neighbourhood lists, the voxel-mean
+// lists, and the choice among them (build_search_index).  Host-side C++17.
+#include <assert.h>
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "elm_grid_layout.hpp"
+#include "elm_host_types.hpp"
+
+using namespace elm;
+using namespace elm_host;
+
+// The block array of the cell grid: 4 slots per block must number below 2^31 (the kernels carry slot numbers as ints); below
+// grid_narrow_limit() bytes stage 1 uses 32-bit byte offsets, beyond it 16-byte units (ELM_GRID=max_block_bytes=N lowers the limit: tests
+// force the wide form onto small maps).
+constexpr uint64_t kGridMaxBlocks = 0x1FFFFFF0ull;
+static uint64_t grid_narrow_limit() {
+    const char* v = nullptr;
+    if (env_token("ELM_GRID", "max_block_bytes", &v)) return std::min<uint64_t>(strtoull(v, nullptr, 10), 0xFFFFFF00ull);
+    return 0xFFFFFF00ull;
+}
+// The cell budget of the dense tables (the cell grid's offsets, the voxel-mean lists' floor-key box): ELM_GRID=max_cells=N, default
+// 1.5e9 = 6 GB of offsets.
+static uint64_t grid_max_cells() {
+    const char* v = nullptr;
+    if (env_token("ELM_GRID", "max_cells", &v)) return strtoull(v, nullptr, 10);
+    return 1500000000ull;
+}
+// Host memory a large temporary may take: MemAvailable of /proc/meminfo (free + reclaimable page cache -- after a big PCD has been read
+// most of the RAM is page cache, and MemFree alone would refuse the grid depending on the cache state); unknown: no limit (the
+// allocations themselves fail with bad_alloc, which the builders handle).
+static uint64_t host_available_bytes() {
+    FILE* f = fopen("/proc/meminfo", "r");
+    if (!f) return ~0ull;
+    char line[256];
+    uint64_t kb = 0;
+    bool found = false;
+    while (fgets(line, sizeof(line), f)) {
+        unsigned long long v = 0;
+        if (sscanf(line, "MemAvailable: %llu kB", &v) == 1) { kb = v; found = true; break; }
+    }
+    fclose(f);
+    return found ? kb * 1024ull : ~0ull;
+}
+
+// The device allocations local to one builder: the builder's own pointer variables, by address.  Whatever they still hold when the
+// builder returns -- on any path -- is released; release_all() at the commit leaves them to the map.
+struct DevLocals {
+    static constexpr int kMax = 8;
+    void** held[kMax];
+    int n = 0;
+    DevLocals(std::initializer_list<void**> ptrs) {
+        assert(ptrs.size() <= (size_t)kMax);
+        for (void** p : ptrs)
+            if (n < kMax) held[n++] = p;
+    }
+    DevLocals(const DevLocals&) = delete;
+    DevLocals& operator=(const DevLocals&) = delete;
+    void release_all() { n = 0; }
+    ~DevLocals() {
+        for (int i = 0; i < n; ++i)
+            if (*held[i]) (void)hipFree(*held[i]);
+    }
+};
+// HIPCHK for the grid builders: out of device memory is "this index is not affordable" (the caller builds another), not an error
+#define HIPCHK_OOM(ctx, call)                                                                          \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);                     \
+            (void)hipGetLastError();                                                                   \
+            return e_ == hipErrorOutOfMemory ? ELM_ERR_UNSUPPORTED : ELM_ERR_DEVICE;                   \
+        }                                                                                              \
+    } while (0)
+
+// The query voxels of a map and the sizes of their lists, for the neighbourhood lists and for the voxel-mean lists: the keys
+// (enumerate_query_keys) go to the device, launch_nbr_count counts every query voxel's neighbour points (counts) and occupied neighbour
+// voxels (nocc), and the list offsets are the running sums of stride(q) -- the caller's rule -- on the host and on the device.  The device
+// arrays live as long as this object.
+struct QueryLists {
+    std::vector<int32_t> qkeys;
+    uint32_t n_q = 0;
+    std::vector<uint32_t> counts, nocc, offs;
+    uint64_t total = 0;
+    int32_t* d_qkeys = nullptr;
+    uint32_t *d_counts = nullptr, *d_nocc = nullptr, *d_off = nullptr;
+    DevLocals own{(void**)&d_qkeys, (void**)&d_counts, (void**)&d_nocc, (void**)&d_off};
+};
+template <class Stride>
+static int count_query_lists(elm_map* m, QueryLists& ql, Stride stride) {
+    elm_ctx* ctx = m->ctx;
+    std::vector<int32_t>& qkeys = ql.qkeys;
+    enumerate_query_keys(m, qkeys);
+    const uint32_t n_q = ql.n_q = (uint32_t)(qkeys.size() / 3);
+    int32_t*& d_qkeys = ql.d_qkeys;
+    uint32_t *&d_counts = ql.d_counts, *&d_nocc = ql.d_nocc, *&d_off = ql.d_off;
+    const size_t nq_alloc = std::max<size_t>(n_q, 1);
+    HIPCHK(ctx, hipMalloc((void**)&d_qkeys, nq_alloc * 3 * sizeof(int32_t)));
+    HIPCHK(ctx, hipMalloc((void**)&d_counts, nq_alloc * sizeof(uint32_t)));
+    HIPCHK(ctx, hipMalloc((void**)&d_nocc, nq_alloc * sizeof(uint32_t)));
+    HIPCHK(ctx, hipMalloc((void**)&d_off, nq_alloc * sizeof(uint32_t)));
+    std::vector<uint32_t>&counts = ql.counts, &nocc = ql.nocc, &offs = ql.offs;
+    counts.resize(n_q); nocc.resize(n_q); offs.resize(n_q);
+    uint64_t total = 0;
+    if (n_q) { // (deterministic: a later build from the same map finds the offsets the lists were written with)
+        HIPCHK(ctx, hipMemcpy(d_qkeys, qkeys.data(), (size_t)n_q * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
+        (void)hipGetLastError();
+        launch_nbr_count(ctx->stream, m->dm, d_qkeys, n_q, d_counts, d_nocc);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        // (the voxel-mean lists read only nocc on the host; their counts come down too -- n_q words, once per build -- so that the step is one)
+        HIPCHK(ctx, hipMemcpy(counts.data(), d_counts, (size_t)n_q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(nocc.data(), d_nocc, (size_t)n_q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t q = 0; q < n_q; ++q) {
+            offs[q] = (uint32_t)total;
+            total += stride(q);
+        }
+        HIPCHK(ctx, hipMemcpy(d_off, offs.data(), (size_t)n_q * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    ql.total = total; // (the caller refuses a total beyond what its offsets hold)
+    return ELM_OK;
+}
+// the probe table over the query voxels: query voxel q at its key with what fields(q, slot) writes
+template <class Fields>
+static int upload_query_slots(elm_ctx* ctx, const QueryLists& ql, uint32_t qcap, HashSlot** d_slots, Fields fields) {
+    const std::vector<HashSlot> qs = fill_slot_table(ql.qkeys.data(), ql.n_q, qcap, fields);
+    HIPCHK(ctx, hipMalloc((void**)d_slots, (size_t)qcap * sizeof(HashSlot)));
+    HIPCHK(ctx, hipMemcpy(*d_slots, qs.data(), (size_t)qcap * sizeof(HashSlot), hipMemcpyHostToDevice));
+    return ELM_OK;
+}
+
+// Voxel-mean lists for VGICP / AVGICP (DevMap::vnbr_blk, vox_rec): built lazily at the first VGICP / AVGICP registration, after
+// CalVoxelCovAll.  The lists hold 16 bytes per slot (float32 mean + voxel id | position code); a voxel's float64 record is stored ONCE in
+// vox_rec (round 6: rounds 2-5 copied the 64-byte record into every list, 27 x).  AVGICP's face sublists (whole records, <= 7 per query
+// voxel) are built only when an AVGICP call asks for them (want_faces): a VGICP map does not pay their bytes.
+int elm_host::build_voxel_neighbourhoods(elm_map* m, bool want_faces) {
+    const bool need_lists = !m->has_vnbr;
+    // faces exist only beside the dense floor-key table; a map whose lists were built without one never gets them
+    const bool need_faces = want_faces && !m->has_vface && !m->vface_refused && (need_lists || m->d_vq_dense != nullptr);
+    if (!need_lists && !need_faces) return ELM_OK;
+    elm_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (m->dm.n_vox > kVidMask) { ctx->last_error = "voxel-mean lists: more than 2^26 voxels"; return ELM_ERR_UNSUPPORTED; }
+    QueryLists ql;
+    int rc;
+    if ((rc = count_query_lists(m, ql, [&](uint32_t q) { return (ql.nocc[q] + 3u) & ~3u; })) != ELM_OK) return rc; // list starts: multiples of four slots
+    const std::vector<int32_t>& qkeys = ql.qkeys;
+    const std::vector<uint32_t>&nocc = ql.nocc, &offs = ql.offs;
+    const uint32_t n_q = ql.n_q;
+    const uint64_t total = ql.total;
+    int32_t* const d_qkeys = ql.d_qkeys;
+    uint32_t *const d_nocc = ql.d_nocc, *const d_off = ql.d_off;
+    if (total >= (1ull << 32)) { ctx->last_error = "voxel-mean lists exceed 2^32 slots"; return ELM_ERR_UNSUPPORTED; }
+    // the dense box of floor keys (when it fits the cell budget and the packed word holds the offsets): no hash probe in the kernel --
+    // one 4-byte load at a computed, spatially coherent address
+    int32_t klo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, khi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    for (uint32_t q = 0; q < n_q; ++q)
+        for (int a = 0; a < 3; ++a) {
+            klo[a] = std::min(klo[a], qkeys[3 * q + a]);
+            khi[a] = std::max(khi[a], qkeys[3 * q + a]);
+        }
+    const int64_t vd[3] = {n_q ? (int64_t)khi[0] - klo[0] + 1 : 0, n_q ? (int64_t)khi[1] - klo[1] + 1 : 0, n_q ? (int64_t)khi[2] - klo[2] + 1 : 0};
+    const uint64_t vcells = (uint64_t)vd[0] * (uint64_t)vd[1] * (uint64_t)vd[2];
+    auto dense_index = [&](uint32_t q) {
+        return ((uint64_t)(qkeys[3 * q] - klo[0]) * (uint64_t)vd[1] + (uint64_t)(qkeys[3 * q + 1] - klo[1])) * (uint64_t)vd[2] + (uint64_t)(qkeys[3 * q + 2] - klo[2]);
+    };
+    const bool dense_ok = n_q && total / 4 < (1ull << 27) && vcells <= grid_max_cells() && m->ctx->kernel_mode == 4;
+    if (need_lists) {
+        const size_t nb = (size_t)(total / 4) + 1; // + one block of padding slots at the end: the target of the filter's loads past a list's last block
+        HIPCHK(ctx, hipMalloc((void**)&m->d_vnbr_blk, nb * sizeof(VoxBlk)));
+        {
+            VoxBlk padblk;
+            for (int u = 0; u < 4; ++u) { padblk.g.x[u] = padblk.g.y[u] = padblk.g.z[u] = 1e18f; padblk.vc[u] = -1; }
+            HIPCHK(ctx, hipMemcpy(m->d_vnbr_blk + (nb - 1), &padblk, sizeof(VoxBlk), hipMemcpyHostToDevice));
+            m->dm.vnbr_pad_blk = (uint32_t)(nb - 1);
+        }
+        HIPCHK(ctx, hipMalloc((void**)&m->d_vox_rec, std::max<size_t>((size_t)m->dm.n_vox * sizeof(VoxRec), 256)));
+        (void)hipGetLastError();
+        launch_vox_rec_fill(ctx->stream, m->dm, m->d_vox_rec);
+        if (n_q) launch_vnbr_fill(ctx->stream, m->dm, d_qkeys, n_q, d_off, m->d_vnbr_blk);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t qcap = next_pow2((uint64_t)n_q * 2);
+        if ((rc = upload_query_slots(ctx, ql, qcap, &m->d_vqslots, [&](uint32_t q, HashSlot& s) { s.start = offs[q]; s.cnt = nocc[q]; })) != ELM_OK) return rc;
+        size_t bytes = nb * sizeof(VoxBlk) + (size_t)m->dm.n_vox * sizeof(VoxRec);
+        if (dense_ok) {
+            std::vector<uint32_t> dense(vcells, 0u);
+            for (uint32_t q = 0; q < n_q; ++q) dense[dense_index(q)] = ((offs[q] >> 2) << 5) | nocc[q]; // first block of four slots, nocc <= 27
+            HIPCHK(ctx, hipMalloc((void**)&m->d_vq_dense, vcells * sizeof(uint32_t)));
+            HIPCHK(ctx, hipMemcpy(m->d_vq_dense, dense.data(), vcells * sizeof(uint32_t), hipMemcpyHostToDevice));
+            m->dm.vq_dense = m->d_vq_dense;
+            m->dm.vq_x0 = klo[0]; m->dm.vq_y0 = klo[1]; m->dm.vq_z0 = klo[2];
+            m->dm.vq_nx = (int32_t)vd[0]; m->dm.vq_ny = (int32_t)vd[1]; m->dm.vq_nz = (int32_t)vd[2];
+            bytes += vcells * sizeof(uint32_t);
+        } else {
+            bytes += (size_t)qcap * sizeof(HashSlot); // (the probe table is read only without the dense one)
+        }
+        m->dm.vqslots = m->d_vqslots;
+        m->dm.vqmask = qcap - 1;
+        m->dm.vox_rec = m->d_vox_rec;
+        m->dm.vnbr_blk = m->d_vnbr_blk;
+        m->has_vnbr = true;
+        m->info.device_bytes += bytes + (dense_ok ? (size_t)qcap * sizeof(HashSlot) : 0);
+        m->info.index_bytes += bytes + (size_t)m->n_bad_vox * 9 * sizeof(double); // + the stored inverses flagged voxels read
+        m->info.index_part_bytes[1] += bytes + (size_t)m->n_bad_vox * 9 * sizeof(double);
+        m->info.n_list_voxels = n_q;
+    }
+    if (need_faces && m->d_vq_dense && n_q) {
+        // AVGICP pairs with the face neighbours only (<= 7 of a list's <= 27 slots): their sublists as whole records, addressed like vq_dense
+        uint32_t *d_fcnt = nullptr, *d_foff = nullptr;
+        DevLocals own{(void**)&d_fcnt, (void**)&d_foff};
+        const size_t nq_alloc = n_q;
+        HIPCHK(ctx, hipMalloc((void**)&d_fcnt, nq_alloc * sizeof(uint32_t)));
+        HIPCHK(ctx, hipMalloc((void**)&d_foff, nq_alloc * sizeof(uint32_t)));
+        (void)hipGetLastError();
+        // the fused AVGICP walk's record format; flagged voxels (NaN normals) are left to its fix-up launch (ELM_CHECK=avg_inline: such maps
+        // keep the nine-entry walk with its in-line fallback)
+        // The fix-up launch pays while few workgroups meet a flagged record (round 4: +14 % with 0.3 % of the voxels flagged); when
+        // flagged voxels are common -- sparse clutter: two or three points per voxel, rank-deficient -- nearly every workgroup is marked,
+        // the second launch repeats the whole walk, and the in-line fallback is the cheaper form: by default the map decides at 1 % of
+        // its voxels (ELM_CHECK=avg_fixup / avg_inline force either form).
+        const bool fx_inline = check_mode("avg_inline"), fx_fixup = check_mode("avg_fixup"), fx_skip = check_mode("avg_skip");
+        const bool fixup_ok = fx_inline ? false : ((fx_fixup || fx_skip) ? true : (uint64_t)m->n_bad_vox * 100ull <= (uint64_t)m->dm.n_vox);
+        const int plain = (m->dm.vox_compact && (m->n_bad_vox == 0 || fixup_ok) && !check_mode("avg_nine") && !check_mode("pair_nine")) ? 1 : 0;
+        launch_vface(ctx->stream, m->dm, d_off, d_nocc, n_q, d_fcnt, nullptr, nullptr, plain);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<uint32_t> fcnt(n_q), foff(n_q);
+        HIPCHK(ctx, hipMemcpy(fcnt.data(), d_fcnt, (size_t)n_q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint64_t ftotal = 0;
+        for (uint32_t q = 0; q < n_q; ++q) { foff[q] = (uint32_t)ftotal; ftotal += fcnt[q]; }
+        if (ftotal < (1ull << 29)) {
+            HIPCHK(ctx, hipMemcpy(d_foff, foff.data(), (size_t)n_q * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHK(ctx, hipMalloc((void**)&m->d_vface, std::max<size_t>((size_t)ftotal * sizeof(VoxRec), 256)));
+            launch_vface(ctx->stream, m->dm, d_off, d_nocc, n_q, d_fcnt, d_foff, m->d_vface, plain);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            std::vector<uint32_t> dense(vcells, 0u);
+            for (uint32_t q = 0; q < n_q; ++q) dense[dense_index(q)] = (foff[q] << 3) | fcnt[q]; // fcnt <= 7
+            HIPCHK(ctx, hipMalloc((void**)&m->d_vqf_dense, vcells * sizeof(uint32_t)));
+            HIPCHK(ctx, hipMemcpy(m->d_vqf_dense, dense.data(), vcells * sizeof(uint32_t), hipMemcpyHostToDevice));
+            m->dm.vface = m->d_vface;
+            m->dm.vqf_dense = m->d_vqf_dense;
+            m->dm.vface_plain = plain;
+            m->dm.vface_flagged = (plain && m->n_bad_vox != 0) ? (fx_skip ? 2 : 1) : 0; // (2: tests only -- no fix-up launch, the flagged pairs are dropped)
+            m->info.layout_flags = (m->info.layout_flags & ~(32 | 64)) | (plain ? 32 : 0) | (m->dm.vface_flagged ? 64 : 0);
+            m->info.device_bytes += vcells * sizeof(uint32_t) + (size_t)ftotal * sizeof(VoxRec);
+            m->info.index_bytes += vcells * sizeof(uint32_t) + (size_t)ftotal * sizeof(VoxRec);
+            m->info.index_part_bytes[2] += vcells * sizeof(uint32_t) + (size_t)ftotal * sizeof(VoxRec);
+            m->has_vface = true;
+        } else {
+            m->vface_refused = true;
+        }
+    } else if (need_faces) {
+        m->vface_refused = true;
+    }
+    return ELM_OK;
+}
+
+// The GICP payload in grid slot order (DevMap::grid_gicp): needs the grid and the point covariances, whichever comes last.
+int elm_host::refresh_grid_gicp(elm_map* m) {
+    if (!m->has_grid || !m->info.has_point_cov || !m->grid_slots) return ELM_OK;
+    elm_ctx* ctx = m->ctx;
+    const bool compact = m->want_gicp_compact;
+    double** dst = compact ? &m->d_grid_gicp8 : &m->d_grid_gicp;
+    const size_t rec_bytes = (compact ? 8 : 16) * sizeof(double);
+    if (!*dst) {
+        HIPCHK(ctx, hipMalloc((void**)dst, m->grid_slots * rec_bytes));
+        m->info.device_bytes += m->grid_slots * rec_bytes;
+    }
+    (void)hipGetLastError();
+    launch_gather_gicp(ctx->stream, m->dm, m->grid_slots, *dst, compact ? 1 : 0);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    m->dm.grid_gicp = m->d_grid_gicp;
+    m->dm.grid_gicp8 = m->d_grid_gicp8;
+    // 2: no point outside the compact form -- the kernel has no full-record fallback and gathers the pair fused (ELM_CHECK=pair_nine: the
+    // nine-entry form with its fallback, as for maps with flagged points; fusing the compact lanes of THOSE kernels too and reading a
+    // flagged point's stored inverse row by row measured 15 % slower in round 5: profiles/r05_kernel_ab.txt)
+    m->dm.gicp_compact = compact ? ((m->n_bad_pts == 0 && !check_mode("pair_nine")) ? 2 : 1) : 0;
+    m->info.layout_flags = (m->info.layout_flags & ~(1 | 8)) | (compact ? 1 : 0) | (m->dm.gicp_compact == 2 ? 8 : 0);
+    return ELM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// the cell grids: what the dense and the two-level form share
+// ------------------------------------------------------------------------------------------------------
+static_assert(sizeof(GridBlk) == 48 && offsetof(GridBlk, x) == 0 && offsetof(GridBlk, y) == 16 && offsetof(GridBlk, z) == 32,
+              "grid_block_layout writes blocks of x[4] y[4] z[4]");
+
+// The stored points on the host and the box of their half-voxel cells, two cells of margin on every side: a block or ball that reaches
+// just past the outermost points stays inside the grid.
+struct GridBox {
+    std::vector<float4> pts;
+    int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+    int64_t dim[3] = {0, 0, 0};
+};
+static int grid_box(elm_map* m, GridBox& box) {
+    elm_ctx* ctx = m->ctx;
+    const size_t n = m->dm.n_pts;
+    const double vs = m->dm.voxel_size;
+    std::vector<float4>& pts = box.pts;
+    pts.resize(n);
+    HIPCHK(ctx, hipMemcpy(pts.data(), m->d_pts, n * sizeof(float4), hipMemcpyDeviceToHost));
+    int32_t* lo = box.lo;
+    int32_t hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    for (size_t i = 0; i < n; ++i) {
+        const float c3[3] = {pts[i].x, pts[i].y, pts[i].z};
+        for (int a = 0; a < 3; ++a) {
+            const int32_t c = grid_cell_of((double)c3[a], vs);
+            lo[a] = std::min(lo[a], c);
+            hi[a] = std::max(hi[a], c);
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        lo[a] -= 2; hi[a] += 2;
+        box.dim[a] = (int64_t)hi[a] - lo[a] + 1;
+    }
+    return ELM_OK;
+}
+
+// A laid-out grid (grid_block_layout) on the host, and its copy on the device: the builder's locals until grid_commit.  d_side is the
+// form's own table (the dense grid's statistics box, the two-level grid's tile table), allocated by the form.
+struct GridHost {
+    std::vector<uint32_t> start, gi;
+    std::vector<GridBlk> gb;
+    uint64_t n_blk = 0;
+};
+struct GridDev {
+    GridBlk* d_blk = nullptr;
+    uint32_t *d_idx = nullptr, *d_start = nullptr;
+    void* d_side = nullptr;
+    DevLocals own{(void**)&d_blk, (void**)&d_idx, (void**)&d_start, &d_side};
+};
+// blocks, slot indices and block starts go up; dm (the builder's copy of the map's view) gets the fields both forms set alike
+static int grid_upload(elm_ctx* ctx, const GridHost& g, GridDev& d, DevMap& dm) {
+    const std::vector<GridBlk>& gb = g.gb;
+    const std::vector<uint32_t>&gi = g.gi, &start = g.start;
+    GridBlk*& d_blk = d.d_blk;
+    uint32_t *&d_idx = d.d_idx, *&d_start = d.d_start;
+    HIPCHK_OOM(ctx, hipMalloc((void**)&d_blk, gb.size() * sizeof(GridBlk)));
+    HIPCHK_OOM(ctx, hipMalloc((void**)&d_idx, gi.size() * sizeof(uint32_t)));
+    HIPCHK_OOM(ctx, hipMalloc((void**)&d_start, start.size() * sizeof(uint32_t)));
+    HIPCHK_OOM(ctx, hipMemcpy(d_blk, gb.data(), gb.size() * sizeof(GridBlk), hipMemcpyHostToDevice));
+    HIPCHK_OOM(ctx, hipMemcpy(d_idx, gi.data(), gi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK_OOM(ctx, hipMemcpy(d_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    dm.grid_blk = d_blk;
+    dm.grid_idx = d_idx;
+    dm.grid_start = d_start;
+    dm.grid_wide = g.n_blk * sizeof(GridBlk) > grid_narrow_limit() ? 1 : 0;
+    dm.grid_nslots = (uint32_t)(4 * g.n_blk);
+    return ELM_OK;
+}
+// Every device step has succeeded: dm and the arrays become the map's, and the GICP records are gathered into slot order.  When those do
+// not fit the grid is given back (the lists read pt_gicp through their index): the map is as before, d still owns the arrays,
+// ELM_ERR_UNSUPPORTED.  The bytes of blocks, slot indices and starts are accounted here, the form's own table by the form.
+static int grid_commit(elm_map* m, const DevMap& dm, const GridHost& g, GridDev& d) {
+    const DevMap dm_before = m->dm;
+    m->dm = dm;
+    m->d_grid_blk = d.d_blk; m->d_grid_idx = d.d_idx; m->d_grid_start = d.d_start;
+    m->has_grid = true;
+    m->grid_slots = g.gi.size();
+    if (refresh_grid_gicp(m) != ELM_OK) {
+        m->d_grid_blk = nullptr; m->d_grid_idx = nullptr; m->d_grid_start = nullptr;
+        m->dm = dm_before;
+        m->has_grid = false;
+        m->grid_slots = 0;
+        (void)hipGetLastError();
+        return ELM_ERR_UNSUPPORTED;
+    }
+    d.own.release_all();
+    const size_t searched = g.gb.size() * sizeof(GridBlk) + g.start.size() * sizeof(uint32_t);
+    m->info.device_bytes += searched + g.gi.size() * sizeof(uint32_t);
+    m->info.nbr_entries = m->dm.n_pts;
+    m->info.index_bytes += searched;
+    m->info.index_part_bytes[0] += searched;
+    return ELM_OK;
+}
+
+// Dense half-voxel cell grid (see DevMap::grid_*): the map points once, counting-sorted by cell on the host (init time), the
+// offsets of every cell of the bounding box (+ 2 cells of margin), and the dense voxel box of walk statistics.
+// ELM_ERR_UNSUPPORTED (and grid_refused) when the grid is not affordable -- the box needs more than max_cells cells, its tables
+// do not fit the host / device memory that is free right now, or an allocation fails half-way -- the caller then builds the
+// neighbourhood lists instead; nothing is left allocated and the map is unchanged.
+static int dense_grid_to_device(elm_map* m, const GridBox& box, const GridHost& g, const int32_t klo[3], const int64_t vd[3], uint64_t vcells) {
+    elm_ctx* ctx = m->ctx;
+    GridDev d;
+    DevMap dm = m->dm;
+    int rc;
+    if ((rc = grid_upload(ctx, g, d, dm)) != ELM_OK) return rc;
+    uint32_t* d_stat = nullptr;
+    HIPCHK_OOM(ctx, hipMalloc((void**)&d_stat, std::max<size_t>(vcells * sizeof(uint32_t), 256)));
+    d.d_side = d_stat;
+    dm.gx0 = box.lo[0]; dm.gy0 = box.lo[1]; dm.gz0 = box.lo[2];
+    dm.gnx = (int32_t)box.dim[0]; dm.gny = (int32_t)box.dim[1]; dm.gnz = (int32_t)box.dim[2];
+    dm.vox_stat = d_stat;
+    dm.vx0 = klo[0] - 1; dm.vy0 = klo[1] - 1; dm.vz0 = klo[2] - 1;
+    dm.vnx = (int32_t)vd[0]; dm.vny = (int32_t)vd[1]; dm.vnz = (int32_t)vd[2];
+    (void)hipGetLastError();
+    launch_vox_stat(ctx->stream, dm, d_stat);
+    HIPCHK_OOM(ctx, hipGetLastError());
+    HIPCHK_OOM(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = grid_commit(m, dm, g, d)) != ELM_OK) return rc;
+    m->d_vox_stat = d_stat;
+    m->info.device_bytes += vcells * sizeof(uint32_t);
+    m->info.n_query_voxels = vcells;
+    m->info.index_bytes += vcells * sizeof(uint32_t); // (not in index_part_bytes[0]: the statistics box is read by the instrumented kernels only)
+    return ELM_OK;
+}
+static int build_cell_grid_impl(elm_map* m, uint64_t max_cells) {
+    elm_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = m->dm.n_pts;
+    const double vs = m->dm.voxel_size;
+    if (n == 0 || m->dm.n_vox == 0) return ELM_ERR_UNSUPPORTED;
+    GridBox box;
+    int rc;
+    if ((rc = grid_box(m, box)) != ELM_OK) return rc;
+    const std::vector<float4>& pts = box.pts;
+    const int32_t* lo = box.lo;
+    const int64_t* dim = box.dim;
+    const uint64_t cells = (uint64_t)dim[0] * (uint64_t)dim[1] * (uint64_t)dim[2];
+    if (dim[0] > 0x7FFFFFF0ll || dim[1] > 0x7FFFFFF0ll || dim[2] > 0x7FFFFFF0ll || cells > max_cells || cells > 0xFFFFFFF0ull) {
+        m->grid_refused = true;
+        return ELM_ERR_UNSUPPORTED;
+    }
+    // dense voxel box of floor keys: a query with floor key f walks the stored keys f-1 .. f+1
+    int32_t klo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, khi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    for (uint32_t v = 0; v < m->dm.n_vox; ++v)
+        for (int a = 0; a < 3; ++a) {
+            klo[a] = std::min(klo[a], m->h_keys[3 * v + a]);
+            khi[a] = std::max(khi[a], m->h_keys[3 * v + a]);
+        }
+    const int64_t vd[3] = {(int64_t)khi[0] - klo[0] + 3, (int64_t)khi[1] - klo[1] + 3, (int64_t)khi[2] - klo[2] + 3};
+    const uint64_t vcells = (uint64_t)vd[0] * (uint64_t)vd[1] * (uint64_t)vd[2];
+    if (vcells > max_cells) {
+        m->grid_refused = true;
+        return ELM_ERR_UNSUPPORTED;
+    }
+    // Byte budget (the cell count alone says nothing about a sparse or elongated map just under it): host transients = the
+    // offsets + the sorted copy (blocks of four: at most one block per point) + two index arrays; device = offsets + statistics +
+    // blocks + slot indices (+ the GICP records in slot order).  Not affordable right now -> the lists.
+    {
+        const uint64_t worst_blk = std::min<uint64_t>(n, cells) + n / 4 + 2;
+        const uint64_t host_need = (cells + 4) * 4 + worst_blk * (sizeof(GridBlk) + 16) + n * 8;
+        const uint64_t dev_need = (cells + 4) * 4 + vcells * 4 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
+        size_t dev_free = 0, dev_total = 0;
+        HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
+        const uint64_t host_free = host_available_bytes();
+        if (host_need > host_free / 10 * 7 || dev_need > (uint64_t)dev_free / 10 * 8) {
+            ctx->last_error = "cell grid: tables exceed the memory that is free (host " + std::to_string(host_need >> 20) + " MB, device " +
+                              std::to_string(dev_need >> 20) + " MB needed)";
+            m->grid_refused = true;
+            return ELM_ERR_UNSUPPORTED;
+        }
+    }
+    // the entry of a point is its linear cell
+    GridHost g;
+    {
+        std::vector<uint32_t> lin(n);
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t l = ((uint64_t)(grid_cell_of((double)pts[i].x, vs) - lo[0]) * (uint64_t)dim[1] + (uint64_t)(grid_cell_of((double)pts[i].y, vs) - lo[1])) * (uint64_t)dim[2] +
+                               (uint64_t)(grid_cell_of((double)pts[i].z, vs) - lo[2]);
+            lin[i] = (uint32_t)l;
+        }
+        // stage 1 addresses blocks by 32-bit BYTE offsets (one scalar base + a lane offset) while the array stays below 4 GB (~275 M map
+        // points), by 32-bit offsets in 16-byte units beyond (template flag WIDE: one 64-bit shift-add per block); slot numbers are ints
+        g.n_blk = grid_block_layout((const float*)pts.data(), n, lin, cells, kGridMaxBlocks, g.start, g.gb, g.gi);
+    }
+    if (g.n_blk > kGridMaxBlocks) { m->grid_refused = true; return ELM_ERR_UNSUPPORTED; }
+    std::vector<float4>().swap(box.pts);
+    // device side: into locals, committed to the map only when every step has succeeded
+    rc = dense_grid_to_device(m, box, g, klo, vd, vcells);
+    if (rc != ELM_OK) m->grid_refused = true; // do not retry a multi-GB build at every registration
+    return rc;
+}
+static int build_cell_grid(elm_map* m, uint64_t max_cells) {
+    if (m->has_grid) return ELM_OK;
+    try {
+        return build_cell_grid_impl(m, max_cells);
+    } catch (const std::bad_alloc&) { // a host table did not fit after all: same answer as the byte budget above
+        m->ctx->last_error = "cell grid: host allocation failed";
+        m->grid_refused = true;
+        return ELM_ERR_UNSUPPORTED;
+    }
+}
+
+// The two-level form of the cell grid (DevMap::grid_tiles): for maps whose bounding box is too large or too sparse for one dense
+// offset table (a city-scale map at half-metre cells: billions of cells, a few hundred thousand of them occupied).  The same
+// blocks, sorted (tile, column, z); offsets only inside occupied tiles and only over each tile's own z range.  Host-side build
+// like the dense one; nothing is left allocated on failure.  This builder never sets grid_refused: build_search_index does, when
+// neither form can be built.
+static int build_tiled_grid_impl(elm_map* m) {
+    elm_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = m->dm.n_pts;
+    const double vs = m->dm.voxel_size;
+    if (n == 0 || m->dm.n_vox == 0) return ELM_ERR_UNSUPPORTED;
+    GridBox box;
+    int rc;
+    if ((rc = grid_box(m, box)) != ELM_OK) return rc;
+    const std::vector<float4>& pts = box.pts;
+    const int32_t* lo = box.lo;
+    const int64_t* dim = box.dim;
+    const int64_t tnx = (dim[0] + kTile - 1) / kTile, tny = (dim[1] + kTile - 1) / kTile;
+    // 64 M tiles = 512 MB of tile table (a 32 km x 32 km box at half-metre cells); the z range of a tile is a 16-bit pair
+    if (tnx * tny > ((int64_t)64 << 20) || dim[2] > 65000 || tnx * kTile > 0x7FFFFFF0ll || tny * kTile > 0x7FFFFFF0ll) return ELM_ERR_UNSUPPORTED;
+    const size_t n_tiles = (size_t)(tnx * tny);
+    auto cell3 = [&](size_t i, int32_t& cx, int32_t& cy, int32_t& cz) {
+        cx = grid_cell_of((double)pts[i].x, vs) - lo[0];
+        cy = grid_cell_of((double)pts[i].y, vs) - lo[1];
+        cz = grid_cell_of((double)pts[i].z, vs) - lo[2];
+    };
+    std::vector<uint16_t> zmin(n_tiles, 0xFFFFu), zmax(n_tiles, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        int32_t cx, cy, cz;
+        cell3(i, cx, cy, cz);
+        const size_t t = (size_t)(cx >> kTileShift) * (size_t)tny + (size_t)(cy >> kTileShift);
+        zmin[t] = std::min<uint16_t>(zmin[t], (uint16_t)cz);
+        zmax[t] = std::max<uint16_t>(zmax[t], (uint16_t)cz);
+    }
+    std::vector<uint2> tiles(n_tiles);
+    uint64_t entries = (uint64_t)kTile * kTile; // entries 0 .. 63: the shared zero run of every empty tile (nz = 0: one entry per column)
+    for (size_t t = 0; t < n_tiles; ++t) {
+        if (zmin[t] == 0xFFFFu) { tiles[t] = make_uint2(0u, 0u); continue; }
+        const uint32_t nz = (uint32_t)zmax[t] - zmin[t] + 1;
+        tiles[t] = make_uint2((uint32_t)entries, (uint32_t)zmin[t] | (nz << 16));
+        entries += (uint64_t)kTile * kTile * (nz + 1);
+        if (entries > 0xFFFFFFF0ull) return ELM_ERR_UNSUPPORTED;
+    }
+    auto entry_of = [&](int32_t cx, int32_t cy, int32_t cz) -> uint32_t {
+        const uint2 te = tiles[(size_t)(cx >> kTileShift) * (size_t)tny + (size_t)(cy >> kTileShift)];
+        const uint32_t z0 = te.y & 0xFFFFu, nz = te.y >> 16;
+        return te.x + (uint32_t)(((cx & (kTile - 1)) << kTileShift) | (cy & (kTile - 1))) * (nz + 1) + ((uint32_t)cz - z0);
+    };
+    // byte budget, as for the dense grid (host_need still counts two tables of entries + 4 words, from before the layout was shared with
+    // the dense grid; the build now takes one: the formula over-counts and is left as it is -- a changed refusal changes which index a map gets)
+    {
+        const uint64_t worst_blk = n + 2;
+        const uint64_t host_need = (entries + 4) * 8 + worst_blk * (sizeof(GridBlk) + 16) + n * 8 + n_tiles * 12;
+        const uint64_t dev_need = (entries + 4) * 4 + n_tiles * 8 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
+        size_t dev_free = 0, dev_total = 0;
+        HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
+        const uint64_t host_free = host_available_bytes();
+        if (host_need > host_free / 10 * 7 || dev_need > (uint64_t)dev_free / 10 * 8) {
+            ctx->last_error = "tiled cell grid: tables exceed the memory that is free";
+            return ELM_ERR_UNSUPPORTED;
+        }
+    }
+    // entry order = (tile, column, z); the extra entry of every column (index nz) holds no point: its start = the column's end
+    GridHost g;
+    {
+        std::vector<uint32_t> ent(n);
+        for (size_t i = 0; i < n; ++i) {
+            int32_t cx, cy, cz;
+            cell3(i, cx, cy, cz);
+            ent[i] = entry_of(cx, cy, cz);
+        }
+        g.n_blk = grid_block_layout((const float*)pts.data(), n, ent, entries, kGridMaxBlocks, g.start, g.gb, g.gi);
+    }
+    if (g.n_blk > kGridMaxBlocks) return ELM_ERR_UNSUPPORTED;
+    for (uint64_t e = 0; e < (uint64_t)kTile * kTile; ++e) g.start[e] = 0; // empty tiles: block 0 .. block 0 (nothing)
+    std::vector<float4>().swap(box.pts);
+    GridDev d;
+    DevMap dm = m->dm;
+    if ((rc = grid_upload(ctx, g, d, dm)) != ELM_OK) return rc;
+    uint2* d_tiles = nullptr;
+    HIPCHK_OOM(ctx, hipMalloc((void**)&d_tiles, n_tiles * sizeof(uint2)));
+    d.d_side = d_tiles;
+    HIPCHK_OOM(ctx, hipMemcpy(d_tiles, tiles.data(), n_tiles * sizeof(uint2), hipMemcpyHostToDevice));
+    dm.grid_tiles = d_tiles;
+    dm.grid_tiled = 1;
+    dm.gtny = (int32_t)tny;
+    dm.gx0 = lo[0]; dm.gy0 = lo[1]; dm.gz0 = lo[2];
+    dm.gnx = (int32_t)(tnx * kTile); dm.gny = (int32_t)(tny * kTile); dm.gnz = (int32_t)dim[2];
+    dm.vox_stat = nullptr;
+    if ((rc = grid_commit(m, dm, g, d)) != ELM_OK) return rc;
+    m->d_grid_tiles = d_tiles;
+    m->info.device_bytes += n_tiles * sizeof(uint2);
+    m->info.n_query_voxels = n_tiles;
+    m->info.layout_flags |= 4;
+    m->info.index_bytes += n_tiles * sizeof(uint2);
+    m->info.index_part_bytes[0] += n_tiles * sizeof(uint2);
+    return ELM_OK;
+}
+static int build_tiled_grid(elm_map* m) {
+    if (m->has_grid) return ELM_OK;
+    try {
+        return build_tiled_grid_impl(m);
+    } catch (const std::bad_alloc&) {
+        m->ctx->last_error = "tiled cell grid: host allocation failed";
+        return ELM_ERR_UNSUPPORTED;
+    }
+}
+
+// Neighbourhood lists (see DevMap): query voxels = every floor key within +-1 of a stored (trunc) key.
+static int build_neighbourhood_lists(elm_map* m) {
+    if (!m) return ELM_ERR_INVALID;
+    if (m->has_nbr) return ELM_OK;
+    elm_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    QueryLists ql;
+    int rc;
+    if ((rc = count_query_lists(m, ql, [&](uint32_t q) { return ql.counts[q]; })) != ELM_OK) return rc;
+    const std::vector<uint32_t>&counts = ql.counts, &nocc = ql.nocc, &offs = ql.offs;
+    const uint32_t n_q = ql.n_q;
+    const uint64_t total = ql.total;
+    int32_t* const d_qkeys = ql.d_qkeys;
+    uint32_t *const d_counts = ql.d_counts, *const d_off = ql.d_off;
+    if (total > 0xFFFFFFF0ull) {
+        ctx->last_error = "neighbourhood lists exceed 2^32 entries";
+        return ELM_ERR_UNSUPPORTED;
+    }
+    HIPCHK(ctx, hipMalloc((void**)&m->d_nbr_pts, std::max<size_t>((size_t)total * sizeof(Pt3), 256) + 64)); // + pad: blocks of 4 are read whole
+    HIPCHK(ctx, hipMalloc((void**)&m->d_nbr_idx, std::max<size_t>((size_t)total * sizeof(uint32_t), 256)));
+    if (n_q) {
+        (void)hipGetLastError();
+        launch_nbr_fill(ctx->stream, m->dm, d_qkeys, n_q, d_off, m->d_nbr_pts, m->d_nbr_idx);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // sort every list by half-voxel cell and write the per-list offset tables (cell-indexed kernel)
+    uint32_t max_count = 0;
+    for (uint32_t q = 0; q < n_q; ++q) max_count = std::max(max_count, counts[q]);
+    const size_t cell_bytes = std::max<size_t>((size_t)n_q * nbr_cell_stride() * sizeof(uint16_t), 256);
+    HIPCHK(ctx, hipMalloc((void**)&m->d_nbr_cell_off, cell_bytes));
+    HIPCHK(ctx, hipMemsetAsync(m->d_nbr_cell_off, 0, cell_bytes, ctx->stream));
+    m->has_cells = max_count <= 1024;
+    if (n_q && m->has_cells) {
+        (void)hipGetLastError();
+        launch_nbr_cellsort(ctx->stream, m->dm, d_qkeys, n_q, d_off, d_counts, m->d_nbr_pts, m->d_nbr_idx, m->d_nbr_cell_off);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t qcap = next_pow2((uint64_t)n_q * 2);
+    if ((rc = upload_query_slots(ctx, ql, qcap, &m->d_qslots, [&](uint32_t q, HashSlot& s) { s.start = offs[q]; s.cnt = counts[q]; s.pad0 = nocc[q]; })) != ELM_OK) return rc;
+    m->dm.qslots = m->d_qslots;
+    m->dm.qmask = qcap - 1;
+    m->dm.n_q = n_q;
+    m->dm.nbr_pts = m->d_nbr_pts;
+    m->dm.nbr_idx = m->d_nbr_idx;
+    m->dm.nbr_cell_off = m->d_nbr_cell_off;
+    m->has_nbr = true;
+    m->info.device_bytes += (size_t)total * (sizeof(Pt3) + sizeof(uint32_t)) + (size_t)qcap * sizeof(HashSlot) + cell_bytes;
+    m->info.n_query_voxels = n_q;
+    m->info.nbr_entries = total;
+    m->info.index_bytes += (size_t)total * sizeof(Pt3) + (size_t)qcap * sizeof(HashSlot) + cell_bytes;
+    m->info.index_part_bytes[3] += (size_t)total * sizeof(Pt3) + (size_t)qcap * sizeof(HashSlot) + cell_bytes;
+    return ELM_OK;
+}
+
+// The P2P / GICP search index of a map: the dense cell grid when its bounding box fits the cell and byte budgets, the two-level
+// (tiled) grid when it does not -- large or sparse maps keep the grid kernel -- and the per-query-voxel neighbourhood lists only
+// when neither can be built (or with ELM_KERNEL=lists; ELM_GRID=tiled forces the two-level form, ELM_GRID=dense forbids it).
+int elm_host::build_search_index(elm_map* m, bool* use_grid) {
+    *use_grid = false;
+    elm_ctx* ctx = m->ctx;
+    if (ctx->kernel_mode == 4 && !m->grid_refused && m->dm.n_pts) {
+        const bool force_tiled = env_token("ELM_GRID", "tiled"), no_tiled = env_token("ELM_GRID", "dense");
+        int rc = force_tiled ? ELM_ERR_UNSUPPORTED : build_cell_grid(m, grid_max_cells());
+        if (rc == ELM_ERR_UNSUPPORTED && !no_tiled) {
+            rc = build_tiled_grid(m);
+            if (rc == ELM_ERR_UNSUPPORTED) m->grid_refused = true; // neither form: do not retry at every registration
+            else if (rc == ELM_OK) m->grid_refused = false;
+        }
+        if (rc == ELM_OK) {
+            *use_grid = true;
+            return ELM_OK;
+        }
+        if (rc != ELM_ERR_UNSUPPORTED) return rc;
+    }
+    return build_neighbourhood_lists(m);
+}
+extern "C" int elm_map_build_neighbourhoods(elm_map* m) {
+    if (!m) return ELM_ERR_INVALID;
+    if (!m->replicas.empty() && group_call(m->ctx)) return elm_multi::map_call(m, 2, 0.0);
+    bool g;
+    return build_search_index(m, &g);
+}

@@ -1,4 +1,5 @@
-// elm_internal.hpp -- device-side data layout shared by the kernels (elm_k_*.hip) and the C ABI (elm_api.cpp).
+// elm_internal.hpp -- device-side data layout shared by the kernels (elm_k_*.hip) and the host units behind the C ABI
+// (elm_ctx.cpp, elm_map.cpp, elm_index.cpp, elm_scan.cpp, elm_api.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

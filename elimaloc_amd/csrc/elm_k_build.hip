@@ -1,6 +1,6 @@
 // elm_k_build.hip -- the device map build (include/elimaloc_hip.h, "device map build"): AddPoints
 // (vhm.cpp:270-285) with VoxelBlock::AddPointWithSpacing (vhm.hpp:106-113) replayed on the device, byte for byte what build_host
-// (elm_api.cpp) makes of the same input.  The input is one array of packed points: the kept stored points of a base map in bucket
+// (elm_map.cpp) makes of the same input.  The input is one array of packed points: the kept stored points of a base map in bucket
 // order (k_bd_keep / k_bd_compact), then the uploaded points.
 //   k_bd_insert     truncated key per point -> scratch open-addressing table (64-bit CAS), atomicMin of the point's index per slot
 //   k_bd_opens      1 for the point that opens its voxel (the smallest index of the slot); its exclusive scan over the input order is

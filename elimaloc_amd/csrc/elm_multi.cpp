@@ -26,7 +26,7 @@
 #include <thread>
 #include <vector>
 
-#include "elm_hostapi.hpp"
+#include "elm_host_types.hpp"
 
 namespace {
 thread_local bool t_in_worker = false;
@@ -175,9 +175,9 @@ int run_all(elm_group* g, const std::function<int(int)>& fn) {
     return ELM_OK;
 }
 
-elm_group* group_of(elm_ctx* lead) { return lead ? elm_host::ctx_group(lead) : nullptr; }
+elm_group* group_of(elm_ctx* lead) { return lead ? lead->group : nullptr; }
 
-// the Hilbert curve over the 64 x 64 ordering cells (2 m, sensor frame) of the device's ordering kernel (elm_api.cpp: hilbert_xy2d)
+// the Hilbert curve over the 64 x 64 ordering cells (2 m, sensor frame) of the device's ordering kernel (elm_scan.cpp: hilbert_xy2d)
 uint32_t hilbert_xy2d(uint32_t order, uint32_t x, uint32_t y) {
     uint32_t d = 0;
     for (uint32_t s = 1u << (order - 1); s > 0; s >>= 1) {
@@ -235,7 +235,7 @@ void destroy(elm_group* g) {
         }
         for (std::thread& t : g->workers) t.join();
     }
-    if (lead) elm_host::ctx_group(lead) = nullptr;
+    if (lead) lead->group = nullptr;
     for (size_t r = 1; r < g->ctx.size(); ++r) elm_ctx_destroy(g->ctx[r]);
     for (double* p : g->hx.out) if (p) (void)hipHostFree(p);
     for (double* p : g->hx.sum) if (p) (void)hipHostFree(p);
@@ -258,16 +258,16 @@ int map_build(elm_ctx* lead, const float* xyz, size_t n, double voxel_size, int 
         for (elm_map* m : maps) if (m) elm_map_destroy(m);
         return rc;
     }
-    elm_host::map_replicas(maps[0]).assign(maps.begin() + 1, maps.end());
+    maps[0]->replicas.assign(maps.begin() + 1, maps.end());
     *out = maps[0];
     return ELM_OK;
 }
 
-static const elm_map* rank_map(const elm_map* lead_map, int r) { return r == 0 ? lead_map : elm_host::map_replicas(const_cast<elm_map*>(lead_map))[(size_t)r - 1]; }
+static const elm_map* rank_map(const elm_map* lead_map, int r) { return r == 0 ? lead_map : lead_map->replicas[(size_t)r - 1]; }
 
 int map_call(elm_map* lead_map, int which, double arg) {
-    elm_group* g = group_of(elm_host::map_ctx(lead_map));
-    if ((int)elm_host::map_replicas(lead_map).size() != g->n - 1) return ELM_ERR_INVALID;
+    elm_group* g = group_of(lead_map->ctx);
+    if ((int)lead_map->replicas.size() != g->n - 1) return ELM_ERR_INVALID;
     std::lock_guard<std::mutex> call(g->call_mu);
     return run_all(g, [&](int r) {
         elm_map* m = const_cast<elm_map*>(rank_map(lead_map, r));
@@ -291,7 +291,7 @@ int scan_upload(elm_ctx* lead, const float* xyz, size_t n, elm_scan** out) {
         for (elm_scan* s : sh) if (s) elm_scan_destroy(s);
         return rc;
     }
-    elm_host::scan_shards(sh[0]).assign(sh.begin() + 1, sh.end());
+    sh[0]->shards.assign(sh.begin() + 1, sh.end());
     *out = sh[0];
     return ELM_OK;
 }
@@ -315,7 +315,7 @@ int reg(elm_ctx* lead, const elm_map* map, const float* scan_xyz, size_t n, cons
         int* is_success, double* fitness_score, double local_cov[36], elm_reg_result* result, elm_iter_trace* trace) {
     elm_group* g = group_of(lead);
     if (!map || !T0 || !cfg || (!scan_xyz && n)) return ELM_ERR_INVALID;
-    if (elm_host::map_ctx(map) != lead || (int)elm_host::map_replicas(const_cast<elm_map*>(map)).size() != g->n - 1) return ELM_ERR_INVALID;
+    if (map->ctx != lead || (int)map->replicas.size() != g->n - 1) return ELM_ERR_INVALID;
     std::lock_guard<std::mutex> call(g->call_mu);
     // RunRegister's per-call contract: the caller's point order, cut into contiguous shards (a LiDAR driver's order is azimuthal: the
     // shards are sectors; elm_scan_upload orders a resident scan spatially first)
@@ -343,9 +343,9 @@ int reg_batch(elm_ctx* lead, const elm_map* map, elm_scan* const* scans, int cou
               elm_reg_result* results, elm_iter_trace* trace) {
     elm_group* g = group_of(lead);
     if (!map || !scans || count <= 0 || !T0 || !cfg || !results || slots < 0) return ELM_ERR_INVALID;
-    if (elm_host::map_ctx(map) != lead || (int)elm_host::map_replicas(const_cast<elm_map*>(map)).size() != g->n - 1) return ELM_ERR_INVALID;
+    if (map->ctx != lead || (int)map->replicas.size() != g->n - 1) return ELM_ERR_INVALID;
     for (int b = 0; b < count; ++b)
-        if (!scans[b] || elm_host::scan_ctx(scans[b]) != lead || (int)elm_host::scan_shards(scans[b]).size() != g->n - 1) {
+        if (!scans[b] || scans[b]->ctx != lead || (int)scans[b]->shards.size() != g->n - 1) {
             elm_host::ctx_set_error(lead, "device group: a scan was not uploaded through the group's lead context (elm_scan_upload)");
             return ELM_ERR_INVALID;
         }
@@ -353,7 +353,7 @@ int reg_batch(elm_ctx* lead, const elm_map* map, elm_scan* const* scans, int cou
     std::vector<std::vector<elm_reg_result>> res(g->n);
     const int rc = run_all(g, [&](int r) {
         std::vector<elm_scan*> mine((size_t)count);
-        for (int b = 0; b < count; ++b) mine[(size_t)b] = r == 0 ? scans[b] : elm_host::scan_shards(scans[b])[(size_t)r - 1];
+        for (int b = 0; b < count; ++b) mine[(size_t)b] = r == 0 ? scans[b] : scans[b]->shards[(size_t)r - 1];
         elm_reg_result* out = results;
         if (r != 0) { res[(size_t)r].resize((size_t)count); out = res[(size_t)r].data(); }
         return slots > 0 ? elm_register_stream(g->ctx[r], rank_map(map, r), mine.data(), count, T0, cfg, slots, out, r == 0 ? trace : nullptr)
@@ -427,17 +427,17 @@ extern "C" int elm_ctx_create_multi(const int* device_ids, int n, elm_ctx** out)
         elm_ctx_destroy(lead);
         return rc;
     }
-    elm_host::ctx_group(lead) = g;
+    lead->group = g;
     *out = lead;
     return ELM_OK;
 }
 
 extern "C" int elm_ctx_group_info(elm_ctx* ctx, int* n_ranks, int* exchange, int* device_ids, int cap) {
     if (!ctx || !n_ranks) return ELM_ERR_INVALID;
-    elm_group* g = elm_host::ctx_group(ctx);
+    elm_group* g = ctx->group;
     *n_ranks = g ? g->n : 1;
     if (exchange) *exchange = g ? g->exchange : 0;
     if (device_ids)
-        for (int r = 0; r < std::min(cap, g ? g->n : 1); ++r) device_ids[r] = g ? g->devices[(size_t)r] : elm_host::ctx_device(ctx);
+        for (int r = 0; r < std::min(cap, g ? g->n : 1); ++r) device_ids[r] = g ? g->devices[(size_t)r] : ctx->device;
     return ELM_OK;
 }

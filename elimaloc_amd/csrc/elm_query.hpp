@@ -11,8 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "elm_hostapi.hpp"
-#include "elm_internal.hpp"
+#include "elm_host_types.hpp"
 
 namespace elm_query {
 
@@ -32,7 +31,7 @@ inline void pose_rows12(const double* T16, double* out12) {
 
 // one rank, no exchange: a device group's lead or a context with a communicator / hook attached is refused
 inline int check_plain(elm_ctx* ctx, const char* what) {
-    if ((elm_host::ctx_group(ctx) && !elm_multi::in_worker()) || elm_host::ctx_exchange_attached(ctx)) {
+    if ((ctx->group && !elm_multi::in_worker()) || ctx->comm || ctx->hook) {
         elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
         return ELM_ERR_UNSUPPORTED;
     }
@@ -62,7 +61,7 @@ inline int check_pose_query(elm_ctx* ctx, const elm_map* map, const elm_scan* sc
     if (!ctx || !map || !scan || n_poses < 0 || !config_ok || (n_poses > 0 && (!poses16 || !stats))) return ELM_ERR_INVALID;
     int rc = check_plain(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::scan_ctx(scan) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (map->ctx != ctx || scan->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
     return poses_finite(poses16, (size_t)n_poses) ? ELM_OK : ELM_ERR_INVALID;
 }
 
@@ -73,10 +72,11 @@ struct PoseQuery {
 };
 // the device made current, the map's fine table for sub and the scan's points
 inline int open_pose_query(elm_ctx* ctx, const elm_map* map, int sub, const elm_scan* scan, PoseQuery& q) {
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     int rc = elm_host::map_fine_table(map, sub, &q.ft, nullptr);
     if (rc != ELM_OK) return rc;
-    q.d_pts = elm_host::scan_dev_points(scan, &q.n);
+    q.d_pts = (const float*)scan->d_pts;
+    q.n = scan->n;
     return ELM_OK;
 }
 // The call itself: the pose rows go up (scratch 1), launch(stream, d_rows, d_part, d_stats, d_arr) queues the kernels on the partials
@@ -120,7 +120,7 @@ int check_object(elm_ctx* ctx, const Obj* o, const char* what) {
     if (!ctx || !o) return ELM_ERR_INVALID;
     int rc = check_plain(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (o->ctx != ctx || o->ctx_id != elm_host::ctx_unique_id(ctx) || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (o->ctx != ctx || o->ctx_id != ctx->id || ctx->in_flight) return ELM_ERR_INVALID;
     return ELM_OK;
 }
 
@@ -153,7 +153,7 @@ int check_accumulate(elm_ctx* ctx, const Obj* o, const elm_scan* const* scans, c
     if (rc != ELM_OK) return rc;
     if (c->sub != o->sub) return ELM_ERR_INVALID;
     for (int j = 0; j < n_jobs; ++j)
-        if (!scans[j] || elm_host::scan_ctx(scans[j]) != ctx) return ELM_ERR_INVALID;
+        if (!scans[j] || scans[j]->ctx != ctx) return ELM_ERR_INVALID;
     return poses_finite(poses16, (size_t)n_jobs) ? ELM_OK : ELM_ERR_INVALID;
 }
 
@@ -165,9 +165,9 @@ inline JobTable build_jobs(const elm_scan* const* scans, const double* poses16, 
     JobTable t;
     t.jobs.resize(n_jobs);
     for (uint32_t j = 0; j < n_jobs; ++j) {
-        size_t n = 0;
-        t.jobs[j].pts = elm_host::scan_dev_points(scans[j], &n);
-        t.jobs[j].n = (uint32_t)n;
+        const size_t n = scans[j]->n;
+        t.jobs[j].pts = (const float*)scans[j]->d_pts;
+        t.jobs[j].n = scans[j]->n;
         t.jobs[j].chunk0 = (uint32_t)t.chunks;
         pose_rows12(poses16 + 16 * (size_t)j, t.jobs[j].rows);
         t.beams += n;

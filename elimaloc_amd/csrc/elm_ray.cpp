@@ -1,5 +1,5 @@
 // elm_ray.cpp -- ray casting (include/elimaloc_hip.h, "ray casting"): the argument checks, the pose rows, the launches
-// of elm_k_ray.hip on the map's fine occupancy table (built and cached by elm_api.cpp) and the download, through the call of one scan at
+// of elm_k_ray.hip on the map's fine occupancy table (built and cached by elm_map.cpp) and the download, through the call of one scan at
 // many poses that elm_query.hpp shares with the free-space check.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -122,7 +122,7 @@ inline double key_of(double q, const DevMap& m) { return trunc(m.inv_vs_exact !=
 // form of the lookup (LDS bitmap / global bitmap / hash probes, from the two byte budgets), the launches, the download.
 int score_impl(elm_ctx* ctx, const elm_map* map, const std::vector<float>& S, const double* poses16, uint32_t n_poses, const elm_reloc_config* c,
                uint32_t* scores) {
-    const DevMap& m = elm_host::map_dev(map);
+    const DevMap& m = map->dm;
     const uint32_t nS = (uint32_t)(S.size() / 3);
     if (m.n_vox == 0 || nS == 0) {
         memset(scores, 0, (size_t)n_poses * sizeof(uint32_t));
@@ -279,8 +279,8 @@ int relocalize_impl(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, siz
         return ELM_ERR_INVALID;
     int rc = check_plain(ctx, "elm_relocalize");
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (map->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     // 1. hypotheses and the score subsample (every ceil(n / cap)-th point of the caller's order, the counted ones)
     const size_t n_hyp = (size_t)g.K * g.W * g.W;
     std::vector<double> poses(n_hyp * 16);
@@ -329,11 +329,11 @@ extern "C" int elm_map_score_poses(elm_ctx* ctx, const elm_map* map, const elm_s
     if (!ctx || !map || !scan || !poses16 || n_poses <= 0 || !score_config_ok(c) || !scores) return ELM_ERR_INVALID;
     int rc = check_plain(ctx, "elm_map_score_poses");
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::scan_ctx(scan) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
+    if (map->ctx != ctx || scan->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
     for (int h = 0; h < n_poses; ++h)
         if (!finite16(poses16 + 16 * (size_t)h)) return ELM_ERR_INVALID;
     try {
-        if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
         std::vector<float> xyz(3 * elm_scan_size(scan)), S;
         if ((rc = elm_scan_download(scan, xyz.data(), xyz.size() / 3)) != ELM_OK) return rc;
         counted_points(xyz.data(), xyz.size() / 3, 1, c->score_max_range_m, S);
@@ -468,7 +468,7 @@ int lattice_field(elm_ctx* ctx, const elm_map* map, const double* T_tilt, const 
         const GroundIndex* gi = nullptr;
         int rc = elm_host::map_ground_index(map, &gi, rect);
         if (rc != ELM_OK) return rc;
-        if (elm_host::map_dev(map).n_pts == 0) rect[0] = rect[1] = rect[2] = rect[3] = 0.0;
+        if (map->dm.n_pts == 0) rect[0] = rect[1] = rect[2] = rect[3] = 0.0;
     }
     if (!lattice_of(c, rect, T_tilt, L)) return ELM_ERR_INVALID;
     const size_t nxy = (size_t)L->NX * L->NY;
@@ -480,7 +480,7 @@ int lattice_field(elm_ctx* ctx, const elm_map* map, const double* T_tilt, const 
         }
     gz.assign(nxy, 0.0);
     valid.assign(nxy, 0);
-    if (elm_host::map_dev(map).n_pts == 0) {
+    if (map->dm.n_pts == 0) {
         for (double& v : gz) v = L->h;
         return ELM_OK;
     }
@@ -722,7 +722,7 @@ int search_setup(Search& S, const std::vector<float>& pts, const elm_reloc_globa
     for (int l = 1; l <= top; ++l) S.w[l] = (uint32_t)(floor((double)((1L << l) - 1) * L.step / S.m->voxel_size) + 2.0);
     if (S.nS == 0) return ELM_OK;
     // the map's key box, z padded to whole 64-bit words per column
-    const std::vector<int32_t>& keys = elm_host::map_host_keys(S.map);
+    const std::vector<int32_t>& keys = S.map->h_keys;
     int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
     for (size_t v = 0; v < keys.size() / 3; ++v)
         for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], keys[3 * v + a]); hi[a] = std::max(hi[a], keys[3 * v + a]); }
@@ -769,8 +769,8 @@ double ms_since(const std::chrono::steady_clock::time_point& t) {
 int common_checks(elm_ctx* ctx, const elm_map* map, const char* what) {
     int rc = check_plain(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (elm_host::map_ctx(map) != ctx || elm_host::ctx_in_flight(ctx)) return ELM_ERR_INVALID;
-    if (hipSetDevice(elm_host::ctx_device(ctx)) != hipSuccess) return ELM_ERR_DEVICE;
+    if (map->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     return ELM_OK;
 }
 
@@ -818,7 +818,7 @@ int relocalize_global_impl(elm_ctx* ctx, const elm_map* map, const float* scan_x
     }
     st.n_counted = (int32_t)(pts.size() / 3);
     // 3. branch-and-bound passes: all leaves >= tau, NMS over them; fewer than top_k kept (and tau > 0): a lower tau
-    Search S{ctx, map, &elm_host::map_dev(map), (hipStream_t)elm_ctx_stream(ctx), &L, &gz, &valid};
+    Search S{ctx, map, &map->dm, (hipStream_t)elm_ctx_stream(ctx), &L, &gz, &valid};
     S.stats = &st;
     if ((rc = search_setup(S, pts, c)) != ELM_OK) return rc;
     st.levels = S.top;

@@ -86,7 +86,7 @@ def _hilbert_lut():
         ys, xs = np.meshgrid(np.arange(64), np.arange(64), indexing="ij")
         x, y, d = xs.copy(), ys.copy(), np.zeros((64, 64), np.int64)
         s = 32
-        while s > 0:  # the textbook xy2d, vectorised over the 64 x 64 cells (elm_api.cpp: hilbert_xy2d)
+        while s > 0:  # the textbook xy2d, vectorised over the 64 x 64 cells (elm_scan.cpp: hilbert_xy2d)
             rx = (x & s) != 0
             ry = (y & s) != 0
             d += s * s * ((3 * rx.astype(np.int64)) ^ ry.astype(np.int64))

@@ -23,7 +23,7 @@ int callback_register(elm_ctx*, const elm_map*, const void*, const float*, unsig
 extern "C" int elm_deskew() { return die("elm_deskew"); }
 extern "C" int elm_deskew_prepare() { return die("elm_deskew_prepare"); }
 extern "C" int elm_register() { return die("elm_register"); }
-extern "C" const char* elm_strerror(int status) { // (the real one lives in elm_api.cpp)
+extern "C" const char* elm_strerror(int status) { // (the real one lives in elm_ctx.cpp)
     static char buf[32];
     snprintf(buf, sizeof buf, "status %d", status);
     return buf;
