@@ -133,12 +133,21 @@ constexpr int kGridWaves = 8; // minimum waves per SIMD of the P2P kernel = a 64
                          // VGPRs, 26 spilled SGPRs at the cap): 6 -> 89.0 k, 7 -> 94.0-94.3 k, 8 -> 95.8-96.4 k registrations/s (hard guesses 20.5 -> 20.8 k);
                          // round 2, with the counters: 5 -> 59.8k, 6 -> 63.9k, 7 -> 65.6k, 8 (35 spills) -> 54.2k.  profiles/r04_sweep.txt
 constexpr int kGicpWaves = 7; // GICP: 5 (the old cap; the kernel used 72 VGPRs anyway) -> 71.2-71.6 k, 7 (one spill) -> 72.5-73.3 k, 8 (8 spills) -> 67.2 k
+// 2 / voxel_size, the cell coordinate of a length.  A power-of-two voxel size has its exact reciprocal in the map (twice it is the
+// quotient bit for bit): the float64 division -- ~15 quarter-rate instructions of the one wavefront the workgroup waits for -- then
+// stays behind a scalar branch
+__device__ __forceinline__ double cells_per_metre(const DevMap& m) { return (m.inv_vs_exact != 0.0) ? 2.0 * m.inv_vs_exact : 2.0 / m.voxel_size; }
+
 // The exact search of ONE undecided point by its group of LPI lanes (stage 2 of k_accumulate_grid): the ball of radius sqrt(R.r2) around g (seeded first when stage 1 found nothing) intersected with the reference's allowed cell
 // range and the grid, float32 keys first, the reference's float64 distances and visiting order on a near tie.  win: block * 4 + slot of the
 // nearest neighbour (-1: none), the same value in every lane of the group; walked: candidate slots this lane tested (instrumented builds).
+// rec: the point's queue record in LDS (R is a copy of it).  The walk is called from a loop over the queue's passes and runs at the kernel's
+// register cap, so what the compiler would hoist out of that loop or hold across the float32 walk for the rare float64 one -- the point's
+// three doubles, a constant pair, the first column as a float -- is pinned or read again where it is used: the P2P instantiations then
+// need no scratch (two spill stores and two reloads per wavefront of EVERY workgroup before).
 template <int TILED, unsigned LPI>
-__device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* __restrict__ lp, const GridHardRec& R, const bool live, const unsigned rl,
-                                               const unsigned lane, int& win_out, int& walked_out) {
+__device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* __restrict__ lp, const GridHardRec& R, const GridHardRec* rec, const bool live,
+                                               const unsigned rl, const unsigned lane, int& win_out, int& walked_out) {
     const GridAxis ax = grid_axis(R.gx, m), ay = grid_axis(R.gy, m), az = grid_axis(R.gz, m);
     int lox = ax.alo, hix = ax.ahi, loy = ay.alo, hiy = ay.ahi, loz = az.alo, hiz = az.ahi;
     int seeded = 0;
@@ -150,7 +159,7 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
     if (__any(live && !(r2s < __builtin_inff()))) { // wave-uniform
         float best = __builtin_inff();
         if (live && !(r2s < __builtin_inff())) {
-            const double inv_h = 2.0 / m.voxel_size;
+            const double inv_h = cells_per_metre(m);
             const int cx0 = (int)floor(R.gx * inv_h - 0.5), cy0 = (int)floor(R.gy * inv_h - 0.5);
             const float shx = (float)R.gx, shy = (float)R.gy, shz = (float)R.gz;
             const f32x2 sxy = {shx, shy}, szl = {shz, (float)(R.gx - (double)shx)}, sl2 = {(float)(R.gy - (double)shy), (float)(R.gz - (double)shz)};
@@ -179,7 +188,7 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
         // per-axis cell range of [g - r, g + r] (1e-6 of margin: a stored coordinate exactly on a cell face counts to the
         // cell further from zero, grid_cell_of)
         const double r = (double)(__builtin_sqrtf(r2s) * 1.000001f) + 1e-6; // float32 root (1 ulp) inside the margin
-        const double inv_h = 2.0 / m.voxel_size;
+        const double inv_h = cells_per_metre(m);
         lox = max(lox, (int)floor((R.gx - r) * inv_h)); hix = min(hix, (int)floor((R.gx + r) * inv_h));
         loy = max(loy, (int)floor((R.gy - r) * inv_h)); hiy = min(hiy, (int)floor((R.gy + r) * inv_h));
         loz = max(loz, (int)floor((R.gz - r) * inv_h)); hiz = min(hiz, (int)floor((R.gz + r) * inv_h));
@@ -215,6 +224,7 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
             r0 = (int)e[0]; r1 = (int)e[nzc];
         };
         int c = (int)rl, nb0 = 0, nb1 = 0;
+        asm volatile("" : "+v"(c)); // (pinned: (float)c + 0.5f of the first column stays out of the caller's loop preheader)
         if (c < ncol) col_run(c, nb0, nb1);
         while (c < ncol) {
             const int b0 = nb0, b1 = nb1;
@@ -254,6 +264,9 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
         // The bucket of a cell: c >= 2 -> c >> 1, -2 <= c <= 1 -> 0, c <= -3 -> (c + 2) >> 1.
         const int ncol64 = need64 ? ncol : 0;
         double bd = DBL_MAX;
+        asm volatile("" : "+v"(bd)); // (pinned: materialised here, not held in two registers from before the caller's loop)
+        asm volatile("" : "+v"(rec));
+        const double qgx = rec->gx, qgy = rec->gy, qgz = rec->gz; // the point again from its record: six registers free across the float32 walk
 #pragma unroll 1
         for (int c = (int)rl; c < ncol64; c += (int)LPI) {
             const int cx = lox + c / ny, cy = loy + c % ny;
@@ -262,7 +275,7 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
 #pragma unroll 1
             for (int k = 4 * (int)e[0]; k < 4 * (int)e[nzc]; ++k) {
                 const Pt3 q = blk_point(lp, k);
-                const double ex = (double)q.x - R.gx, ey = (double)q.y - R.gy, ez = (double)q.z - R.gz;
+                const double ex = (double)q.x - qgx, ey = (double)q.y - qgy, ez = (double)q.z - qgz;
                 bd = fmin((ex * ex + ey * ey) + ez * ez, bd);
             }
         }
@@ -284,7 +297,7 @@ __device__ __forceinline__ void grid_ball_walk(const DevMap& m, const GridBlk* _
 #pragma unroll 1
                 for (int k = 4 * (int)e[z]; k < 4 * (int)e[z + 1]; ++k) {
                     const Pt3 q = blk_point(lp, k);
-                    const double ex = (double)q.x - R.gx, ey = (double)q.y - R.gy, ez = (double)q.z - R.gz;
+                    const double ex = (double)q.x - qgx, ey = (double)q.y - qgy, ez = (double)q.z - qgz;
                     if ((ex * ex + ey * ey) + ez * ez != dmin) continue;
                     const unsigned gi = m.grid_idx[k];
                     if (rank < brank || (rank == brank && gi < bgi)) { brank = rank; bgi = gi; bk = k; }

@@ -423,7 +423,8 @@ __device__ __forceinline__ int row_sum_int(int v) {
 constexpr int kRedPass = 8;    // values per pass of the block reduction (16 KB of LDS per workgroup)
 
 constexpr int kBlocksPerTrip = 2;
-constexpr int kHardLanes = 4; // measured: 16 -> 56.9k, 8 -> 55.6k, 4 -> 63.0k, 2 -> 60.3k, 1 -> 55.2k registrations/s
+constexpr int kHardLanes = 4; // measured: 16 -> 56.9k, 8 -> 55.6k, 4 -> 63.0k, 2 -> 60.3k, 1 -> 55.2k registrations/s; a run-time width sized to the
+                              // queue (16 lanes up to 4 points, 8 up to 8, else 4): -0.3 .. -0.5 % against 4 throughout (profiles/stage2_ab.txt)
 constexpr int kCellWaves = 5; // minimum waves per SIMD: caps the kernel at 96 VGPRs (measured: 5 -> 42.0k, unconstrained 4 -> 39.4k, 6 spills -> 36.5k registrations/s)
 
 // an undecided point handed to the workgroup-cooperative exact stage of k_accumulate_cell

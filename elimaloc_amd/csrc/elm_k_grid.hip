@@ -15,6 +15,11 @@ namespace elm {
 // STATS = 0: no statistics load, 18 (P2P) / 29 reduced values, no per-point bookkeeping in stage 2.
 // WIDE = 1: the block array does not fit 32-bit byte offsets (4 GB = ~275 M map points): stage 1 carries offsets in 16-byte units
 // (three per block) and forms the 64-bit address per block with one shift-add; everything else addresses blocks by index already.
+// how many set bits of a wavefront mask lie below this lane (v_mbcnt: no lane mask in vector registers)
+__device__ __forceinline__ unsigned rank_below(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
 template <int METHOD, int COMPACT, int TILED, int STATS, int WIDE>
 __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWaves) : kGicpWaves)) void k_accumulate_grid( // (the instrumented P2P build holds 20.7 KB of LDS: 7 workgroups per CU)
        const DevMap m, const ScanDesc* __restrict__ scans, int batch,
@@ -238,46 +243,51 @@ __global__ __launch_bounds__(kBlock, (METHOD == ELM_P2P ? (STATS ? 7 : kGridWave
         }
     }
     // ---- stage 2: queue the undecided points in thread order, kHardLanes lanes per point
+    // Every wavefront queues its undecided points in its OWN 64-record segment of the queue (nothing of s_buf's lower half is in use
+    // yet, and the slot needs no count of another wavefront), so ONE barrier publishes the records and the four counts together.
     const unsigned long long hm = __ballot(hard);
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    GridHardRec* __restrict__ s_rec = reinterpret_cast<GridHardRec*>(s_buf);
+    static_assert(kBlock == 256 && sizeof(GridHardRec) * kBlock <= sizeof(double) * (kRedPass / 2) * kBlock, "four segments in the lower half of s_buf");
     if (lane == 0) s_cnt[wave] = (unsigned)__popcll(hm);
-    __syncthreads();
-    unsigned n_hard = 0, my_slot = 0;
-#pragma unroll
-    for (unsigned w = 0; w < kBlock / 64; ++w) {
-        my_slot += (w < wave) ? s_cnt[w] : 0u;
-        n_hard += s_cnt[w];
+    if (hard) {
+        GridHardRec r;
+        float pxf_, pyf_;
+        load_g(r.gx, r.gy, r.gz, pxf_, pyf_);
+        r.r2 = hr2; r.win = -1;
+        s_rec[64u * wave + rank_below(hm)] = r;
     }
-    my_slot += (unsigned)__popcll(hm & ((1ull << lane) - 1ull));
+    __syncthreads();
+    const unsigned c0 = s_cnt[0], c1 = c0 + s_cnt[1], c2 = c1 + s_cnt[2], n_hard = c2 + s_cnt[3]; // (uniform) where the segments end in queue order
     if (n_hard) { // uniform
-        GridHardRec* __restrict__ s_rec = reinterpret_cast<GridHardRec*>(s_buf);
-        if (hard) {
-            GridHardRec r;
-            float pxf_, pyf_;
-            load_g(r.gx, r.gy, r.gz, pxf_, pyf_);
-            r.r2 = hr2; r.win = -1;
-            s_rec[my_slot] = r;
-        }
-        __syncthreads();
         constexpr unsigned LPI = kHardLanes; // lanes per undecided point (a power of two <= 16: one DPP row holds 16 / LPI points)
         const unsigned rl = threadIdx.x & (LPI - 1u), row = threadIdx.x / LPI;
-        for (unsigned it0 = 0; it0 < n_hard; it0 += kBlock / LPI) {
+        // A scalar guard AROUND the loop, not a break inside it: what the compiler hoists out of the loop is then computed by the
+        // wavefronts that serve a point (in most workgroups the first alone), not by those that only wait for them
+        const unsigned wrow = ((unsigned)__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63u) / LPI; // the first queue position this wavefront serves
+        if (wrow < n_hard) for (unsigned it0 = 0; it0 + wrow < n_hard; it0 += kBlock / LPI) { // this wavefront has a point in this pass
             const unsigned it = it0 + row;
-            if (it0 + (threadIdx.x & ~63u) / LPI >= n_hard) break; // wave-uniform: this wavefront has no point in this pass
             const bool live = it < n_hard;
-            const GridHardRec R = s_rec[live ? it : 0];
+            const unsigned q = live ? it : 0u;
+            // queue position -> record: past the end of a segment's records, on to the next segment
+            const unsigned ri = q + ((q >= c0) ? 64u - c0 : 0u) + ((q >= c1) ? 64u - (c1 - c0) : 0u) + ((q >= c2) ? 64u - (c2 - c1) : 0u);
+            const GridHardRec R = s_rec[ri];
             int win, walked;
-            grid_ball_walk<TILED, LPI>(m, lp, R, live, rl, lane, win, walked);
+            grid_ball_walk<TILED, LPI>(m, lp, R, &s_rec[ri], live, rl, lane, win, walked);
             if (kStats) walked = group_sum_int<LPI>(walked);
             if (rl == 0 && live) {
-                s_rec[it].win = win; // into the record's spare word: no group but this one reads the record
-                if (kStats) s_tst[it] = walked;
+                s_rec[ri].win = win; // into the record's spare word: no group but this one reads the record
+                if (kStats) s_tst[ri] = walked;
             }
         }
         __syncthreads();
         if (hard) {
-            bj = s_rec[my_slot].win;
-            if (kStats) n_tested += s_tst[my_slot];
+            // the slot again from the ballot (two scalar registers), not a vector register held across the walk
+            unsigned long long hm2 = hm;
+            asm volatile("" : "+s"(hm2));
+            const unsigned slot = 64u * wave + rank_below(hm2);
+            bj = s_rec[slot].win;
+            if (kStats) n_tested += s_tst[slot];
         }
         __syncthreads(); // the queue is dead: the reduction may overwrite it
     }
