@@ -233,6 +233,15 @@ class GrowthObjectStatsC(C.Structure):
                 ("max_cells", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class CellGridDesc(C.Structure):
+    """elm_cell_grid_desc: the cell grid's fields of the map's view and the counts of its arrays."""
+    _fields_ = [(n, C.c_int32) for n in ("gx0", "gy0", "gz0", "gnx", "gny", "gnz", "vx0", "vy0", "vz0", "vnx", "vny", "vnz", "gtny",
+                                          "grid_tiled", "grid_wide")] + [("grid_nslots", C.c_uint32), ("n_start_words", C.c_uint64),
+                                                                         ("n_blocks", C.c_uint64), ("n_tiles", C.c_uint64)]
+
+
+INDEX_BUILD_HOST, INDEX_BUILD_DEVICE, INDEX_STAGES = 0, 1, 5
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -260,6 +269,7 @@ EXPORTS = [
     "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
     "elm_growth_object_rule_default", "elm_growth_find_objects", "elm_growth_objects", "elm_growth_cell_objects", "elm_growth_beam_objects",
     "elm_map_build_device", "elm_map_build_device_stages",
+    "elm_map_set_index_build", "elm_map_index_build_stages", "elm_map_download_cell_grid",
 ]
 
 
@@ -348,6 +358,10 @@ def lib():
     L.elm_map_build.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
     L.elm_map_build_device.argtypes = [vp, vp, C.POINTER(C.c_uint8), fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
     L.elm_map_build_device_stages.argtypes = [vp, dp]
+    u32p = C.POINTER(C.c_uint32)
+    L.elm_map_set_index_build.argtypes = [vp, C.c_int]
+    L.elm_map_index_build_stages.argtypes = [vp, dp]
+    L.elm_map_download_cell_grid.argtypes = [vp, C.POINTER(CellGridDesc), u32p, C.c_size_t, fp, C.c_size_t, u32p, C.c_size_t, u32p, C.c_size_t]
     L.elm_map_destroy.argtypes = [vp]
     L.elm_map_destroy.restype = None
     L.elm_map_cal_voxel_cov_all.argtypes = [vp]

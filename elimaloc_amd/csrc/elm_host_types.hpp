@@ -127,11 +127,14 @@ struct elm_map {
     uint32_t* d_vox_stat = nullptr;
     double* d_grid_gicp = nullptr; // the GICP records in grid slot order (built with the grid / refreshed by CalPointCovAll)
     size_t grid_slots = 0;
+    uint64_t grid_start_words = 0; // words of d_grid_start: entries + 4
     bool has_grid = false;
     bool want_gicp_compact = false; // the grid gets 64-byte GICP records (points outside the compact form are flagged and read pt_gicp)
     unsigned n_bad_pts = 0, n_bad_vox = 0; // covariances outside the compact form (diagnostics)
     unsigned n_asym_pts = 0, n_asym_vox = 0; // ... of which the stored inverse is not symmetric: such a map carries side records (choose_path)
     bool grid_refused = false; // the bounding box needs more cells than the budget: neighbourhood lists instead
+    int index_build = 0;       // elm_map_set_index_build: who lays the cell grid out (ELM_INDEX_BUILD_HOST / _DEVICE)
+    double index_stage_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; // the device producer's stages (elm_map_index_build_stages)
     bool warned_slow_path = false; // choose_path has said that this map's covariance methods run the per-pair kernels
     bool has_vnbr = false; // voxel-mean lists (VGICP / AVGICP)
     bool has_vface = false, vface_refused = false; // AVGICP's face sublists (built at the first AVGICP call; refused: no dense table / too many records)

@@ -302,6 +302,13 @@ struct GridBox {
     int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
     int64_t dim[3] = {0, 0, 0};
 };
+// box.lo / hi: the outermost cells of the points -> the box with its margin
+static void grid_box_margin(GridBox& box, int32_t hi[3]) {
+    for (int a = 0; a < 3; ++a) {
+        box.lo[a] -= 2; hi[a] += 2;
+        box.dim[a] = (int64_t)hi[a] - box.lo[a] + 1;
+    }
+}
 static int grid_box(elm_map* m, GridBox& box) {
     elm_ctx* ctx = m->ctx;
     const size_t n = m->dm.n_pts;
@@ -319,10 +326,23 @@ static int grid_box(elm_map* m, GridBox& box) {
             hi[a] = std::max(hi[a], c);
         }
     }
-    for (int a = 0; a < 3; ++a) {
-        lo[a] -= 2; hi[a] += 2;
-        box.dim[a] = (int64_t)hi[a] - lo[a] + 1;
-    }
+    grid_box_margin(box, hi);
+    return ELM_OK;
+}
+// the same box from the device (k_gb_box): the points stay where they are, six words come down
+static int grid_box_device(elm_map* m, GridBox& box, int* d_box) {
+    elm_ctx* ctx = m->ctx;
+    const int32_t init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+    int32_t got[6];
+    HIPCHK(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+    (void)hipGetLastError();
+    launch_gb_box(ctx->stream, m->d_pts, (unsigned)m->dm.n_pts, m->dm.voxel_size, d_box);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(got, d_box, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int32_t hi[3];
+    for (int a = 0; a < 3; ++a) { box.lo[a] = got[a]; hi[a] = got[3 + a]; }
+    grid_box_margin(box, hi);
     return ELM_OK;
 }
 
@@ -339,8 +359,22 @@ struct GridDev {
     void* d_side = nullptr;
     DevLocals own{(void**)&d_blk, (void**)&d_idx, (void**)&d_start, &d_side};
 };
-// blocks, slot indices and block starts go up; dm (the builder's copy of the map's view) gets the fields both forms set alike
-static int grid_upload(elm_ctx* ctx, const GridHost& g, GridDev& d, DevMap& dm) {
+// What a producer -- the host layout or the device build -- hands to the shared finish of its form: the arrays in d, and their counts.
+struct GridCounts {
+    uint64_t n_blk = 0;     // blocks (4 * n_blk slots)
+    uint64_t n_start = 0;   // words of grid_start: entries + 4
+    bool on_device = false; // the device producer ran to the end (layout_flags bit 9)
+};
+// dm (the builder's copy of the map's view) gets the fields both forms and both producers set alike
+static void grid_dm_common(DevMap& dm, const GridDev& d, const GridCounts& c) {
+    dm.grid_blk = d.d_blk;
+    dm.grid_idx = d.d_idx;
+    dm.grid_start = d.d_start;
+    dm.grid_wide = c.n_blk * sizeof(GridBlk) > grid_narrow_limit() ? 1 : 0;
+    dm.grid_nslots = (uint32_t)(4 * c.n_blk);
+}
+// the host producer: blocks, slot indices and block starts go up
+static int grid_upload(elm_ctx* ctx, const GridHost& g, GridDev& d) {
     const std::vector<GridBlk>& gb = g.gb;
     const std::vector<uint32_t>&gi = g.gi, &start = g.start;
     GridBlk*& d_blk = d.d_blk;
@@ -351,50 +385,104 @@ static int grid_upload(elm_ctx* ctx, const GridHost& g, GridDev& d, DevMap& dm) 
     HIPCHK_OOM(ctx, hipMemcpy(d_blk, gb.data(), gb.size() * sizeof(GridBlk), hipMemcpyHostToDevice));
     HIPCHK_OOM(ctx, hipMemcpy(d_idx, gi.data(), gi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK_OOM(ctx, hipMemcpy(d_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    dm.grid_blk = d_blk;
-    dm.grid_idx = d_idx;
-    dm.grid_start = d_start;
-    dm.grid_wide = g.n_blk * sizeof(GridBlk) > grid_narrow_limit() ? 1 : 0;
-    dm.grid_nslots = (uint32_t)(4 * g.n_blk);
     return ELM_OK;
 }
 // Every device step has succeeded: dm and the arrays become the map's, and the GICP records are gathered into slot order.  When those do
 // not fit the grid is given back (the lists read pt_gicp through their index): the map is as before, d still owns the arrays,
-// ELM_ERR_UNSUPPORTED.  The bytes of blocks, slot indices and starts are accounted here, the form's own table by the form.
-static int grid_commit(elm_map* m, const DevMap& dm, const GridHost& g, GridDev& d) {
+// ELM_ERR_UNSUPPORTED.  ALL the grid's bytes and counts in elm_map_info are accounted here, for both forms and both producers: blocks,
+// slot indices and starts, and the form's own table d.d_side -- the dense grid's statistics box (side_cells words; not in
+// index_part_bytes[0]: it is read by the instrumented kernels only) or the two-level grid's tile table (side_cells tiles).
+static int grid_commit(elm_map* m, const DevMap& dm, const GridCounts& c, GridDev& d, uint64_t side_cells) {
     const DevMap dm_before = m->dm;
     m->dm = dm;
     m->d_grid_blk = d.d_blk; m->d_grid_idx = d.d_idx; m->d_grid_start = d.d_start;
     m->has_grid = true;
-    m->grid_slots = g.gi.size();
+    m->grid_slots = (size_t)(4 * c.n_blk);
+    m->grid_start_words = c.n_start;
     if (refresh_grid_gicp(m) != ELM_OK) {
         m->d_grid_blk = nullptr; m->d_grid_idx = nullptr; m->d_grid_start = nullptr;
         m->dm = dm_before;
         m->has_grid = false;
         m->grid_slots = 0;
+        m->grid_start_words = 0;
         (void)hipGetLastError();
         return ELM_ERR_UNSUPPORTED;
     }
+    const bool tiled = dm.grid_tiled != 0;
+    if (tiled) m->d_grid_tiles = (uint2*)d.d_side;
+    else m->d_vox_stat = (uint32_t*)d.d_side;
     d.own.release_all();
-    const size_t searched = g.gb.size() * sizeof(GridBlk) + g.start.size() * sizeof(uint32_t);
-    m->info.device_bytes += searched + g.gi.size() * sizeof(uint32_t);
+    const size_t searched = (size_t)c.n_blk * sizeof(GridBlk) + (size_t)c.n_start * sizeof(uint32_t);
+    const size_t side = (size_t)side_cells * (tiled ? sizeof(uint2) : sizeof(uint32_t));
+    m->info.device_bytes += searched + (size_t)(4 * c.n_blk) * sizeof(uint32_t) + side;
     m->info.nbr_entries = m->dm.n_pts;
-    m->info.index_bytes += searched;
-    m->info.index_part_bytes[0] += searched;
+    m->info.n_query_voxels = side_cells;
+    m->info.index_bytes += searched + side;
+    m->info.index_part_bytes[0] += searched + (tiled ? side : 0);
+    if (tiled) m->info.layout_flags |= 4;
+    if (c.on_device) m->info.layout_flags |= 512;
     return ELM_OK;
 }
 
-// Dense half-voxel cell grid (see DevMap::grid_*): the map points once, counting-sorted by cell on the host (init time), the
-// offsets of every cell of the bounding box (+ 2 cells of margin), and the dense voxel box of walk statistics.
-// ELM_ERR_UNSUPPORTED (and grid_refused) when the grid is not affordable -- the box needs more than max_cells cells, its tables
-// do not fit the host / device memory that is free right now, or an allocation fails half-way -- the caller then builds the
-// neighbourhood lists instead; nothing is left allocated and the map is unchanged.
-static int dense_grid_to_device(elm_map* m, const GridBox& box, const GridHost& g, const int32_t klo[3], const int64_t vd[3], uint64_t vcells) {
+// ---- the decisions both producers share: which boxes and budgets a form accepts (host arithmetic on the box integers and counts)
+static bool dense_box_refused(const int64_t dim[3], uint64_t cells, uint64_t max_cells) {
+    return dim[0] > 0x7FFFFFF0ll || dim[1] > 0x7FFFFFF0ll || dim[2] > 0x7FFFFFF0ll || cells > max_cells || cells > 0xFFFFFFF0ull;
+}
+// dense voxel box of floor keys: a query with floor key f walks the stored keys f-1 .. f+1
+static uint64_t dense_vox_box(const elm_map* m, int32_t klo[3], int64_t vd[3]) {
+    int32_t khi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    klo[0] = klo[1] = klo[2] = INT32_MAX;
+    for (uint32_t v = 0; v < m->dm.n_vox; ++v)
+        for (int a = 0; a < 3; ++a) {
+            klo[a] = std::min(klo[a], m->h_keys[3 * v + a]);
+            khi[a] = std::max(khi[a], m->h_keys[3 * v + a]);
+        }
+    for (int a = 0; a < 3; ++a) vd[a] = (int64_t)khi[a] - klo[a] + 3;
+    return (uint64_t)vd[0] * (uint64_t)vd[1] * (uint64_t)vd[2];
+}
+// Byte budget (the cell count alone says nothing about a sparse or elongated map just under it): host transients = the
+// offsets + the sorted copy (blocks of four: at most one block per point) + two index arrays; device = offsets + statistics +
+// blocks + slot indices (+ the GICP records in slot order).  Not affordable right now -> the lists.  The device producer has no host
+// tables (host_tables = false drops the host term) and adds its scratch (dev_scratch) to the device need.
+static int grid_budget(elm_map* m, const char* what, uint64_t host_need, uint64_t dev_need, bool host_tables, uint64_t dev_scratch, bool* ok) {
     elm_ctx* ctx = m->ctx;
-    GridDev d;
+    size_t dev_free = 0, dev_total = 0;
+    HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
+    const uint64_t host_free = host_available_bytes();
+    dev_need += dev_scratch;
+    *ok = !((host_tables && host_need > host_free / 10 * 7) || dev_need > (uint64_t)dev_free / 10 * 8);
+    if (!*ok)
+        ctx->last_error = std::string(what) + ": tables exceed the memory that is free (host " + std::to_string((host_tables ? host_need : 0) >> 20) +
+                          " MB, device " + std::to_string(dev_need >> 20) + " MB needed)";
+    return ELM_OK;
+}
+static int dense_budget(elm_map* m, uint64_t cells, uint64_t vcells, bool host_tables, uint64_t dev_scratch, bool* ok) {
+    const uint64_t n = m->dm.n_pts;
+    const uint64_t worst_blk = std::min<uint64_t>(n, cells) + n / 4 + 2;
+    const uint64_t host_need = (cells + 4) * 4 + worst_blk * (sizeof(GridBlk) + 16) + n * 8;
+    const uint64_t dev_need = (cells + 4) * 4 + vcells * 4 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
+    return grid_budget(m, "cell grid", host_need, dev_need, host_tables, dev_scratch, ok);
+}
+// 64 M tiles = 512 MB of tile table (a 32 km x 32 km box at half-metre cells); the z range of a tile is a 16-bit pair
+static bool tiled_box_refused(const int64_t dim[3], int64_t tnx, int64_t tny) {
+    return tnx * tny > ((int64_t)64 << 20) || dim[2] > 65000 || tnx * kTile > 0x7FFFFFF0ll || tny * kTile > 0x7FFFFFF0ll;
+}
+// (host_need still counts two tables of entries + 4 words, from before the layout was shared with the dense grid; the build now takes
+// one: the formula over-counts and is left as it is -- a changed refusal changes which index a map gets)
+static int tiled_budget(elm_map* m, uint64_t entries, uint64_t n_tiles, bool host_tables, uint64_t dev_scratch, bool* ok) {
+    const uint64_t n = m->dm.n_pts;
+    const uint64_t worst_blk = n + 2;
+    const uint64_t host_need = (entries + 4) * 8 + worst_blk * (sizeof(GridBlk) + 16) + n * 8 + n_tiles * 12;
+    const uint64_t dev_need = (entries + 4) * 4 + n_tiles * 8 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
+    return grid_budget(m, "tiled cell grid", host_need, dev_need, host_tables, dev_scratch, ok);
+}
+
+// ---- the finish both producers share: d holds blocks, slot indices and starts; the form's own table, the map's view, the commit
+// Dense form: the statistics box is allocated and filled here (launch_vox_stat reads the grid through dm).
+static int dense_grid_finish(elm_map* m, const GridBox& box, const GridCounts& c, GridDev& d, const int32_t klo[3], const int64_t vd[3], uint64_t vcells) {
+    elm_ctx* ctx = m->ctx;
     DevMap dm = m->dm;
-    int rc;
-    if ((rc = grid_upload(ctx, g, d, dm)) != ELM_OK) return rc;
+    grid_dm_common(dm, d, c);
     uint32_t* d_stat = nullptr;
     HIPCHK_OOM(ctx, hipMalloc((void**)&d_stat, std::max<size_t>(vcells * sizeof(uint32_t), 256)));
     d.d_side = d_stat;
@@ -407,56 +495,312 @@ static int dense_grid_to_device(elm_map* m, const GridBox& box, const GridHost& 
     launch_vox_stat(ctx->stream, dm, d_stat);
     HIPCHK_OOM(ctx, hipGetLastError());
     HIPCHK_OOM(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = grid_commit(m, dm, g, d)) != ELM_OK) return rc;
-    m->d_vox_stat = d_stat;
-    m->info.device_bytes += vcells * sizeof(uint32_t);
-    m->info.n_query_voxels = vcells;
-    m->info.index_bytes += vcells * sizeof(uint32_t); // (not in index_part_bytes[0]: the statistics box is read by the instrumented kernels only)
+    return grid_commit(m, dm, c, d, vcells);
+}
+// Two-level form: d.d_side is the tile table, already on the device.
+static int tiled_grid_finish(elm_map* m, const GridBox& box, const GridCounts& c, GridDev& d, int64_t tnx, int64_t tny) {
+    DevMap dm = m->dm;
+    grid_dm_common(dm, d, c);
+    dm.grid_tiles = (const uint2*)d.d_side;
+    dm.grid_tiled = 1;
+    dm.gtny = (int32_t)tny;
+    dm.gx0 = box.lo[0]; dm.gy0 = box.lo[1]; dm.gz0 = box.lo[2];
+    dm.gnx = (int32_t)(tnx * kTile); dm.gny = (int32_t)(tny * kTile); dm.gnz = (int32_t)box.dim[2];
+    dm.vox_stat = nullptr;
+    return grid_commit(m, dm, c, d, (uint64_t)(tnx * tny));
+}
+
+// ------------------------------------------------------------------------------------------------------
+// the device producer (elm_k_gridbuild.hip): opt-in per map (elm_map_set_index_build)
+// ------------------------------------------------------------------------------------------------------
+constexpr int kTryHost = 1; // not an error: this build is the host producer's (scratch not affordable, out of device memory, a size beyond the device kernels' 32-bit indices)
+// the device allocations of one device build, released on every path; get(): hipErrorOutOfMemory -> kTryHost
+struct GridScratch {
+    std::vector<void*> held;
+    GridScratch() = default;
+    GridScratch(const GridScratch&) = delete;
+    GridScratch& operator=(const GridScratch&) = delete;
+    ~GridScratch() {
+        for (void* p : held) (void)hipFree(p);
+    }
+    template <class T>
+    int get(elm_ctx* ctx, T** p, size_t count) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, std::max<size_t>(count * sizeof(T), 256));
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("device index build: hipMalloc: ") + hipGetErrorString(e);
+            (void)hipGetLastError();
+            return e == hipErrorOutOfMemory ? kTryHost : ELM_ERR_DEVICE;
+        }
+        held.push_back(v);
+        *p = (T*)v;
+        return ELM_OK;
+    }
+};
+// hipEvents around the stages (elm_map_index_build_stages)
+static_assert(sizeof(elm_map::index_stage_ms) == ELM_INDEX_STAGES * sizeof(double), "one slot per stage");
+struct GridStageClock {
+    hipEvent_t ev[ELM_INDEX_STAGES + 1] = {};
+    int n = 0;
+    ~GridStageClock() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t mark(hipStream_t st) {
+        if (n > ELM_INDEX_STAGES) return hipSuccess;
+        hipError_t e = hipEventCreate(&ev[n]);
+        if (e == hipSuccess) e = hipEventRecord(ev[n], st);
+        ++n;
+        return e;
+    }
+    void read(double ms[ELM_INDEX_STAGES]) const {
+        for (int k = 0; k < ELM_INDEX_STAGES; ++k) {
+            float f = 0.0f;
+            ms[k] = (k + 1 < n && ev[k] && ev[k + 1] && hipEventElapsedTime(&f, ev[k], ev[k + 1]) == hipSuccess) ? (double)f : 0.0;
+        }
+    }
+};
+// what the sort and the scans need beside the table of entries + 4 words: 16 bytes per point (key and payload, twice), the histogram
+// of one radix pass and the workgroup sums of the longest scan
+static uint64_t grid_device_scratch_bytes(uint64_t n, uint64_t entries) {
+    const uint64_t hist_words = bd_rx_hist_words((unsigned)n);
+    return n * 16 + hist_words * 4 + (std::max<uint64_t>(entries + 4, hist_words) / 1024 + 1) * 4 + 1024;
+}
+// the sizes the device kernels index with 32 bits (beyond: the host producer)
+static bool grid_device_sizes_ok(uint64_t n, uint64_t entries) { return n < 0x7FFFFFFFull && entries + 4 <= 0xF0000000ull; }
+
+// From the counts in d.d_start (entries + 4 words, the trailing four zero) and the unsorted (entry, point number) pairs in key[0] / val[0]:
+// the stable sort by entry, the block starts, n_blk down, blocks and slots allocated, padded and filled.  The tail both forms share.
+struct GridSortBufs {
+    unsigned *key[2] = {nullptr, nullptr}, *val[2] = {nullptr, nullptr}, *hist = nullptr, *blk = nullptr, *total = nullptr;
+};
+static int grid_device_layout(elm_map* m, GridStageClock& clk, const GridSortBufs& b, uint64_t entries, unsigned zero_head,
+                              GridDev& d, GridCounts& c) {
+    elm_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const unsigned n = (unsigned)m->dm.n_pts;
+    (void)hipGetLastError();
+    // order inside an entry = input order: stable 8-bit passes over the bits the entries have
+    unsigned bits = 0, cur = 0;
+    while (bits < 32 && ((uint64_t)1 << bits) < entries) ++bits;
+    const unsigned hist_words = (unsigned)bd_rx_hist_words(n);
+    for (unsigned shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        launch_bd_rx_hist(st, b.key[cur], n, shift, b.hist);
+        launch_bd_scan(st, b.hist, hist_words, b.blk, b.total);
+        launch_bd_rx_scatter(st, b.key[cur], b.val[cur], n, shift, b.hist, b.key[cur ^ 1], b.val[cur ^ 1]);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, clk.mark(st));
+    // block starts
+    launch_gb_blocks(st, d.d_start, (unsigned)entries);
+    launch_bd_scan(st, d.d_start, (unsigned)entries, b.blk, b.total);
+    launch_gb_start_fin(st, d.d_start, (unsigned)entries, zero_head, b.total);
+    HIPCHK(ctx, hipGetLastError());
+    unsigned blocks = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&blocks, b.total, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    c.n_blk = (uint64_t)blocks + 1; // block 0: four padding slots
+    c.n_start = entries + 4;
+    HIPCHK(ctx, clk.mark(st));
+    if (c.n_blk > kGridMaxBlocks) return ELM_ERR_UNSUPPORTED; // (the host's refusal: the caller marks the map)
+    // fill
+    for (void** p : {(void**)&d.d_blk, (void**)&d.d_idx}) {
+        const size_t bytes = p == (void**)&d.d_blk ? (size_t)c.n_blk * sizeof(GridBlk) : (size_t)c.n_blk * 4 * sizeof(uint32_t);
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("device index build: hipMalloc: ") + hipGetErrorString(e);
+            (void)hipGetLastError();
+            return e == hipErrorOutOfMemory ? kTryHost : ELM_ERR_DEVICE;
+        }
+    }
+    launch_gb_pad(st, d.d_blk, d.d_idx, c.n_blk);
+    launch_gb_fill(st, m->d_pts, b.key[cur], b.val[cur], n, d.d_start, d.d_blk, d.d_idx);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, clk.mark(st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return ELM_OK;
 }
+static int grid_sort_bufs(elm_ctx* ctx, GridScratch& sc, GridSortBufs& b, uint64_t n, uint64_t entries) {
+    const uint64_t hist_words = bd_rx_hist_words((unsigned)n);
+    int rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = sc.get(ctx, &b.key[k], n)) != ELM_OK) return rc;
+        if ((rc = sc.get(ctx, &b.val[k], n)) != ELM_OK) return rc;
+    }
+    if ((rc = sc.get(ctx, &b.hist, hist_words)) != ELM_OK) return rc;
+    if ((rc = sc.get(ctx, &b.blk, std::max<uint64_t>(entries + 4, hist_words) / 1024 + 1)) != ELM_OK) return rc;
+    return sc.get(ctx, &b.total, 4);
+}
+// the table of entries + 4 words, zeroed: the counts, then the block starts (it becomes the map's grid_start)
+static int grid_start_table(elm_ctx* ctx, GridDev& d, uint64_t entries) {
+    const hipError_t e = hipMalloc((void**)&d.d_start, (entries + 4) * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("device index build: hipMalloc: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? kTryHost : ELM_ERR_DEVICE;
+    }
+    HIPCHK(ctx, hipMemsetAsync(d.d_start, 0, (entries + 4) * sizeof(uint32_t), ctx->stream));
+    return ELM_OK;
+}
+
+// The dense form on the device.  ELM_OK; ELM_ERR_UNSUPPORTED exactly where the host producer refuses (same functions, same numbers; the
+// caller sets grid_refused as it does for the host's refusals); kTryHost; an error.
+static int build_cell_grid_device(elm_map* m, uint64_t max_cells) {
+    elm_ctx* ctx = m->ctx;
+    const uint64_t n = m->dm.n_pts;
+    if (!grid_device_sizes_ok(n, 0)) return kTryHost;
+    GridScratch sc;
+    GridStageClock clk;
+    int rc;
+    int* d_box = nullptr;
+    if ((rc = sc.get(ctx, &d_box, 8)) != ELM_OK) return rc;
+    HIPCHK(ctx, clk.mark(ctx->stream));
+    GridBox box;
+    if ((rc = grid_box_device(m, box, d_box)) != ELM_OK) return rc;
+    HIPCHK(ctx, clk.mark(ctx->stream));
+    const int64_t* dim = box.dim;
+    const uint64_t cells = (uint64_t)dim[0] * (uint64_t)dim[1] * (uint64_t)dim[2];
+    if (dense_box_refused(dim, cells, max_cells)) return ELM_ERR_UNSUPPORTED;
+    int32_t klo[3];
+    int64_t vd[3];
+    const uint64_t vcells = dense_vox_box(m, klo, vd);
+    if (vcells > max_cells) return ELM_ERR_UNSUPPORTED;
+    if (!grid_device_sizes_ok(n, cells)) return kTryHost;
+    bool ok = false;
+    if ((rc = dense_budget(m, cells, vcells, false, grid_device_scratch_bytes(n, cells), &ok)) != ELM_OK) return rc;
+    if (!ok) return kTryHost; // (the host producer decides with its own terms)
+    GridDev d;
+    GridSortBufs b;
+    if ((rc = grid_start_table(ctx, d, cells)) != ELM_OK) return rc;
+    if ((rc = grid_sort_bufs(ctx, sc, b, n, cells)) != ELM_OK) return rc;
+    (void)hipGetLastError();
+    launch_gb_entry_dense(ctx->stream, m->d_pts, (unsigned)n, m->dm.voxel_size, box.lo, (uint64_t)dim[1], (uint64_t)dim[2], b.key[0], b.val[0], d.d_start);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, clk.mark(ctx->stream));
+    GridCounts c;
+    if ((rc = grid_device_layout(m, clk, b, cells, 0u, d, c)) != ELM_OK) return rc;
+    c.on_device = true;
+    rc = dense_grid_finish(m, box, c, d, klo, vd, vcells);
+    if (rc == ELM_OK) clk.read(m->index_stage_ms);
+    return rc;
+}
+// The two-level form on the device; results as build_cell_grid_device.
+static int build_tiled_grid_device(elm_map* m) {
+    elm_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = m->dm.n_pts;
+    if (!grid_device_sizes_ok(n, 0)) return kTryHost;
+    GridScratch sc;
+    GridStageClock clk;
+    int rc;
+    int* d_box = nullptr; // six box words, then the 64-bit total of the tile entries
+    if ((rc = sc.get(ctx, &d_box, 8)) != ELM_OK) return rc;
+    HIPCHK(ctx, clk.mark(st));
+    GridBox box;
+    if ((rc = grid_box_device(m, box, d_box)) != ELM_OK) return rc;
+    HIPCHK(ctx, clk.mark(st));
+    const int64_t* dim = box.dim;
+    const int64_t tnx = (dim[0] + kTile - 1) / kTile, tny = (dim[1] + kTile - 1) / kTile;
+    if (tiled_box_refused(dim, tnx, tny)) return ELM_ERR_UNSUPPORTED;
+    const uint64_t n_tiles = (uint64_t)(tnx * tny);
+    // z range and entries per tile; the total in 64 bits before the 32-bit scan is trusted
+    unsigned *d_zmin = nullptr, *d_zmax = nullptr, *d_tcnt = nullptr, *d_tblk = nullptr, *d_ttot = nullptr;
+    unsigned long long* d_total64 = (unsigned long long*)(d_box + 6);
+    GridDev d;
+    uint2* d_tiles = nullptr;
+    {
+        size_t dev_free = 0, dev_total = 0;
+        HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
+        if (n_tiles * 20 + n * 16 > (uint64_t)dev_free / 10 * 8) return kTryHost;
+    }
+    if ((rc = sc.get(ctx, &d_zmin, n_tiles)) != ELM_OK) return rc;
+    if ((rc = sc.get(ctx, &d_zmax, n_tiles)) != ELM_OK) return rc;
+    if ((rc = sc.get(ctx, &d_tcnt, n_tiles)) != ELM_OK) return rc;
+    if ((rc = sc.get(ctx, &d_tblk, n_tiles / 1024 + 1)) != ELM_OK) return rc;
+    if ((rc = sc.get(ctx, &d_ttot, 4)) != ELM_OK) return rc;
+    {
+        const hipError_t e = hipMalloc((void**)&d_tiles, n_tiles * sizeof(uint2));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return e == hipErrorOutOfMemory ? kTryHost : ELM_ERR_DEVICE;
+        }
+        d.d_side = d_tiles;
+    }
+    HIPCHK(ctx, hipMemsetAsync(d_zmin, 0xFF, n_tiles * sizeof(unsigned), st));
+    HIPCHK(ctx, hipMemsetAsync(d_zmax, 0, n_tiles * sizeof(unsigned), st));
+    HIPCHK(ctx, hipMemsetAsync(d_total64, 0, sizeof(unsigned long long), st));
+    (void)hipGetLastError();
+    launch_gb_tile_z(st, m->d_pts, (unsigned)n, m->dm.voxel_size, box.lo, (uint64_t)tny, d_zmin, d_zmax);
+    launch_gb_tile_cnt(st, d_zmin, d_zmax, (unsigned)n_tiles, d_tcnt, d_total64);
+    HIPCHK(ctx, hipGetLastError());
+    unsigned long long tile_entries = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&tile_entries, d_total64, sizeof(tile_entries), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    // entries 0 .. 63: the shared zero run of every empty tile (nz = 0: one entry per column)
+    const uint64_t entries = (uint64_t)kTile * kTile + tile_entries;
+    if (entries > 0xFFFFFFF0ull) return ELM_ERR_UNSUPPORTED;
+    if (!grid_device_sizes_ok(n, entries)) return kTryHost;
+    bool ok = false;
+    if ((rc = tiled_budget(m, entries, n_tiles, false, grid_device_scratch_bytes(n, entries) + n_tiles * 12, &ok)) != ELM_OK) return rc;
+    if (!ok) return kTryHost;
+    launch_bd_scan(st, d_tcnt, (unsigned)n_tiles, d_tblk, d_ttot);
+    launch_gb_tiles(st, d_zmin, d_zmax, d_tcnt, (unsigned)n_tiles, d_tiles);
+    HIPCHK(ctx, hipGetLastError());
+    GridSortBufs b;
+    if ((rc = grid_start_table(ctx, d, entries)) != ELM_OK) return rc;
+    if ((rc = grid_sort_bufs(ctx, sc, b, n, entries)) != ELM_OK) return rc;
+    // entry order = (tile, column, z); the extra entry of every column (index nz) holds no point: its start = the column's end
+    launch_gb_entry_tiled(st, m->d_pts, (unsigned)n, m->dm.voxel_size, box.lo, (uint64_t)tny, d_tiles, b.key[0], b.val[0], d.d_start);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, clk.mark(st));
+    GridCounts c;
+    if ((rc = grid_device_layout(m, clk, b, entries, (unsigned)(kTile * kTile), d, c)) != ELM_OK) return rc;
+    c.on_device = true;
+    rc = tiled_grid_finish(m, box, c, d, tnx, tny);
+    if (rc == ELM_OK) clk.read(m->index_stage_ms);
+    return rc;
+}
+
+// Dense half-voxel cell grid (see DevMap::grid_*): the map points once, counting-sorted by cell on the host (init time), the
+// offsets of every cell of the bounding box (+ 2 cells of margin), and the dense voxel box of walk statistics.
+// ELM_ERR_UNSUPPORTED (and grid_refused) when the grid is not affordable -- the box needs more than max_cells cells, its tables
+// do not fit the host / device memory that is free right now, or an allocation fails half-way -- the caller then builds the
+// neighbourhood lists instead; nothing is left allocated and the map is unchanged.
 static int build_cell_grid_impl(elm_map* m, uint64_t max_cells) {
     elm_ctx* ctx = m->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t n = m->dm.n_pts;
     const double vs = m->dm.voxel_size;
     if (n == 0 || m->dm.n_vox == 0) return ELM_ERR_UNSUPPORTED;
-    GridBox box;
     int rc;
+    if (m->index_build == ELM_INDEX_BUILD_DEVICE) { // the same form from the device producer; kTryHost: from this one after all
+        rc = build_cell_grid_device(m, max_cells);
+        if (rc != kTryHost) {
+            if (rc != ELM_OK) m->grid_refused = true; // as for the host's refusals below
+            return rc;
+        }
+    }
+    GridBox box;
     if ((rc = grid_box(m, box)) != ELM_OK) return rc;
     const std::vector<float4>& pts = box.pts;
     const int32_t* lo = box.lo;
     const int64_t* dim = box.dim;
     const uint64_t cells = (uint64_t)dim[0] * (uint64_t)dim[1] * (uint64_t)dim[2];
-    if (dim[0] > 0x7FFFFFF0ll || dim[1] > 0x7FFFFFF0ll || dim[2] > 0x7FFFFFF0ll || cells > max_cells || cells > 0xFFFFFFF0ull) {
+    if (dense_box_refused(dim, cells, max_cells)) {
         m->grid_refused = true;
         return ELM_ERR_UNSUPPORTED;
     }
-    // dense voxel box of floor keys: a query with floor key f walks the stored keys f-1 .. f+1
-    int32_t klo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, khi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-    for (uint32_t v = 0; v < m->dm.n_vox; ++v)
-        for (int a = 0; a < 3; ++a) {
-            klo[a] = std::min(klo[a], m->h_keys[3 * v + a]);
-            khi[a] = std::max(khi[a], m->h_keys[3 * v + a]);
-        }
-    const int64_t vd[3] = {(int64_t)khi[0] - klo[0] + 3, (int64_t)khi[1] - klo[1] + 3, (int64_t)khi[2] - klo[2] + 3};
-    const uint64_t vcells = (uint64_t)vd[0] * (uint64_t)vd[1] * (uint64_t)vd[2];
+    int32_t klo[3];
+    int64_t vd[3];
+    const uint64_t vcells = dense_vox_box(m, klo, vd);
     if (vcells > max_cells) {
         m->grid_refused = true;
         return ELM_ERR_UNSUPPORTED;
     }
-    // Byte budget (the cell count alone says nothing about a sparse or elongated map just under it): host transients = the
-    // offsets + the sorted copy (blocks of four: at most one block per point) + two index arrays; device = offsets + statistics +
-    // blocks + slot indices (+ the GICP records in slot order).  Not affordable right now -> the lists.
     {
-        const uint64_t worst_blk = std::min<uint64_t>(n, cells) + n / 4 + 2;
-        const uint64_t host_need = (cells + 4) * 4 + worst_blk * (sizeof(GridBlk) + 16) + n * 8;
-        const uint64_t dev_need = (cells + 4) * 4 + vcells * 4 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
-        size_t dev_free = 0, dev_total = 0;
-        HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
-        const uint64_t host_free = host_available_bytes();
-        if (host_need > host_free / 10 * 7 || dev_need > (uint64_t)dev_free / 10 * 8) {
-            ctx->last_error = "cell grid: tables exceed the memory that is free (host " + std::to_string(host_need >> 20) + " MB, device " +
-                              std::to_string(dev_need >> 20) + " MB needed)";
+        bool ok = false;
+        if ((rc = dense_budget(m, cells, vcells, true, 0, &ok)) != ELM_OK) return rc;
+        if (!ok) {
             m->grid_refused = true;
             return ELM_ERR_UNSUPPORTED;
         }
@@ -477,7 +821,13 @@ static int build_cell_grid_impl(elm_map* m, uint64_t max_cells) {
     if (g.n_blk > kGridMaxBlocks) { m->grid_refused = true; return ELM_ERR_UNSUPPORTED; }
     std::vector<float4>().swap(box.pts);
     // device side: into locals, committed to the map only when every step has succeeded
-    rc = dense_grid_to_device(m, box, g, klo, vd, vcells);
+    {
+        GridDev d;
+        GridCounts c;
+        c.n_blk = g.n_blk;
+        c.n_start = g.start.size();
+        if ((rc = grid_upload(ctx, g, d)) == ELM_OK) rc = dense_grid_finish(m, box, c, d, klo, vd, vcells);
+    }
     if (rc != ELM_OK) m->grid_refused = true; // do not retry a multi-GB build at every registration
     return rc;
 }
@@ -503,15 +853,18 @@ static int build_tiled_grid_impl(elm_map* m) {
     const size_t n = m->dm.n_pts;
     const double vs = m->dm.voxel_size;
     if (n == 0 || m->dm.n_vox == 0) return ELM_ERR_UNSUPPORTED;
-    GridBox box;
     int rc;
+    if (m->index_build == ELM_INDEX_BUILD_DEVICE) { // the same form from the device producer; kTryHost: from this one after all
+        rc = build_tiled_grid_device(m);
+        if (rc != kTryHost) return rc;
+    }
+    GridBox box;
     if ((rc = grid_box(m, box)) != ELM_OK) return rc;
     const std::vector<float4>& pts = box.pts;
     const int32_t* lo = box.lo;
     const int64_t* dim = box.dim;
     const int64_t tnx = (dim[0] + kTile - 1) / kTile, tny = (dim[1] + kTile - 1) / kTile;
-    // 64 M tiles = 512 MB of tile table (a 32 km x 32 km box at half-metre cells); the z range of a tile is a 16-bit pair
-    if (tnx * tny > ((int64_t)64 << 20) || dim[2] > 65000 || tnx * kTile > 0x7FFFFFF0ll || tny * kTile > 0x7FFFFFF0ll) return ELM_ERR_UNSUPPORTED;
+    if (tiled_box_refused(dim, tnx, tny)) return ELM_ERR_UNSUPPORTED;
     const size_t n_tiles = (size_t)(tnx * tny);
     auto cell3 = [&](size_t i, int32_t& cx, int32_t& cy, int32_t& cz) {
         cx = grid_cell_of((double)pts[i].x, vs) - lo[0];
@@ -540,19 +893,11 @@ static int build_tiled_grid_impl(elm_map* m) {
         const uint32_t z0 = te.y & 0xFFFFu, nz = te.y >> 16;
         return te.x + (uint32_t)(((cx & (kTile - 1)) << kTileShift) | (cy & (kTile - 1))) * (nz + 1) + ((uint32_t)cz - z0);
     };
-    // byte budget, as for the dense grid (host_need still counts two tables of entries + 4 words, from before the layout was shared with
-    // the dense grid; the build now takes one: the formula over-counts and is left as it is -- a changed refusal changes which index a map gets)
+    // byte budget, as for the dense grid
     {
-        const uint64_t worst_blk = n + 2;
-        const uint64_t host_need = (entries + 4) * 8 + worst_blk * (sizeof(GridBlk) + 16) + n * 8 + n_tiles * 12;
-        const uint64_t dev_need = (entries + 4) * 4 + n_tiles * 8 + worst_blk * (sizeof(GridBlk) + 16) + (m->info.has_point_cov ? worst_blk * 4 * (m->want_gicp_compact ? 64 : 128) : 0);
-        size_t dev_free = 0, dev_total = 0;
-        HIPCHK(ctx, hipMemGetInfo(&dev_free, &dev_total));
-        const uint64_t host_free = host_available_bytes();
-        if (host_need > host_free / 10 * 7 || dev_need > (uint64_t)dev_free / 10 * 8) {
-            ctx->last_error = "tiled cell grid: tables exceed the memory that is free";
-            return ELM_ERR_UNSUPPORTED;
-        }
+        bool ok = false;
+        if ((rc = tiled_budget(m, entries, n_tiles, true, 0, &ok)) != ELM_OK) return rc;
+        if (!ok) return ELM_ERR_UNSUPPORTED;
     }
     // entry order = (tile, column, z); the extra entry of every column (index nz) holds no point: its start = the column's end
     GridHost g;
@@ -569,26 +914,15 @@ static int build_tiled_grid_impl(elm_map* m) {
     for (uint64_t e = 0; e < (uint64_t)kTile * kTile; ++e) g.start[e] = 0; // empty tiles: block 0 .. block 0 (nothing)
     std::vector<float4>().swap(box.pts);
     GridDev d;
-    DevMap dm = m->dm;
-    if ((rc = grid_upload(ctx, g, d, dm)) != ELM_OK) return rc;
+    GridCounts c;
+    c.n_blk = g.n_blk;
+    c.n_start = g.start.size();
+    if ((rc = grid_upload(ctx, g, d)) != ELM_OK) return rc;
     uint2* d_tiles = nullptr;
     HIPCHK_OOM(ctx, hipMalloc((void**)&d_tiles, n_tiles * sizeof(uint2)));
     d.d_side = d_tiles;
     HIPCHK_OOM(ctx, hipMemcpy(d_tiles, tiles.data(), n_tiles * sizeof(uint2), hipMemcpyHostToDevice));
-    dm.grid_tiles = d_tiles;
-    dm.grid_tiled = 1;
-    dm.gtny = (int32_t)tny;
-    dm.gx0 = lo[0]; dm.gy0 = lo[1]; dm.gz0 = lo[2];
-    dm.gnx = (int32_t)(tnx * kTile); dm.gny = (int32_t)(tny * kTile); dm.gnz = (int32_t)dim[2];
-    dm.vox_stat = nullptr;
-    if ((rc = grid_commit(m, dm, g, d)) != ELM_OK) return rc;
-    m->d_grid_tiles = d_tiles;
-    m->info.device_bytes += n_tiles * sizeof(uint2);
-    m->info.n_query_voxels = n_tiles;
-    m->info.layout_flags |= 4;
-    m->info.index_bytes += n_tiles * sizeof(uint2);
-    m->info.index_part_bytes[0] += n_tiles * sizeof(uint2);
-    return ELM_OK;
+    return tiled_grid_finish(m, box, c, d, tnx, tny);
 }
 static int build_tiled_grid(elm_map* m) {
     if (m->has_grid) return ELM_OK;
@@ -683,4 +1017,49 @@ extern "C" int elm_map_build_neighbourhoods(elm_map* m) {
     if (!m->replicas.empty() && group_call(m->ctx)) return elm_multi::map_call(m, 2, 0.0);
     bool g;
     return build_search_index(m, &g);
+}
+
+// ---- device index build: the preference, the stage times, the read-back of the grid
+extern "C" int elm_map_set_index_build(elm_map* m, int where) {
+    if (!m || (where != ELM_INDEX_BUILD_HOST && where != ELM_INDEX_BUILD_DEVICE)) return ELM_ERR_INVALID;
+    elm_ctx* ctx = m->ctx;
+    if (!m->replicas.empty() || group_call(ctx) || ctx->comm || ctx->hook) {
+        ctx->last_error = "elm_map_set_index_build: one rank only (not a map with replicas, a device group's lead, nor with a communicator or hook attached)";
+        return ELM_ERR_UNSUPPORTED;
+    }
+    if (m->has_grid) return ELM_OK; // built: nothing changes
+    m->index_build = where;
+    return ELM_OK;
+}
+extern "C" int elm_map_index_build_stages(const elm_map* m, double ms[ELM_INDEX_STAGES]) {
+    if (!m || !ms || !m->has_grid || !(m->info.layout_flags & 512)) return ELM_ERR_INVALID;
+    for (int k = 0; k < ELM_INDEX_STAGES; ++k) ms[k] = m->index_stage_ms[k];
+    return ELM_OK;
+}
+extern "C" int elm_map_download_cell_grid(const elm_map* m, elm_cell_grid_desc* desc, uint32_t* start, size_t start_cap, float* blocks12,
+                                          size_t block_cap, uint32_t* slot_point, size_t slot_cap, uint32_t* tiles2, size_t tile_cap) {
+    if (!m || !desc) return ELM_ERR_INVALID;
+    elm_ctx* ctx = m->ctx;
+    if (!m->has_grid) {
+        ctx->last_error = "elm_map_download_cell_grid: the map has no cell grid";
+        return ELM_ERR_UNSUPPORTED;
+    }
+    const DevMap& dm = m->dm;
+    elm_cell_grid_desc ds{};
+    ds.gx0 = dm.gx0; ds.gy0 = dm.gy0; ds.gz0 = dm.gz0; ds.gnx = dm.gnx; ds.gny = dm.gny; ds.gnz = dm.gnz;
+    ds.vx0 = dm.vx0; ds.vy0 = dm.vy0; ds.vz0 = dm.vz0; ds.vnx = dm.vnx; ds.vny = dm.vny; ds.vnz = dm.vnz;
+    ds.gtny = dm.gtny; ds.grid_tiled = dm.grid_tiled; ds.grid_wide = dm.grid_wide; ds.grid_nslots = dm.grid_nslots;
+    ds.n_start_words = m->grid_start_words;
+    ds.n_blocks = m->grid_slots / 4;
+    ds.n_tiles = dm.grid_tiled ? (uint64_t)(dm.gnx / kTile) * (uint64_t)(dm.gny / kTile) : 0;
+    *desc = ds;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t ns = std::min<size_t>(start_cap, ds.n_start_words), nb = std::min<size_t>(block_cap, ds.n_blocks),
+                 ni = std::min<size_t>(slot_cap, m->grid_slots), nt = std::min<size_t>(tile_cap, ds.n_tiles);
+    if (start && ns) HIPCHK(ctx, hipMemcpy(start, m->d_grid_start, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (blocks12 && nb) HIPCHK(ctx, hipMemcpy(blocks12, m->d_grid_blk, nb * sizeof(GridBlk), hipMemcpyDeviceToHost));
+    if (slot_point && ni) HIPCHK(ctx, hipMemcpy(slot_point, m->d_grid_idx, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tiles2 && nt) HIPCHK(ctx, hipMemcpy(tiles2, m->d_grid_tiles, nt * sizeof(uint2), hipMemcpyDeviceToHost));
+    return ELM_OK;
 }

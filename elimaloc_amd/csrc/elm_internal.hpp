@@ -486,6 +486,28 @@ void launch_bd_replay(hipStream_t s, const Pt3* in, unsigned* order, const unsig
 void launch_bd_emit(hipStream_t s, const Pt3* in, const unsigned* order, const unsigned* vid, const unsigned* off, const unsigned* kcnt,
                     const unsigned* kstart, unsigned n_vox, unsigned n, float4* out, uint2* ranges);
 
+// device build of the cell grid (elm_k_gridbuild.hip): the stages elm_index.cpp queues.  At most 2^31 - 1 points and
+// entries; every array but blk / idx / the tile table is the caller's scratch.
+// box: lo[3] (INT32_MAX before the call), hi[3] (INT32_MIN): the half-voxel cells of the stored points, without the margin
+void launch_gb_box(hipStream_t s, const float4* pts, unsigned n, double vs, int* box);
+// key[i] = entry of point i, val[i] = i, cnt[entry] (zero before the call) += 1.  lo: the box with its margin; ny, nz: its cells along y, z
+void launch_gb_entry_dense(hipStream_t s, const float4* pts, unsigned n, double vs, const int32_t lo[3], uint64_t ny, uint64_t nz, unsigned* key,
+                           unsigned* val, unsigned* cnt);
+// two-level form: zmin (all ones before the call) / zmax (zero) per tile; tcnt[t] = 64 * (nz + 1) or 0, *total (zero before) their 64-bit
+// sum; tiles from the exclusive scan of tcnt; then the entries through the tile table
+void launch_gb_tile_z(hipStream_t s, const float4* pts, unsigned n, double vs, const int32_t lo[3], uint64_t tny, unsigned* zmin, unsigned* zmax);
+void launch_gb_tile_cnt(hipStream_t s, const unsigned* zmin, const unsigned* zmax, unsigned n_tiles, unsigned* tcnt, unsigned long long* total);
+void launch_gb_tiles(hipStream_t s, const unsigned* zmin, const unsigned* zmax, const unsigned* tcnt, unsigned n_tiles, uint2* tiles);
+void launch_gb_entry_tiled(hipStream_t s, const float4* pts, unsigned n, double vs, const int32_t lo[3], uint64_t tny, const uint2* tiles,
+                           unsigned* key, unsigned* val, unsigned* cnt);
+// a[e] = blocks of entry e (from its count); after launch_bd_scan over the entries: a = grid_start (zero_head: entries forced to 0)
+void launch_gb_blocks(hipStream_t s, unsigned* a, unsigned entries);
+void launch_gb_start_fin(hipStream_t s, unsigned* a, unsigned entries, unsigned zero_head, const unsigned* total);
+void launch_gb_pad(hipStream_t s, GridBlk* blk, uint32_t* idx, uint64_t n_blk);
+// skey / sval: the points sorted by entry (stable); every point to slot 4 * start[entry] + its rank in the entry
+void launch_gb_fill(hipStream_t s, const float4* pts, const unsigned* skey, const unsigned* sval, unsigned n, const unsigned* start, GridBlk* blk,
+                    uint32_t* idx);
+
 struct DeskewDev {
     double time_scan_cur, time_scan_end;
     int32_t imu_pointer_cur;

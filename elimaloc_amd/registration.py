@@ -349,12 +349,15 @@ def default_context():
 class VoxelHashMap:
     """vhm.hpp:89-335.  Points are (n,3) float32 arrays (the PCD map and the LiDAR are float32, pcm.hpp:205-215)."""
 
-    def __init__(self, voxel_size=1.0, max_points_per_voxel=30, ctx=None, device_build=False):
-        """device_build: the map is built by elm_map_build_device (the same map, byte for byte) instead of the host build."""
+    def __init__(self, voxel_size=1.0, max_points_per_voxel=30, ctx=None, device_build=False, device_index=False):
+        """device_build: the map is built by elm_map_build_device (the same map, byte for byte) instead of the host build.
+        device_index: the map's P2P / GICP cell grid is laid out on the device (elm_map_set_index_build; the same grid, byte for byte);
+        maps derived from this one (Updated, WithoutStale(device=True), WithAppeared(device=True)) keep the preference."""
         self.ctx = ctx or default_context()
         self.voxel_size_ = float(voxel_size)
         self.max_points_per_voxel_ = int(max_points_per_voxel)
         self.device_build_ = bool(device_build)
+        self.device_index_ = bool(device_index)
         self._pending = []
         self._derived = False  # made from a base map on the device: _pending is filled from a download when it is first needed
         self._h = None
@@ -407,6 +410,7 @@ class VoxelHashMap:
                 check(_lib.lib().elm_map_build(self.ctx._h, _fp(allp), allp.shape[0], self.voxel_size_,
                                                self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build")
             self._h = h
+            self._set_index_build()
             if self._want_voxel_cov:
                 check(_lib.lib().elm_map_cal_voxel_cov_all(self._h), self.ctx._h, "elm_map_cal_voxel_cov_all")
             if self._want_point_cov is not None:
@@ -414,11 +418,15 @@ class VoxelHashMap:
                       "elm_map_cal_point_cov_all")
         return self._h
 
+    def _set_index_build(self):
+        if self.device_index_:
+            check(_lib.lib().elm_map_set_index_build(self._h, _lib.INDEX_BUILD_DEVICE), self.ctx._h, "elm_map_set_index_build")
+
     def _derive(self, drop, extra):
         """A new map (same voxel size, cap, context and build path) built on the device from this map's stored points without those that
         drop (uint8 [n_points], None: none) marks, followed by extra [k, 3]: the stored points stay in HBM."""
         extra = np.ascontiguousarray(extra, dtype=np.float32).reshape(-1, 3)
-        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx, self.device_build_)
+        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx, self.device_build_, self.device_index_)
         dptr = None
         if drop is not None:
             drop = np.ascontiguousarray(drop, dtype=np.uint8)
@@ -430,6 +438,7 @@ class VoxelHashMap:
                                               self.max_points_per_voxel_, C.byref(h)), self.ctx._h, "elm_map_build_device")
         out._h = h
         out._derived = True
+        out._set_index_build()
         return out
 
     def Updated(self, points):
@@ -455,6 +464,31 @@ class VoxelHashMap:
     def BuildNeighbourhoods(self):
         """Pay the neighbourhood-list build (P2P/GICP streaming layout) now instead of on the first registration."""
         check(_lib.lib().elm_map_build_neighbourhoods(self._handle()), self.ctx._h, "elm_map_build_neighbourhoods")
+
+    def CellGrid(self):
+        """The P2P / GICP cell grid as it lies on the device (elm_map_download_cell_grid; it is not built by this call: ElmError when the
+        map has none) -> dict: desc (dict of the descriptor's fields), start uint32 [entries + 4], blocks float32 [n_blocks, 3, 4]
+        (x[4] y[4] z[4]), slot_point uint32 [4 n_blocks], tiles uint32 [n_tiles, 2]."""
+        L = _lib.lib()
+        d = _lib.CellGridDesc()
+        check(L.elm_map_download_cell_grid(self._handle(), C.byref(d), None, 0, None, 0, None, 0, None, 0), self.ctx._h,
+              "elm_map_download_cell_grid")
+        start = np.zeros(int(d.n_start_words), np.uint32)
+        blocks = np.zeros((int(d.n_blocks), 3, 4), np.float32)
+        slot_point = np.zeros(4 * int(d.n_blocks), np.uint32)
+        tiles = np.zeros((int(d.n_tiles), 2), np.uint32)
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        check(L.elm_map_download_cell_grid(self._handle(), C.byref(d), u32(start), start.size, _fp(blocks), blocks.shape[0], u32(slot_point),
+                                           slot_point.size, u32(tiles), tiles.shape[0]), self.ctx._h, "elm_map_download_cell_grid")
+        return {"desc": {n: int(getattr(d, n)) for n, _ in d._fields_}, "start": start, "blocks": blocks, "slot_point": slot_point,
+                "tiles": tiles}
+
+    def IndexBuildStages(self):
+        """Device milliseconds of the stages of this map's device index build (elm_map_index_build_stages): box, entries and counts, sort,
+        block starts, padding and fill."""
+        ms = np.zeros(_lib.INDEX_STAGES)
+        check(_lib.lib().elm_map_index_build_stages(self._handle(), _dp(ms)), self.ctx._h, "elm_map_index_build_stages")
+        return ms
 
     def Empty(self):  # vhm.hpp:325
         return bool(_lib.lib().elm_map_empty(self._handle()))

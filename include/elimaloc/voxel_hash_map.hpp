@@ -144,6 +144,12 @@ struct VoxelHashMap {
     // sequential AddPoints calls produce in the reference).
     // true: the map is built by elm_map_build_device (the same map, byte for byte) instead of the host build
     void BuildOnDevice(bool on) { device_build_ = on; }
+    // true: the map's P2P / GICP cell grid is laid out on the device (elm_map_set_index_build: the same grid, byte for byte) instead of
+    // on the host; holds for the index this map builds from now on and for the maps derived from it.  An index already built stays.
+    void BuildIndexOnDevice(bool on) {
+        device_index_ = on;
+        if (map_) elimaloc::check(elm_map_set_index_build(map_, on ? ELM_INDEX_BUILD_DEVICE : ELM_INDEX_BUILD_HOST), ctx(), "elm_map_set_index_build");
+    }
     void AddPoints(const RadarPointVector& points) {
         Materialize();
         xyz_.reserve(xyz_.size() + 3 * points.size());
@@ -403,6 +409,7 @@ struct VoxelHashMap {
                                 "elm_map_build_device");
             else
                 elimaloc::check(elm_map_build(ctx(), xyz_.data(), xyz_.size() / 3, voxel_size_, max_points_per_voxel_, &map_), ctx(), "elm_map_build");
+            if (device_index_) elimaloc::check(elm_map_set_index_build(map_, ELM_INDEX_BUILD_DEVICE), ctx(), "elm_map_set_index_build");
             if (want_voxel_cov_) elimaloc::check(elm_map_cal_voxel_cov_all(map_), ctx(), "CalVoxelCovAll");
             if (want_point_cov_ > 0) elimaloc::check(elm_map_cal_point_cov_all(map_, want_point_cov_), ctx(), "CalPointCovAll");
         }
@@ -426,8 +433,10 @@ private:
         out.Clear();
         out.Init(voxel_size_, max_points_per_voxel_);
         out.device_build_ = device_build_;
+        out.device_index_ = device_index_;
         out.map_ = m;
         out.derived_ = true;
+        if (device_index_) elimaloc::check(elm_map_set_index_build(m, ELM_INDEX_BUILD_DEVICE), ctx(), "elm_map_set_index_build");
     }
     // a map made by Derive holds no input points: before it takes more, its stored points (which replay to themselves) become its input
     void Materialize() {
@@ -442,6 +451,7 @@ private:
     std::vector<float> xyz_;
     mutable elm_map* map_ = nullptr;
     bool device_build_ = false;
+    bool device_index_ = false;
     bool derived_ = false;
     bool want_voxel_cov_ = false;
     double want_point_cov_ = -1.0;

@@ -134,7 +134,9 @@ typedef struct elm_map_info {
                            *        SVD): GICP's kernels on this map also write the 15 antisymmetric side sums per workgroup and the solve restores
                            *        all 36 entries of J^T M J (LDLT on the lower triangle, as the reference); ELM_CHECK=strict_pairs runs
                            *        the reference's per-pair arithmetic instead (the in-product checker, 12-27 times slower),
-                           * bit 8: the same for the voxel covariances (VGICP / AVGICP). */
+                           * bit 8: the same for the voxel covariances (VGICP / AVGICP),
+                           * bit 9: the cell grid of this map was built on the device (elm_map_set_index_build; set only when the device
+                           *        producer ran to the end). */
     uint64_t device_bytes;
     uint64_t n_query_voxels; /* cell grid: voxels of the dense statistics box; neighbourhood lists: query voxels (0 until built) */
     uint64_t nbr_entries;    /* cell grid: == n_points (every map point once); neighbourhood lists: ~27 x n_points */
@@ -203,8 +205,9 @@ void elm_map_destroy(elm_map* map);
 int elm_map_cal_voxel_cov_all(elm_map* map);
 /* VoxelHashMap::CalPointCovAll (vhm.hpp:252-257), HIP kernel over map points */
 int elm_map_cal_point_cov_all(elm_map* map, double d_search_dist);
-/* Build the search index of the P2P / GICP correspondence search now instead of on the first registration (an init-time cost of a few
- * seconds on a 10 M-point map): the dense half-voxel CELL GRID -- the map points once more, sorted by cell in 48-byte blocks of four,
+/* Build the search index of the P2P / GICP correspondence search now instead of on the first registration (an init-time cost of about
+ * 0.3 s on a 10 M-point map with the host build, 4 ms with the device index build below): the dense half-voxel CELL GRID -- the map
+ * points once more, sorted by cell in 48-byte blocks of four,
  * plus one offset per cell of the bounding box -- when the box fits the cell and byte budgets; its two-level form (tiles of 8 x 8 columns
  * with their own z range) when it does not; the round-1 neighbourhood lists (per query voxel the points of its 27 buckets, 27x the map)
  * only when neither can be built or ELM_KERNEL=lists asks for them.  Results do not depend on which index is in use (the reference's
@@ -756,6 +759,47 @@ int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uint8_t* drop,
  * their sum.  ELM_ERR_INVALID: no such build. */
 #define ELM_BUILD_STAGES 7
 int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]);
+
+/* ---------------------------------------------------------------- device index build -------------- */
+/* The P2P / GICP cell grid of a map (dense or two-level) is laid out on the host by default: the stored points come down, are
+ * counting-sorted by cell on one thread and go up again.  With ELM_INDEX_BUILD_DEVICE the same grid is built on the device from the stored
+ * points where they lie: the box of half-voxel cells (six words come down), the entry of every point, the counts, a stable radix sort
+ * of (entry, point number) by entry, the block starts (one word comes down: the block count), padding and fill.  The arrays it leaves
+ * -- block starts, blocks, slot points, tile table -- and every field of the map's view are byte for byte the host build's, so
+ * elm_map_get_info (but for layout_flags bit 9), registrations and elm_map_get_correspondences are too.  WHICH form a map gets is decided
+ * by the same host arithmetic on the same numbers (ELM_GRID as ever); the device producer drops the host-memory term of the byte budget
+ * and adds its scratch (16 bytes per point, 1 KB per 1024 points for the sort's histogram, 12 bytes per tile of the two-level form; no
+ * word per entry beyond the table that becomes grid_start).  When that scratch is not affordable, a device allocation fails, or a size
+ * passes the device kernels' 32-bit indices (2^31 - 1 points, 0xF0000000 entries), the host producer builds the same form and bit 9 stays
+ * clear.  The preference is stored on the map and governs every later build of its P2P / GICP search index (the lazy build at the first
+ * registration and elm_map_build_neighbourhoods); the voxel-mean lists and the neighbourhood lists are host builds either way.
+ *   ELM_OK               also when the index is already built: nothing changes
+ *   ELM_ERR_INVALID      map NULL, where not one of the two values
+ *   ELM_ERR_UNSUPPORTED  (text in elm_last_error) a map with replicas, the lead of a device group, a communicator or hook attached */
+#define ELM_INDEX_BUILD_HOST 0
+#define ELM_INDEX_BUILD_DEVICE 1
+int elm_map_set_index_build(elm_map* map, int where);
+/* Device milliseconds of the stages of the map's device index build: [0] box, [1] entries and counts (two-level form: with the tile
+ * table), [2] sort, [3] block starts, [4] padding and fill.  ELM_ERR_INVALID: the map's grid was not built on the device. */
+#define ELM_INDEX_STAGES 5
+int elm_map_index_build_stages(const elm_map* map, double ms[ELM_INDEX_STAGES]);
+/* The cell grid as it lies on the device (whoever built it).  desc gets the fields of the map's view and the full counts; each array
+ * may be NULL, and at most its cap entries are written: start n_start_words words, blocks12 n_blocks x 12 floats (x[4] y[4] z[4]; cap
+ * in blocks), slot_point 4 * n_blocks words (cap in words), tiles2 n_tiles x 2 words (cap in tiles; n_tiles = 0 for the dense form).
+ * Does not build anything: ELM_ERR_UNSUPPORTED when the map has no cell grid (not built yet, or it has neighbourhood lists). */
+typedef struct elm_cell_grid_desc {
+    int32_t gx0, gy0, gz0, gnx, gny, gnz; /* the box of cells (two-level form: gnx, gny rounded up to whole tiles) */
+    int32_t vx0, vy0, vz0, vnx, vny, vnz; /* dense form: the statistics box of voxels */
+    int32_t gtny;
+    int32_t grid_tiled;
+    int32_t grid_wide;
+    uint32_t grid_nslots;
+    uint64_t n_start_words;
+    uint64_t n_blocks;
+    uint64_t n_tiles;
+} elm_cell_grid_desc;
+int elm_map_download_cell_grid(const elm_map* map, elm_cell_grid_desc* desc, uint32_t* start, size_t start_cap, float* blocks12, size_t block_cap,
+                               uint32_t* slot_point, size_t slot_cap, uint32_t* tiles2, size_t tile_cap);
 
 /* ---------------------------------------------------------------- deskew -------------------------- */
 /* Tables produced by ImuDeskewInfo / OdomDeskewInfo (pcm.cpp:533-729). */
