@@ -290,9 +290,9 @@ extern "C" int elm_ctx_measure_h2d(elm_ctx* ctx, const void* host, size_t bytes,
 // what the other host units ask of a context (elm_hostapi.hpp)
 namespace elm_host {
 void ctx_set_error(elm_ctx* ctx, const std::string& text) { if (ctx) ctx->last_error = text; }
-void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc) {
-    *rc = dev_reserve(ctx, ctx->d_reloc[which], bytes);
-    return *rc == ELM_OK ? ctx->d_reloc[which].p : nullptr;
+void* ctx_reloc_scratch(elm_ctx* ctx, ScratchSlot slot, size_t bytes, int* rc) {
+    *rc = dev_reserve(ctx, ctx->d_reloc[slot], bytes);
+    return *rc == ELM_OK ? ctx->d_reloc[slot].p : nullptr;
 }
 bool ctx_is_alive(const elm_ctx* ctx, uint64_t id) { return ctx_alive(ctx, id); }
 int free_space_form() { return check_mode("free_wave") ? 1 : 0; }

@@ -293,4 +293,20 @@ __device__ __forceinline__ void store_chunk_partial(const uint32_t (&v)[W], uint
     if (tid < (uint32_t)W) out[tid] = ((wcnt[0][tid] + wcnt[1][tid]) + wcnt[2][tid]) + wcnt[3][tid];
 }
 
+// Its counterpart in the sum kernels: word k of the n consecutive chunk partials at p (W words each), summed in chunk order -- the first
+// N32 words in 32 bits into a32[k], the others in 64 bits into a64[k - N32] (none: nullptr).
+template <int W, int N32>
+__device__ __forceinline__ void sum_chunk_partials(const uint32_t* __restrict__ p, uint32_t n, uint32_t* a32, uint64_t* a64) {
+#pragma unroll
+    for (int k = 0; k < N32; ++k) a32[k] = 0;
+#pragma unroll
+    for (int k = N32; k < W; ++k) a64[k - N32] = 0;
+    for (uint32_t c = 0; c < n; ++c, p += W) {
+#pragma unroll
+        for (int k = 0; k < N32; ++k) a32[k] += p[k];
+#pragma unroll
+        for (int k = N32; k < W; ++k) a64[k - N32] += p[k];
+    }
+}
+
 } // namespace elm

@@ -231,11 +231,8 @@ int find_objects_impl(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule*
     if (e != hipSuccess) return dev_error(ctx, what, e);
     uint32_t cnt[kObjCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
     e = hipMemsetAsync(g->o.counters, 0, kObjCounters * sizeof(uint32_t), st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch_obj_find(st, g->t, g->o, rule->min_hit, rule->hit_per_through, rule->connectivity, rule->min_cells, (uint32_t)g->count);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launched([&] { launch_obj_find(st, g->t, g->o, rule->min_hit, rule->hit_per_through, rule->connectivity, rule->min_cells, (uint32_t)g->count); });
     if (e == hipSuccess) e = hipMemcpyAsync(cnt, g->o.counters, sizeof(cnt), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
@@ -256,9 +253,7 @@ int find_objects_impl(elm_ctx* ctx, elm_growth* g, const elm_growth_object_rule*
     std::vector<ObjRecord> rec(n_listed);
     std::vector<uint32_t> listed(n_listed);
     if (n_listed) {
-        (void)hipGetLastError();
-        launch_obj_gather(st, g->o, n_listed, g->o_out);
-        e = hipGetLastError();
+        e = launched([&] { launch_obj_gather(st, g->o, n_listed, g->o_out); });
         if (e == hipSuccess) e = hipMemcpyAsync(rec.data(), g->o_out, (size_t)n_listed * sizeof(ObjRecord), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(listed.data(), g->o.listed, (size_t)n_listed * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -356,12 +351,11 @@ int beam_objects_impl(elm_ctx* ctx, const elm_growth* g, const elm_scan* scan, c
     job.n = scan->n;
     pose_rows12(T16, job.rows);
     if (!n) return ELM_OK;
-    int32_t* d_out = (int32_t*)elm_host::ctx_reloc_scratch(ctx, 13, n * sizeof(int32_t), &rc);
-    if (!d_out) return rc;
+    QueryScratch scr{ctx};
+    int32_t* d_out = scr.take<int32_t>(elm_host::kScrBeamArrays, n);
+    if (scr.rc != ELM_OK) return scr.rc;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
-    (void)hipGetLastError();
-    launch_obj_beams(st, *ft, walk_params(*c), g->t, g->o, job, d_out);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launched([&] { launch_obj_beams(st, *ft, walk_params(*c), g->t, g->o, job, d_out); });
     if (e == hipSuccess) e = hipMemcpyAsync(obj, d_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e == hipSuccess ? ELM_OK : dev_error(ctx, what, e);

@@ -39,7 +39,8 @@ struct elm_ctx {
     uint16_t* d_hilbert = nullptr; // Hilbert index of every cell of the ordering grid (kOrderCells^2 entries)
     DevBuf d_order_jobs, d_order_tmp, d_arena, d_raw, d_flagged, d_asym;
     DevBuf d_q0, d_q1, d_q2, d_q3, d_q4, d_q5; // scratch of elm_map_get_correspondences / elm_align_clouds_local (kept between calls)
-    DevBuf d_reloc[16]; // scratch of elm_map_score_poses / elm_relocalize (0 .. 4) and of elm_relocalize_global (elm_reloc.cpp; kept between calls)
+    DevBuf d_reloc[elm_host::kScrCount]; // the query scratch, one buffer per ScratchSlot (elm_hostapi.hpp): relocalization and the map
+                                         // queries of elm_query.hpp; kept between calls
     bool work_counters = false; // elm_ctx_set_work_counters: the accumulate launches also sum the work counters of
                                 // elm_reg_result (n_cand_total, n_occ_total, n_tested_total, fallback_blocks); off: those fields read 0
     void* h_jobs = nullptr; // pinned: ordering job descriptors

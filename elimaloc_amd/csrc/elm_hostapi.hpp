@@ -22,8 +22,29 @@ int callback_register(elm_ctx* ctx, const elm_map* map, const void* stage, const
 // (the structs behind the handles are in elm_host_types.hpp, which needs HIP; what follows DOES something and stays a function)
 // ... for elm_multi.cpp
 void ctx_set_error(elm_ctx* ctx, const std::string& text);
-// ... for elm_reloc.cpp
-void* ctx_reloc_scratch(elm_ctx* ctx, int which, size_t bytes, int* rc); // grow-only device scratch 0..15 of the context (nullptr: *rc)
+// ... for elm_reloc.cpp and the map queries (elm_query.hpp)
+// The context's query scratch, one grow-only device buffer per role: asking a slot for more bytes than it holds frees what it held, so a
+// pointer into a slot is good until the next call that takes that slot.  A call takes its slots, queues its work and joins its stream
+// before it returns; nothing is held between calls.
+// A global search (elm_relocalize_global) HOLDS kScrPoints, kScrRows (its rotations), kScrBitmap, kScrGroundField and kScrLevelWindows
+// from search_setup to its end, over many launches: nothing that runs during a search may take one of those five.  Its batches take
+// kScrNodes, kScrNodePartials, kScrNodeOut, kScrLeafIds and kScrLeafRows, and never kScrPartials or kScrStats.
+enum ScratchSlot {
+    kScrPoints,       // the counted points of a score call or a search
+    kScrRows,         // pose rows, or the job table of an accumulate call; a search's rotations (held)
+    kScrBitmap,       // the level-0 occupancy bitmap
+    kScrPartials,     // per-chunk partial sums
+    kScrStats,        // per-pose / per-job stats, or scores
+    kScrGroundXY, kScrGroundZ, kScrGroundFound, // elm_map_ground_heights: queries, heights, flags
+    kScrNodes, kScrNodePartials, kScrNodeOut,   // a search's batch of nodes, its partials, its bounds or leaf scores
+    kScrLeafIds, kScrLeafRows,                  // a search's batch of leaves and their pose rows
+    kScrBeamArrays,   // per-beam outputs of a query, per-beam events, elm_growth_beam_objects' output
+    kScrWindowTmp,    // search_setup's temporary between the two window passes
+    kScrGroundField,  // a search's ground field (held)
+    kScrLevelWindows, // a search's level windows (held)
+    kScrCount
+};
+void* ctx_reloc_scratch(elm_ctx* ctx, ScratchSlot slot, size_t bytes, int* rc); // the slot with at least `bytes` (nullptr: *rc)
 // the map's ground-field bin index (built at the first call, kept with the map) and the xy bounds of its stored points {x_lo, x_hi, y_lo, y_hi}
 int map_ground_index(const elm_map* m, const elm::GroundIndex** gi, double bounds[4]);
 // ... for elm_free.cpp

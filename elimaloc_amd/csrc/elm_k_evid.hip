@@ -73,20 +73,14 @@ __global__ __launch_bounds__(256) void k_evid_sum(const uint32_t* __restrict__ p
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n_jobs) return;
     const uint32_t c0 = jobs[j].chunk0, c1 = c0 + (jobs[j].n + 255u) / 256u;
-    uint32_t a[7] = {0, 0, 0, 0, 0, 0, 0};
-    uint64_t e = 0, s = 0;
-    for (uint32_t c = c0; c < c1; ++c) {
-        const uint32_t* p = partial + (size_t)c * kEvidWords;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) a[k] += p[k];
-        e += p[7];
-        s += p[8];
-    }
+    uint32_t a[7];
+    uint64_t s[2]; // the events, the steps
+    sum_chunk_partials<kEvidWords, 7>(partial + (size_t)c0 * kEvidWords, c1 - c0, a, s);
     elm_evidence_stats o;
     o.n_cast = a[0]; o.n_observing = a[1]; o.n_walked = a[2]; o.n_truncated = a[3];
     o.n_through_beams = a[4]; o.n_end_hit = a[5]; o.n_end_free = a[6]; o._pad = 0;
-    o.n_through_events = e;
-    o.n_steps = s;
+    o.n_through_events = s[0];
+    o.n_steps = s[1];
     stats[j] = o;
 }
 

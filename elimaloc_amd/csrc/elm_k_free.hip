@@ -112,18 +112,13 @@ __global__ __launch_bounds__(256) void k_free_sum(const uint32_t* __restrict__ p
                                                   elm_freespace_stats* __restrict__ stats) {
     const uint32_t h = blockIdx.x * 256u + threadIdx.x;
     if (h >= n_poses) return;
-    uint32_t a[4] = {0, 0, 0, 0};
-    uint64_t s = 0, hs = 0;
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-        const uint32_t* p = partial + ((size_t)h * n_chunks + c) * kFreeWords;
-        a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3];
-        s += p[4];
-        hs += p[5];
-    }
+    uint32_t a[4];
+    uint64_t s[2];
+    sum_chunk_partials<kFreeWords, 4>(partial + (size_t)h * n_chunks * kFreeWords, n_chunks, a, s);
     elm_freespace_stats o;
     o.n_counted = a[0]; o.n_pierced = a[1]; o.n_end_occupied = a[2]; o.n_supported = a[3];
-    o.n_samples = s;
-    o.n_hit_samples = hs;
+    o.n_samples = s[0];
+    o.n_hit_samples = s[1];
     stats[h] = o;
 }
 

@@ -121,14 +121,9 @@ __global__ __launch_bounds__(256) void k_ray_sum(const uint32_t* __restrict__ pa
                                                  elm_raycast_stats* __restrict__ stats) {
     const uint32_t h = blockIdx.x * 256u + threadIdx.x;
     if (h >= n_poses) return;
-    uint32_t a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t s = 0;
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-        const uint32_t* p = partial + ((size_t)h * n_chunks + c) * kRayWords;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a[k] += p[k];
-        s += p[8];
-    }
+    uint32_t a[8];
+    uint64_t s;
+    sum_chunk_partials<kRayWords, 8>(partial + (size_t)h * n_chunks * kRayWords, n_chunks, a, &s);
     elm_raycast_stats o;
     o.n_cast = a[0]; o.n_hit = a[1]; o.n_miss = a[2]; o.n_truncated = a[3];
     o.n_compared = a[4]; o.n_match = a[5]; o.n_through = a[6]; o.n_front = a[7];

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "elm_internal.hpp"
+#include "elm_dev_fine.hpp"
 #include "elm_dev_pairs.hpp"
 
 namespace elm {
@@ -105,8 +106,8 @@ __global__ __launch_bounds__(256) void k_reloc_score(const DevMap m, const float
 __global__ __launch_bounds__(256) void k_reloc_sum(const uint32_t* __restrict__ partial, uint32_t n_chunks, uint32_t n_poses, uint32_t* __restrict__ scores) {
     const uint32_t h = blockIdx.x * 256u + threadIdx.x;
     if (h >= n_poses) return;
-    uint32_t s = 0;
-    for (uint32_t c = 0; c < n_chunks; ++c) s += partial[(size_t)h * n_chunks + c];
+    uint32_t s;
+    sum_chunk_partials<1, 1>(partial + (size_t)h * n_chunks, n_chunks, &s, nullptr);
     scores[h] = s;
 }
 

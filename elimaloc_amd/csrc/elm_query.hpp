@@ -1,7 +1,7 @@
-// elm_query.hpp -- the host side that the plain map queries share: the free-space check (elm_free.cpp), the ray cast (elm_ray.cpp), the
-// map evidence (elm_evid.cpp) and the map growth (elm_grow.cpp), with check_plain for the relocalization calls (elm_reloc.cpp).  The small
-// argument checks; the call of one scan at many poses (ray cast, free-space check); the call of many (scan, pose) jobs on an object that
-// counts (evidence, growth).  Host-side C++17, everything inline.
+// elm_query.hpp -- the host side that the calls on the context's query scratch share: the free-space check (elm_free.cpp), the ray cast
+// (elm_ray.cpp), the map evidence (elm_evid.cpp), the map growth (elm_grow.cpp) and relocalization (elm_reloc.cpp).  The small argument
+// checks, the scratch taker and the launch check; the call of one scan at many poses (ray cast, free-space check); the call of many
+// (scan, pose) jobs on an object that counts (evidence, growth).  Host-side C++17, everything inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -54,6 +54,25 @@ int guard_alloc(elm_ctx* ctx, const char* what, Body body) {
     }
 }
 
+// The context's scratch slots (elm_hostapi.hpp), taken one after another: after the first failure take() returns nullptr without asking
+// further, and rc holds that failure.
+struct QueryScratch {
+    elm_ctx* ctx;
+    int rc = ELM_OK;
+    template <class T>
+    T* take(elm_host::ScratchSlot s, size_t count) {
+        return rc == ELM_OK ? (T*)elm_host::ctx_reloc_scratch(ctx, s, count * sizeof(T), &rc) : nullptr;
+    }
+};
+
+// launch(), and what its launches say: an error left behind by an earlier call is dropped first
+template <class Launch>
+hipError_t launched(Launch launch) {
+    (void)hipGetLastError();
+    launch();
+    return hipGetLastError();
+}
+
 // ---- one scan at many poses (ray cast, free-space check)
 // The argument checks of the entry point, config_ok being the call's own verdict on its config.  ELM_OK: go on, unless n_poses is 0.
 inline int check_pose_query(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses, bool config_ok,
@@ -79,10 +98,10 @@ inline int open_pose_query(elm_ctx* ctx, const elm_map* map, int sub, const elm_
     q.n = scan->n;
     return ELM_OK;
 }
-// The call itself: the pose rows go up (scratch 1), launch(stream, d_rows, d_part, d_stats, d_arr) queues the kernels on the partials
-// (scratch 3: part_words per pose and 256-beam chunk), the stats (scratch 4) and the per-beam outputs (scratch 13: arr_bytes, or nullptr
-// when none is asked for), the stats come down, download(stream, d_arr) queues the per-beam copies, and the stream is joined.  A scan
-// without points: zero stats.
+// The call itself: the pose rows go up (kScrRows), launch(stream, d_rows, d_part, d_stats, d_arr) queues the kernels on the partials
+// (kScrPartials: part_words per pose and 256-beam chunk), the stats (kScrStats) and the per-beam outputs (kScrBeamArrays: arr_bytes, or
+// nullptr when none is asked for), the stats come down, download(stream, d_arr) queues the per-beam copies, and the stream is joined.  A
+// scan without points: zero stats.
 template <class Stats, class Launch, class Download>
 int run_pose_query(elm_ctx* ctx, const PoseQuery& q, const double* poses16, uint32_t n_poses, int part_words, Stats* stats, size_t arr_bytes,
                    const char* what, Launch launch, Download download) {
@@ -93,19 +112,15 @@ int run_pose_query(elm_ctx* ctx, const PoseQuery& q, const double* poses16, uint
     std::vector<double> rows((size_t)n_poses * 12);
     for (uint32_t h = 0; h < n_poses; ++h) pose_rows12(poses16 + 16 * (size_t)h, &rows[12 * (size_t)h]);
     const uint32_t n_chunks = (uint32_t)((q.n + 255) / 256);
-    int rc = ELM_OK;
-    double* d_rows = (double*)elm_host::ctx_reloc_scratch(ctx, 1, rows.size() * sizeof(double), &rc);
-    uint32_t* d_part = d_rows ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)n_poses * n_chunks * part_words * sizeof(uint32_t), &rc) : nullptr;
-    Stats* d_stats = d_part ? (Stats*)elm_host::ctx_reloc_scratch(ctx, 4, (size_t)n_poses * sizeof(Stats), &rc) : nullptr;
-    char* d_arr = d_stats && arr_bytes ? (char*)elm_host::ctx_reloc_scratch(ctx, 13, arr_bytes, &rc) : nullptr;
-    if (!d_stats || (arr_bytes && !d_arr)) return rc;
+    QueryScratch scr{ctx};
+    double* d_rows = scr.take<double>(elm_host::kScrRows, rows.size());
+    uint32_t* d_part = scr.take<uint32_t>(elm_host::kScrPartials, (size_t)n_poses * n_chunks * part_words);
+    Stats* d_stats = scr.take<Stats>(elm_host::kScrStats, n_poses);
+    char* d_arr = arr_bytes ? scr.take<char>(elm_host::kScrBeamArrays, arr_bytes) : nullptr;
+    if (scr.rc != ELM_OK) return scr.rc;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     hipError_t e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch(st, d_rows, d_part, d_stats, d_arr);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launched([&] { launch(st, d_rows, d_part, d_stats, d_arr); });
     if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, (size_t)n_poses * sizeof(Stats), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = download(st, d_arr);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -177,10 +192,10 @@ inline JobTable build_jobs(const elm_scan* const* scans, const double* poses16, 
 }
 
 // The call itself, after the guard that no counter can wrap (one beam adds at most 1 to any counter, and the object never takes more
-// than 2^32 - 1 beams; `what` and `items` word its refusal).  The job table goes up (scratch 1), launch(stream, d_jobs, n_chunks, d_part,
-// d_stats, d_events) queues the kernels on the partials (scratch 3: part_words per chunk), the stats (scratch 4) and the first job's
-// per-beam events (scratch 13, nullptr when not asked for); the stats come down when asked for, then(stream) queues what else the call
-// reads back, the events come down and the stream is joined.
+// than 2^32 - 1 beams; `what` and `items` word its refusal).  The job table goes up (kScrRows), launch(stream, d_jobs, n_chunks, d_part,
+// d_stats, d_events) queues the kernels on the partials (kScrPartials: part_words per chunk), the stats (kScrStats) and the first job's
+// per-beam events (kScrBeamArrays, nullptr when not asked for); the stats come down when asked for, then(stream) queues what else the
+// call reads back, the events come down and the stream is joined.
 template <class Stats, class Launch, class Then>
 int run_jobs(elm_ctx* ctx, const JobTable& t, uint64_t& total_beams, const char* what, const char* items, int part_words, Stats* stats,
              uint16_t* events, Launch launch, Then then) {
@@ -192,19 +207,15 @@ int run_jobs(elm_ctx* ctx, const JobTable& t, uint64_t& total_beams, const char*
     if (stats) memset(stats, 0, n_jobs * sizeof(*stats));
     if (t.chunks == 0) return ELM_OK;
     const size_t n_ev = events ? t.jobs[0].n : 0;
-    int rc = ELM_OK;
-    elm::EvidJob* d_jobs = (elm::EvidJob*)elm_host::ctx_reloc_scratch(ctx, 1, n_jobs * sizeof(elm::EvidJob), &rc);
-    uint32_t* d_part = d_jobs ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)t.chunks * part_words * sizeof(uint32_t), &rc) : nullptr;
-    Stats* d_stats = d_part ? (Stats*)elm_host::ctx_reloc_scratch(ctx, 4, n_jobs * sizeof(Stats), &rc) : nullptr;
-    uint16_t* d_ev = d_stats && n_ev ? (uint16_t*)elm_host::ctx_reloc_scratch(ctx, 13, n_ev * sizeof(uint16_t), &rc) : nullptr;
-    if (!d_stats || (n_ev && !d_ev)) return rc;
+    QueryScratch scr{ctx};
+    elm::EvidJob* d_jobs = scr.take<elm::EvidJob>(elm_host::kScrRows, n_jobs);
+    uint32_t* d_part = scr.take<uint32_t>(elm_host::kScrPartials, (size_t)t.chunks * part_words);
+    Stats* d_stats = scr.take<Stats>(elm_host::kScrStats, n_jobs);
+    uint16_t* d_ev = n_ev ? scr.take<uint16_t>(elm_host::kScrBeamArrays, n_ev) : nullptr;
+    if (scr.rc != ELM_OK) return scr.rc;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     hipError_t e = hipMemcpyAsync(d_jobs, t.jobs.data(), n_jobs * sizeof(elm::EvidJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch(st, d_jobs, (uint32_t)t.chunks, d_part, d_stats, d_ev);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launched([&] { launch(st, d_jobs, (uint32_t)t.chunks, d_part, d_stats, d_ev); });
     if (e == hipSuccess) total_beams += t.beams; // the launch is queued: the counters will take these beams
     if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, n_jobs * sizeof(Stats), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = then(st);

@@ -14,7 +14,8 @@
 #include "elm_query.hpp"
 
 using namespace elm;
-using elm_query::check_plain;
+using namespace elm_host; // the scratch slots
+using namespace elm_query;
 
 extern "C" void elm_reloc_config_default(elm_reloc_config* c) {
     if (!c) return;
@@ -39,8 +40,6 @@ constexpr int kMaxTopK = 1024;
 // the dynamic LDS of the staged form: the wave counts + the bitmap within 64 KiB
 constexpr uint64_t kLdsBitmapMax = 65536 - (uint64_t)kRelocHyp * 4 * sizeof(uint32_t);
 
-bool finite_nonneg(double v) { return isfinite(v) && v >= 0.0; }
-
 // the fields elm_map_score_poses reads
 bool score_config_ok(const elm_reloc_config* c) {
     return c && isfinite(c->score_max_range_m) && c->score_max_range_m > 0.0 && c->lds_budget_bytes >= 0 && c->bitmap_max_bytes >= 0;
@@ -52,9 +51,9 @@ struct HypGrid {
 };
 
 bool grid_of(const elm_reloc_config* c, HypGrid* g) {
-    if (!score_config_ok(c) || !finite_nonneg(c->radius_xy_m) || !(isfinite(c->step_xy_m) && c->step_xy_m > 0.0) ||
-        !finite_nonneg(c->yaw_range_deg) || !(isfinite(c->step_yaw_deg) && c->step_yaw_deg > 0.0) || c->max_score_points <= 0 ||
-        c->top_k <= 0 || c->top_k > kMaxTopK || !finite_nonneg(c->nms_xy_m) || !finite_nonneg(c->nms_yaw_deg))
+    if (!score_config_ok(c) || !fin_ge0(c->radius_xy_m) || !(isfinite(c->step_xy_m) && c->step_xy_m > 0.0) ||
+        !fin_ge0(c->yaw_range_deg) || !(isfinite(c->step_yaw_deg) && c->step_yaw_deg > 0.0) || c->max_score_points <= 0 ||
+        c->top_k <= 0 || c->top_k > kMaxTopK || !fin_ge0(c->nms_xy_m) || !fin_ge0(c->nms_yaw_deg))
         return false;
     const double mm = floor(c->radius_xy_m / c->step_xy_m + 1e-9);
     g->full = c->yaw_range_deg >= 180.0;
@@ -72,12 +71,6 @@ double dyaw_deg(const HypGrid& g, const elm_reloc_config* c, long k) {
     if (k == 0) return 0.0;
     const double a = (double)((k + 1) / 2) * c->step_yaw_deg;
     return (k & 1) ? a : -a;
-}
-
-bool finite16(const double* T) {
-    for (int i = 0; i < 16; ++i)
-        if (!isfinite(T[i])) return false;
-    return true;
 }
 
 // R = Rz(dyaw_deg) R0 with the host's cos / sin (dyaw 0: exactly 1 and 0, so R carries R0 itself)
@@ -141,10 +134,9 @@ int score_impl(elm_ctx* ctx, const elm_map* map, const std::vector<float>& S, co
     std::vector<double> rows((size_t)n_poses * 12);
     double kmin[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, kmax[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     for (uint32_t h = 0; h < n_poses; ++h) {
-        const double* T = poses16 + 16 * (size_t)h;
         double* P = rows.data() + 12 * (size_t)h;
+        pose_rows12(poses16 + 16 * (size_t)h, P);
         for (int r = 0; r < 3; ++r) {
-            for (int q = 0; q < 4; ++q) P[r * 4 + q] = T[q * 4 + r];
             const double a0 = P[r * 4], a1 = P[r * 4 + 1], a2 = P[r * 4 + 2], t = P[r * 4 + 3];
             const double qlo = ((a0 * (a0 >= 0.0 ? lo[0] : hi[0]) + a1 * (a1 >= 0.0 ? lo[1] : hi[1])) + a2 * (a2 >= 0.0 ? lo[2] : hi[2])) + t;
             const double qhi = ((a0 * (a0 >= 0.0 ? hi[0] : lo[0]) + a1 * (a1 >= 0.0 ? hi[1] : lo[1])) + a2 * (a2 >= 0.0 ? hi[2] : lo[2])) + t;
@@ -173,28 +165,23 @@ int score_impl(elm_ctx* ctx, const elm_map* map, const std::vector<float>& S, co
     }
     if (form == 2) box = RelocBox{0, 0, 0, 0, 0, 0};
     const uint32_t n_chunks = (nS + kRelocChunk - 1) / kRelocChunk;
-    int rc = ELM_OK;
-    float* d_pts = (float*)elm_host::ctx_reloc_scratch(ctx, 0, (size_t)nS * 3 * sizeof(float), &rc);
-    double* d_rows = d_pts ? (double*)elm_host::ctx_reloc_scratch(ctx, 1, rows.size() * sizeof(double), &rc) : nullptr;
-    unsigned long long* d_bits = d_rows ? (unsigned long long*)elm_host::ctx_reloc_scratch(ctx, 2, std::max<uint64_t>(words64, 1) * 8, &rc) : nullptr;
-    uint32_t* d_part = d_bits ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 3, (size_t)n_poses * n_chunks * sizeof(uint32_t), &rc) : nullptr;
-    uint32_t* d_scores = d_part ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 4, (size_t)n_poses * sizeof(uint32_t), &rc) : nullptr;
-    if (!d_scores) return rc;
+    QueryScratch scr{ctx};
+    float* d_pts = scr.take<float>(kScrPoints, (size_t)nS * 3);
+    double* d_rows = scr.take<double>(kScrRows, rows.size());
+    unsigned long long* d_bits = scr.take<unsigned long long>(kScrBitmap, std::max<uint64_t>(words64, 1));
+    uint32_t* d_part = scr.take<uint32_t>(kScrPartials, (size_t)n_poses * n_chunks);
+    uint32_t* d_scores = scr.take<uint32_t>(kScrStats, n_poses);
+    if (scr.rc != ELM_OK) return scr.rc;
     hipError_t e = hipMemcpyAsync(d_pts, S.data(), (size_t)nS * 3 * sizeof(float), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        if (form < 2) launch_reloc_bitmap(st, m, box, n_cells, d_bits);
-        launch_reloc_score(st, form, m, d_pts, nS, d_rows, n_poses, box, (const uint32_t*)d_bits, (uint32_t)(2 * words64), d_part, d_scores);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launched([&] {
+            if (form < 2) launch_reloc_bitmap(st, m, box, n_cells, d_bits);
+            launch_reloc_score(st, form, m, d_pts, nS, d_rows, n_poses, box, (const uint32_t*)d_bits, (uint32_t)(2 * words64), d_part, d_scores);
+        });
     if (e == hipSuccess) e = hipMemcpyAsync(scores, d_scores, (size_t)n_poses * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        elm_host::ctx_set_error(ctx, std::string("relocalization scores: ") + hipGetErrorString(e));
-        return ELM_ERR_DEVICE;
-    }
-    return ELM_OK;
+    return e == hipSuccess ? ELM_OK : dev_error(ctx, "relocalization scores", e);
 }
 
 // the counted points: ((x*x + y*y) + z*z) <= r_max^2 in float64
@@ -274,7 +261,7 @@ int refine_kept(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t 
 int relocalize_impl(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_guess[16], const elm_reloc_config* c,
                     const elm_reg_config* reg, double T_out[16], elm_reg_result* result, elm_reloc_candidate* cands, int cap, int* n_cands) {
     HypGrid g;
-    if (!ctx || !map || !scan_xyz || n == 0 || n > 0x7FFFFFFFull || !T_guess || !finite16(T_guess) || !grid_of(c, &g) || !reg ||
+    if (!ctx || !map || !scan_xyz || n == 0 || n > 0x7FFFFFFFull || !T_guess || !poses_finite(T_guess, 1) || !grid_of(c, &g) || !reg ||
         reg->icp_method < ELM_P2P || reg->icp_method > ELM_AVGICP || !T_out || !result || cap < 0 || (cap > 0 && !cands))
         return ELM_ERR_INVALID;
     int rc = check_plain(ctx, "elm_relocalize");
@@ -318,7 +305,7 @@ int relocalize_impl(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, siz
 
 extern "C" int elm_reloc_make_hypotheses(const double T_guess[16], const elm_reloc_config* c, double* poses16, size_t cap, size_t* n) {
     HypGrid g;
-    if (!T_guess || !finite16(T_guess) || !grid_of(c, &g) || !n || (cap && !poses16)) return ELM_ERR_INVALID;
+    if (!T_guess || !poses_finite(T_guess, 1) || !grid_of(c, &g) || !n || (cap && !poses16)) return ELM_ERR_INVALID;
     *n = (size_t)g.K * g.W * g.W;
     if (cap) make_hypotheses(g, T_guess, c, poses16, std::min(cap, *n));
     return ELM_OK;
@@ -326,33 +313,23 @@ extern "C" int elm_reloc_make_hypotheses(const double T_guess[16], const elm_rel
 
 extern "C" int elm_map_score_poses(elm_ctx* ctx, const elm_map* map, const elm_scan* scan, const double* poses16, int n_poses,
                                    const elm_reloc_config* c, uint32_t* scores) {
-    if (!ctx || !map || !scan || !poses16 || n_poses <= 0 || !score_config_ok(c) || !scores) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, "elm_map_score_poses");
+    if (n_poses <= 0) return ELM_ERR_INVALID; // no poses: refused here, where the other pose queries return at once
+    int rc = check_pose_query(ctx, map, scan, poses16, n_poses, score_config_ok(c), scores, "elm_map_score_poses");
     if (rc != ELM_OK) return rc;
-    if (map->ctx != ctx || scan->ctx != ctx || ctx->in_flight) return ELM_ERR_INVALID;
-    for (int h = 0; h < n_poses; ++h)
-        if (!finite16(poses16 + 16 * (size_t)h)) return ELM_ERR_INVALID;
-    try {
+    return guard_alloc(ctx, "elm_map_score_poses", [&] {
         if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
         std::vector<float> xyz(3 * elm_scan_size(scan)), S;
         if ((rc = elm_scan_download(scan, xyz.data(), xyz.size() / 3)) != ELM_OK) return rc;
         counted_points(xyz.data(), xyz.size() / 3, 1, c->score_max_range_m, S);
         return score_impl(ctx, map, S, poses16, (uint32_t)n_poses, c, scores);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_map_score_poses: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    });
 }
 
 extern "C" int elm_relocalize(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_guess[16],
                               const elm_reloc_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
                               elm_reloc_candidate* cands, int cap, int* n_cands) {
-    try {
-        return relocalize_impl(ctx, map, scan_xyz, n, T_guess, c, reg, T_out, result, cands, cap, n_cands);
-    } catch (const std::bad_alloc&) {
-        if (ctx) elm_host::ctx_set_error(ctx, "elm_relocalize: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, "elm_relocalize",
+                       [&] { return relocalize_impl(ctx, map, scan_xyz, n, T_guess, c, reg, T_out, result, cands, cap, n_cands); });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -384,7 +361,7 @@ constexpr uint32_t kNodeBatch = 1u << 20; // nodes / leaves per launch
 bool global_config_ok(const elm_reloc_global_config* c) {
     if (!c || !(isfinite(c->step_xy_m) && c->step_xy_m > 0.0) || !(isfinite(c->step_yaw_deg) && c->step_yaw_deg > 0.0) ||
         !(isfinite(c->score_max_range_m) && c->score_max_range_m > 0.0) || isnan(c->score_min_height_m) || c->score_min_height_m == HUGE_VAL ||
-        c->max_score_points <= 0 || c->top_k <= 0 || c->top_k > kMaxTopK || !finite_nonneg(c->nms_xy_m) || !finite_nonneg(c->nms_yaw_deg) ||
+        c->max_score_points <= 0 || c->top_k <= 0 || c->top_k > kMaxTopK || !fin_ge0(c->nms_xy_m) || !fin_ge0(c->nms_yaw_deg) ||
         c->pool_min <= 0 || c->max_kz_span <= 0 || c->bitmap_max_bytes < 0)
         return false;
     const double r[4] = {c->x_min, c->x_max, c->y_min, c->y_max};
@@ -395,7 +372,7 @@ bool global_config_ok(const elm_reloc_global_config* c) {
 
 // T_tilt = [R0 | (0, 0, h)]: finite, no xy translation, bottom row (0 0 0 1)
 bool tilt_ok(const double* T) {
-    return T && finite16(T) && T[12] == 0.0 && T[13] == 0.0 && T[3] == 0.0 && T[7] == 0.0 && T[11] == 0.0 && T[15] == 1.0;
+    return T && poses_finite(T, 1) && T[12] == 0.0 && T[13] == 0.0 && T[3] == 0.0 && T[7] == 0.0 && T[11] == 0.0 && T[15] == 1.0;
 }
 
 struct Lattice {
@@ -406,6 +383,14 @@ struct Lattice {
     size_t size() const { return (size_t)K * NX * NY; }
     double x(long i) const { return x0 + (double)i * step; }
     double y(long j) const { return y0 + (double)j * step; }
+    // leaf h = (k NX + i) NY + j as a column-major 4 x 4 pose standing on the ground field gz
+    void pose16(size_t h, const std::vector<double>& gz, double* T) const {
+        const size_t k = h / ((size_t)NX * NY), i = h / NY % NX, j = h % NY;
+        for (int q = 0; q < 3; ++q)
+            for (int r = 0; r < 3; ++r) T[q * 4 + r] = rot[k * 9 + r * 3 + q];
+        T[3] = T[7] = T[11] = 0.0;
+        T[12] = x((long)i); T[13] = y((long)j); T[14] = gz[i * NY + j]; T[15] = 1.0;
+    }
 };
 
 // the lattice over rect {x_min, x_max, y_min, y_max}; false: more than 2^31 - 1 poses
@@ -428,11 +413,6 @@ bool lattice_of(const elm_reloc_global_config* c, const double rect[4], const do
     return true;
 }
 
-int hip_fail(elm_ctx* ctx, const char* what, hipError_t e) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
-    return ELM_ERR_DEVICE;
-}
-
 int ground_impl(elm_ctx* ctx, const elm_map* map, const double* xy, size_t n, double* z, int32_t* found) {
     const GroundIndex* gi = nullptr;
     double bounds[4];
@@ -440,22 +420,19 @@ int ground_impl(elm_ctx* ctx, const elm_map* map, const double* xy, size_t n, do
     if (rc != ELM_OK || n == 0) return rc;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     const size_t batch = (size_t)1 << 22;
-    double* d_xy = (double*)elm_host::ctx_reloc_scratch(ctx, 5, std::min(n, batch) * 2 * sizeof(double), &rc);
-    double* d_z = d_xy ? (double*)elm_host::ctx_reloc_scratch(ctx, 6, std::min(n, batch) * sizeof(double), &rc) : nullptr;
-    int32_t* d_f = d_z ? (int32_t*)elm_host::ctx_reloc_scratch(ctx, 7, std::min(n, batch) * sizeof(int32_t), &rc) : nullptr;
-    if (!d_f) return rc;
+    QueryScratch scr{ctx};
+    double* d_xy = scr.take<double>(kScrGroundXY, std::min(n, batch) * 2);
+    double* d_z = scr.take<double>(kScrGroundZ, std::min(n, batch));
+    int32_t* d_f = scr.take<int32_t>(kScrGroundFound, std::min(n, batch));
+    if (scr.rc != ELM_OK) return scr.rc;
     for (size_t o = 0; o < n; o += batch) {
         const size_t m = std::min(batch, n - o);
         hipError_t e = hipMemcpyAsync(d_xy, xy + 2 * o, m * 2 * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            (void)hipGetLastError();
-            launch_ground_heights(st, *gi, d_xy, (uint32_t)m, d_z, d_f);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launched([&] { launch_ground_heights(st, *gi, d_xy, (uint32_t)m, d_z, d_f); });
         if (e == hipSuccess) e = hipMemcpyAsync(z + o, d_z, m * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(found + o, d_f, m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return hip_fail(ctx, "ground heights", e);
+        if (e != hipSuccess) return dev_error(ctx, "ground heights", e);
     }
     return ELM_OK;
 }
@@ -517,16 +494,33 @@ struct Search {
     long nI(int l) const { return (L->NX + (1L << l) - 1) >> l; }
     long nJ(int l) const { return (L->NY + (1L << l) - 1) >> l; }
 
+    // One batched call: per slice of kNodeBatch of the n items, stage(scr, o, b, d_part, d_out) takes the slots of the slice's input,
+    // uploads it and queues the launches on the partials and the output (nothing once scr has failed); the b output words come down
+    // into out + o, and the stream is joined.
+    template <class Stage>
+    int batched(size_t n, uint32_t* out, const char* what, Stage stage) {
+        const uint32_t n_chunks = (nS + kRelocChunk - 1) / kRelocChunk;
+        for (size_t o = 0; o < n; o += kNodeBatch) {
+            const uint32_t b = (uint32_t)std::min<size_t>(kNodeBatch, n - o);
+            QueryScratch scr{ctx};
+            uint32_t* d_part = scr.take<uint32_t>(kScrNodePartials, (size_t)b * n_chunks);
+            uint32_t* d_out = scr.take<uint32_t>(kScrNodeOut, b);
+            hipError_t e = stage(scr, o, b, d_part, d_out);
+            if (scr.rc != ELM_OK) return scr.rc;
+            if (e == hipSuccess) e = hipMemcpyAsync(out + o, d_out, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return dev_error(ctx, what, e);
+        }
+        return ELM_OK;
+    }
+
     int bound(int l, const std::vector<uint32_t>& nodes, std::vector<uint32_t>& out) { // nodes: (k, I, J) triples
         const size_t n = nodes.size() / 3;
         out.resize(n);
         if (stats) { stats->nodes_bounded[l] += (int64_t)n; stats->point_evals += (int64_t)n * nS; }
         if (nS == 0) { std::fill(out.begin(), out.end(), 0u); return ELM_OK; }
-        const uint32_t n_chunks = (nS + kRelocChunk - 1) / kRelocChunk;
         std::vector<RelocNode> rec;
-        int rc = ELM_OK;
-        for (size_t o = 0; o < n; o += kNodeBatch) {
-            const uint32_t b = (uint32_t)std::min<size_t>(kNodeBatch, n - o);
+        return batched(n, out.data(), "global relocalization bounds", [&](QueryScratch& scr, size_t o, uint32_t b, uint32_t* d_part, uint32_t* d_out) {
             rec.resize(b);
             for (uint32_t q = 0; q < b; ++q) {
                 const uint32_t k = nodes[3 * (o + q)], I = nodes[3 * (o + q) + 1], J = nodes[3 * (o + q) + 2];
@@ -537,22 +531,16 @@ struct Search {
                 r.zlo = zmin[l][(size_t)I * nJ(l) + J]; r.zhi = zmax[l][(size_t)I * nJ(l) + J];
                 r.k = (int32_t)k; r._pad = 0;
             }
-            RelocNode* d_nodes = (RelocNode*)elm_host::ctx_reloc_scratch(ctx, 8, (size_t)b * sizeof(RelocNode), &rc);
-            uint32_t* d_part = d_nodes ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 9, (size_t)b * n_chunks * sizeof(uint32_t), &rc) : nullptr;
-            uint32_t* d_out = d_part ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 10, (size_t)b * sizeof(uint32_t), &rc) : nullptr;
-            if (!d_out) return rc;
+            RelocNode* d_nodes = scr.take<RelocNode>(kScrNodes, b);
+            if (scr.rc != ELM_OK) return hipSuccess;
             hipError_t e = hipMemcpyAsync(d_nodes, rec.data(), (size_t)b * sizeof(RelocNode), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                (void)hipGetLastError();
-                launch_reloc_bound(st, *m, d_pts, nS, d_nodes, b, d_rot, box, d_lv + (size_t)(l - 1) * words, w[l],
-                                   (uint32_t)std::max(stats_kz_cap, 1), d_part, d_out);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(out.data() + o, d_out, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return hip_fail(ctx, "global relocalization bounds", e);
-        }
-        return ELM_OK;
+            if (e == hipSuccess)
+                e = launched([&] {
+                    launch_reloc_bound(st, *m, d_pts, nS, d_nodes, b, d_rot, box, d_lv + (size_t)(l - 1) * words, w[l],
+                                       (uint32_t)std::max(stats_kz_cap, 1), d_part, d_out);
+                });
+            return e;
+        });
     }
     int stats_kz_cap = 64;
 
@@ -561,27 +549,18 @@ struct Search {
         out.resize(n);
         if (stats) { stats->leaves_scored += (int64_t)n; stats->point_evals += (int64_t)n * nS; }
         if (nS == 0) { std::fill(out.begin(), out.end(), 0u); return ELM_OK; }
-        const uint32_t n_chunks = (nS + kRelocChunk - 1) / kRelocChunk;
-        int rc = ELM_OK;
-        for (size_t o = 0; o < n; o += kNodeBatch) {
-            const uint32_t b = (uint32_t)std::min<size_t>(kNodeBatch, n - o);
-            uint32_t* d_h = (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 11, (size_t)b * sizeof(uint32_t), &rc);
-            double* d_rows = d_h ? (double*)elm_host::ctx_reloc_scratch(ctx, 12, (size_t)b * 12 * sizeof(double), &rc) : nullptr;
-            uint32_t* d_part = d_rows ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 9, (size_t)b * n_chunks * sizeof(uint32_t), &rc) : nullptr;
-            uint32_t* d_out = d_part ? (uint32_t*)elm_host::ctx_reloc_scratch(ctx, 10, (size_t)b * sizeof(uint32_t), &rc) : nullptr;
-            if (!d_out) return rc;
+        return batched(n, out.data(), "global relocalization leaf scores", [&](QueryScratch& scr, size_t o, uint32_t b, uint32_t* d_part, uint32_t* d_out) {
+            uint32_t* d_h = scr.take<uint32_t>(kScrLeafIds, b);
+            double* d_rows = scr.take<double>(kScrLeafRows, (size_t)b * 12);
+            if (scr.rc != ELM_OK) return hipSuccess;
             hipError_t e = hipMemcpyAsync(d_h, hyps.data() + o, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                (void)hipGetLastError();
-                launch_reloc_leaf_rows(st, d_h, b, d_rot, L->x0, L->y0, L->step, (uint32_t)L->NX, (uint32_t)L->NY, d_gz, d_rows);
-                launch_reloc_score(st, 1, *m, d_pts, nS, d_rows, b, box, (const uint32_t*)d_b0, 0, d_part, d_out);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(out.data() + o, d_out, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return hip_fail(ctx, "global relocalization leaf scores", e);
-        }
-        return ELM_OK;
+            if (e == hipSuccess)
+                e = launched([&] {
+                    launch_reloc_leaf_rows(st, d_h, b, d_rot, L->x0, L->y0, L->step, (uint32_t)L->NX, (uint32_t)L->NY, d_gz, d_rows);
+                    launch_reloc_score(st, 1, *m, d_pts, nS, d_rows, b, box, (const uint32_t*)d_b0, 0, d_part, d_out);
+                });
+            return e;
+        });
     }
 
     // the valid children at level l - 1 of a level-l node
@@ -689,7 +668,6 @@ struct Search {
 // the search's device state: counted points, rotations, ground field, the level-0 bitmap of the map's key box and the level windows
 int search_setup(Search& S, const std::vector<float>& pts, const elm_reloc_global_config* c) {
     const Lattice& L = *S.L;
-    int rc = ELM_OK;
     S.nS = (uint32_t)(pts.size() / 3);
     S.stats_kz_cap = c->max_kz_span;
     // ground-height pyramids over the valid leaves (invalid: +inf / -inf, so a node without a valid leaf has zmin > zmax)
@@ -735,31 +713,30 @@ int search_setup(Search& S, const std::vector<float>& pts, const elm_reloc_globa
         return ELM_ERR_UNSUPPORTED;
     }
     S.box = RelocBox{lo[0], lo[1], lo[2], (uint32_t)nx, (uint32_t)ny, (uint32_t)nz};
-    S.d_pts = (float*)elm_host::ctx_reloc_scratch(S.ctx, 0, pts.size() * sizeof(float), &rc);
-    S.d_rot = S.d_pts ? (double*)elm_host::ctx_reloc_scratch(S.ctx, 1, L.rot.size() * sizeof(double), &rc) : nullptr;
-    S.d_b0 = S.d_rot ? (unsigned long long*)elm_host::ctx_reloc_scratch(S.ctx, 2, S.words * 4, &rc) : nullptr;
-    S.d_gz = S.d_b0 ? (double*)elm_host::ctx_reloc_scratch(S.ctx, 3, S.gz->size() * sizeof(double), &rc) : nullptr;
-    S.d_lv = S.d_gz ? (uint32_t*)elm_host::ctx_reloc_scratch(S.ctx, 13, std::max<uint64_t>(S.words * 4 * (uint64_t)top, 4), &rc) : nullptr;
-    uint32_t* d_tmp = S.d_lv ? (uint32_t*)elm_host::ctx_reloc_scratch(S.ctx, 14, S.words * 4, &rc) : nullptr;
-    if (!d_tmp) return rc;
+    QueryScratch scr{S.ctx}; // the first five are held to the end of the search (elm_hostapi.hpp)
+    S.d_pts = scr.take<float>(kScrPoints, pts.size());
+    S.d_rot = scr.take<double>(kScrRows, L.rot.size());
+    S.d_b0 = scr.take<unsigned long long>(kScrBitmap, S.words / 2); // nz is whole 64-bit words
+    S.d_gz = scr.take<double>(kScrGroundField, S.gz->size());
+    S.d_lv = scr.take<uint32_t>(kScrLevelWindows, std::max<uint64_t>(S.words * (uint64_t)top, 1));
+    uint32_t* d_tmp = scr.take<uint32_t>(kScrWindowTmp, S.words);
+    if (scr.rc != ELM_OK) return scr.rc;
     hipError_t e = hipMemcpyAsync(S.d_pts, pts.data(), pts.size() * sizeof(float), hipMemcpyHostToDevice, S.st);
     if (e == hipSuccess) e = hipMemcpyAsync(S.d_rot, L.rot.data(), L.rot.size() * sizeof(double), hipMemcpyHostToDevice, S.st);
     if (e == hipSuccess) e = hipMemcpyAsync(S.d_gz, S.gz->data(), S.gz->size() * sizeof(double), hipMemcpyHostToDevice, S.st);
-    if (e == hipSuccess) {
-        (void)hipGetLastError();
-        launch_reloc_bitmap(S.st, *S.m, S.box, cells, S.d_b0);
-        const uint32_t nzw = (uint32_t)(nz / 32);
-        for (int l = 1; l <= top; ++l) {
-            const uint32_t* in = l == 1 ? (const uint32_t*)S.d_b0 : S.d_lv + (size_t)(l - 2) * S.words;
-            const uint32_t wp = S.w[l - 1];
-            launch_reloc_window_or(S.st, in, d_tmp, (uint32_t)nx, (uint32_t)ny, nzw, 0, wp, S.w[l]);
-            launch_reloc_window_or(S.st, d_tmp, S.d_lv + (size_t)(l - 1) * S.words, (uint32_t)nx, (uint32_t)ny, nzw, 1, wp, S.w[l]);
-        }
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launched([&] {
+            launch_reloc_bitmap(S.st, *S.m, S.box, cells, S.d_b0);
+            const uint32_t nzw = (uint32_t)(nz / 32);
+            for (int l = 1; l <= top; ++l) {
+                const uint32_t* in = l == 1 ? (const uint32_t*)S.d_b0 : S.d_lv + (size_t)(l - 2) * S.words;
+                const uint32_t wp = S.w[l - 1];
+                launch_reloc_window_or(S.st, in, d_tmp, (uint32_t)nx, (uint32_t)ny, nzw, 0, wp, S.w[l]);
+                launch_reloc_window_or(S.st, d_tmp, S.d_lv + (size_t)(l - 1) * S.words, (uint32_t)nx, (uint32_t)ny, nzw, 1, wp, S.w[l]);
+            }
+        });
     if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e != hipSuccess) return hip_fail(S.ctx, "global relocalization bitmaps", e);
-    return ELM_OK;
+    return e == hipSuccess ? ELM_OK : dev_error(S.ctx, "global relocalization bitmaps", e);
 }
 
 double ms_since(const std::chrono::steady_clock::time_point& t) {
@@ -849,12 +826,7 @@ int relocalize_global_impl(elm_ctx* ctx, const elm_map* map, const float* scan_x
     std::vector<double> T0(kept.size() * 16);
     std::vector<uint32_t> kept_scores(kept.size());
     for (size_t b = 0; b < kept.size(); ++b) {
-        const long h = kept[b], k = h / NXY, i = h / L.NY % L.NX, j = h % L.NY;
-        double* T = &T0[16 * b];
-        for (int q = 0; q < 3; ++q)
-            for (int r = 0; r < 3; ++r) T[q * 4 + r] = L.rot[(size_t)k * 9 + r * 3 + q];
-        T[3] = T[7] = T[11] = 0.0;
-        T[12] = L.x(i); T[13] = L.y(j); T[14] = gz[(size_t)i * L.NY + j]; T[15] = 1.0;
+        L.pose16(kept[b], gz, &T0[16 * b]);
         for (size_t q = 0; q < leaves.size(); ++q)
             if (leaves[q] == kept[b]) { kept_scores[b] = scores[q]; break; }
     }
@@ -868,13 +840,10 @@ int relocalize_global_impl(elm_ctx* ctx, const elm_map* map, const float* scan_x
 
 extern "C" int elm_map_ground_heights(elm_ctx* ctx, const elm_map* map, const double* xy, size_t n, double* z, int32_t* found) {
     if (!ctx || !map || (n && (!xy || !z || !found)) || n > 0xFFFFFFFFull) return ELM_ERR_INVALID;
-    try {
+    return guard_alloc(ctx, "elm_map_ground_heights", [&] {
         int rc = common_checks(ctx, map, "elm_map_ground_heights");
         return rc != ELM_OK ? rc : ground_impl(ctx, map, xy, n, z, found);
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_map_ground_heights: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    });
 }
 
 extern "C" int elm_reloc_global_hypotheses(elm_ctx* ctx, const elm_map* map, const double T_tilt[16], const elm_reloc_global_config* c,
@@ -888,7 +857,7 @@ extern "C" int elm_reloc_global_hypotheses(elm_ctx* ctx, const elm_map* map, con
         return ELM_OK;
     }
     if (!ctx || !map) return ELM_ERR_INVALID;
-    try {
+    return guard_alloc(ctx, "elm_reloc_global_hypotheses", [&] {
         int rc = common_checks(ctx, map, "elm_reloc_global_hypotheses");
         if (rc != ELM_OK) return rc;
         Lattice L;
@@ -898,28 +867,16 @@ extern "C" int elm_reloc_global_hypotheses(elm_ctx* ctx, const elm_map* map, con
         *n = L.size();
         const size_t m = std::min(cap, *n);
         for (size_t h = 0; h < m; ++h) {
-            const size_t k = h / ((size_t)L.NX * L.NY), i = h / L.NY % L.NX, j = h % L.NY;
-            double* T = poses16 + 16 * h;
-            for (int q = 0; q < 3; ++q)
-                for (int r = 0; r < 3; ++r) T[q * 4 + r] = L.rot[k * 9 + r * 3 + q];
-            T[3] = T[7] = T[11] = 0.0;
-            T[12] = L.x((long)i); T[13] = L.y((long)j); T[14] = gz[i * L.NY + j]; T[15] = 1.0;
-            valid[h] = ok[i * L.NY + j];
+            L.pose16(h, gz, poses16 + 16 * h);
+            valid[h] = ok[h % ((size_t)L.NX * L.NY)];
         }
         return ELM_OK;
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, "elm_reloc_global_hypotheses: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    });
 }
 
 extern "C" int elm_relocalize_global(elm_ctx* ctx, const elm_map* map, const float* scan_xyz, size_t n, const double T_tilt[16],
                                      const elm_reloc_global_config* c, const elm_reg_config* reg, double T_out[16], elm_reg_result* result,
                                      elm_reloc_candidate* cands, int cap, int* n_cands, elm_reloc_global_stats* stats) {
-    try {
-        return relocalize_global_impl(ctx, map, scan_xyz, n, T_tilt, c, reg, T_out, result, cands, cap, n_cands, stats);
-    } catch (const std::bad_alloc&) {
-        if (ctx) elm_host::ctx_set_error(ctx, "elm_relocalize_global: host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
+    return guard_alloc(ctx, "elm_relocalize_global",
+                       [&] { return relocalize_global_impl(ctx, map, scan_xyz, n, T_tilt, c, reg, T_out, result, cands, cap, n_cands, stats); });
 }

@@ -232,7 +232,100 @@ def _colmajor16(T):
     return np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4).T).ravel()
 
 
-class Context:
+def _ptr(a):
+    """a numpy array as the C pointer to its element type (None stays None)"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
+def _pose_block(poses):
+    """poses [n, 4, 4] (or one [4, 4]) -> the column-major flat float64 block the C calls read"""
+    return np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+
+
+def _resident(ctx, scan):
+    """a Scan, or (m, 3) points uploaded for the call"""
+    return scan if isinstance(scan, Scan) else Scan(ctx, scan)
+
+
+def _callers_order(sc, given):
+    """The index that puts the per-beam outputs of the resident scan sc back into the order of `given`, the points it was uploaded from;
+    None for a Scan (it is answered in its resident order) or an empty scan.  Equal points are equal beams with equal outputs, so the
+    points are matched by their bytes."""
+    if isinstance(given, Scan) or not sc.n:
+        return None
+    key = np.dtype((np.void, 12))
+    res = np.ascontiguousarray(sc.points()).view(key).ravel()
+    own = np.ascontiguousarray(given, dtype=np.float32).reshape(-1, 3).view(key).ravel()
+    order = np.argsort(res, kind="stable")
+    return order[np.searchsorted(res[order], own)]
+
+
+def _sized(ctx, name, call, make, limit=None):
+    """The size-then-fill pair of a C call that answers into buffers of the caller's: call(None, 0, byref(n)) asks for the size,
+    make(rows) makes the buffers (never empty), call(buffers, m, byref(n)) fills them -> (m, buffers), m the size or `limit` if less."""
+    n = C.c_size_t(0)
+    check(call(None, 0, C.byref(n)), ctx._h, name)
+    m = n.value if limit is None else min(n.value, int(limit))
+    bufs = make(max(m, 1))
+    check(call(bufs, m, C.byref(n)), ctx._h, name)
+    return m, bufs
+
+
+class _Owned:
+    """An object that owns one C handle, kept in the attribute _attr: close() hands it to _destroy and forgets it, garbage collection
+    closes quietly."""
+    _attr = "_h"
+
+    def close(self):
+        h = getattr(self, self._attr, None)
+        if h:
+            self._destroy(h)
+            setattr(self, self._attr, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _MapChild(_Owned):
+    """An owned handle (_h) made for a map as it was built then (map, _map_h): _handle() gives it while both stand."""
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ElmError(f"{type(self).__name__}: closed")
+        if self.map._h is not self._map_h:
+            raise ElmError(f"{type(self).__name__}: its map was rebuilt or cleared")
+        return self._h
+
+
+def _accumulate(obj, single, batch, StatsC, stats_dict, scans, poses, cfg, events):
+    """MapEvidence.Accumulate and MapGrowth.Accumulate: `single` / `batch` name the two C entry points."""
+    h, L, who = obj._handle(), _lib.lib(), type(obj).__name__
+    if isinstance(scans, Scan) or (isinstance(scans, np.ndarray) and scans.ndim == 2):
+        sc = _resident(obj.ctx, scans)
+        st = StatsC()
+        ev = np.zeros(max(sc.n, 1), np.uint16) if events else None
+        check(getattr(L, single)(obj.ctx._h, h, sc._h, _dp(_colmajor16(poses)), C.byref(cfg), C.byref(st), _ptr(ev)), obj.ctx._h, single)
+        if not events:
+            return stats_dict(st)
+        ev, back = ev[:sc.n], _callers_order(sc, scans)
+        return stats_dict(st), (ev if back is None else np.ascontiguousarray(ev[back]))
+    if events:
+        raise ElmError(f"{who}.Accumulate: events are returned for a single scan only")
+    scs = [_resident(obj.ctx, s) for s in scans]
+    P = _pose_block(poses)
+    n = len(scs)
+    if P.size // 16 != n:
+        raise ElmError(f"{who}.Accumulate: one pose per scan")
+    hs = (C.c_void_p * max(n, 1))(*[s._h.value for s in scs])
+    st = (StatsC * max(n, 1))()
+    check(getattr(L, batch)(obj.ctx._h, h, hs, _dp(P), n, C.byref(cfg), st), obj.ctx._h, batch)
+    return [stats_dict(st[j]) for j in range(n)]
+
+
+class Context(_Owned):
     """One GPU, one HIP stream -- or, Context.multi([0, 1, ...]), the LEAD context of a device group: N GPUs inside this process, maps
     replicated, scans sharded, one all-reduce of the packed sums per ICP iteration (elm_ctx_create_multi).  elm_ctx_create fails without a
     gfx950 device."""
@@ -260,16 +353,8 @@ class Context:
         check(_lib.lib().elm_ctx_group_info(self._h, C.byref(n), C.byref(ex), ids, 64), self._h, "elm_ctx_group_info")
         return n.value, ex.value, [ids[i] for i in range(n.value)]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().elm_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        _lib.lib().elm_ctx_destroy(h)
 
     def synchronize(self):
         check(_lib.lib().elm_ctx_synchronize(self._h), self._h, "elm_ctx_synchronize")
@@ -574,8 +659,8 @@ class VoxelHashMap:
         """Voxel-occupancy scores (elm_map_score_poses) of poses [n, 4, 4] for a scan (a resident Scan, or (m, 3) points uploaded for the
         call): per pose the number of scan points within cfg.score_max_range_m whose stored key under the pose is a voxel of the map."""
         cfg = cfg if cfg is not None else RelocConfig()
-        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
-        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        sc = _resident(self.ctx, scan)
+        P = _pose_block(poses)
         n = P.size // 16
         out = np.zeros(max(n, 1), np.uint32)
         check(_lib.lib().elm_map_score_poses(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg),
@@ -584,13 +669,10 @@ class VoxelHashMap:
 
     def FineCells(self, sub=4):
         """The occupied fine cells (elm_map_fine_cells): floor(stored point / (voxel_size / sub)) -> int32 [n, 3], ascending (x, y, z)."""
-        n = C.c_size_t(0)
-        L = _lib.lib()
-        check(L.elm_map_fine_cells(self.ctx._h, self._handle(), int(sub), None, 0, C.byref(n)), self.ctx._h, "elm_map_fine_cells")
-        out = np.zeros((max(n.value, 1), 3), np.int32)
-        check(L.elm_map_fine_cells(self.ctx._h, self._handle(), int(sub), out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
-              self.ctx._h, "elm_map_fine_cells")
-        return out[:n.value]
+        m, out = _sized(self.ctx, "elm_map_fine_cells",
+                        lambda b, cap, n: _lib.lib().elm_map_fine_cells(self.ctx._h, self._handle(), int(sub), _ptr(b), cap, n),
+                        lambda rows: np.zeros((rows, 3), np.int32))
+        return out[:m]
 
     def CheckFreeSpace(self, scan, poses, cfg=None, hits=False):
         """Free-space check (elm_map_check_free_space) of poses [n, 4, 4] for a scan (a resident Scan, or (m, 3) points uploaded for the
@@ -598,25 +680,18 @@ class VoxelHashMap:
         point (pierced), the end points in / next to an occupied cell, the samples and the occupied samples.  hits=True: also the occupied
         samples of every ray, uint16 [n, m]; in the caller's point order for an array, in the resident order (Scan.points()) for a Scan."""
         cfg = cfg if cfg is not None else FreeSpaceConfig()
-        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
-        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        sc = _resident(self.ctx, scan)
+        P = _pose_block(poses)
         n = P.size // 16
         st = (FreeSpaceStatsC * max(n, 1))()
         H = np.zeros((max(n, 1), sc.n), np.uint16) if hits else None
-        check(_lib.lib().elm_map_check_free_space(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st,
-                                                  H.ctypes.data_as(C.POINTER(C.c_uint16)) if hits else None), self.ctx._h,
+        check(_lib.lib().elm_map_check_free_space(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st, _ptr(H)), self.ctx._h,
               "elm_map_check_free_space")
         out = [FreeSpaceStats(st[h]) for h in range(n)]
         if not hits:
             return out
-        H = H[:n]
-        if not isinstance(scan, Scan):  # back to the caller's order: equal points have equal counts, so match by the points' bytes
-            key = np.dtype((np.void, 12))
-            res = np.ascontiguousarray(sc.points()).view(key).ravel()
-            own = np.ascontiguousarray(scan, dtype=np.float32).reshape(-1, 3).view(key).ravel()
-            order = np.argsort(res, kind="stable")
-            H = H[:, order[np.searchsorted(res[order], own)]] if sc.n else H
-        return out, H
+        back = _callers_order(sc, scan)
+        return out, (H[:n] if back is None else H[:n][:, back])
 
     def RayCast(self, beams, poses, cfg=None, ranges=False, cells=False, flags=False):
         """Ray cast (elm_map_raycast) of beams at poses [n, 4, 4]: beam i runs from cfg.origin through point i of `beams` (a resident Scan,
@@ -627,8 +702,8 @@ class VoxelHashMap:
         [n, m] (0 not cast, 1 hit, 2 miss, 3 truncated) -- in the caller's beam order for an array, in the resident order (Scan.points())
         for a Scan."""
         cfg = cfg if cfg is not None else RayCastConfig()
-        sc = beams if isinstance(beams, Scan) else Scan(self.ctx, beams)
-        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        sc = _resident(self.ctx, beams)
+        P = _pose_block(poses)
         n = P.size // 16
         st = (RayCastStatsC * max(n, 1))()
         rows = max(n, 1)
@@ -640,22 +715,14 @@ class VoxelHashMap:
             arr["cell"] = np.zeros((rows, sc.n, 3), np.int32)
         if flags:
             arr["flag"] = np.zeros((rows, sc.n), np.uint8)
-        check(_lib.lib().elm_map_raycast(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st,
-                                         _dp(arr["range_in"]) if ranges else None, _dp(arr["range_out"]) if ranges else None,
-                                         arr["cell"].ctypes.data_as(C.POINTER(C.c_int32)) if cells else None,
-                                         arr["flag"].ctypes.data_as(C.POINTER(C.c_uint8)) if flags else None), self.ctx._h, "elm_map_raycast")
+        check(_lib.lib().elm_map_raycast(self.ctx._h, self._handle(), sc._h, _dp(P), n, C.byref(cfg), st, _ptr(arr.get("range_in")),
+                                         _ptr(arr.get("range_out")), _ptr(arr.get("cell")), _ptr(arr.get("flag"))), self.ctx._h,
+              "elm_map_raycast")
         out = [RayCastStats(st[h]) for h in range(n)]
         if not arr:
             return out
-        arr = {k: v[:n] for k, v in arr.items()}
-        if not isinstance(beams, Scan) and sc.n:  # back to the caller's order: equal points are equal beams, so match by the points' bytes
-            key = np.dtype((np.void, 12))
-            res = np.ascontiguousarray(sc.points()).view(key).ravel()
-            own = np.ascontiguousarray(beams, dtype=np.float32).reshape(-1, 3).view(key).ravel()
-            order = np.argsort(res, kind="stable")
-            back = order[np.searchsorted(res[order], own)]
-            arr = {k: np.ascontiguousarray(v[:, back]) for k, v in arr.items()}
-        return out, arr
+        back = _callers_order(sc, beams)
+        return out, {k: v[:n] if back is None else np.ascontiguousarray(v[:n][:, back]) for k, v in arr.items()}
 
     def RenderScan(self, pose, beams, cfg=None, noise=0.0, seed=None, return_index=False):
         """The scan a sensor at `pose` [4, 4] would record with the beam model `beams` (an (m, 3) array or a resident Scan): one RayCast,
@@ -763,18 +830,11 @@ class VoxelHashMap:
         hyp = (k NX + i) NY + j; a pose without ground under it is not valid.  max_poses: only the first ones."""
         cfg = cfg if cfg is not None else GlobalRelocConfig()
         T = _colmajor16(T_tilt)
-        n = C.c_size_t(0)
-        check(_lib.lib().elm_reloc_global_hypotheses(self.ctx._h, self._handle(), _dp(T), C.byref(cfg), None, None, 0, C.byref(n)),
-              self.ctx._h, "elm_reloc_global_hypotheses")
-        if max_poses is not None:
-            n.value = min(n.value, int(max_poses))
-        cnt = C.c_size_t(0)
-        out = np.empty((max(n.value, 1), 16))
-        valid = np.zeros(max(n.value, 1), np.int32)
-        check(_lib.lib().elm_reloc_global_hypotheses(self.ctx._h, self._handle(), _dp(T), C.byref(cfg), _dp(out),
-                                                     valid.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(cnt)),
-              self.ctx._h, "elm_reloc_global_hypotheses")
-        return out[:n.value].reshape(-1, 4, 4).transpose(0, 2, 1).copy(), valid[:n.value] != 0
+        m, (out, valid) = _sized(self.ctx, "elm_reloc_global_hypotheses",
+                                 lambda b, cap, n: _lib.lib().elm_reloc_global_hypotheses(self.ctx._h, self._handle(), _dp(T), C.byref(cfg),
+                                                                                          *map(_ptr, b or (None, None)), cap, n),
+                                 lambda rows: (np.empty((rows, 16)), np.zeros(rows, np.int32)), max_poses)
+        return out[:m].reshape(-1, 4, 4).transpose(0, 2, 1).copy(), valid[:m] != 0
 
     def GetAdjacentVoxels(self, point, search_range):  # vhm.cpp:208-243: keys only, whether or not such voxels exist
         v = self.PointToVoxel(point, self.voxel_size_).astype(np.int64)
@@ -800,7 +860,7 @@ class VoxelHashMap:
         return pts[first]
 
 
-class Scan:
+class Scan(_Owned):
     """A device-resident source scan (sensor frame)."""
 
     def __init__(self, ctx, xyz, n_total=None):
@@ -817,19 +877,11 @@ class Scan:
         check(_lib.lib().elm_scan_download(self._h, _fp(out), self.n), self.ctx._h, "elm_scan_download")
         return out[:self.n]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().elm_scan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        _lib.lib().elm_scan_destroy(h)
 
 
-class MapEvidence:
+class MapEvidence(_MapChild):
     """Map change evidence (elm_evidence, include/elimaloc_hip.h "map evidence"): two uint32 counters per occupied fine cell of a map,
     resident on the device.  Made by VoxelHashMap.Evidence(sub)."""
 
@@ -839,62 +891,21 @@ class MapEvidence:
         self._h = C.c_void_p()
         check(_lib.lib().elm_evidence_create(self.ctx._h, self._map_h, self.sub, C.byref(self._h)), self.ctx._h, "elm_evidence_create")
 
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise ElmError("MapEvidence: closed")
-        if self.map._h is not self._map_h:
-            raise ElmError("MapEvidence: its map was rebuilt or cleared")
-        return self._h
-
     def Accumulate(self, scans, poses, cfg=None, events=False):
         """Accumulate observations (elm_evidence_accumulate / _batch).  scans: one scan (a resident Scan, or (m, 3) points uploaded for the
         call) with one pose [4, 4] -> its EvidenceStats dict; or a list of scans with poses [n, 4, 4] -> a list of dicts, all jobs in one
         launch (the same Scan may appear several times).  events=True (one scan only): also the through events of every beam, uint16 [m],
         in the resident order (Scan.points()) for a Scan, in the caller's order for an array."""
-        cfg = cfg if cfg is not None else EvidenceConfig(sub=self.sub)
-        h = self._handle()
-        L = _lib.lib()
-        single = isinstance(scans, Scan) or (isinstance(scans, np.ndarray) and scans.ndim == 2)
-        if single:
-            sc = scans if isinstance(scans, Scan) else Scan(self.ctx, scans)
-            T = _colmajor16(poses)
-            st = EvidenceStatsC()
-            ev = np.zeros(max(sc.n, 1), np.uint16) if events else None
-            check(L.elm_evidence_accumulate(self.ctx._h, h, sc._h, _dp(T), C.byref(cfg), C.byref(st),
-                                            ev.ctypes.data_as(C.POINTER(C.c_uint16)) if events else None), self.ctx._h, "elm_evidence_accumulate")
-            if not events:
-                return EvidenceStats(st)
-            ev = ev[:sc.n]
-            if not isinstance(scans, Scan) and sc.n:  # back to the caller's order: equal points are equal beams
-                key = np.dtype((np.void, 12))
-                res = np.ascontiguousarray(sc.points()).view(key).ravel()
-                own = np.ascontiguousarray(scans, dtype=np.float32).reshape(-1, 3).view(key).ravel()
-                order = np.argsort(res, kind="stable")
-                ev = np.ascontiguousarray(ev[order[np.searchsorted(res[order], own)]])
-            return EvidenceStats(st), ev
-        if events:
-            raise ElmError("MapEvidence.Accumulate: events are returned for a single scan only")
-        scs = [s if isinstance(s, Scan) else Scan(self.ctx, s) for s in scans]
-        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
-        if P.size // 16 != len(scs):
-            raise ElmError("MapEvidence.Accumulate: one pose per scan")
-        n = len(scs)
-        hs = (C.c_void_p * max(n, 1))(*[s._h.value for s in scs])
-        st = (EvidenceStatsC * max(n, 1))()
-        check(L.elm_evidence_accumulate_batch(self.ctx._h, h, hs, _dp(P), n, C.byref(cfg), st), self.ctx._h, "elm_evidence_accumulate_batch")
-        return [EvidenceStats(st[j]) for j in range(n)]
+        return _accumulate(self, "elm_evidence_accumulate", "elm_evidence_accumulate_batch", EvidenceStatsC, EvidenceStats, scans, poses,
+                           cfg if cfg is not None else EvidenceConfig(sub=self.sub), events)
 
     def Counts(self):
         """(through, hit): uint32 [n_cells] each, entry for entry with map.FineCells(sub)."""
-        n = C.c_size_t(0)
-        L = _lib.lib()
         h = self._handle()
-        check(L.elm_evidence_counts(self.ctx._h, h, None, None, 0, C.byref(n)), self.ctx._h, "elm_evidence_counts")
-        t, hit = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
-        u32 = C.POINTER(C.c_uint32)
-        check(L.elm_evidence_counts(self.ctx._h, h, t.ctypes.data_as(u32), hit.ctypes.data_as(u32), n.value, C.byref(n)), self.ctx._h,
-              "elm_evidence_counts")
-        return t[:n.value], hit[:n.value]
+        m, (t, hit) = _sized(self.ctx, "elm_evidence_counts",
+                             lambda b, cap, n: _lib.lib().elm_evidence_counts(self.ctx._h, h, *map(_ptr, b or (None, None)), cap, n),
+                             lambda rows: (np.zeros(rows, np.uint32), np.zeros(rows, np.uint32)))
+        return t[:m], hit[:m]
 
     def Reset(self):
         check(_lib.lib().elm_evidence_reset(self.ctx._h, self._handle()), self.ctx._h, "elm_evidence_reset")
@@ -902,28 +913,17 @@ class MapEvidence:
     def StalePoints(self, rule=None):
         """bool [n_points] in map.Pointcloud() order: the stored points whose fine cell is stale by `rule` (EvidenceRule())."""
         rule = rule if rule is not None else EvidenceRule()
-        n = C.c_size_t(0)
-        L = _lib.lib()
         h = self._handle()
-        check(L.elm_evidence_stale_points(self.ctx._h, h, C.byref(rule), None, 0, C.byref(n)), self.ctx._h, "elm_evidence_stale_points")
-        f = np.zeros(max(n.value, 1), np.uint8)
-        check(L.elm_evidence_stale_points(self.ctx._h, h, C.byref(rule), f.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n)),
-              self.ctx._h, "elm_evidence_stale_points")
-        return f[:n.value].astype(bool)
+        m, f = _sized(self.ctx, "elm_evidence_stale_points",
+                      lambda b, cap, n: _lib.lib().elm_evidence_stale_points(self.ctx._h, h, C.byref(rule), _ptr(b), cap, n),
+                      lambda rows: np.zeros(rows, np.uint8))
+        return f[:m].astype(bool)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().elm_evidence_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        _lib.lib().elm_evidence_destroy(h)
 
 
-class MapGrowth:
+class MapGrowth(_MapChild):
     """Map growth (elm_growth, include/elimaloc_hip.h "map growth"): a device-resident table of candidate fine cells that the map does not
     hold, filled by the observations themselves.  Made by VoxelHashMap.Growth(capacity, sub)."""
 
@@ -933,51 +933,14 @@ class MapGrowth:
         self._h = C.c_void_p()
         check(_lib.lib().elm_growth_create(self.ctx._h, self._map_h, self.sub, self.capacity, C.byref(self._h)), self.ctx._h, "elm_growth_create")
 
-    def _handle(self):
-        if not getattr(self, "_h", None):
-            raise ElmError("MapGrowth: closed")
-        if self.map._h is not self._map_h:
-            raise ElmError("MapGrowth: its map was rebuilt or cleared")
-        return self._h
-
     def Accumulate(self, scans, poses, cfg=None, events=False):
         """One accumulate call (elm_growth_accumulate / _batch).  scans: one scan (a resident Scan, or (m, 3) points uploaded for the call)
         with one pose [4, 4] -> its GrowthStats dict; or a list of scans with poses [n, 4, 4] -> a list of dicts, all jobs in ONE call: the
         end points of all jobs are recorded before any beam walks (the same Scan may appear several times).  events=True (one scan only):
         also the through events of every beam, uint16 [m], in the resident order (Scan.points()) for a Scan, in the caller's order for an
         array."""
-        cfg = cfg if cfg is not None else GrowthConfig(sub=self.sub)
-        h = self._handle()
-        L = _lib.lib()
-        single = isinstance(scans, Scan) or (isinstance(scans, np.ndarray) and scans.ndim == 2)
-        if single:
-            sc = scans if isinstance(scans, Scan) else Scan(self.ctx, scans)
-            T = _colmajor16(poses)
-            st = GrowthStatsC()
-            ev = np.zeros(max(sc.n, 1), np.uint16) if events else None
-            check(L.elm_growth_accumulate(self.ctx._h, h, sc._h, _dp(T), C.byref(cfg), C.byref(st),
-                                          ev.ctypes.data_as(C.POINTER(C.c_uint16)) if events else None), self.ctx._h, "elm_growth_accumulate")
-            if not events:
-                return GrowthStats(st)
-            ev = ev[:sc.n]
-            if not isinstance(scans, Scan) and sc.n:  # back to the caller's order: equal points are equal beams
-                key = np.dtype((np.void, 12))
-                res = np.ascontiguousarray(sc.points()).view(key).ravel()
-                own = np.ascontiguousarray(scans, dtype=np.float32).reshape(-1, 3).view(key).ravel()
-                order = np.argsort(res, kind="stable")
-                ev = np.ascontiguousarray(ev[order[np.searchsorted(res[order], own)]])
-            return GrowthStats(st), ev
-        if events:
-            raise ElmError("MapGrowth.Accumulate: events are returned for a single scan only")
-        scs = [s if isinstance(s, Scan) else Scan(self.ctx, s) for s in scans]
-        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
-        if P.size // 16 != len(scs):
-            raise ElmError("MapGrowth.Accumulate: one pose per scan")
-        n = len(scs)
-        hs = (C.c_void_p * max(n, 1))(*[s._h.value for s in scs])
-        st = (GrowthStatsC * max(n, 1))()
-        check(L.elm_growth_accumulate_batch(self.ctx._h, h, hs, _dp(P), n, C.byref(cfg), st), self.ctx._h, "elm_growth_accumulate_batch")
-        return [GrowthStats(st[j]) for j in range(n)]
+        return _accumulate(self, "elm_growth_accumulate", "elm_growth_accumulate_batch", GrowthStatsC, GrowthStats, scans, poses,
+                           cfg if cfg is not None else GrowthConfig(sub=self.sub), events)
 
     def Count(self):
         """The candidate cells held now (known on the host after every call: no download)."""
@@ -1000,13 +963,11 @@ class MapGrowth:
     def AppearedPoints(self, rule=None):
         """float64 [k, 3]: the mean end point of every candidate cell that `rule` (GrowthRule()) calls appeared, in cell order."""
         rule = rule if rule is not None else GrowthRule()
-        n = C.c_size_t(0)
-        L = _lib.lib()
         h = self._handle()
-        check(L.elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), None, 0, C.byref(n)), self.ctx._h, "elm_growth_appeared_points")
-        out = np.zeros((max(n.value, 1), 3))
-        check(L.elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), _dp(out), n.value, C.byref(n)), self.ctx._h, "elm_growth_appeared_points")
-        return out[:n.value]
+        m, out = _sized(self.ctx, "elm_growth_appeared_points",
+                        lambda b, cap, n: _lib.lib().elm_growth_appeared_points(self.ctx._h, h, C.byref(rule), _ptr(b), cap, n),
+                        lambda rows: np.zeros((rows, 3)))
+        return out[:m]
 
     def FindObjects(self, rule=None):
         """The appeared cells grouped into objects on the device (elm_growth_find_objects; `rule`: GrowthObjectRule()) -> the stats dict
@@ -1020,13 +981,9 @@ class MapGrowth:
     def Objects(self):
         """The objects in ascending label order, as a dict of arrays: label int32 [m, 3], n_cells uint32 [m], lo / hi int32 [m, 3] (the
         bounding box in cells, inclusive), hit / through uint64 [m], cell_sum uint64 [m, 3] (the sum of e + 2^20 over the member cells)."""
-        L = _lib.lib()
         h = self._handle()
-        n = C.c_size_t(0)
-        check(L.elm_growth_objects(self.ctx._h, h, None, 0, C.byref(n)), self.ctx._h, "elm_growth_objects")
-        m = n.value
-        buf = (GrowthObjectC * max(m, 1))()
-        check(L.elm_growth_objects(self.ctx._h, h, buf, m, C.byref(n)), self.ctx._h, "elm_growth_objects")
+        m, buf = _sized(self.ctx, "elm_growth_objects", lambda b, cap, n: _lib.lib().elm_growth_objects(self.ctx._h, h, b, cap, n),
+                        lambda rows: (GrowthObjectC * rows)())
         a = np.frombuffer(buf, dtype=np.dtype([("label", np.int32, 3), ("n_cells", np.uint32), ("lo", np.int32, 3), ("hi", np.int32, 3),
                                                ("hit", np.uint64), ("through", np.uint64), ("cell_sum", np.uint64, 3)]))[:m]
         return {k: np.ascontiguousarray(a[k]) for k in a.dtype.names}
@@ -1034,13 +991,10 @@ class MapGrowth:
     def CellObjects(self):
         """int32 [count], one value per candidate cell in Cells()' order: the index of its object, -2 for a member of a small component,
         -1 for a cell that is not a member."""
-        L = _lib.lib()
         h = self._handle()
-        n = C.c_size_t(0)
-        check(L.elm_growth_cell_objects(self.ctx._h, h, None, 0, C.byref(n)), self.ctx._h, "elm_growth_cell_objects")
-        m = n.value
-        out = np.full(max(m, 1), -1, np.int32)
-        check(L.elm_growth_cell_objects(self.ctx._h, h, out.ctypes.data_as(C.POINTER(C.c_int32)), m, C.byref(n)), self.ctx._h, "elm_growth_cell_objects")
+        m, out = _sized(self.ctx, "elm_growth_cell_objects",
+                        lambda b, cap, n: _lib.lib().elm_growth_cell_objects(self.ctx._h, h, _ptr(b), cap, n),
+                        lambda rows: np.full(rows, -1, np.int32))
         return out[:m]
 
     def BeamObjects(self, scan, pose, cfg=None):
@@ -1049,7 +1003,7 @@ class MapGrowth:
         small component, -1 for anything else (elm_growth_beam_objects)."""
         cfg = cfg if cfg is not None else GrowthConfig(sub=self.sub)
         h = self._handle()
-        sc = scan if isinstance(scan, Scan) else Scan(self.ctx, scan)
+        sc = _resident(self.ctx, scan)
         out = np.full(max(sc.n, 1), -1, np.int32)
         check(_lib.lib().elm_growth_beam_objects(self.ctx._h, h, sc._h, _dp(_colmajor16(pose)), C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_int32))),
               self.ctx._h, "elm_growth_beam_objects")
@@ -1058,19 +1012,11 @@ class MapGrowth:
     def Reset(self):
         check(_lib.lib().elm_growth_reset(self.ctx._h, self._handle()), self.ctx._h, "elm_growth_reset")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().elm_growth_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        _lib.lib().elm_growth_destroy(h)
 
 
-class PinnedBuffer:
+class PinnedBuffer(_Owned):
     """Page-locked host memory (elm_host_alloc) viewed as a float32 numpy array."""
 
     def __init__(self, n_floats):
@@ -1079,17 +1025,11 @@ class PinnedBuffer:
             raise ElmError("elm_host_alloc failed")
         self.array = np.ctypeslib.as_array((C.c_float * int(n_floats)).from_address(self.ptr))
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            self.array = None
-            _lib.lib().elm_host_free(self.ptr)
-            self.ptr = None
+    _attr = "ptr"
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, ptr):
+        self.array = None
+        _lib.lib().elm_host_free(ptr)
 
 
 def _result_dict(r, trace=None):
@@ -1264,7 +1204,7 @@ class Registration:
     def pack_inputs(scans, initial_guesses):
         """(ctypes array of scan handles, contiguous column-major float64 guesses) as the C ABI takes them."""
         arr = (C.c_void_p * len(scans))(*[s._h for s in scans])
-        T0 = np.ascontiguousarray(np.asarray(initial_guesses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        T0 = _pose_block(initial_guesses)
         return arr, T0
 
     def RunRegisterStream(self, scans, voxel_map, initial_guesses, slots=32, m_config=None, trace=False, raw=False):
@@ -1302,7 +1242,7 @@ class Registration:
         else:
             ptrs = [k.ctypes.data for k in keep]
         arr = (C.c_void_p * B)(*ptrs)
-        T0 = np.ascontiguousarray(np.asarray(initial_guesses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1)
+        T0 = _pose_block(initial_guesses)
         return arr, npts, T0, keep
 
     def RunRegisterStreamHost(self, packed, voxel_map, slots=32, m_config=None, trace=False, raw=False):

@@ -208,3 +208,47 @@ int main(int argc, char**) {
                                "-I", os.path.join(ROOT, "include", "elimaloc"), "-I", os.path.join(ROOT, "include"), str(src),
                                "-L", libdir, "-lelimaloc_hip", "-Wl,-rpath," + libdir, "-o", str(exe)])
         assert subprocess.run([str(exe)]).returncode == 0
+
+
+@pytest.mark.gpu
+def test_score_poses_return_codes(L):
+    """elm_map_score_poses: every refusal before the device is touched is ELM_ERR_INVALID, the null check comes before the one-rank check,
+    and valid arguments on a context with a hook attached are ELM_ERR_UNSUPPORTED."""
+    from elimaloc_amd import _lib
+    from elimaloc_amd.registration import Context, RelocConfig, Scan, VoxelHashMap
+    INVALID, UNSUPPORTED = -1, -5
+    rng = np.random.default_rng(5)
+    world = rng.uniform(-3.0, 3.0, (200, 3)).astype(np.float32)
+    pts = world[:10].copy()
+    T = np.ascontiguousarray(np.eye(4)).ravel()
+    two = np.tile(T, 2)
+    nan2 = two.copy()
+    nan2[16 + 13] = float("nan")
+    cfg = RelocConfig()
+    out = np.zeros(2, np.uint32)
+    u32 = out.ctypes.data_as(C.POINTER(C.c_uint32))
+    ctx, other = Context(0), Context(0)
+    vm, ovm = VoxelHashMap(1.0, 30, ctx), VoxelHashMap(1.0, 30, other)
+    vm.AddPoints(world)
+    ovm.AddPoints(world)
+    sc, osc = Scan(ctx, pts), Scan(other, pts)
+
+    def code(c=ctx, m=vm, s=sc, poses=T, n=1, config=cfg, scores=u32):
+        return L.elm_map_score_poses(c._h, m._handle(), s._h, None if poses is None else _dp(poses), n,
+                                     None if config is None else C.byref(config), scores)
+
+    assert code() == _lib.ELM_OK and out[0] > 0
+    assert code(n=0) == INVALID and code(n=-1) == INVALID
+    assert code(scores=None) == INVALID and code(poses=None) == INVALID
+    assert code(poses=two, n=2) == _lib.ELM_OK and code(poses=nan2, n=2) == INVALID
+    assert code(config=RelocConfig(score_max_range_m=0.0)) == INVALID and code(config=None) == INVALID
+    assert code(m=ovm) == INVALID and code(s=osc) == INVALID
+    ctx.set_allreduce_hook(lambda p, n, s: 0)
+    assert code(scores=None) == INVALID and code(poses=None) == INVALID and code(n=0) == INVALID  # the null check comes first
+    assert code() == UNSUPPORTED and "one rank" in L.elm_last_error(ctx._h).decode()
+    assert code(m=ovm) == UNSUPPORTED  # ... and the one-rank check before the owners'
+    ctx.set_allreduce_hook(None)
+    assert code() == _lib.ELM_OK
+    del vm, ovm, sc, osc
+    ctx.close()
+    other.close()
