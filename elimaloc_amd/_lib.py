@@ -242,6 +242,29 @@ class CellGridDesc(C.Structure):
 
 INDEX_BUILD_HOST, INDEX_BUILD_DEVICE, INDEX_STAGES = 0, 1, 5
 
+
+class BuildSourcesC(C.Structure):
+    """elm_build_sources (include/elimaloc_hip.h, device map build from resident sources)."""
+    _fields_ = [("base", C.c_void_p), ("keep_within", C.c_int32), ("keep_center", C.c_double * 3), ("keep_radius_m", C.c_double),
+                ("scans", C.POINTER(C.c_void_p)), ("poses16", C.POINTER(C.c_double)), ("n_jobs", C.c_int32)]
+
+
+class BuildSourcesStatsC(C.Structure):
+    """elm_build_sources_stats: the counts of one elm_map_build_device_from."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_base_kept", "n_base_dropped", "n_scan_points", "n_points", "n_voxels")]
+
+
+class OdometryConfigC(C.Structure):
+    """elm_odometry_config (include/elimaloc_hip.h, LiDAR odometry on a rolling local map)."""
+    _fields_ = [("voxel_size", C.c_double), ("max_points_per_voxel", C.c_int32), ("max_range_m", C.c_double),
+                ("key_min_trans_m", C.c_double), ("key_min_rot_rad", C.c_double), ("reg", RegConfig)]
+
+
+class OdometryStepC(C.Structure):
+    """elm_odometry_step: what one elm_odometry_step_scan did."""
+    _fields_ = [("T", C.c_double * 16), ("registered", C.c_int32), ("is_success", C.c_int32), ("inserted", C.c_int32), ("reg", RegResult),
+                ("build", BuildSourcesStatsC)]
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -268,7 +291,9 @@ EXPORTS = [
     "elm_growth_config_default", "elm_growth_rule_default", "elm_growth_create", "elm_growth_destroy", "elm_growth_reset",
     "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
     "elm_growth_object_rule_default", "elm_growth_find_objects", "elm_growth_objects", "elm_growth_cell_objects", "elm_growth_beam_objects",
-    "elm_map_build_device", "elm_map_build_device_stages",
+    "elm_map_build_device", "elm_map_build_device_stages", "elm_map_build_device_from",
+    "elm_odometry_config_default", "elm_odometry_create", "elm_odometry_destroy", "elm_odometry_reset", "elm_odometry_predict",
+    "elm_odometry_step_scan", "elm_odometry_map",
     "elm_map_set_index_build", "elm_map_index_build_stages", "elm_map_download_cell_grid",
 ]
 
@@ -358,6 +383,17 @@ def lib():
     L.elm_map_build.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
     L.elm_map_build_device.argtypes = [vp, vp, C.POINTER(C.c_uint8), fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
     L.elm_map_build_device_stages.argtypes = [vp, dp]
+    L.elm_map_build_device_from.argtypes = [vp, C.POINTER(BuildSourcesC), C.c_double, C.c_int, C.POINTER(vp), C.POINTER(BuildSourcesStatsC)]
+    L.elm_odometry_config_default.argtypes = [C.POINTER(OdometryConfigC)]
+    L.elm_odometry_config_default.restype = None
+    L.elm_odometry_create.argtypes = [vp, C.POINTER(OdometryConfigC), C.POINTER(vp)]
+    L.elm_odometry_destroy.argtypes = [vp]
+    L.elm_odometry_destroy.restype = None
+    L.elm_odometry_reset.argtypes = [vp]
+    L.elm_odometry_predict.argtypes = [vp, dp]
+    L.elm_odometry_step_scan.argtypes = [vp, vp, dp, C.POINTER(OdometryStepC)]
+    L.elm_odometry_map.argtypes = [vp]
+    L.elm_odometry_map.restype = vp
     u32p = C.POINTER(C.c_uint32)
     L.elm_map_set_index_build.argtypes = [vp, C.c_int]
     L.elm_map_index_build_stages.argtypes = [vp, dp]

@@ -72,8 +72,23 @@ hipError_t read_word(hipStream_t st, const unsigned* d_word, unsigned* out) {
     return e == hipSuccess ? hipStreamSynchronize(st) : e;
 }
 
-int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double vs, int cap, elm_map** out) {
+// Who fills d_pos (the kept stored points of base) and d_in + K (the new points): the host's arrays (elm_map_build_device: drop bytes
+// and xyz go up), or the device's own producers (elm_map_build_device_from: the sphere and the job table).  n: the new points.
+struct BuildInput {
     const char* what = "elm_map_build_device";
+    const uint8_t* drop = nullptr; // host
+    const float* xyz = nullptr;    // host
+    size_t n = 0;
+    bool within = false; // device: keep the stored points inside the sphere
+    double center[3] = {0.0, 0.0, 0.0}, r2 = 0.0;
+    const JobTable* jobs = nullptr; // device: the new points are the jobs' scans at their poses (n = jobs->beams)
+    elm_build_sources_stats* stats = nullptr;
+};
+
+int build_impl(elm_ctx* ctx, const elm_map* base, const BuildInput& in, double vs, int cap, elm_map** out) {
+    const char* what = in.what;
+    const uint8_t* drop = in.drop;
+    const size_t n = in.n;
     if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     (void)hipGetLastError(); // drop stale errors of other libraries
@@ -91,14 +106,15 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
     unsigned* d_pos = nullptr;
     uint8_t* d_drop = nullptr;
     e = evs.mark(st);
-    if (e == hipSuccess && drop && n_base) {
+    if (e == hipSuccess && (drop || in.within) && n_base) {
         unsigned* d_blk = nullptr;
-        e = sc.get(&d_drop, n_base);
+        if (drop) e = sc.get(&d_drop, n_base);
         if (e == hipSuccess) e = sc.get(&d_pos, n_base);
         if (e == hipSuccess) e = sc.get(&d_blk, (size_t)n_base / 1024 + 1);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_drop, drop, n_base, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && drop) e = hipMemcpyAsync(d_drop, drop, n_base, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
-            launch_bd_keep(st, d_drop, n_base, d_pos);
+            if (drop) launch_bd_keep(st, d_drop, n_base, d_pos);
+            else launch_bd_keep_within(st, base->dm.pts, n_base, in.center, in.r2, d_pos);
             launch_bd_scan(st, d_pos, n_base, d_blk, d_total);
             e = read_word(st, d_total, &K);
         }
@@ -111,8 +127,26 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
     const unsigned N = K + (unsigned)n;
     Pt3* d_in = nullptr;
     e = sc.get(&d_in, N);
-    if (e == hipSuccess && K) launch_bd_compact(st, base->dm.pts, d_drop, d_pos, n_base, d_in);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(d_in + K, xyz, n * sizeof(Pt3), hipMemcpyHostToDevice, st); // (Pt3 is three packed floats)
+    if (e == hipSuccess && K) launch_bd_compact(st, base->dm.pts, d_drop, d_pos, n_base, K, d_in);
+    std::vector<uint32_t> pt0; // (read by the copy until the stream is joined)
+    if (e == hipSuccess && n && in.jobs) {
+        const size_t n_jobs = in.jobs->jobs.size();
+        EvidJob* d_jobs = nullptr;
+        uint32_t* d_pt0 = nullptr;
+        pt0.resize(n_jobs);
+        uint32_t first = 0;
+        for (size_t j = 0; j < n_jobs; ++j) {
+            pt0[j] = first;
+            first += in.jobs->jobs[j].n;
+        }
+        e = sc.get(&d_jobs, n_jobs);
+        if (e == hipSuccess) e = sc.get(&d_pt0, n_jobs);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, in.jobs->jobs.data(), n_jobs * sizeof(EvidJob), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_pt0, pt0.data(), n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) launch_bd_transform(st, d_jobs, (uint32_t)n_jobs, (uint32_t)in.jobs->chunks, d_pt0, d_in + K);
+    } else if (e == hipSuccess && n) {
+        e = hipMemcpyAsync(d_in + K, in.xyz, n * sizeof(Pt3), hipMemcpyHostToDevice, st); // (Pt3 is three packed floats)
+    }
     if (e == hipSuccess) e = evs.mark(st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
 
@@ -215,6 +249,7 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const flo
         std::copy(ms, ms + ELM_BUILD_STAGES, t_stage_ms);
         t_stage_ctx = ctx->id;
         t_stage_valid = true;
+        if (in.stats) *in.stats = elm_build_sources_stats{K, n_base - K, n, n_pts, n_vox};
     }
     return rc;
 }
@@ -232,7 +267,45 @@ extern "C" int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uin
         elm_host::ctx_set_error(ctx, "elm_map_build_device: more than 2^31 - 1 input points");
         return ELM_ERR_UNSUPPORTED;
     }
-    return guard_alloc(ctx, "elm_map_build_device", [&] { return build_impl(ctx, base, drop, xyz, n, voxel_size, max_points_per_voxel, out); });
+    BuildInput in;
+    in.drop = drop;
+    in.xyz = xyz;
+    in.n = n;
+    return guard_alloc(ctx, "elm_map_build_device", [&] { return build_impl(ctx, base, in, voxel_size, max_points_per_voxel, out); });
+}
+
+extern "C" int elm_map_build_device_from(elm_ctx* ctx, const elm_build_sources* src, double voxel_size, int max_points_per_voxel, elm_map** out,
+                                         elm_build_sources_stats* stats) {
+    const char* what = "elm_map_build_device_from";
+    if (out) *out = nullptr;
+    if (!ctx || !src || !out || !(voxel_size > 0.0) || max_points_per_voxel <= 0) return ELM_ERR_INVALID;
+    if (src->n_jobs < 0 || src->n_jobs > kEvidMaxJobs || (src->n_jobs > 0 && (!src->scans || !src->poses16))) return ELM_ERR_INVALID;
+    if ((src->keep_within != 0 && src->keep_within != 1) || (src->keep_within == 1 && !src->base)) return ELM_ERR_INVALID;
+    if (!finite3(src->keep_center) || !fin_ge0(src->keep_radius_m)) return ELM_ERR_INVALID;
+    for (int j = 0; j < src->n_jobs; ++j)
+        if (!src->scans[j]) return ELM_ERR_INVALID;
+    if (!poses_finite(src->poses16, (size_t)src->n_jobs)) return ELM_ERR_INVALID;
+    const int rc = check_plain(ctx, what);
+    if (rc != ELM_OK) return rc;
+    if ((src->base && src->base->ctx != ctx) || ctx->in_flight) return ELM_ERR_INVALID;
+    for (int j = 0; j < src->n_jobs; ++j)
+        if (src->scans[j]->ctx != ctx) return ELM_ERR_INVALID;
+    return guard_alloc(ctx, what, [&] {
+        const JobTable jobs = build_jobs(src->scans, src->poses16, (uint32_t)src->n_jobs);
+        if (jobs.beams > kBuildMaxPoints) {
+            elm_host::ctx_set_error(ctx, std::string(what) + ": more than 2^31 - 1 input points");
+            return (int)ELM_ERR_UNSUPPORTED;
+        }
+        BuildInput in;
+        in.what = what;
+        in.n = (size_t)jobs.beams;
+        in.within = src->keep_within == 1;
+        std::copy(src->keep_center, src->keep_center + 3, in.center);
+        in.r2 = src->keep_radius_m * src->keep_radius_m;
+        in.jobs = &jobs;
+        in.stats = stats;
+        return build_impl(ctx, src->base, in, voxel_size, max_points_per_voxel, out);
+    });
 }
 
 extern "C" int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]) {

@@ -465,7 +465,12 @@ constexpr unsigned kBdTableFull = 2u; // flags: the scratch table took no more k
 void launch_bd_scan(hipStream_t s, unsigned* a, unsigned n, unsigned* blk, unsigned* total);
 // pos[i] = 1 where drop[i] == 0 (scan it); then out[pos[i]] = pts[i] for those points (drop == nullptr: out[i] = pts[i])
 void launch_bd_keep(hipStream_t s, const uint8_t* drop, unsigned n, unsigned* pos);
-void launch_bd_compact(hipStream_t s, const float4* pts, const uint8_t* drop, const unsigned* pos, unsigned n, Pt3* out);
+// without drop but with pos (scanned marks, total their sum): out[pos[i]] = pts[i] for the marked points
+void launch_bd_compact(hipStream_t s, const float4* pts, const uint8_t* drop, const unsigned* pos, unsigned n, unsigned total, Pt3* out);
+// device producers of the same input: pos[i] = 1 where stored point i lies within sqrt(r2) of c (scan it);
+// out[pt0[j] + i] = float32(pose of job j applied to its point i), jobs / n_chunks as launch_evid_walk, pt0[n_jobs] the jobs' first points
+void launch_bd_keep_within(hipStream_t s, const float4* pts, unsigned n, const double c[3], double r2, unsigned* pos);
+void launch_bd_transform(hipStream_t s, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks, const uint32_t* pt0, Pt3* out);
 // table / first: 2^cap_log2 >= 2 n entries, all ones before the call; slot: n entries; flags: zero before the call
 void launch_bd_insert(hipStream_t s, const Pt3* in, unsigned n, double vs, unsigned long long* table, unsigned* first, unsigned cap_log2,
                       unsigned* slot, unsigned* flags);

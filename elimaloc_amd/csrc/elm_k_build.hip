@@ -1,7 +1,8 @@
 // elm_k_build.hip -- the device map build (include/elimaloc_hip.h, "device map build"): AddPoints
 // (vhm.cpp:270-285) with VoxelBlock::AddPointWithSpacing (vhm.hpp:106-113) replayed on the device, byte for byte what build_host
 // (elm_map.cpp) makes of the same input.  The input is one array of packed points: the kept stored points of a base map in bucket
-// order (k_bd_keep / k_bd_compact), then the uploaded points.
+// order (k_bd_keep / k_bd_compact), then the uploaded points.  elm_map_build_device_from fills the same array
+// from the device alone: k_bd_keep_within marks the stored points inside a sphere, k_bd_transform writes resident scans at their poses.
 //   k_bd_insert     truncated key per point -> scratch open-addressing table (64-bit CAS), atomicMin of the point's index per slot
 //   k_bd_opens      1 for the point that opens its voxel (the smallest index of the slot); its exclusive scan over the input order is
 //                   the voxel id in first-seen order
@@ -15,6 +16,7 @@
 // sums by one workgroup in chunks of 1024 as k_ds_offsets, added back).
 #include <hip/hip_runtime.h>
 
+#include "elm_dev_fine.hpp"
 #include "elm_internal.hpp"
 #include "elm_dev_scan.hpp"
 
@@ -65,21 +67,61 @@ __global__ __launch_bounds__(256) void k_bd_keep(const uint8_t* __restrict__ dro
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) pos[i] = drop[i] == 0 ? 1u : 0u;
 }
-// drop == nullptr: every point, to its own index
-__global__ __launch_bounds__(256) void k_bd_compact(const float4* __restrict__ pts, const uint8_t* __restrict__ drop,
-                                                    const unsigned* __restrict__ pos, unsigned n, Pt3* __restrict__ out) {
+// pos[i] = 1 for the stored point inside the closed sphere: ((dx dx + dy dy) + dz dz) <= r2 in float64 from the float32 coordinates (a
+// NaN coordinate fails the comparison and is dropped).  No drop bytes exist on this path.
+__global__ __launch_bounds__(256) void k_bd_keep_within(const float4* __restrict__ pts, unsigned n, double cx, double cy, double cz, double r2,
+                                                        unsigned* __restrict__ pos) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n || (drop && drop[i] != 0)) return;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
+    pos[i] = ((dx * dx + dy * dy) + dz * dz) <= r2 ? 1u : 0u;
+}
+// drop: the point is kept where its byte is 0, and goes to pos[i].  No drop but pos (the scanned marks of k_bd_keep_within, total their
+// sum): the point is kept where the scan steps after it.  Neither: every point, to its own index.
+__global__ __launch_bounds__(256) void k_bd_compact(const float4* __restrict__ pts, const uint8_t* __restrict__ drop,
+                                                    const unsigned* __restrict__ pos, unsigned n, unsigned total, Pt3* __restrict__ out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    unsigned dst = i;
+    if (drop) {
+        if (drop[i] != 0) return;
+        dst = pos[i];
+    } else if (pos) {
+        dst = pos[i];
+        if ((i + 1 < n ? pos[i + 1] : total) == dst) return;
+    }
     const float4 p = pts[i];
     Pt3 q;
     q.x = p.x; q.y = p.y; q.z = p.z;
-    out[drop ? pos[i] : i] = q;
+    out[dst] = q;
+}
+// Workgroup = 256 consecutive points of one job (job_of_chunk, as the evidence walk): point i of the job goes to out[pt0[job] + i] as
+// float32(R p + t), pose_apply's association in float64, one rounding to nearest at the end.
+__global__ __launch_bounds__(256) void k_bd_transform(const EvidJob* __restrict__ jobs, uint32_t n_jobs, const uint32_t* __restrict__ pt0,
+                                                      Pt3* __restrict__ out) {
+    const EvidJob* J = job_of_chunk(jobs, n_jobs, blockIdx.x);
+    const uint32_t i = (blockIdx.x - J->chunk0) * 256u + threadIdx.x;
+    if (i >= J->n) return;
+    const PoseRows P = load_pose_rows(J->rows);
+    const float* p = J->pts + 3 * (size_t)i;
+    double q0, q1, q2;
+    pose_apply(P, (double)p[0], (double)p[1], (double)p[2], q0, q1, q2);
+    Pt3 q;
+    q.x = (float)q0; q.y = (float)q1; q.z = (float)q2;
+    out[(size_t)pt0[J - jobs] + i] = q;
 }
 void launch_bd_keep(hipStream_t s, const uint8_t* drop, unsigned n, unsigned* pos) {
     hipLaunchKernelGGL(k_bd_keep, dim3((n + 255) / 256), dim3(256), 0, s, drop, n, pos);
 }
-void launch_bd_compact(hipStream_t s, const float4* pts, const uint8_t* drop, const unsigned* pos, unsigned n, Pt3* out) {
-    hipLaunchKernelGGL(k_bd_compact, dim3((n + 255) / 256), dim3(256), 0, s, pts, drop, pos, n, out);
+void launch_bd_keep_within(hipStream_t s, const float4* pts, unsigned n, const double c[3], double r2, unsigned* pos) {
+    hipLaunchKernelGGL(k_bd_keep_within, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, c[0], c[1], c[2], r2, pos);
+}
+void launch_bd_compact(hipStream_t s, const float4* pts, const uint8_t* drop, const unsigned* pos, unsigned n, unsigned total, Pt3* out) {
+    hipLaunchKernelGGL(k_bd_compact, dim3((n + 255) / 256), dim3(256), 0, s, pts, drop, pos, n, total, out);
+}
+void launch_bd_transform(hipStream_t s, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks, const uint32_t* pt0, Pt3* out) {
+    if (n_chunks) hipLaunchKernelGGL(k_bd_transform, dim3(n_chunks), dim3(256), 0, s, jobs, n_jobs, pt0, out);
 }
 
 // ---- stage 1: key and insert --------------------------------------------------------------------------------

@@ -531,6 +531,42 @@ class VoxelHashMap:
         as it is and resident, and only `points` cross the bus."""
         return self._derive(None, points)
 
+    def UpdatedFromScans(self, scans, poses, keep_center=None, keep_radius=None, stats=False):
+        """A new map (same voxel size, cap, context and build path) built on the device from inputs that are already there
+        (elm_map_build_device_from): this map's stored points -- all of them, or with keep_center [3] and keep_radius those within the
+        closed sphere -- followed by the resident scans (a list of Scan; the same Scan may repeat) at their poses [n, 4, 4] (map <- scan
+        frame), each point float32(R p + t).  Nothing but the job table crosses the bus; this map stays as it is.  A map without points
+        (never built) gives a build from the scans alone.  stats=True: also the dict of elm_build_sources_stats."""
+        if (keep_center is None) != (keep_radius is None):
+            raise ElmError("UpdatedFromScans: keep_center and keep_radius go together")
+        scans = list(scans)
+        for sc in scans:
+            if not isinstance(sc, Scan):
+                raise ElmError("UpdatedFromScans: the scans are resident Scan objects")
+        P = _pose_block(poses) if len(scans) else np.zeros(0)
+        if P.size // 16 != len(scans):
+            raise ElmError("UpdatedFromScans: one pose per scan")
+        out = VoxelHashMap(self.voxel_size_, self.max_points_per_voxel_, self.ctx, self.device_build_, self.device_index_)
+        has_base = self._h is not None or bool(self._pending) or keep_center is not None
+        src = _lib.BuildSourcesC()
+        src.base = self._handle() if has_base else None
+        src.keep_within = 0 if keep_center is None else 1
+        if keep_center is not None:
+            src.keep_center = (C.c_double * 3)(*[float(x) for x in np.asarray(keep_center, dtype=np.float64).reshape(3)])
+            src.keep_radius_m = float(keep_radius)
+        hs = (C.c_void_p * max(len(scans), 1))(*[sc._h.value for sc in scans])
+        src.scans = hs
+        src.poses16 = _dp(P) if len(scans) else None
+        src.n_jobs = len(scans)
+        st = _lib.BuildSourcesStatsC()
+        h = C.c_void_p()
+        check(_lib.lib().elm_map_build_device_from(self.ctx._h, C.byref(src), self.voxel_size_, self.max_points_per_voxel_, C.byref(h),
+                                                   C.byref(st)), self.ctx._h, "elm_map_build_device_from")
+        out._h = h
+        out._derived = True
+        out._set_index_build()
+        return (out, {n: int(getattr(st, n)) for n, _ in st._fields_}) if stats else out
+
     def CalVoxelCovAll(self):  # vhm.hpp:183-193
         self._want_voxel_cov = True
         if self._h is not None:
@@ -1014,6 +1050,84 @@ class MapGrowth(_MapChild):
 
     def _destroy(self, h):
         _lib.lib().elm_growth_destroy(h)
+
+
+def OdometryConfig(**kw):
+    """elm_odometry_config with its defaults (voxel 1.0 m, cap 30, max_range_m 100, both keyframe thresholds 0 = every scan is inserted,
+    reg = RegistrationConfig()).  reg: a RegistrationConfig; any other keyword that is a field of it is set on reg."""
+    cfg = _lib.OdometryConfigC()
+    _lib.lib().elm_odometry_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k == "reg":
+            cfg.reg = v
+        elif k == "max_points_per_voxel":
+            cfg.max_points_per_voxel = int(v)
+        elif k in ("voxel_size", "max_range_m", "key_min_trans_m", "key_min_rot_rad"):
+            setattr(cfg, k, float(v))
+        elif hasattr(cfg.reg, k):
+            setattr(cfg.reg, k, int(v) if k in ("icp_method", "max_iteration", "i_max_thread", "use_radar_cov") else v)
+        else:
+            raise AttributeError(f"OdometryConfig has no field {k}")
+    return cfg
+
+
+class _BorrowedMap(VoxelHashMap):
+    """A VoxelHashMap view of a map handle that another object owns (LidarOdometry.Map()): read it, register against it; it is never
+    rebuilt or destroyed from here, and it is good until its owner replaces it."""
+
+    def _release(self):
+        self._h = None
+
+    def AddPoints(self, points):
+        raise ElmError("the local map belongs to its LidarOdometry: derive a new map from it (Updated, UpdatedFromScans) instead")
+
+
+class LidarOdometry(_Owned):
+    """LiDAR odometry on a rolling local map kept on the device (elm_odometry, include/elimaloc_hip.h): every scan is registered against
+    the local map and, when it is a keyframe, inserted by one device build that also forgets what is farther than max_range_m from the
+    new pose.  No point crosses the bus after the scan's own upload."""
+
+    def __init__(self, cfg=None, ctx=None):
+        self.ctx = ctx or default_context()
+        self.cfg = cfg if cfg is not None else OdometryConfig()
+        self._h = C.c_void_p()
+        check(_lib.lib().elm_odometry_create(self.ctx._h, C.byref(self.cfg), C.byref(self._h)), self.ctx._h, "elm_odometry_create")
+
+    def Step(self, scan, guess=None):
+        """One scan (a resident Scan, or (m, 3) points uploaded for the call) from guess [4, 4] (None: Predict()) -> dict: T [4, 4],
+        registered, is_success, inserted (bools), reg (the registration's result dict, None for the first scan), build (the insert's
+        elm_build_sources_stats as a dict, None without an insert)."""
+        sc = _resident(self.ctx, scan)
+        st = _lib.OdometryStepC()
+        g = None if guess is None else _colmajor16(guess)
+        check(_lib.lib().elm_odometry_step_scan(self._h, sc._h, None if g is None else _dp(g), C.byref(st)), self.ctx._h,
+              "elm_odometry_step_scan")
+        return dict(T=np.array(st.T).reshape(4, 4).T.copy(), registered=bool(st.registered), is_success=bool(st.is_success),
+                    inserted=bool(st.inserted), reg=_result_dict(st.reg) if st.registered else None,
+                    build={n: int(getattr(st.build, n)) for n, _ in st.build._fields_} if st.inserted else None)
+
+    def Predict(self):
+        """The constant-velocity guess of the next pose [4, 4]: T_{k-1} (T_{k-2}^-1 T_{k-1}); the last pose with one, identity with none."""
+        T = np.empty(16)
+        check(_lib.lib().elm_odometry_predict(self._h, _dp(T)), self.ctx._h, "elm_odometry_predict")
+        return T.reshape(4, 4).T.copy()
+
+    def Map(self):
+        """The local map as a VoxelHashMap view (None before the first scan): owned by this object, valid until the next inserting Step,
+        Reset or close."""
+        h = _lib.lib().elm_odometry_map(self._h)
+        if not h:
+            return None
+        m = _BorrowedMap(float(self.cfg.voxel_size), int(self.cfg.max_points_per_voxel), self.ctx)
+        m._h = C.c_void_p(h)
+        m._derived = True
+        return m
+
+    def Reset(self):
+        check(_lib.lib().elm_odometry_reset(self._h), self.ctx._h, "elm_odometry_reset")
+
+    def _destroy(self, h):
+        _lib.lib().elm_odometry_destroy(h)
 
 
 class PinnedBuffer(_Owned):

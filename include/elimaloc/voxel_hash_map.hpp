@@ -174,6 +174,42 @@ struct VoxelHashMap {
             for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)points[i].pose(k);
         Derive(nullptr, xyz.data(), points.size(), out);
     }
+    // `out` becomes the device build (elm_map_build_device_from) of this map's stored points -- all of them, or with keep_center those
+    // within keep_radius of it (a closed sphere) -- followed by the scans (sensor frame, PointStruct::pose) at their poses, map <- scan
+    // frame: each scan is uploaded once and transformed on the device, point = float32(R p + t); the stored points never leave HBM and
+    // no drop flags exist.  stats, when given: the counts of the build.
+    void UpdatedFromScans(const std::vector<RadarPointVector>& scans, const std::vector<elimaloc::Matrix4d>& poses, VoxelHashMap& out,
+                          const elimaloc::Vector3d* keep_center = nullptr, double keep_radius = 0.0,
+                          elm_build_sources_stats* stats = nullptr) const {
+        if (scans.size() != poses.size()) elimaloc::check(ELM_ERR_INVALID, ctx(), "VoxelHashMap::UpdatedFromScans");
+        std::vector<double> T(16 * poses.size());
+        for (size_t h = 0; h < poses.size(); ++h)
+            for (int k = 0; k < 16; ++k) T[16 * h + k] = poses[h].data()[k]; // column-major on both sides
+        std::vector<elm_scan*> res(scans.size(), nullptr);
+        int rc = ELM_OK;
+        for (size_t j = 0; j < scans.size() && rc == ELM_OK; ++j) {
+            std::vector<float> xyz(3 * scans[j].size());
+            for (size_t i = 0; i < scans[j].size(); ++i)
+                for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)scans[j][i].pose(k);
+            rc = elm_scan_upload(ctx(), xyz.data(), scans[j].size(), scans[j].size(), &res[j]);
+        }
+        elm_map* m = nullptr;
+        if (rc == ELM_OK) {
+            elm_build_sources src;
+            src.base = handle();
+            src.keep_within = keep_center ? 1 : 0;
+            for (int k = 0; k < 3; ++k) src.keep_center[k] = keep_center ? (*keep_center)(k) : 0.0;
+            src.keep_radius_m = keep_center ? keep_radius : 0.0;
+            src.scans = res.data();
+            src.poses16 = T.data();
+            src.n_jobs = (int32_t)scans.size();
+            rc = elm_map_build_device_from(ctx(), &src, voxel_size_, max_points_per_voxel_, &m, stats);
+        }
+        for (elm_scan* s : res)
+            if (s) elm_scan_destroy(s);
+        elimaloc::check(rc, ctx(), "elm_map_build_device_from");
+        out.Adopt(*this, m);
+    }
     void CalVoxelCovAll() { // vhm.hpp:183-193
         want_voxel_cov_ = true;
         elimaloc::check(elm_map_cal_voxel_cov_all(handle()), ctx(), "CalVoxelCovAll");
@@ -430,12 +466,19 @@ private:
     void Derive(const uint8_t* drop, const float* xyz, size_t n, VoxelHashMap& out) const {
         elm_map* m = nullptr;
         elimaloc::check(elm_map_build_device(ctx(), handle(), drop, xyz, n, voxel_size_, max_points_per_voxel_, &m), ctx(), "elm_map_build_device");
-        out.Clear();
-        out.Init(voxel_size_, max_points_per_voxel_);
-        out.device_build_ = device_build_;
-        out.device_index_ = device_index_;
-        out.map_ = m;
-        out.derived_ = true;
+        out.Adopt(*this, m);
+    }
+    // this map becomes m, a device build made from `from`: its sizes and build preferences
+    void Adopt(const VoxelHashMap& from, elm_map* m) {
+        const double vs = from.voxel_size_;
+        const int cap = from.max_points_per_voxel_;
+        const bool db = from.device_build_, di = from.device_index_;
+        Clear();
+        Init(vs, cap);
+        device_build_ = db;
+        device_index_ = di;
+        map_ = m;
+        derived_ = true;
         if (device_index_) elimaloc::check(elm_map_set_index_build(m, ELM_INDEX_BUILD_DEVICE), ctx(), "elm_map_set_index_build");
     }
     // a map made by Derive holds no input points: before it takes more, its stored points (which replay to themselves) become its input

@@ -753,12 +753,90 @@ int elm_growth_beam_objects(elm_ctx* ctx, const elm_growth* g, const elm_scan* s
  * refusal *out is NULL, nothing stays allocated and the context is usable. */
 int elm_map_build_device(elm_ctx* ctx, const elm_map* base, const uint8_t* drop, const float* xyz, size_t n, double voxel_size,
                          int max_points_per_voxel, elm_map** out);
-/* Device milliseconds (hipEvents on the context's stream) of the stages of the last successful elm_map_build_device of this thread on
- * ctx: ms[0] base points compacted and xyz uploaded, [1] key and insert, [2] voxel ids, [3] raw counts, [4] grouping (the sort), [5]
+/* Device milliseconds (hipEvents on the context's stream) of the stages of the last successful elm_map_build_device or
+ * elm_map_build_device_from of this thread on ctx: ms[0] base points compacted and xyz uploaded (or transformed), [1] key and insert, [2] voxel ids, [3] raw counts, [4] grouping (the sort), [5]
  * replay, [6] kept points and ranges written; the host's share (slot table, transfers of keys and ranges) is the call's wall clock less
  * their sum.  ELM_ERR_INVALID: no such build. */
 #define ELM_BUILD_STAGES 7
 int elm_map_build_device_stages(const elm_ctx* ctx, double ms[ELM_BUILD_STAGES]);
+
+/* ---------------------------------------------------------------- device map build from resident sources */
+/* The device build with both of its inputs produced on the device: which stored points of `base` stay is decided by a sphere, and the new
+ * points are resident scans at their poses.  Nothing but the job table crosses the bus.  The result is the map that
+ *   elm_map_build_device(ctx, base, drop, xyz, n, voxel_size, max_points_per_voxel, out)
+ * returns -- byte for byte, in every sense given above -- for these drop and xyz:
+ *   drop[i] = 0 iff keep_within == 0, or ((dx dx + dy dy) + dz dz) <= r2 with dx = x - keep_center[0], dy = y - keep_center[1],
+ *       dz = z - keep_center[2] in float64, (x, y, z) the stored point's float32 coordinates widened, r2 = keep_radius_m * keep_radius_m
+ *       computed once on the host; no fused multiply-add.  The sphere is closed.
+ *   xyz = every job's resident points in device order (the order of elm_scan_download), the jobs in their order; each point becomes
+ *       q_r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r in float64 (the association of elm_evidence_accumulate's end points), rounded to float32
+ *       (to nearest).
+ *   base       may be NULL (a build from the scans alone); it is not modified
+ *   scans      n_jobs resident scans; the same scan may appear several times; may be NULL when n_jobs = 0
+ *   poses16    n_jobs column-major 4 x 4, map <- scan frame (what elm_evidence_accumulate takes); only [R | t] is read
+ *   stats      may be NULL: the stored points of base kept / dropped, the points of all jobs, the points and voxels of the result
+ * ELM_ERR_INVALID: ctx, src or out NULL, scans or poses16 NULL with n_jobs > 0, a NULL scan, voxel_size <= 0 or NaN,
+ * max_points_per_voxel <= 0, a base or scan of another context, a batch in flight, n_jobs outside 0 .. 4096, a non-finite entry of
+ * poses16, keep_center or keep_radius_m, a negative radius, keep_within not 0 or 1, keep_within == 1 without a base.
+ * ELM_ERR_UNSUPPORTED with a text in elm_last_error: as elm_map_build_device, applied to the transformed points (a coordinate that is
+ * not finite or whose quotient by voxel_size is not inside (-2^20, 2^20), more than 2^31 - 1 points, the lead of a device group, a
+ * communicator or hook attached).  After any refusal *out is NULL, nothing stays allocated and the context is usable. */
+typedef struct elm_build_sources {
+    const elm_map* base;             /* may be NULL */
+    int32_t keep_within;             /* 0: keep every stored point of base; 1: keep those within keep_radius_m of keep_center */
+    double keep_center[3];
+    double keep_radius_m;
+    const elm_scan* const* scans;    /* n_jobs resident scans (may repeat) */
+    const double* poses16;           /* n_jobs column-major 4x4, map <- scan frame */
+    int32_t n_jobs;                  /* 0 .. 4096 */
+} elm_build_sources;
+typedef struct elm_build_sources_stats { uint64_t n_base_kept, n_base_dropped, n_scan_points, n_points, n_voxels; } elm_build_sources_stats;
+int elm_map_build_device_from(elm_ctx* ctx, const elm_build_sources* src, double voxel_size, int max_points_per_voxel, elm_map** out,
+                              elm_build_sources_stats* stats);
+
+/* ---------------------------------------------------------------- LiDAR odometry on a rolling local map */
+/* One object holds one local map (owned, device resident) and the pose history.  Every scan is registered against the local map
+ * (elm_register_batch of the one resident scan) and, when it is a keyframe, inserted by elm_map_build_device_from: base = the current map,
+ * the stored points farther than max_range_m from the new pose's translation forgotten, the scan added at the new pose.  No point crosses
+ * the bus after the scan's own upload.  Poses are column-major 4 x 4, map <- scan frame.  The rules:
+ *   first scan     no registration: registered = 0, is_success = 1, the pose is the guess (identity when T_guess is NULL), inserted = 1.
+ *   later scans    one elm_register_batch against the current map from the guess (elm_odometry_predict when T_guess is NULL):
+ *                  registered = 1, reg = its result.  is_success == 0: the step returns ELM_OK with that result and T = the result's
+ *                  pose, inserts nothing and leaves the pose history untouched.
+ *   keyframe test  insert iff sqrt((dx dx + dy dy) + dz dz) >= key_min_trans_m or ((R00 + R11) + R22 - 1) / 2 <= cos(key_min_rot_rad),
+ *                  d = t_new - t_key and R = R_key^T R_new (R_ii = (K_0i N_0i + K_1i N_1i) + K_2i N_2i) against the last INSERTED pose.
+ *                  With both thresholds 0 every scan is inserted; a threshold that should never fire alone is set large (pi for the
+ *                  rotation), not 0.
+ *   insert         elm_map_build_device_from(base = the map, keep_within = 1, keep_center = the new translation, keep_radius_m =
+ *                  max_range_m, the one scan at the new pose); on the new map elm_map_set_index_build(ELM_INDEX_BUILD_DEVICE), then
+ *                  elm_map_cal_point_cov_all(reg.gicp_cov_search_dist) for GICP, elm_map_cal_voxel_cov_all for VGICP / AVGICP; then the
+ *                  old map is destroyed.  A failed build (its status is returned) leaves the old map and the history in place.
+ *   history        the poses of the steps that succeeded, inserted or not.  Prediction is constant velocity in float64 on the host:
+ *                  T_{k-1} (T_{k-2}^-1 T_{k-1}) with the rigid inverse [R^T, -R^T t]; with one pose that pose, with none the identity.
+ *   scope          one rank only, as every query object: no device group's lead, no communicator or hook.
+ * ELM_ERR_INVALID: a NULL argument (T_guess may be NULL), voxel_size <= 0 or NaN, max_points_per_voxel <= 0, max_range_m / key_min_trans_m
+ * / key_min_rot_rad negative or not finite, reg.icp_method outside the four methods, a scan of another context, a non-finite guess, a
+ * batch in flight, an object whose context is gone. */
+typedef struct elm_odometry elm_odometry;
+typedef struct elm_odometry_config {
+    double voxel_size; int32_t max_points_per_voxel;   /* of the local map */
+    double max_range_m;                                /* stored points farther than this from the new pose's translation are forgotten at an insert */
+    double key_min_trans_m, key_min_rot_rad;           /* insert only when the pose moved this far from the last inserted one (0, 0: every scan) */
+    elm_reg_config reg;                                /* method, gates, search distances: all four methods are legal */
+} elm_odometry_config;
+typedef struct elm_odometry_step {
+    double T[16]; int32_t registered, is_success, inserted; elm_reg_result reg; elm_build_sources_stats build;
+} elm_odometry_step;
+/* voxel 1.0 m, cap 30, max_range_m 100, both key thresholds 0, reg = elm_reg_config_default */
+void elm_odometry_config_default(elm_odometry_config* cfg);
+int  elm_odometry_create(elm_ctx* ctx, const elm_odometry_config* cfg, elm_odometry** out);
+void elm_odometry_destroy(elm_odometry* odom);
+/* forgets the map and the history: the next scan is a first scan */
+int  elm_odometry_reset(elm_odometry* odom);
+int  elm_odometry_predict(const elm_odometry* odom, double T_guess[16]);
+int  elm_odometry_step_scan(elm_odometry* odom, const elm_scan* scan, const double T_guess[16] /* NULL: predict */, elm_odometry_step* out);
+/* owned by the object, valid until the next inserting step / reset / destroy; NULL before the first */
+const elm_map* elm_odometry_map(const elm_odometry* odom);
 
 /* ---------------------------------------------------------------- device index build -------------- */
 /* The P2P / GICP cell grid of a map (dense or two-level) is laid out on the host by default: the stored points come down, are
