@@ -265,6 +265,35 @@ class OdometryStepC(C.Structure):
     _fields_ = [("T", C.c_double * 16), ("registered", C.c_int32), ("is_success", C.c_int32), ("inserted", C.c_int32), ("reg", RegResult),
                 ("build", BuildSourcesStatsC)]
 
+class PlacesConfigC(C.Structure):
+    """elm_places_config (include/elimaloc_hip.h, place recognition)."""
+    _fields_ = [("n_rings", C.c_int32), ("n_layers", C.c_int32), ("r_min_m", C.c_double), ("r_max_m", C.c_double),
+                ("z_min_m", C.c_double), ("z_max_m", C.c_double)]
+
+
+class PlacesStatsC(C.Structure):
+    """elm_places_stats: the counts of one described scan."""
+    _fields_ = [("n_points", C.c_uint32), ("n_used", C.c_uint32), ("n_bits", C.c_uint32)]
+
+
+class PlacesQueryConfigC(C.Structure):
+    """elm_places_query_config: the selection of one query."""
+    _fields_ = [("top_k", C.c_int32), ("min_dice_q16", C.c_uint32), ("exclude_id_lo", C.c_int64), ("exclude_id_hi", C.c_int64)]
+
+
+class PlaceMatchC(C.Structure):
+    """elm_place_match: one (query, entry) pair."""
+    _fields_ = [("dice_q16", C.c_uint32), ("inter", C.c_uint16), ("shift", C.c_uint16)]
+
+
+class PlaceCandidateC(C.Structure):
+    """elm_place_candidate: one selected entry of a query."""
+    _fields_ = [("entry", C.c_uint32), ("dice_q16", C.c_uint32), ("id", C.c_int64), ("inter", C.c_uint16), ("shift", C.c_uint16),
+                ("_pad", C.c_uint32), ("yaw_rad", C.c_double)]
+
+
+PLACES_SECTORS, PLACES_MAX_TOP_K = 64, 16
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -294,6 +323,8 @@ EXPORTS = [
     "elm_map_build_device", "elm_map_build_device_stages", "elm_map_build_device_from",
     "elm_odometry_config_default", "elm_odometry_create", "elm_odometry_destroy", "elm_odometry_reset", "elm_odometry_predict",
     "elm_odometry_step_scan", "elm_odometry_map",
+    "elm_places_config_default", "elm_places_tables", "elm_places_create", "elm_places_destroy", "elm_places_reset", "elm_places_size",
+    "elm_places_describe", "elm_places_add", "elm_places_add_words", "elm_places_download", "elm_places_match_words", "elm_places_query",
     "elm_map_set_index_build", "elm_map_index_build_stages", "elm_map_download_cell_grid",
 ]
 
@@ -527,6 +558,22 @@ def lib():
                                               C.POINTER(C.c_size_t)]
     L.elm_relocalize_global.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(GlobalRelocConfigC), C.POINTER(RegConfig), dp,
                                         C.POINTER(RegResult), C.POINTER(RelocCandidate), C.c_int, ip, C.POINTER(GlobalRelocStats)]
+    u64p, i64p, pqc = C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(PlacesQueryConfigC)
+    L.elm_places_config_default.argtypes = [C.POINTER(PlacesConfigC)]
+    L.elm_places_config_default.restype = None
+    L.elm_places_tables.argtypes = [C.POINTER(PlacesConfigC), dp, dp, dp]
+    L.elm_places_create.argtypes = [vp, C.POINTER(PlacesConfigC), C.c_int, C.POINTER(vp)]
+    L.elm_places_destroy.argtypes = [vp]
+    L.elm_places_destroy.restype = None
+    L.elm_places_reset.argtypes = [vp, vp]
+    L.elm_places_size.argtypes = [vp, vp, C.POINTER(C.c_size_t)]
+    L.elm_places_describe.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, u64p, C.POINTER(PlacesStatsC)]
+    L.elm_places_add.argtypes = [vp, vp, C.POINTER(vp), dp, i64p, C.c_int, C.POINTER(PlacesStatsC)]
+    L.elm_places_add_words.argtypes = [vp, vp, u64p, i64p, C.c_size_t]
+    L.elm_places_download.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p, i64p, C.POINTER(C.c_uint32)]
+    L.elm_places_match_words.argtypes = [vp, vp, u64p, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32), C.POINTER(PlaceMatchC)]
+    L.elm_places_query.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32),
+                                   C.POINTER(PlaceMatchC), C.POINTER(PlacesStatsC)]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

@@ -42,6 +42,9 @@ enum ScratchSlot {
     kScrWindowTmp,    // search_setup's temporary between the two window passes
     kScrGroundField,  // a search's ground field (held)
     kScrLevelWindows, // a search's level windows (held)
+    kScrPlaceWords,   // place recognition: the query descriptors (or a describe call's), then their n_bits
+    kScrPlaceMatches, // ... every (query, entry) pair
+    kScrPlaceCands,   // ... the query configs, the candidates and their counts
     kScrCount
 };
 void* ctx_reloc_scratch(elm_ctx* ctx, ScratchSlot slot, size_t bytes, int* rc); // the slot with at least `bytes` (nullptr: *rc)

@@ -403,6 +403,25 @@ constexpr int kEvidWords = 9; // a partial: cast, observing, walked, truncated, 
 void launch_evid_walk(hipStream_t s, const FineTable& ft, const EvidParams& ep, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks,
                       const uint32_t* base, uint32_t* through, uint32_t* hit, uint32_t* partial, elm_evidence_stats* stats, uint16_t* events);
 
+// place recognition (elm_k_place.hip): scan descriptors of n_rings x n_layers words of 64 sector bits, their exact
+// match at all 64 yaw shifts and the top-k selection
+constexpr int kPlaceSectors = ELM_PLACES_SECTORS;
+constexpr int kPlaceMaxWords = 512; // 32 rings x 16 layers: 4 KB of LDS per describing workgroup
+constexpr int kPlaceMaxTopK = ELM_PLACES_MAX_TOP_K;
+struct PlaceParams {
+    int32_t n_rings, n_layers;
+    const double* tables; // device: ring_edge2 [n_rings + 1], z_edge [n_layers + 1], dir [64][2]
+};
+// jobs / n_chunks as launch_evid_walk (the rows are the levelling poses); words [n_jobs][W] zero before the call, n_bits [n_jobs],
+// stats [n_jobs] zero before the call
+void launch_pl_describe(hipStream_t s, const PlaceParams& pp, const EvidJob* jobs, uint32_t n_jobs, uint32_t n_chunks, unsigned long long* words,
+                        uint32_t* n_bits, elm_places_stats* stats);
+void launch_pl_bits(hipStream_t s, const unsigned long long* words, uint32_t W, uint32_t n_desc, uint32_t* n_bits);
+// matches [n_queries][n_entries], cands [n_queries][kPlaceMaxTopK], n_cands [n_queries]; nothing is launched without queries or entries
+void launch_pl_match(hipStream_t s, const unsigned long long* qwords, const uint32_t* q_bits, uint32_t n_queries, const unsigned long long* dwords,
+                     const uint32_t* d_bits, const long long* ids, uint32_t W, uint32_t n_entries, const elm_places_query_config* cfgs,
+                     elm_place_match* matches, elm_place_candidate* cands, int32_t* n_cands);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

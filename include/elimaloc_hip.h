@@ -838,6 +838,100 @@ int  elm_odometry_step_scan(elm_odometry* odom, const elm_scan* scan, const doub
 /* owned by the object, valid until the next inserting step / reset / destroy; NULL before the first */
 const elm_map* elm_odometry_map(const elm_odometry* odom);
 
+/* ---------------------------------------------------------------- place recognition --------------- */
+/* Have I been here before?  A places object holds, resident on the device, a database of binary scan DESCRIPTORS with a caller-given
+ * int64 id each, and answers a query descriptor with the top entries of an EXACT search: every entry at every one of the 64 yaw shifts,
+ * no prefilter and no tree.  One rank only.
+ * THE DESCRIPTOR.  W = n_rings * n_layers words of 64 bits; word = ring * n_layers + layer, bit = sector (ELM_PLACES_SECTORS = 64, so a
+ * yaw shift of the scan is a 64-bit rotate of every word).  Three float64 tables, computed once on the host (elm_places_tables):
+ *   ring_edge2[i] = e_i * e_i, e_i = r_min_m + ((r_max_m - r_min_m) * i) / n_rings for i = 0 .. n_rings, e_n = r_max_m exactly;
+ *   z_edge[j]     = z_min_m + ((z_max_m - z_min_m) * j) / n_layers for j = 0 .. n_layers, the last = z_max_m exactly;
+ *   dir[k]        = (cos, sin)(2 pi k / 64): dir[0] = (1, 0); dir[1 .. 7] from libm; dir[8] = (c, c), c = cos(pi / 4) from libm;
+ *                   dir[16 - k] = (dir[k].y, dir[k].x) for k = 0 .. 7; dir[k] = (-dir[k - 16].y, dir[k - 16].x) for k = 17 .. 63; zeros
+ *                   are stored as +0.0.  So dir[k + 16] is exactly dir[k] turned a quarter, and an exact quarter turn of a scan,
+ *                   (x, y) -> (-y, x), rotates every word of its descriptor left by exactly 16 bits.
+ * A table that is not finite or not strictly increasing is ELM_ERR_INVALID.
+ * One job is one resident scan with a LEVELLING pose T_level = [R | t] (sensor roll and pitch, and height: relocalization's T_tilt;
+ * NULL: identity).  Per point p (float32 -> float64), all arithmetic float64 without contraction:
+ *   q_r = ((R_r0 p_x + R_r1 p_y) + R_r2 p_z) + t_r (the association of "map evidence");
+ *   r2 = q_x q_x + q_y q_y; the ring is the i with ring_edge2[i] <= r2 < ring_edge2[i + 1];
+ *   the layer is the j with z_edge[j] <= q_z < z_edge[j + 1];
+ *   the sector is the smallest k with cross(dir[k], q) >= 0 and cross(dir[(k + 1) & 63], q) < 0, cross(d, q) = d_x q_y - d_y q_x;
+ *   a point without a ring, a layer or a sector (a NaN, q_x = q_y = 0) is dropped; every other point sets its bit.
+ * THE MATCH, in integers.  For a query a and an entry b and a shift k in 0 .. 63: inter(k) = sum over the words of
+ * popcount(a_w & rotl64(b_w, k)).  The pair's result is the largest inter at the smallest such k, and
+ *   dice_q16 = ((uint64)inter << 17) / (n_bits(a) + n_bits(b)), 0 when that sum is 0 (65536 = identical);
+ *   yaw_rad  = -2 pi k / 64 wrapped to (-pi, pi]: -(2 pi k) / 64 for k < 32, (2 pi (64 - k)) / 64 otherwise; the yaw of the query's
+ *              sensor relative to the entry's, T_query ~ T_entry * Rz(yaw_rad).
+ * THE SELECTION, per query: of the entries with dice_q16 >= min_dice_q16 whose id lies outside the closed range [exclude_id_lo,
+ * exclude_id_hi] (lo > hi excludes nothing), the first top_k by dice descending, then entry index ascending.
+ * OR, integer sums and maxima of distinct keys have no order to protect: the same bytes on every run and for every job order. */
+#define ELM_PLACES_SECTORS 64
+#define ELM_PLACES_MAX_TOP_K 16
+typedef struct elm_places elm_places;
+typedef struct elm_places_config {
+    int32_t n_rings;        /* 1 .. 32 */
+    int32_t n_layers;       /* 1 .. 16 */
+    double r_min_m, r_max_m; /* the rings cut [r_min_m, r_max_m) evenly in the levelled xy range */
+    double z_min_m, z_max_m; /* the layers cut [z_min_m, z_max_m) evenly in the levelled height */
+} elm_places_config;
+typedef struct elm_places_stats {
+    uint32_t n_points;      /* the scan's points */
+    uint32_t n_used;        /* the points that set a bit */
+    uint32_t n_bits;        /* the popcount of the descriptor */
+} elm_places_stats;
+typedef struct elm_places_query_config {
+    int32_t top_k;          /* 1 .. ELM_PLACES_MAX_TOP_K */
+    uint32_t min_dice_q16;
+    int64_t exclude_id_lo, exclude_id_hi;
+} elm_places_query_config;
+typedef struct elm_place_match {
+    uint32_t dice_q16;
+    uint16_t inter, shift;
+} elm_place_match;
+typedef struct elm_place_candidate {
+    uint32_t entry;         /* index in the database */
+    uint32_t dice_q16;
+    int64_t id;
+    uint16_t inter, shift;
+    uint32_t _pad;
+    double yaw_rad;
+} elm_place_candidate;
+/* 16 rings over 2 .. 42 m, 8 layers over -3 .. 9 m */
+void elm_places_config_default(elm_places_config* c);
+/* The tables of cfg, each when not NULL: ring_edge2[n_rings + 1], z_edge[n_layers + 1], dir[64][2].  Host only. */
+int elm_places_tables(const elm_places_config* cfg, double* ring_edge2, double* z_edge, double* dir);
+/* An empty database of `capacity` entries (1 .. 65536), fixed for its life.  ELM_ERR_UNSUPPORTED on a device group's lead or with a
+ * communicator / hook attached, here and in every call below that takes ctx. */
+int elm_places_create(elm_ctx* ctx, const elm_places_config* cfg, int capacity, elm_places** out);
+void elm_places_destroy(elm_places* pl);
+/* the database empty again */
+int elm_places_reset(elm_ctx* ctx, elm_places* pl);
+int elm_places_size(elm_ctx* ctx, const elm_places* pl, size_t* n);
+/* The descriptors of n_jobs (1 .. 4096) resident scans, scans[j] levelled by levels16 + 16 j (column-major; levels16 NULL: identity),
+ * into words_out[n_jobs][W] and, when not NULL, stats[n_jobs].  The database is not touched.  Jobs may have any sizes, 0 included; the
+ * same scan may appear several times.  ELM_ERR_INVALID: a non-finite level entry, a scan or object of another context, a batch in flight. */
+int elm_places_describe(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans, const double* levels16, int n_jobs, uint64_t* words_out,
+                        elm_places_stats* stats);
+/* The same descriptors appended as n_jobs entries in job order with ids[j].  A call that would overfill the database is refused with
+ * ELM_ERR_UNSUPPORTED and leaves it as it was. */
+int elm_places_add(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans, const double* levels16, const int64_t* ids, int n_jobs,
+                   elm_places_stats* stats);
+/* n descriptors from the host, words[n][W], appended (a saved database loaded again; n = 0 is allowed). */
+int elm_places_add_words(elm_ctx* ctx, elm_places* pl, const uint64_t* words, const int64_t* ids, size_t n);
+/* Entries first .. first + count - 1, each output when not NULL: words[count][W], ids[count], n_bits[count].  ELM_ERR_INVALID beyond
+ * the database's size. */
+int elm_places_download(elm_ctx* ctx, const elm_places* pl, size_t first, size_t count, uint64_t* words, int64_t* ids, uint32_t* n_bits);
+/* n_queries (1 .. 4096) descriptors words[n_queries][W] against every entry: cands[n_queries][ELM_PLACES_MAX_TOP_K] of which the first
+ * n_cands[q] are written for query q under query_cfg[q]; matches, when not NULL: [n_queries][size], every (query, entry) pair.  An
+ * empty database answers no candidates. */
+int elm_places_match_words(elm_ctx* ctx, elm_places* pl, const uint64_t* words, int n_queries, const elm_places_query_config* query_cfg,
+                           elm_place_candidate* cands, int32_t* n_cands, elm_place_match* matches);
+/* The same on resident scans: described into scratch (stats, when not NULL: [n_queries]), then matched. */
+int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans, const double* levels16, int n_queries,
+                     const elm_places_query_config* query_cfg, elm_place_candidate* cands, int32_t* n_cands, elm_place_match* matches,
+                     elm_places_stats* stats);
+
 /* ---------------------------------------------------------------- device index build -------------- */
 /* The P2P / GICP cell grid of a map (dense or two-level) is laid out on the host by default: the stored points come down, are
  * counting-sorted by cell on one thread and go up again.  With ELM_INDEX_BUILD_DEVICE the same grid is built on the device from the stored
