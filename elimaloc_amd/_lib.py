@@ -294,6 +294,39 @@ class PlaceCandidateC(C.Structure):
 
 PLACES_SECTORS, PLACES_MAX_TOP_K = 64, 16
 
+
+class PoseGraphConfigC(C.Structure):
+    """elm_posegraph_config (include/elimaloc_hip.h, pose graph)."""
+    _fields_ = [("max_iterations", C.c_int32), ("pcg_max_iterations", C.c_int32), ("pcg_check_every", C.c_int32), ("_pad", C.c_int32),
+                ("lambda_init", C.c_double), ("lambda_up", C.c_double), ("lambda_down", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("cost_rel_tol", C.c_double), ("step_tol", C.c_double), ("pcg_rel_tol", C.c_double),
+                ("huber_k", C.c_double)]
+
+
+class PoseGraphLinearizeStatsC(C.Structure):
+    """elm_posegraph_linearize_stats."""
+    _fields_ = [("chi2", C.c_double), ("cost", C.c_double), ("grad_inf_norm", C.c_double), ("n_outliers", C.c_int64)]
+
+
+class PoseGraphSolveStatsC(C.Structure):
+    """elm_posegraph_solve_stats."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("rel_residual", C.c_double)]
+
+
+class PoseGraphResultC(C.Structure):
+    """elm_posegraph_result."""
+    _fields_ = [("solves", C.c_int32), ("accepted", C.c_int32), ("rejected", C.c_int32), ("stop_reason", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_final", C.c_double), ("pcg_iterations_total", C.c_int64)]
+
+
+class PoseGraphTraceC(C.Structure):
+    """elm_posegraph_trace: one solve of an optimize call."""
+    _fields_ = [("cost", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int32), ("pcg_iterations", C.c_int32)]
+
+
+POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
+PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 # every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
@@ -326,6 +359,10 @@ EXPORTS = [
     "elm_places_config_default", "elm_places_tables", "elm_places_create", "elm_places_destroy", "elm_places_reset", "elm_places_size",
     "elm_places_describe", "elm_places_add", "elm_places_add_words", "elm_places_download", "elm_places_match_words", "elm_places_query",
     "elm_map_set_index_build", "elm_map_index_build_stages", "elm_map_download_cell_grid",
+    "elm_posegraph_config_default", "elm_posegraph_create", "elm_posegraph_destroy", "elm_posegraph_reset", "elm_posegraph_size",
+    "elm_posegraph_add_nodes", "elm_posegraph_set_poses", "elm_posegraph_get_poses", "elm_posegraph_set_fixed", "elm_posegraph_add_edges",
+    "elm_posegraph_linearize", "elm_posegraph_download_linearization", "elm_posegraph_solve", "elm_posegraph_optimize",
+    "elm_posegraph_edge_terms",
 ]
 
 
@@ -574,6 +611,24 @@ def lib():
     L.elm_places_match_words.argtypes = [vp, vp, u64p, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32), C.POINTER(PlaceMatchC)]
     L.elm_places_query.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32),
                                    C.POINTER(PlaceMatchC), C.POINTER(PlacesStatsC)]
+    u8p, i32p, szt = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t
+    L.elm_posegraph_config_default.argtypes = [C.POINTER(PoseGraphConfigC)]
+    L.elm_posegraph_config_default.restype = None
+    L.elm_posegraph_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.elm_posegraph_destroy.argtypes = [vp]
+    L.elm_posegraph_destroy.restype = None
+    L.elm_posegraph_reset.argtypes = [vp, vp]
+    L.elm_posegraph_size.argtypes = [vp, vp, C.POINTER(szt), C.POINTER(szt)]
+    L.elm_posegraph_add_nodes.argtypes = [vp, vp, dp, u8p, szt]
+    L.elm_posegraph_set_poses.argtypes = [vp, vp, szt, szt, dp]
+    L.elm_posegraph_get_poses.argtypes = [vp, vp, szt, szt, dp]
+    L.elm_posegraph_set_fixed.argtypes = [vp, vp, szt, szt, u8p]
+    L.elm_posegraph_add_edges.argtypes = [vp, vp, i32p, i32p, dp, dp, szt]
+    L.elm_posegraph_linearize.argtypes = [vp, vp, C.c_double, C.POINTER(PoseGraphLinearizeStatsC)]
+    L.elm_posegraph_download_linearization.argtypes = [vp, vp, dp, dp, dp, dp, dp, dp, dp]
+    L.elm_posegraph_solve.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(PoseGraphSolveStatsC)]
+    L.elm_posegraph_optimize.argtypes = [vp, vp, C.POINTER(PoseGraphConfigC), C.POINTER(PoseGraphResultC), C.POINTER(PoseGraphTraceC), C.c_int]
+    L.elm_posegraph_edge_terms.argtypes = [dp, dp, dp, dp, dp, dp]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

@@ -1,0 +1,204 @@
+// elm_dev_pgraph.hpp -- the pose graph's relative-pose edge (include/elimaloc_hip.h, "pose graph"): SO(3) Log through the
+// unit quaternion, the inverse right Jacobian, the residual and its two 6 x 6 Jacobians, the Huber weight and cost, and the retraction.
+// Host and device run this same code (elm_posegraph_edge_terms is the host's call of it).  Float64, row-major, no contraction.
+#pragma once
+#include "elm_la.hpp"
+
+namespace elm {
+
+constexpr double kPgLogSmallN = 1e-8;    // |vec| of the unit quaternion below which Log is 2 vec (the next term is n^2 / 3 relative)
+constexpr double kPgSeriesTheta = 1e-2;  // below it c(theta) is its series 1/12 + theta^2/720 + theta^4/30240
+
+// Log of a rotation matrix: the unit quaternion as matrix_to_angle forms it, signed to w >= 0; phi = vec * (theta / n),
+// theta = 2 atan2(n, w); below kPgLogSmallN phi = 2 vec.  Also returns theta and the quaternion's (w, n) = (cos, sin)(theta / 2).
+// Log(I) is exactly 0.
+ELM_HD void pg_log(const double R[9], double phi[3], double& theta, double& qw_out, double& n_out) {
+    const double tr = R[0] + R[4] + R[8];
+    double qw, qx, qy, qz;
+    if (tr > 0.0) {
+        double t = sqrt(tr + 1.0);
+        qw = 0.5 * t;
+        t = 0.5 / t;
+        qx = (R[7] - R[5]) * t;
+        qy = (R[2] - R[6]) * t;
+        qz = (R[3] - R[1]) * t;
+    } else if (R[0] >= R[4] && R[0] >= R[8]) { // the largest diagonal entry leads (the three cases written out: no indexed registers)
+        double t = sqrt(R[0] - R[4] - R[8] + 1.0);
+        qx = 0.5 * t;
+        t = 0.5 / t;
+        qw = (R[7] - R[5]) * t;
+        qy = (R[3] + R[1]) * t;
+        qz = (R[6] + R[2]) * t;
+    } else if (R[4] >= R[8]) {
+        double t = sqrt(R[4] - R[8] - R[0] + 1.0);
+        qy = 0.5 * t;
+        t = 0.5 / t;
+        qw = (R[2] - R[6]) * t;
+        qz = (R[7] + R[5]) * t;
+        qx = (R[1] + R[3]) * t;
+    } else {
+        double t = sqrt(R[8] - R[0] - R[4] + 1.0);
+        qz = 0.5 * t;
+        t = 0.5 / t;
+        qw = (R[3] - R[1]) * t;
+        qx = (R[2] + R[6]) * t;
+        qy = (R[5] + R[7]) * t;
+    }
+    if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+    const double n = sqrt((qx * qx + qy * qy) + qz * qz);
+    double k;
+    if (n < kPgLogSmallN) {
+        k = 2.0;
+        theta = 2.0 * n;
+    } else {
+        theta = 2.0 * atan2(n, qw);
+        k = theta / n;
+    }
+    phi[0] = qx * k;
+    phi[1] = qy * k;
+    phi[2] = qz * k;
+    qw_out = qw;
+    n_out = n;
+}
+
+// c(theta) of J^-1 = I + [phi]x / 2 + c [phi]x^2: 1/theta^2 - (1 + cos theta) / (2 theta sin theta), whose second term is
+// cot(theta / 2) / (2 theta) = w / (2 theta n) with the quaternion's w = cos(theta / 2), n = sin(theta / 2) -- the same number without
+// the cancellation of 1 + cos theta near pi.  Below kPgSeriesTheta the series.
+ELM_HD double pg_jinv_c(double theta, double qw, double n) {
+    if (theta < kPgSeriesTheta) {
+        const double t2 = theta * theta;
+        return (1.0 / 12.0 + t2 / 720.0) + (t2 * t2) / 30240.0;
+    }
+    return 1.0 / (theta * theta) - qw / ((2.0 * theta) * n);
+}
+
+ELM_HD void pg_jinv(const double phi[3], double c, double J[9]) {
+    const double x = phi[0], y = phi[1], z = phi[2];
+    // [phi]x^2 = phi phi^T - |phi|^2 I
+    const double xx = x * x, yy = y * y, zz = z * z;
+    J[0] = 1.0 - c * (yy + zz);
+    J[4] = 1.0 - c * (xx + zz);
+    J[8] = 1.0 - c * (xx + yy);
+    const double cxy = c * (x * y), cxz = c * (x * z), cyz = c * (y * z);
+    J[1] = cxy - 0.5 * z;
+    J[3] = cxy + 0.5 * z;
+    J[2] = cxz + 0.5 * y;
+    J[6] = cxz - 0.5 * y;
+    J[5] = cyz - 0.5 * x;
+    J[7] = cyz + 0.5 * x;
+}
+
+// r = a^T b (3 x 3, row-major)
+ELM_HD void pg_mul3_at(const double a[9], const double b[9], double r[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r[i * 3 + j] = (a[i] * b[j] + a[3 + i] * b[3 + j]) + a[6 + i] * b[6 + j];
+}
+ELM_HD void pg_mul3_atv(const double a[9], const double v[3], double r[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] = (a[i] * v[0] + a[3 + i] * v[1]) + a[6 + i] * v[2];
+}
+
+// One pose as the twelve rows of pose_rows12: P[r * 4 + q] = (R_r0, R_r1, R_r2, t_r).
+ELM_HD void pg_split(const double P[12], double R[9], double t[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        R[r * 3] = P[r * 4];
+        R[r * 3 + 1] = P[r * 4 + 1];
+        R[r * 3 + 2] = P[r * 4 + 2];
+        t[r] = P[r * 4 + 3];
+    }
+}
+
+// The residual alone (the cost kernel): r = [R_Z^T (d - t_Z); Log(R_Z^T R_i^T R_j)], d = R_i^T (t_j - t_i).
+ELM_HD void pg_residual(const double Pi[12], const double Pj[12], const double PZ[12], double r[6]) {
+    double Ri[9], ti[3], Rj[9], tj[3], RZ[9], tZ[3];
+    pg_split(Pi, Ri, ti);
+    pg_split(Pj, Rj, tj);
+    pg_split(PZ, RZ, tZ);
+    const double dt[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]};
+    double d[3], Rij[9], RE[9];
+    pg_mul3_atv(Ri, dt, d);
+    pg_mul3_at(Ri, Rj, Rij);
+    pg_mul3_at(RZ, Rij, RE);
+    const double e[3] = {d[0] - tZ[0], d[1] - tZ[1], d[2] - tZ[2]};
+    pg_mul3_atv(RZ, e, r);
+    double theta, qw, n, phi[3];
+    pg_log(RE, phi, theta, qw, n);
+    r[3] = phi[0];
+    r[4] = phi[1];
+    r[5] = phi[2];
+}
+
+// The residual and the non-zero 3 x 3 blocks of the Jacobians A = dr/dx_i, B = dr/dx_j (rows in the order of r, columns of x):
+//   A = [ Att  Atr ;  0  Arr ] = [ -R_Z^T   R_Z^T [d]x ;  0  -J^-1 R_j^T R_i ],   B = [ Btt  0 ;  0  Brr ] = [ R_E  0 ;  0  J^-1 ].
+struct PgBlocks {
+    double Att[9], Atr[9], Arr[9], Btt[9], Brr[9];
+};
+ELM_HD void pg_edge_blocks(const double Pi[12], const double Pj[12], const double PZ[12], double r[6], PgBlocks& K) {
+    double Ri[9], ti[3], Rj[9], tj[3], RZ[9], tZ[3];
+    pg_split(Pi, Ri, ti);
+    pg_split(Pj, Rj, tj);
+    pg_split(PZ, RZ, tZ);
+    const double dt[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]};
+    double d[3], Rij[9];
+    pg_mul3_atv(Ri, dt, d);
+    pg_mul3_at(Ri, Rj, Rij);
+    pg_mul3_at(RZ, Rij, K.Btt);
+    const double e[3] = {d[0] - tZ[0], d[1] - tZ[1], d[2] - tZ[2]};
+    pg_mul3_atv(RZ, e, r);
+    double theta, qw, n, phi[3];
+    pg_log(K.Btt, phi, theta, qw, n);
+    r[3] = phi[0];
+    r[4] = phi[1];
+    r[5] = phi[2];
+    pg_jinv(phi, pg_jinv_c(theta, qw, n), K.Brr);
+    const double dx[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+    pg_mul3_at(RZ, dx, K.Atr);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            K.Att[a * 3 + b] = -RZ[b * 3 + a];
+            // -(J Rij^T)[a][b]
+            K.Arr[a * 3 + b] = -((K.Brr[a * 3] * Rij[b * 3] + K.Brr[a * 3 + 1] * Rij[b * 3 + 1]) + K.Brr[a * 3 + 2] * Rij[b * 3 + 2]);
+        }
+}
+// the same as full row-major 6 x 6 matrices
+ELM_HD void pg_edge_terms(const double Pi[12], const double Pj[12], const double PZ[12], double r[6], double A[36], double B[36]) {
+    PgBlocks K;
+    pg_edge_blocks(Pi, Pj, PZ, r, K);
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            A[a * 6 + b] = K.Att[a * 3 + b];
+            A[a * 6 + 3 + b] = K.Atr[a * 3 + b];
+            A[(3 + a) * 6 + b] = 0.0;
+            A[(3 + a) * 6 + 3 + b] = K.Arr[a * 3 + b];
+            B[a * 6 + b] = K.Btt[a * 3 + b];
+            B[a * 6 + 3 + b] = 0.0;
+            B[(3 + a) * 6 + b] = 0.0;
+            B[(3 + a) * 6 + 3 + b] = K.Brr[a * 3 + b];
+        }
+}
+
+// Huber on s = r^T Omega r: the weight, and the cost rho.  k = 0: off.  s == k^2 is an inlier.
+ELM_HD double pg_huber_weight(double s, double k) { return (k > 0.0 && s > k * k) ? k / sqrt(s) : 1.0; }
+ELM_HD double pg_huber_cost(double s, double k) { return (k > 0.0 && s > k * k) ? (2.0 * k) * sqrt(s) - k * k : s; }
+
+// The retraction of x = [v; w]: R <- R Exp(w), t <- t + R v, on pose rows.
+ELM_HD void pg_retract(const double P[12], const double x[6], double out[12]) {
+    double R[9], t[3], E[9], Rn[9];
+    pg_split(P, R, t);
+    rotvec_to_matrix(x + 3, E);
+    mul3(R, E, Rn);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        out[r * 4] = Rn[r * 3];
+        out[r * 4 + 1] = Rn[r * 3 + 1];
+        out[r * 4 + 2] = Rn[r * 3 + 2];
+        out[r * 4 + 3] = t[r] + ((R[r * 3] * x[0] + R[r * 3 + 1] * x[1]) + R[r * 3 + 2] * x[2]);
+    }
+}
+
+} // namespace elm

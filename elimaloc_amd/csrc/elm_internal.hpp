@@ -422,6 +422,48 @@ void launch_pl_match(hipStream_t s, const unsigned long long* qwords, const uint
                      const uint32_t* d_bits, const long long* ids, uint32_t W, uint32_t n_entries, const elm_places_query_config* cfgs,
                      elm_place_match* matches, elm_place_candidate* cands, int32_t* n_cands);
 
+// pose graph (elm_k_pgraph.hip): the device's view of one graph.  Edge arrays are component-major with the stride
+// e_stride (array[component * e_stride + edge]); node arrays are node-major.
+constexpr uint32_t kPgLanesPerEdge = 8;   // k_pg_linearize: the lane of a group is the column
+constexpr uint32_t kPgNodesPerBlock = 32; // k_pg_spmv: a lane group of 8 per node, the lane is the row
+constexpr uint32_t kPgHubDegree = 64;     // a node with more incident edges takes a whole wavefront of k_pg_spmv_hub
+constexpr uint32_t kPgBlock = 256;        // the per-node and per-edge kernels, and the lanes that reduce partial slots
+struct PgState {
+    double rz[2];     // r^T z before the iteration of that parity
+    double rz0;
+    uint32_t stop[2]; // the solve is over for the launches of the iteration of that parity
+    uint32_t iters, converged;
+};
+struct PgOut {
+    double chi2, cost, n_outliers, dmax, grad_inf;
+};
+struct PgDev {
+    uint32_t N, E, e_stride, n_hubs;
+    const int32_t *ei, *ej;
+    const double *Z, *info;          // [E][12] pose rows, [E][36]
+    const uint8_t* fixed;            // [N]
+    double *r, *A, *B, *s, *w;       // [6], [36], [36], [1], [1] components
+    double *gi, *gj, *Hii, *Hij, *Hjj; // [6], [6], [36], [36], [36] components
+    const uint32_t *inc_start, *inc; // CSR: [N + 1]; edge << 1 | side (0: the node is i, 1: j), ascending edge per node
+    const uint32_t* hubs;            // the nodes of degree > kPgHubDegree, ascending
+    double *Hd, *g, *Minv;           // [N][36], [N][6], [N][36]
+    uint8_t* active;                 // [N]: the solve moves the node
+    double *x, *rr, *z, *p, *q;      // [N][6]
+    double *part_pq, *part_rz, *part_cost, *part_max;
+    PgState* state;
+    PgOut* out;
+};
+constexpr uint32_t pg_pq_slots(uint32_t N, uint32_t n_hubs) { return (N + kPgNodesPerBlock - 1) / kPgNodesPerBlock + n_hubs; }
+constexpr uint32_t pg_blocks(uint32_t n) { return (n + kPgBlock - 1) / kPgBlock; }
+void launch_pg_linearize(hipStream_t s, const PgDev& d, const double* poses, double huber_k);
+// sum != 0: H_vv and g_v summed from the edges' contributions first; always: the active rule, the damping and the inverses
+void launch_pg_nodes(hipStream_t s, const PgDev& d, double lambda, int sum);
+void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, double tol);
+void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, double lambda, double tol, uint32_t it);
+void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, double* trial);
+// chi2, cost and outliers at `poses` into d.out, with the largest |x| of the last retraction; want_grad: also max |g_v| over active nodes
+void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double huber_k, int want_grad);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

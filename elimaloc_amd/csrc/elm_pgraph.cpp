@@ -1,0 +1,610 @@
+// elm_pgraph.cpp -- the pose graph (include/elimaloc_hip.h, "pose graph"): the object (nodes, edges, the
+// linearization and the solver's vectors resident on the device, of capacities fixed at creation), the argument checks, the incidence
+// lists (a stable counting sort of (edge, side) by node, redone when the edge set has changed), the conjugate-gradient driver that
+// queues pcg_check_every iterations between two reads of the device's state, and the Levenberg-Marquardt loop around it.  The launches
+// are those of elm_k_pgraph.hip.  Host-side C++17.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "elm_dev_pgraph.hpp"
+#include "elm_query.hpp"
+
+using namespace elm;
+using namespace elm_query;
+
+struct elm_posegraph {
+    elm_ctx* ctx = nullptr;
+    uint64_t ctx_id = 0; // the owning context's unique id (as maps and scans keep it)
+    uint32_t n_cap = 0, e_cap = 0, N = 0, E = 0;
+    std::vector<uint8_t> fixed;     // [N]: the host's copy
+    std::vector<int32_t> ei, ej;    // [E]: the host's copy
+    bool csr_dirty = true, lin_valid = false;
+    uint32_t n_hubs = 0;
+    char* blob = nullptr;           // every device array below, one allocation
+    double *poses = nullptr, *trial = nullptr;
+    uint32_t *d_inc_start = nullptr, *d_inc = nullptr, *d_hubs = nullptr;
+    int32_t *d_ei = nullptr, *d_ej = nullptr;
+    double *d_Z = nullptr, *d_info = nullptr;
+    uint8_t* d_fixed = nullptr;
+    PgDev dev{};
+};
+
+extern "C" void elm_posegraph_config_default(elm_posegraph_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->max_iterations = 20;
+    c->pcg_max_iterations = 2000;
+    c->pcg_check_every = 32;
+    c->lambda_init = 1e-4;
+    c->lambda_up = 10.0;
+    c->lambda_down = 0.1;
+    c->lambda_min = 1e-12;
+    c->lambda_max = 1e8;
+    c->cost_rel_tol = 1e-12;
+    c->step_tol = 1e-10;
+    c->pcg_rel_tol = 1e-8;
+    c->huber_k = 0.0;
+}
+
+namespace {
+
+constexpr int kPgDefaultCheckEvery = 32;
+
+bool config_ok(const elm_posegraph_config* c) {
+    if (!c || c->max_iterations < 1 || c->pcg_max_iterations < 1 || c->pcg_check_every < 1) return false;
+    if (!fin_ge0(c->lambda_init) || !fin_ge0(c->lambda_min) || !fin_ge0(c->lambda_max) || c->lambda_min > c->lambda_max) return false;
+    if (!(isfinite(c->lambda_up) && c->lambda_up >= 1.0) || !(isfinite(c->lambda_down) && c->lambda_down > 0.0 && c->lambda_down <= 1.0)) return false;
+    return fin_ge0(c->cost_rel_tol) && fin_ge0(c->step_tol) && fin_ge0(c->pcg_rel_tol) && fin_ge0(c->huber_k);
+}
+
+void pg_free(elm_posegraph* pg) {
+    if (!pg) return;
+    if (elm_host::ctx_is_alive(pg->ctx, pg->ctx_id)) (void)hipSetDevice(pg->ctx->device); // a context destroyed first: just release
+    if (pg->blob) (void)hipFree(pg->blob);
+    delete pg;
+}
+
+// the device arrays carved from one allocation, each aligned to 256 bytes
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) / 256 * 256;
+        return p;
+    }
+};
+
+void carve(elm_posegraph* pg, Carver& c) {
+    const size_t Nc = pg->n_cap, Ec = pg->e_cap;
+    PgDev& d = pg->dev;
+    pg->poses = c.take<double>(12 * Nc);
+    pg->trial = c.take<double>(12 * Nc);
+    pg->d_fixed = c.take<uint8_t>(Nc);
+    pg->d_ei = c.take<int32_t>(Ec);
+    pg->d_ej = c.take<int32_t>(Ec);
+    pg->d_Z = c.take<double>(12 * Ec);
+    pg->d_info = c.take<double>(36 * Ec);
+    pg->d_inc_start = c.take<uint32_t>(Nc + 1);
+    pg->d_inc = c.take<uint32_t>(2 * Ec);
+    pg->d_hubs = c.take<uint32_t>(2 * Ec / (kPgHubDegree + 1) + 1);
+    d.r = c.take<double>(6 * Ec);
+    d.A = c.take<double>(36 * Ec);
+    d.B = c.take<double>(36 * Ec);
+    d.s = c.take<double>(Ec);
+    d.w = c.take<double>(Ec);
+    d.gi = c.take<double>(6 * Ec);
+    d.gj = c.take<double>(6 * Ec);
+    d.Hii = c.take<double>(36 * Ec);
+    d.Hij = c.take<double>(36 * Ec);
+    d.Hjj = c.take<double>(36 * Ec);
+    d.Hd = c.take<double>(36 * Nc);
+    d.g = c.take<double>(6 * Nc);
+    d.Minv = c.take<double>(36 * Nc);
+    d.active = c.take<uint8_t>(Nc);
+    d.x = c.take<double>(6 * Nc);
+    d.rr = c.take<double>(6 * Nc);
+    d.z = c.take<double>(6 * Nc);
+    d.p = c.take<double>(6 * Nc);
+    d.q = c.take<double>(6 * Nc);
+    d.part_pq = c.take<double>(pg_pq_slots((uint32_t)Nc, (uint32_t)(2 * Ec / (kPgHubDegree + 1) + 1)));
+    d.part_rz = c.take<double>(pg_blocks((uint32_t)Nc));
+    d.part_cost = c.take<double>(3 * (size_t)pg_blocks((uint32_t)Ec));
+    d.part_max = c.take<double>(pg_blocks((uint32_t)Nc));
+    d.state = c.take<PgState>(1);
+    d.out = c.take<PgOut>(1);
+    d.e_stride = (uint32_t)Ec;
+    d.ei = pg->d_ei;
+    d.ej = pg->d_ej;
+    d.Z = pg->d_Z;
+    d.info = pg->d_info;
+    d.fixed = pg->d_fixed;
+    d.inc_start = pg->d_inc_start;
+    d.inc = pg->d_inc;
+    d.hubs = pg->d_hubs;
+}
+
+int create_impl(elm_ctx* ctx, uint32_t n_cap, uint32_t e_cap, elm_posegraph** out) {
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
+    elm_posegraph* pg = new elm_posegraph();
+    pg->ctx = ctx;
+    pg->ctx_id = ctx->id;
+    pg->n_cap = n_cap;
+    pg->e_cap = e_cap;
+    Carver size{nullptr};
+    carve(pg, size);
+    // zeroed on the context's stream and joined: a memset on the null stream may still be running when the first upload on the
+    // context's (non-blocking) stream lands, and would then wipe it
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    hipError_t e = hipMalloc((void**)&pg->blob, size.off);
+    if (e == hipSuccess) e = hipMemsetAsync(pg->blob, 0, size.off, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        pg_free(pg);
+        return dev_error(ctx, "elm_posegraph_create", e);
+    }
+    Carver real{pg->blob};
+    carve(pg, real);
+    *out = pg;
+    return ELM_OK;
+}
+
+int refuse_full(elm_ctx* ctx, const char* what, const char* items, size_t have, size_t n, size_t cap) {
+    elm_host::ctx_set_error(ctx, std::string(what) + ": " + std::to_string(have) + " + " + std::to_string(n) + " " + items + " exceed the capacity of " +
+                                     std::to_string(cap));
+    return ELM_ERR_UNSUPPORTED;
+}
+
+void rows12_to_pose16(const double* P, double* T16) {
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 4; ++q) T16[q * 4 + r] = P[r * 4 + q];
+    T16[3] = T16[7] = T16[11] = 0.0;
+    T16[15] = 1.0;
+}
+
+int join(elm_ctx* ctx, hipStream_t st, hipError_t e, const char* what) {
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? (int)ELM_OK : dev_error(ctx, what, e);
+}
+
+// the incidence lists of the current edge set: per node its (edge, side) entries in ascending edge index, and the hubs
+hipError_t upload_csr(elm_posegraph* pg, hipStream_t st, std::vector<uint32_t>& start, std::vector<uint32_t>& inc, std::vector<uint32_t>& hubs) {
+    const uint32_t N = pg->N, E = pg->E;
+    start.assign((size_t)N + 1, 0u);
+    for (uint32_t e = 0; e < E; ++e) {
+        ++start[(size_t)pg->ei[e] + 1];
+        ++start[(size_t)pg->ej[e] + 1];
+    }
+    for (uint32_t v = 0; v < N; ++v) start[v + 1] += start[v];
+    inc.assign(2 * (size_t)E + 1, 0u);
+    std::vector<uint32_t> at(start.begin(), start.end() - 1);
+    for (uint32_t e = 0; e < E; ++e) { // edges ascending: every list ends up ascending
+        inc[at[pg->ei[e]]++] = e << 1;
+        inc[at[pg->ej[e]]++] = (e << 1) | 1u;
+    }
+    hubs.clear();
+    for (uint32_t v = 0; v < N; ++v)
+        if (start[v + 1] - start[v] > kPgHubDegree) hubs.push_back(v);
+    pg->n_hubs = (uint32_t)hubs.size();
+    hubs.push_back(0u);
+    hipError_t e = hipMemcpyAsync(pg->d_inc_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && E) e = hipMemcpyAsync(pg->d_inc, inc.data(), 2 * (size_t)E * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(pg->d_hubs, hubs.data(), hubs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st); // the host vectors are read until here
+    return e;
+}
+
+const PgDev& dev_view(elm_posegraph* pg) {
+    pg->dev.N = pg->N;
+    pg->dev.E = pg->E;
+    pg->dev.n_hubs = pg->n_hubs;
+    return pg->dev;
+}
+
+// queues the linearization at the current poses with the damping lambda
+hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda) {
+    hipError_t e = hipSuccess;
+    if (pg->csr_dirty) {
+        std::vector<uint32_t> start, inc, hubs;
+        e = upload_csr(pg, st, start, inc, hubs);
+        if (e != hipSuccess) return e;
+        pg->csr_dirty = false;
+    }
+    const PgDev& d = dev_view(pg);
+    return launched([&] {
+        launch_pg_linearize(st, d, pg->poses, huber_k);
+        launch_pg_nodes(st, d, lambda, 1);
+    });
+}
+
+// The conjugate gradients on the current linearization and damping (k_pg_nodes has run with this lambda): check_every iterations are
+// queued, then the state comes down once.
+int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, double tol, int max_it, int check_every, PgState& state, const char* what) {
+    const PgDev& d = dev_view(pg);
+    memset(&state, 0, sizeof(state));
+    if (!pg->N) return ELM_OK;
+    hipError_t e = launched([&] { launch_pg_pcg_begin(st, d, tol); });
+    uint32_t it = 0;
+    while (e == hipSuccess) {
+        const uint32_t upto = (uint32_t)std::min<int64_t>((int64_t)it + check_every, max_it);
+        e = launched([&] {
+            for (; it < upto; ++it) launch_pg_pcg_iteration(st, d, lambda, tol, it);
+        });
+        if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(PgState), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess || state.stop[it & 1u] || it >= (uint32_t)max_it) break;
+    }
+    return e == hipSuccess ? (int)ELM_OK : dev_error(ctx, what, e);
+}
+
+double rel_residual(const PgState& s, uint32_t N) {
+    if (!N || !(s.rz0 > 0.0)) return 0.0;
+    return sqrt(s.rz[s.iters & 1u]) / sqrt(s.rz0);
+}
+
+// the cost record at `poses` (and the largest |x| of the retraction queued before it)
+int cost_at(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const double* poses, double huber_k, int want_grad, PgOut& out, const char* what) {
+    const PgDev& d = dev_view(pg);
+    hipError_t e = launched([&] { launch_pg_cost(st, d, poses, huber_k, want_grad); });
+    if (e == hipSuccess) e = hipMemcpyAsync(&out, d.out, sizeof(PgOut), hipMemcpyDeviceToHost, st);
+    return join(ctx, st, e, what);
+}
+
+int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c, elm_posegraph_result* res, elm_posegraph_trace* trace, int trace_cap) {
+    const char* what = "elm_posegraph_optimize";
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    elm_posegraph_result R{};
+    double lambda = c.lambda_init;
+    pg->lin_valid = false;
+    hipError_t e = queue_linearize(pg, st, c.huber_k, lambda);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    PgOut o{};
+    int rc = cost_at(ctx, pg, st, pg->poses, c.huber_k, 0, o, what);
+    if (rc != ELM_OK) return rc;
+    pg->lin_valid = true;
+    double F = o.cost;
+    R.cost_initial = R.cost_final = F;
+    R.lambda_final = lambda;
+    R.stop_reason = F == 0.0 ? ELM_PG_STOP_COST_ZERO : ELM_PG_STOP_MAX_ITERATIONS;
+    while (R.stop_reason == ELM_PG_STOP_MAX_ITERATIONS && R.solves < c.max_iterations) {
+        PgState s{};
+        rc = run_pcg(ctx, pg, st, lambda, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+        if (rc != ELM_OK) return rc;
+        const PgDev& d = dev_view(pg);
+        e = launched([&] { launch_pg_retract(st, d, pg->poses, pg->trial); });
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        rc = cost_at(ctx, pg, st, pg->trial, c.huber_k, 0, o, what);
+        if (rc != ELM_OK) return rc;
+        const double F_new = o.cost, used = lambda;
+        const bool accept = F_new < F;
+        ++R.solves;
+        R.pcg_iterations_total += s.iters;
+        bool stop = false;
+        if (accept) {
+            ++R.accepted;
+            std::swap(pg->poses, pg->trial);
+            pg->lin_valid = false; // the linearization is that of the poses before the step until it is redone below
+            const double dec = F - F_new, F_old = F;
+            F = F_new;
+            lambda = std::max(lambda * c.lambda_down, c.lambda_min);
+            if (F == 0.0) R.stop_reason = ELM_PG_STOP_COST_ZERO, stop = true;
+            else if (dec <= c.cost_rel_tol * F_old) R.stop_reason = ELM_PG_STOP_COST_TOL, stop = true;
+            else if (o.dmax <= c.step_tol) R.stop_reason = ELM_PG_STOP_STEP_TOL, stop = true;
+            else if (R.solves >= c.max_iterations) stop = true;
+            if (!stop) {
+                e = queue_linearize(pg, st, c.huber_k, lambda);
+                if (e != hipSuccess) return dev_error(ctx, what, e);
+                pg->lin_valid = true;
+            }
+        } else {
+            ++R.rejected;
+            if (o.dmax <= c.step_tol) R.stop_reason = ELM_PG_STOP_STEP_TOL, stop = true;
+            else if (lambda >= c.lambda_max) R.stop_reason = ELM_PG_STOP_LAMBDA_MAX, stop = true;
+            else {
+                lambda = std::min(lambda * c.lambda_up, c.lambda_max);
+                e = launched([&] { launch_pg_nodes(st, d, lambda, 0); });
+                if (e != hipSuccess) return dev_error(ctx, what, e);
+            }
+        }
+        if (trace && R.solves <= trace_cap) {
+            elm_posegraph_trace& t = trace[R.solves - 1];
+            t.cost = F_new;
+            t.lambda = used;
+            t.accepted = accept ? 1 : 0;
+            t.pcg_iterations = (int32_t)s.iters;
+        }
+        if (stop) break;
+    }
+    rc = join(ctx, st, hipSuccess, what);
+    if (rc != ELM_OK) return rc;
+    R.cost_final = F;
+    R.lambda_final = lambda;
+    if (res) *res = R;
+    return ELM_OK;
+}
+
+bool range_ok(size_t first, size_t count, size_t size) { return first <= size && count <= size - first; }
+
+} // namespace
+
+extern "C" int elm_posegraph_edge_terms(const double* Ti16, const double* Tj16, const double* Z16, double* r, double* A, double* B) {
+    if (!Ti16 || !Tj16 || !Z16 || !poses_finite(Ti16, 1) || !poses_finite(Tj16, 1) || !poses_finite(Z16, 1)) return ELM_ERR_INVALID;
+    double Pi[12], Pj[12], PZ[12], rr[6], AA[36], BB[36];
+    pose_rows12(Ti16, Pi);
+    pose_rows12(Tj16, Pj);
+    pose_rows12(Z16, PZ);
+    pg_edge_terms(Pi, Pj, PZ, rr, AA, BB);
+    if (r) memcpy(r, rr, sizeof(rr));
+    if (A) memcpy(A, AA, sizeof(AA));
+    if (B) memcpy(B, BB, sizeof(BB));
+    return ELM_OK;
+}
+
+extern "C" int elm_posegraph_create(elm_ctx* ctx, int node_capacity, int edge_capacity, elm_posegraph** out) {
+    if (!ctx || !out || node_capacity < 1 || node_capacity > ELM_POSEGRAPH_MAX_NODES || edge_capacity < 1 || edge_capacity > ELM_POSEGRAPH_MAX_EDGES)
+        return ELM_ERR_INVALID;
+    *out = nullptr;
+    int rc = check_plain(ctx, "elm_posegraph_create");
+    if (rc != ELM_OK) return rc;
+    if (ctx->in_flight) return ELM_ERR_INVALID;
+    return guard_alloc(ctx, "elm_posegraph_create", [&] { return create_impl(ctx, (uint32_t)node_capacity, (uint32_t)edge_capacity, out); });
+}
+
+extern "C" void elm_posegraph_destroy(elm_posegraph* pg) { pg_free(pg); }
+
+extern "C" int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg) {
+    int rc = check_object(ctx, pg, "elm_posegraph_reset");
+    if (rc != ELM_OK) return rc;
+    pg->N = pg->E = 0;
+    pg->fixed.clear();
+    pg->ei.clear();
+    pg->ej.clear();
+    pg->csr_dirty = true;
+    pg->lin_valid = false;
+    return ELM_OK;
+}
+
+extern "C" int elm_posegraph_size(elm_ctx* ctx, const elm_posegraph* pg, size_t* n_nodes, size_t* n_edges) {
+    if (!n_nodes || !n_edges) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, "elm_posegraph_size");
+    if (rc != ELM_OK) return rc;
+    *n_nodes = pg->N;
+    *n_edges = pg->E;
+    return ELM_OK;
+}
+
+extern "C" int elm_posegraph_add_nodes(elm_ctx* ctx, elm_posegraph* pg, const double* poses16, const uint8_t* fixed, size_t n) {
+    const char* what = "elm_posegraph_add_nodes";
+    if (!ctx || !pg || (n && !poses16)) return ELM_ERR_INVALID;
+    if (n > (size_t)ELM_POSEGRAPH_MAX_NODES || !poses_finite(poses16, n)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (n > (size_t)(pg->n_cap - pg->N)) return refuse_full(ctx, what, "nodes", pg->N, n, pg->n_cap);
+    if (!n) return ELM_OK;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        std::vector<double> rows(12 * n);
+        for (size_t k = 0; k < n; ++k) pose_rows12(poses16 + 16 * k, &rows[12 * k]);
+        std::vector<uint8_t> fx(n, 0);
+        if (fixed)
+            for (size_t k = 0; k < n; ++k) fx[k] = fixed[k] ? 1 : 0;
+        pg->fixed.reserve((size_t)pg->N + n);
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        hipError_t e = hipMemcpyAsync(pg->poses + 12 * (size_t)pg->N, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pg->d_fixed + pg->N, fx.data(), n, hipMemcpyHostToDevice, st);
+        int rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        pg->fixed.insert(pg->fixed.end(), fx.begin(), fx.end());
+        pg->N += (uint32_t)n;
+        pg->csr_dirty = true;
+        pg->lin_valid = false;
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_set_poses(elm_ctx* ctx, elm_posegraph* pg, size_t first, size_t count, const double* poses16) {
+    const char* what = "elm_posegraph_set_poses";
+    if (!ctx || !pg || (count && !poses16)) return ELM_ERR_INVALID;
+    if (count > (size_t)ELM_POSEGRAPH_MAX_NODES || !poses_finite(poses16, count)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
+    if (!count) return ELM_OK;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        std::vector<double> rows(12 * count);
+        for (size_t k = 0; k < count; ++k) pose_rows12(poses16 + 16 * k, &rows[12 * k]);
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        pg->lin_valid = false;
+        return join(ctx, st, hipMemcpyAsync(pg->poses + 12 * first, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st), what);
+    });
+}
+
+extern "C" int elm_posegraph_get_poses(elm_ctx* ctx, const elm_posegraph* pg, size_t first, size_t count, double* poses16) {
+    const char* what = "elm_posegraph_get_poses";
+    if (!ctx || !pg || (count && !poses16)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
+    if (!count) return ELM_OK;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        std::vector<double> rows(12 * count);
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        int rc = join(ctx, st, hipMemcpyAsync(rows.data(), pg->poses + 12 * first, rows.size() * sizeof(double), hipMemcpyDeviceToHost, st), what);
+        if (rc != ELM_OK) return rc;
+        for (size_t k = 0; k < count; ++k) rows12_to_pose16(&rows[12 * k], poses16 + 16 * k);
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_set_fixed(elm_ctx* ctx, elm_posegraph* pg, size_t first, size_t count, const uint8_t* fixed) {
+    const char* what = "elm_posegraph_set_fixed";
+    if (!ctx || !pg || (count && !fixed)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
+    if (!count) return ELM_OK;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        std::vector<uint8_t> fx(count);
+        for (size_t k = 0; k < count; ++k) fx[k] = fixed[k] ? 1 : 0;
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        int rc = join(ctx, st, hipMemcpyAsync(pg->d_fixed + first, fx.data(), count, hipMemcpyHostToDevice, st), what);
+        if (rc != ELM_OK) return rc;
+        std::copy(fx.begin(), fx.end(), pg->fixed.begin() + (long)first);
+        pg->lin_valid = false;
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const int32_t* i, const int32_t* j, const double* Z16, const double* info36,
+                                       size_t n) {
+    const char* what = "elm_posegraph_add_edges";
+    if (!ctx || !pg || (n && (!i || !j || !Z16 || !info36))) return ELM_ERR_INVALID;
+    if (n > (size_t)ELM_POSEGRAPH_MAX_EDGES || !poses_finite(Z16, n)) return ELM_ERR_INVALID;
+    for (size_t k = 0; k < n; ++k) {
+        if (i[k] < 0 || j[k] < 0 || i[k] == j[k]) return ELM_ERR_INVALID;
+        const double* om = info36 + 36 * k;
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b)
+                if (!isfinite(om[a * 6 + b]) || om[a * 6 + b] != om[b * 6 + a]) return ELM_ERR_INVALID;
+    }
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    for (size_t k = 0; k < n; ++k)
+        if ((uint32_t)i[k] >= pg->N || (uint32_t)j[k] >= pg->N) return ELM_ERR_INVALID;
+    if (n > (size_t)(pg->e_cap - pg->E)) return refuse_full(ctx, what, "edges", pg->E, n, pg->e_cap);
+    if (!n) return ELM_OK;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        std::vector<double> rows(12 * n);
+        for (size_t k = 0; k < n; ++k) pose_rows12(Z16 + 16 * k, &rows[12 * k]);
+        pg->ei.reserve((size_t)pg->E + n);
+        pg->ej.reserve((size_t)pg->E + n);
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        const size_t E0 = pg->E;
+        hipError_t e = hipMemcpyAsync(pg->d_ei + E0, i, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pg->d_ej + E0, j, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pg->d_Z + 12 * E0, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pg->d_info + 36 * E0, info36, 36 * n * sizeof(double), hipMemcpyHostToDevice, st);
+        int rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        pg->ei.insert(pg->ei.end(), i, i + n);
+        pg->ej.insert(pg->ej.end(), j, j + n);
+        pg->E += (uint32_t)n;
+        pg->csr_dirty = true;
+        pg->lin_valid = false;
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_linearize(elm_ctx* ctx, elm_posegraph* pg, double huber_k, elm_posegraph_linearize_stats* stats) {
+    const char* what = "elm_posegraph_linearize";
+    if (!ctx || !pg || !fin_ge0(huber_k)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        pg->lin_valid = false;
+        hipError_t e = queue_linearize(pg, st, huber_k, 0.0);
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        PgOut o{};
+        int rc = cost_at(ctx, pg, st, pg->poses, huber_k, 1, o, what);
+        if (rc != ELM_OK) return rc;
+        pg->lin_valid = true;
+        if (stats) {
+            stats->chi2 = o.chi2;
+            stats->cost = o.cost;
+            stats->grad_inf_norm = o.grad_inf;
+            stats->n_outliers = (int64_t)o.n_outliers;
+        }
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_download_linearization(elm_ctx* ctx, const elm_posegraph* pg, double* r, double* A, double* B, double* s, double* w,
+                                                    double* grad, double* diag) {
+    const char* what = "elm_posegraph_download_linearization";
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (!pg->lin_valid) return ELM_ERR_INVALID;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        const size_t E = pg->E, N = pg->N, S = pg->e_cap;
+        const PgDev& d = pg->dev;
+        // component-major on the device, [E][components] for the caller: each component row comes down, then the transpose
+        struct Part { double* dst; const double* src; size_t comps; };
+        const Part parts[3] = {{r, d.r, 6}, {A, d.A, 36}, {B, d.B, 36}};
+        std::vector<double> tmp[3];
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 3 && E; ++k) {
+            if (!parts[k].dst) continue;
+            tmp[k].resize(parts[k].comps * E);
+            for (size_t c = 0; c < parts[k].comps && e == hipSuccess; ++c)
+                e = hipMemcpyAsync(&tmp[k][c * E], parts[k].src + c * S, E * sizeof(double), hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess && s && E) e = hipMemcpyAsync(s, d.s, E * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && w && E) e = hipMemcpyAsync(w, d.w, E * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && grad && N) e = hipMemcpyAsync(grad, d.g, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && diag && N) e = hipMemcpyAsync(diag, d.Hd, 36 * N * sizeof(double), hipMemcpyDeviceToHost, st);
+        int rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        for (int k = 0; k < 3 && E; ++k)
+            if (parts[k].dst)
+                for (size_t c = 0; c < parts[k].comps; ++c)
+                    for (size_t q = 0; q < E; ++q) parts[k].dst[q * parts[k].comps + c] = tmp[k][c * E + q];
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_solve(elm_ctx* ctx, elm_posegraph* pg, double lambda, double pcg_rel_tol, int pcg_max_iterations, double* delta,
+                                   elm_posegraph_solve_stats* stats) {
+    const char* what = "elm_posegraph_solve";
+    if (!ctx || !pg || !fin_ge0(lambda) || !fin_ge0(pcg_rel_tol) || pcg_max_iterations < 1) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (!pg->lin_valid) return ELM_ERR_INVALID;
+    return guard_alloc(ctx, what, [&] {
+        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+        const PgDev& d = dev_view(pg);
+        hipError_t e = launched([&] { launch_pg_nodes(st, d, lambda, 0); });
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        PgState s{};
+        int rc = run_pcg(ctx, pg, st, lambda, pcg_rel_tol, pcg_max_iterations, kPgDefaultCheckEvery, s, what);
+        if (rc != ELM_OK) return rc;
+        if (delta && pg->N) {
+            rc = join(ctx, st, hipMemcpyAsync(delta, d.x, 6 * (size_t)pg->N * sizeof(double), hipMemcpyDeviceToHost, st), what);
+            if (rc != ELM_OK) return rc;
+        }
+        if (stats) {
+            stats->iterations = (int32_t)s.iters;
+            stats->converged = (int32_t)s.converged;
+            stats->rel_residual = rel_residual(s, pg->N);
+        }
+        return (int)ELM_OK;
+    });
+}
+
+extern "C" int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config* cfg, elm_posegraph_result* result,
+                                      elm_posegraph_trace* trace, int trace_cap) {
+    const char* what = "elm_posegraph_optimize";
+    if (!ctx || !pg || !config_ok(cfg) || trace_cap < 0 || (trace_cap > 0 && !trace)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    if (std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end()) {
+        elm_host::ctx_set_error(ctx, std::string(what) + ": no fixed node (the gauge is free)");
+        return ELM_ERR_INVALID;
+    }
+    return guard_alloc(ctx, what, [&] { return optimize_impl(ctx, pg, *cfg, result, trace_cap > 0 ? trace : nullptr, trace_cap); });
+}

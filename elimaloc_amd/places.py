@@ -216,6 +216,7 @@ class LoopCloser:
         self.m_config = m_config
         self.reg = registration if registration is not None else Registration(m_config, ctx=self.ctx)
         self.scans, self.poses = [], []
+        self.loops = []  # AddLoop: (entry_a, entry_b, T_a_b, information)
 
     def Insert(self, scan, T_world_sensor, T_level=None):
         sc = _resident(self.ctx, scan)
@@ -255,3 +256,50 @@ class LoopCloser:
         T, ok, fit, cov, cands = self.reg.Relocalize(pts, m, self.Guess(candidate), self.reloc, self.m_config)
         return dict(T=T, is_success=ok, fitness_score=fit, local_cov=cov, candidates=cands,
                     T_entry_query=np.linalg.inv(self.poses[candidate["entry"]]) @ T)
+
+    def AddLoop(self, entry_a, entry_b, T_a_b, information=None):
+        """A loop constraint for Close: T_a_b ~ T_a^-1 T_b between two entries (Verify's T_entry_query, with the query inserted as an
+        entry); information: 6 x 6 symmetric in the order [translation; rotation] (default: the identity)."""
+        n = len(self.scans)
+        a, b = int(entry_a), int(entry_b)
+        if not (0 <= a < n and 0 <= b < n) or a == b:
+            raise ElmError("LoopCloser.AddLoop: two different entries")
+        info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
+        self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
+
+    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False):
+        """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
+        Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
+        -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
+        The default informations are the identity, which weighs a metre like a radian and an odometry step like a verified loop: a
+        caller with real data passes informations that say how good its odometry and its loops are."""
+        from .posegraph import PoseGraph
+        n = len(self.scans)
+        if n < 2:
+            raise ElmError("LoopCloser.Close: at least two entries")
+        P = np.stack(self.poses)
+        pg = PoseGraph(n, n - 1 + max(len(self.loops), 1), self.ctx)
+        try:
+            fx = np.zeros(n, bool)
+            fx[list(fixed)] = True
+            pg.AddNodes(P, fx)
+            Z = np.linalg.inv(P[:-1]) @ P[1:]
+            pg.AddEdges(np.arange(n - 1), np.arange(1, n), Z, None if odom_information is None else np.asarray(odom_information, dtype=np.float64))
+            if self.loops:
+                pg.AddEdges([l[0] for l in self.loops], [l[1] for l in self.loops], np.stack([l[2] for l in self.loops]),
+                            np.stack([l[3] for l in self.loops]))
+            res = pg.Optimize(cfg)
+            out = pg.Poses()
+        finally:
+            pg.close()
+        if apply:
+            self.poses = [out[k].copy() for k in range(n)]
+        return out, res
+
+    def Map(self, poses=None):
+        """The whole-log device build of the kept scans at the current (or the given) poses."""
+        P = np.stack(self.poses) if poses is None else np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if P.shape[0] != len(self.scans):
+            raise ElmError("LoopCloser.Map: one pose per entry")
+        base = VoxelHashMap(self.voxel_size, self.max_points_per_voxel, self.ctx, device_build=True)
+        return base.UpdatedFromScans(self.scans, P)

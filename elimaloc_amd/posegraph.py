@@ -1,0 +1,143 @@
+"""Pose graph (include/elimaloc_hip.h "pose graph"): nodes and relative-pose edges resident on the GPU, their SE(3)
+linearization, the damped normal equations solved by block-Jacobi preconditioned conjugate gradients, and Levenberg-Marquardt around
+that -- from odometry constraints and loop constraints to corrected poses."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import (ElmError, PG_STOP, PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC, PoseGraphTraceC,
+                   check)
+from .registration import _Owned, _dp, _pose_block, _ptr, default_context
+
+_INT_FIELDS = ("max_iterations", "pcg_max_iterations", "pcg_check_every")
+
+
+def PoseGraphConfig(**kw):
+    """elm_posegraph_config with its defaults (20 solves, lambda 1e-4 x10 up / x0.1 down in [1e-12, 1e8], cost_rel_tol 1e-12, step_tol
+    1e-10, PCG to 1e-8 in at most 2000 iterations checked every 32, Huber off)."""
+    cfg = PoseGraphConfigC()
+    _lib.lib().elm_posegraph_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"PoseGraphConfig has no field {k}")
+        setattr(cfg, k, int(v) if k in _INT_FIELDS else float(v))
+    return cfg
+
+
+def EdgeTerms(Ti, Tj, Z):
+    """(r [6], A [6, 6], B [6, 6]) of one edge: the library's own residual and Jacobians (host only, the code the kernel runs)."""
+    r, A, B = np.zeros(6), np.zeros((6, 6)), np.zeros((6, 6))
+    check(_lib.lib().elm_posegraph_edge_terms(_dp(_pose_block(Ti)), _dp(_pose_block(Tj)), _dp(_pose_block(Z)), _dp(r), _dp(A), _dp(B)), None,
+          "elm_posegraph_edge_terms")
+    return r, A, B
+
+
+def _result(res, trace, n):
+    out = dict(solves=int(res.solves), accepted=int(res.accepted), rejected=int(res.rejected), cost_initial=float(res.cost_initial),
+               cost_final=float(res.cost_final), lambda_final=float(res.lambda_final), pcg_iterations_total=int(res.pcg_iterations_total),
+               stop_reason=PG_STOP.get(int(res.stop_reason), int(res.stop_reason)))
+    out["trace"] = [dict(cost=float(t.cost), lambda_=float(t.lambda_), accepted=bool(t.accepted), pcg_iterations=int(t.pcg_iterations))
+                    for t in trace[:min(n, out["solves"])]]
+    return out
+
+
+class PoseGraph(_Owned):
+    """A pose graph resident on the device (elm_posegraph), of capacities fixed at creation (nodes 1 .. 2^20, edges 1 .. 2^22)."""
+
+    def __init__(self, node_capacity=1024, edge_capacity=4096, ctx=None):
+        self.ctx = ctx if ctx is not None else default_context()
+        self.node_capacity, self.edge_capacity = int(node_capacity), int(edge_capacity)
+        self._h = C.c_void_p()
+        check(_lib.lib().elm_posegraph_create(self.ctx._h, self.node_capacity, self.edge_capacity, C.byref(self._h)), self.ctx._h,
+              "elm_posegraph_create")
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ElmError("PoseGraph: closed")
+        return self._h
+
+    def _call(self, name, *args):
+        check(getattr(_lib.lib(), name)(self.ctx._h, self._handle(), *args), self.ctx._h, name)
+
+    def Size(self):
+        """-> (n_nodes, n_edges)"""
+        n, e = C.c_size_t(0), C.c_size_t(0)
+        self._call("elm_posegraph_size", C.byref(n), C.byref(e))
+        return int(n.value), int(e.value)
+
+    def Reset(self):
+        self._call("elm_posegraph_reset")
+
+    def AddNodes(self, poses, fixed=None):
+        """poses [n, 4, 4] appended; fixed: bool per node (default: all free)."""
+        P = _pose_block(poses)
+        n = P.size // 16
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
+        if fx is not None and fx.size != n:
+            raise ElmError("PoseGraph.AddNodes: one fixed flag per node")
+        self._call("elm_posegraph_add_nodes", _dp(P) if n else None, _ptr(fx) if n else None, n)
+
+    def SetPoses(self, poses, first=0):
+        P = _pose_block(poses)
+        self._call("elm_posegraph_set_poses", int(first), P.size // 16, _dp(P) if P.size else None)
+
+    def Poses(self, first=0, count=None):
+        """-> poses [count, 4, 4] (default: to the end)"""
+        count = self.Size()[0] - int(first) if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ElmError("PoseGraph.Poses: beyond the graph's nodes")
+        out = np.zeros((max(count, 1), 16))
+        self._call("elm_posegraph_get_poses", int(first), count, _dp(out))
+        return np.ascontiguousarray(out[:count].reshape(-1, 4, 4).transpose(0, 2, 1))
+
+    def SetFixed(self, fixed, first=0):
+        fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
+        self._call("elm_posegraph_set_fixed", int(first), fx.size, _ptr(fx) if fx.size else None)
+
+    def AddEdges(self, i, j, Z, information=None):
+        """Edges (i[k], j[k], Z[k] ~ T_i^-1 T_j, information[k] 6 x 6 symmetric in the order [v; w], default identity) appended."""
+        i = np.ascontiguousarray(np.asarray(i, dtype=np.int32).reshape(-1))
+        j = np.ascontiguousarray(np.asarray(j, dtype=np.int32).reshape(-1))
+        Zb = _pose_block(Z)
+        n = i.size
+        info = np.tile(np.eye(6), (n, 1, 1)) if information is None else np.asarray(information, dtype=np.float64)
+        info = np.ascontiguousarray(np.broadcast_to(info, (n, 6, 6)) if info.ndim == 2 else info.reshape(-1, 6, 6))
+        if j.size != n or Zb.size != 16 * n or info.shape[0] != n:
+            raise ElmError("PoseGraph.AddEdges: one j, Z and information per edge")
+        self._call("elm_posegraph_add_edges", _ptr(i) if n else None, _ptr(j) if n else None, _dp(Zb) if n else None, _dp(info) if n else None, n)
+
+    def Linearize(self, huber_k=0.0):
+        """Residuals, Jacobians, weights and the normal equations' blocks at the current poses -> dict(chi2, cost, grad_inf_norm, n_outliers)."""
+        st = PoseGraphLinearizeStatsC()
+        self._call("elm_posegraph_linearize", float(huber_k), C.byref(st))
+        return dict(chi2=float(st.chi2), cost=float(st.cost), grad_inf_norm=float(st.grad_inf_norm), n_outliers=int(st.n_outliers))
+
+    def Linearization(self):
+        """The current linearization -> dict(r [E, 6], A [E, 6, 6], B [E, 6, 6], s [E], w [E], grad [N, 6], diag [N, 6, 6])."""
+        N, E = self.Size()
+        n, e = max(N, 1), max(E, 1)
+        r, A, B, s, w = np.zeros((e, 6)), np.zeros((e, 6, 6)), np.zeros((e, 6, 6)), np.zeros(e), np.zeros(e)
+        grad, diag = np.zeros((n, 6)), np.zeros((n, 6, 6))
+        self._call("elm_posegraph_download_linearization", _dp(r), _dp(A), _dp(B), _dp(s), _dp(w), _dp(grad), _dp(diag))
+        return dict(r=r[:E], A=A[:E], B=B[:E], s=s[:E], w=w[:E], grad=grad[:N], diag=diag[:N])
+
+    def Solve(self, lambda_=0.0, pcg_rel_tol=1e-8, pcg_max_iterations=2000):
+        """The step of the current linearization -> (delta [N, 6], dict(iterations, rel_residual, converged))."""
+        N = self.Size()[0]
+        delta = np.zeros((max(N, 1), 6))
+        st = PoseGraphSolveStatsC()
+        self._call("elm_posegraph_solve", float(lambda_), float(pcg_rel_tol), int(pcg_max_iterations), _dp(delta), C.byref(st))
+        return delta[:N], dict(iterations=int(st.iterations), rel_residual=float(st.rel_residual), converged=bool(st.converged))
+
+    def Optimize(self, cfg=None, trace_cap=64):
+        """Levenberg-Marquardt from the current poses, which it replaces -> dict(solves, accepted, rejected, cost_initial, cost_final,
+        lambda_final, pcg_iterations_total, stop_reason, trace: per solve dict(cost, lambda_, accepted, pcg_iterations))."""
+        cfg = cfg if cfg is not None else PoseGraphConfig()
+        res = PoseGraphResultC()
+        trace = (PoseGraphTraceC * max(int(trace_cap), 1))()
+        self._call("elm_posegraph_optimize", C.byref(cfg), C.byref(res), trace, int(trace_cap))
+        return _result(res, trace, int(trace_cap))
+
+    def _destroy(self, h):
+        _lib.lib().elm_posegraph_destroy(h)

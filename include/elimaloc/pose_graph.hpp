@@ -1,0 +1,162 @@
+// pose_graph.hpp -- the pose graph (include/elimaloc_hip.h, "pose graph"): the C++ face of elm_posegraph in the shim's types.  Nodes and
+// relative-pose edges resident on the device, their linearization, the damped normal equations solved by preconditioned conjugate
+// gradients, and Levenberg-Marquardt: from odometry and loop constraints to corrected poses.  The residual, the Jacobians, the robust
+// weight and the rules of the outer loop are those of the C header.
+#pragma once
+#include <utility>
+#include <vector>
+
+#include "registration.hpp"
+
+struct PoseGraphConfig {
+    int max_iterations = 20, pcg_max_iterations = 2000, pcg_check_every = 32;
+    double lambda_init = 1e-4, lambda_up = 10.0, lambda_down = 0.1, lambda_min = 1e-12, lambda_max = 1e8;
+    double cost_rel_tol = 1e-12, step_tol = 1e-10, pcg_rel_tol = 1e-8, huber_k = 0.0;
+    elm_posegraph_config c_struct() const {
+        elm_posegraph_config c;
+        elm_posegraph_config_default(&c);
+        c.max_iterations = max_iterations;
+        c.pcg_max_iterations = pcg_max_iterations;
+        c.pcg_check_every = pcg_check_every;
+        c.lambda_init = lambda_init;
+        c.lambda_up = lambda_up;
+        c.lambda_down = lambda_down;
+        c.lambda_min = lambda_min;
+        c.lambda_max = lambda_max;
+        c.cost_rel_tol = cost_rel_tol;
+        c.step_tol = step_tol;
+        c.pcg_rel_tol = pcg_rel_tol;
+        c.huber_k = huber_k;
+        return c;
+    }
+};
+
+struct PoseGraphEdge {
+    int i = 0, j = 1;
+    elimaloc::Matrix4d Z = elimaloc::Matrix4d::Identity();           // ~ T_i^-1 T_j
+    elimaloc::Matrix6d information = elimaloc::Matrix6d::Identity(); // symmetric, in the order [translation; rotation]
+};
+
+struct PoseGraphLinearization {
+    std::vector<double> r, A, B, s, w, grad, diag; // [E][6], [E][36], [E][36], [E], [E], [N][6], [N][36], row-major
+};
+
+class PoseGraph {
+public:
+    using Poses = std::vector<elimaloc::Matrix4d>;
+    PoseGraph(int node_capacity, int edge_capacity) {
+        elimaloc::check(elm_posegraph_create(VoxelHashMap::ctx(), node_capacity, edge_capacity, &pg_), VoxelHashMap::ctx(), "elm_posegraph_create");
+    }
+    PoseGraph(const PoseGraph&) = delete; // owns device memory
+    PoseGraph& operator=(const PoseGraph&) = delete;
+    ~PoseGraph() { elm_posegraph_destroy(pg_); }
+
+    inline size_t Nodes() const { return sizes().first; }
+    inline size_t Edges() const { return sizes().second; }
+    inline void Reset() { elimaloc::check(elm_posegraph_reset(VoxelHashMap::ctx(), pg_), VoxelHashMap::ctx(), "elm_posegraph_reset"); }
+
+    inline void AddNodes(const Poses& poses, const std::vector<bool>* fixed = nullptr) {
+        elimaloc::check(!fixed || fixed->size() == poses.size() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "PoseGraph::AddNodes: one flag per node");
+        const std::vector<double> block = flat(poses);
+        std::vector<uint8_t> fx(poses.size() + 1, 0);
+        for (size_t k = 0; fixed && k < poses.size(); ++k) fx[k] = (*fixed)[k] ? 1 : 0;
+        elimaloc::check(elm_posegraph_add_nodes(VoxelHashMap::ctx(), pg_, block.data(), fx.data(), poses.size()), VoxelHashMap::ctx(),
+                        "elm_posegraph_add_nodes");
+    }
+    inline void SetPoses(const Poses& poses, size_t first = 0) {
+        const std::vector<double> block = flat(poses);
+        elimaloc::check(elm_posegraph_set_poses(VoxelHashMap::ctx(), pg_, first, poses.size(), block.data()), VoxelHashMap::ctx(),
+                        "elm_posegraph_set_poses");
+    }
+    inline Poses GetPoses() const {
+        const size_t n = Nodes();
+        std::vector<double> block(16 * n + 1);
+        elimaloc::check(elm_posegraph_get_poses(VoxelHashMap::ctx(), pg_, 0, n, block.data()), VoxelHashMap::ctx(), "elm_posegraph_get_poses");
+        Poses out(n);
+        for (size_t k = 0; k < n; ++k)
+            for (int q = 0; q < 16; ++q) out[k].data()[q] = block[16 * k + (size_t)q];
+        return out;
+    }
+    inline void SetFixed(const std::vector<bool>& fixed, size_t first = 0) {
+        std::vector<uint8_t> fx(fixed.size() + 1, 0);
+        for (size_t k = 0; k < fixed.size(); ++k) fx[k] = fixed[k] ? 1 : 0;
+        elimaloc::check(elm_posegraph_set_fixed(VoxelHashMap::ctx(), pg_, first, fixed.size(), fx.data()), VoxelHashMap::ctx(),
+                        "elm_posegraph_set_fixed");
+    }
+    inline void AddEdges(const std::vector<PoseGraphEdge>& edges) {
+        const size_t n = edges.size();
+        std::vector<int32_t> i(n + 1), j(n + 1);
+        std::vector<double> Z(16 * n + 1), info(36 * n + 1);
+        for (size_t k = 0; k < n; ++k) {
+            i[k] = edges[k].i;
+            j[k] = edges[k].j;
+            for (int q = 0; q < 16; ++q) Z[16 * k + (size_t)q] = edges[k].Z.data()[q];
+            for (int r = 0; r < 6; ++r)
+                for (int c = 0; c < 6; ++c) info[36 * k + (size_t)(r * 6 + c)] = edges[k].information(r, c);
+        }
+        elimaloc::check(elm_posegraph_add_edges(VoxelHashMap::ctx(), pg_, i.data(), j.data(), Z.data(), info.data(), n), VoxelHashMap::ctx(),
+                        "elm_posegraph_add_edges");
+    }
+    inline elm_posegraph_linearize_stats Linearize(double huber_k = 0.0) {
+        elm_posegraph_linearize_stats st;
+        elimaloc::check(elm_posegraph_linearize(VoxelHashMap::ctx(), pg_, huber_k, &st), VoxelHashMap::ctx(), "elm_posegraph_linearize");
+        return st;
+    }
+    inline PoseGraphLinearization Linearization() const {
+        const size_t N = Nodes(), E = Edges();
+        PoseGraphLinearization L;
+        L.r.assign(6 * E + 1, 0.0);
+        L.A.assign(36 * E + 1, 0.0);
+        L.B.assign(36 * E + 1, 0.0);
+        L.s.assign(E + 1, 0.0);
+        L.w.assign(E + 1, 0.0);
+        L.grad.assign(6 * N + 1, 0.0);
+        L.diag.assign(36 * N + 1, 0.0);
+        elimaloc::check(elm_posegraph_download_linearization(VoxelHashMap::ctx(), pg_, L.r.data(), L.A.data(), L.B.data(), L.s.data(), L.w.data(),
+                                                             L.grad.data(), L.diag.data()),
+                        VoxelHashMap::ctx(), "elm_posegraph_download_linearization");
+        L.r.pop_back();
+        L.A.pop_back();
+        L.B.pop_back();
+        L.s.pop_back();
+        L.w.pop_back();
+        L.grad.pop_back();
+        L.diag.pop_back();
+        return L;
+    }
+    // the step of the current linearization, [Nodes()][6]
+    inline std::vector<double> Solve(double lambda, double pcg_rel_tol = 1e-8, int pcg_max_iterations = 2000, elm_posegraph_solve_stats* stats = nullptr) {
+        std::vector<double> delta(6 * Nodes() + 1);
+        elimaloc::check(elm_posegraph_solve(VoxelHashMap::ctx(), pg_, lambda, pcg_rel_tol, pcg_max_iterations, delta.data(), stats), VoxelHashMap::ctx(),
+                        "elm_posegraph_solve");
+        delta.pop_back();
+        return delta;
+    }
+    inline elm_posegraph_result Optimize(const PoseGraphConfig& config = PoseGraphConfig(), std::vector<elm_posegraph_trace>* trace = nullptr) {
+        const elm_posegraph_config c = config.c_struct();
+        elm_posegraph_result res;
+        std::vector<elm_posegraph_trace> tr((size_t)(c.max_iterations > 0 ? c.max_iterations : 0) + 1);
+        elimaloc::check(elm_posegraph_optimize(VoxelHashMap::ctx(), pg_, &c, &res, tr.data(), (int)tr.size() - 1), VoxelHashMap::ctx(),
+                        "elm_posegraph_optimize");
+        if (trace) trace->assign(tr.begin(), tr.begin() + res.solves);
+        return res;
+    }
+    // host only: the residual and Jacobians of one edge (row-major r[6], A[36], B[36])
+    static inline void EdgeTerms(const elimaloc::Matrix4d& Ti, const elimaloc::Matrix4d& Tj, const elimaloc::Matrix4d& Z, double* r, double* A, double* B) {
+        elimaloc::check(elm_posegraph_edge_terms(Ti.data(), Tj.data(), Z.data(), r, A, B), nullptr, "elm_posegraph_edge_terms");
+    }
+
+private:
+    static std::vector<double> flat(const Poses& poses) {
+        std::vector<double> block(16 * poses.size() + 1);
+        for (size_t k = 0; k < poses.size(); ++k)
+            for (int q = 0; q < 16; ++q) block[16 * k + (size_t)q] = poses[k].data()[q];
+        return block;
+    }
+    std::pair<size_t, size_t> sizes() const {
+        size_t n = 0, e = 0;
+        elimaloc::check(elm_posegraph_size(VoxelHashMap::ctx(), pg_, &n, &e), VoxelHashMap::ctx(), "elm_posegraph_size");
+        return std::make_pair(n, e);
+    }
+    elm_posegraph* pg_ = nullptr;
+};

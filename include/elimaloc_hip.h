@@ -932,6 +932,116 @@ int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans,
                      const elm_places_query_config* query_cfg, elm_place_candidate* cands, int32_t* n_cands, elm_place_match* matches,
                      elm_places_stats* stats);
 
+/* ---------------------------------------------------------------- pose graph ---------------------- */
+/* Given odometry constraints and loop constraints, the corrected poses.  A pose graph object holds, resident on the device, NODES (poses)
+ * and relative-pose EDGES, linearizes them on the GPU, solves the damped normal equations by block-Jacobi preconditioned conjugate
+ * gradients on the GPU, and runs Levenberg-Marquardt around that.  One rank only.  Everything is float64 without contraction.
+ * NODES.  T_v = [R_v | t_v], world <- node, column-major 4 x 4 here, the twelve pose rows on the device; a `fixed` flag each.
+ * TANGENT AND RETRACTION.  x = [v; w], translation first: R <- R Exp(w), t <- t + R v, Exp = Rodrigues (zero -> identity).
+ * EDGES.  (i, j, Z, Omega): Z ~ T_i^-1 T_j; Omega 6 x 6, symmetric, row-major, in the order of x.  i == j, an index past the node count,
+ * a non-finite entry or an Omega that is not exactly symmetric is ELM_ERR_INVALID; duplicate edges and i > j are legal.
+ * RESIDUAL.  d = R_i^T (t_j - t_i), R_E = R_Z^T (R_i^T R_j), r = [r_t; r_R] = [R_Z^T (d - t_Z); Log(R_E)].
+ * LOG goes through the unit quaternion (w, vec) of the matrix, signed to w >= 0: n = |vec|, theta = 2 atan2(n, w),
+ * phi = vec (theta / n); below n = 1e-8, phi = 2 vec.  Log(I) is exactly 0.
+ * JACOBIANS, rows in the order of r, columns in the order of x:
+ *   A = dr/dx_i = [ -R_Z^T   R_Z^T [d]x ;  0  -J^-1(phi) R_j^T R_i ]      B = dr/dx_j = [ R_E  0 ;  0  J^-1(phi) ]
+ *   J^-1(phi) = I + [phi]x / 2 + c(theta) [phi]x^2,  c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta).
+ * Built: the second term of c is evaluated as w / (2 theta n) with the quaternion's w = cos(theta / 2), n = sin(theta / 2) -- the same
+ * number, (1 + cos) / sin = cot(theta / 2), without the cancellation of 1 + cos theta near pi; below theta = 1e-2 c is its series
+ * 1/12 + theta^2/720 + theta^4/30240 (both branches good to 1e-11 relative there).  The formulas agree with central differences of the
+ * residual (tests/test_posegraph_abi.py).
+ * ROBUST WEIGHT.  Huber on s_e = r^T Omega r: w_e = 1 if s_e <= k^2 else k / sqrt(s_e); cost rho_e = s_e if s_e <= k^2 else
+ * 2 k sqrt(s_e) - k^2.  huber_k = 0 turns it off.  s_e == k^2 is an inlier.
+ * NORMAL EQUATIONS.  H_vv = sum_e w_e X^T Omega X, H_ij = w_e A^T Omega B, g_v = sum_e w_e X^T Omega r (X = A for v = i, B for v = j);
+ * every per-node sum runs over the node's incident edges IN ASCENDING EDGE INDEX, one addition per edge.  That order makes the results
+ * the same bytes from run to run; they are NOT invariant under a permutation of the edges.
+ * FIXED NODES have delta = 0 and their rows and columns are left out; a free node whose diagonal block is all zero (no edges) is
+ * treated as fixed for the solve and stays where it is.  A connected component without a fixed node is the caller's business: with
+ * lambda > 0 the damping keeps the solve defined and the component's gauge floats; with lambda = 0 the system is singular.
+ * STEP.  (H + lambda diag(H)) delta = -g by preconditioned conjugate gradients from delta = 0, the preconditioner the inverse of the
+ * node's damped diagonal block; it stops at sqrt(r^T M^-1 r) <= pcg_rel_tol sqrt(r0^T M^-1 r0) or at pcg_max_iterations;
+ * pcg_rel_tol = 0 runs exactly pcg_max_iterations.  Every inner product is a fixed tree over partial sums whose number and order depend
+ * on the node count and the edge set alone.
+ * OUTER LOOP (elm_posegraph_optimize).  F = sum rho_e at the poses; F == 0 stops at once.  Per solve: solve, retract into trial poses,
+ * F_new there.  F_new < F: accept, lambda <- max(lambda lambda_down, lambda_min), then stop on F_new == 0, on
+ * F - F_new <= cost_rel_tol F, on max |delta| <= step_tol, on the solve count, else linearize again.  Otherwise: reject, the poses and
+ * the linearization stay; stop on max |delta| <= step_tol or when lambda is already lambda_max; else lambda <- min(lambda lambda_up,
+ * lambda_max) and only the damped diagonal and its inverses are redone.
+ * LIMITS.  node_capacity 1 .. 2^20, edge_capacity 1 .. 2^22, fixed for the object's life; device memory about 0.6 KB per node and
+ * 1.7 KB per edge of capacity. */
+typedef struct elm_posegraph elm_posegraph;
+#define ELM_POSEGRAPH_MAX_NODES (1 << 20)
+#define ELM_POSEGRAPH_MAX_EDGES (1 << 22)
+#define ELM_PG_STOP_MAX_ITERATIONS 1
+#define ELM_PG_STOP_COST_TOL 2
+#define ELM_PG_STOP_STEP_TOL 3
+#define ELM_PG_STOP_LAMBDA_MAX 4
+#define ELM_PG_STOP_COST_ZERO 5
+typedef struct elm_posegraph_config {
+    int32_t max_iterations;     /* solves, >= 1 */
+    int32_t pcg_max_iterations; /* >= 1 */
+    int32_t pcg_check_every;    /* PCG iterations queued between two reads of the device's done word, >= 1 */
+    int32_t _pad;
+    double lambda_init, lambda_up, lambda_down, lambda_min, lambda_max;
+    double cost_rel_tol, step_tol, pcg_rel_tol, huber_k;
+} elm_posegraph_config;
+typedef struct elm_posegraph_linearize_stats {
+    double chi2;          /* sum s_e */
+    double cost;          /* sum rho_e */
+    double grad_inf_norm; /* max |g_v| over the nodes the solve moves */
+    int64_t n_outliers;   /* edges with w_e < 1 */
+} elm_posegraph_linearize_stats;
+typedef struct elm_posegraph_solve_stats {
+    int32_t iterations;
+    int32_t converged;    /* the stop test was met (never with pcg_rel_tol = 0) */
+    double rel_residual;  /* sqrt(r^T M^-1 r) / sqrt(r0^T M^-1 r0) of the recurrence; 0 when the right-hand side is 0 */
+} elm_posegraph_solve_stats;
+typedef struct elm_posegraph_result {
+    int32_t solves, accepted, rejected, stop_reason; /* ELM_PG_STOP_* */
+    double cost_initial, cost_final, lambda_final;
+    int64_t pcg_iterations_total;
+} elm_posegraph_result;
+typedef struct elm_posegraph_trace {
+    double cost;    /* F_new of the solve's trial poses */
+    double lambda;  /* the solve's damping */
+    int32_t accepted, pcg_iterations;
+} elm_posegraph_trace;
+/* 20 solves, lambda 1e-4 (x 10 up, x 0.1 down, in [1e-12, 1e8]), cost_rel_tol 1e-12, step_tol 1e-10, PCG to 1e-8 in at most 2000
+ * iterations checked every 32, Huber off */
+void elm_posegraph_config_default(elm_posegraph_config* c);
+/* An empty graph.  ELM_ERR_UNSUPPORTED on a device group's lead or with a communicator / hook attached, here and in every call below
+ * that takes ctx; ELM_ERR_INVALID while a batch is in flight. */
+int elm_posegraph_create(elm_ctx* ctx, int node_capacity, int edge_capacity, elm_posegraph** out);
+void elm_posegraph_destroy(elm_posegraph* pg);
+/* no nodes, no edges */
+int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg);
+int elm_posegraph_size(elm_ctx* ctx, const elm_posegraph* pg, size_t* n_nodes, size_t* n_edges);
+/* n nodes appended: poses16[n][16] column-major, finite; fixed[n] (NULL: all free).  A call that would overfill is ELM_ERR_UNSUPPORTED
+ * and changes nothing (as for edges). */
+int elm_posegraph_add_nodes(elm_ctx* ctx, elm_posegraph* pg, const double* poses16, const uint8_t* fixed, size_t n);
+int elm_posegraph_set_poses(elm_ctx* ctx, elm_posegraph* pg, size_t first, size_t count, const double* poses16);
+int elm_posegraph_get_poses(elm_ctx* ctx, const elm_posegraph* pg, size_t first, size_t count, double* poses16);
+int elm_posegraph_set_fixed(elm_ctx* ctx, elm_posegraph* pg, size_t first, size_t count, const uint8_t* fixed);
+/* n edges appended: i[n], j[n], Z16[n][16] column-major, info36[n][36] row-major */
+int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const int32_t* i, const int32_t* j, const double* Z16, const double* info36, size_t n);
+/* Residuals, Jacobians, weights and the normal equations' blocks at the current poses; stats when not NULL.  huber_k >= 0. */
+int elm_posegraph_linearize(elm_ctx* ctx, elm_posegraph* pg, double huber_k, elm_posegraph_linearize_stats* stats);
+/* The current linearization, each output when not NULL: r[E][6], A[E][36], B[E][36], s[E], w[E], grad[N][6] (g_v as summed, for
+ * fixed nodes too), diag[N][36] (H_vv undamped).  ELM_ERR_INVALID without one (the graph changed since, or never linearized). */
+int elm_posegraph_download_linearization(elm_ctx* ctx, const elm_posegraph* pg, double* r, double* A, double* B, double* s, double* w,
+                                         double* grad, double* diag);
+/* The step of the current linearization: delta[N][6] (when not NULL) and stats (when not NULL).  lambda >= 0, pcg_rel_tol >= 0,
+ * pcg_max_iterations >= 1.  The PCG iterations are queued pcg_check_every = 32 at a time. */
+int elm_posegraph_solve(elm_ctx* ctx, elm_posegraph* pg, double lambda, double pcg_rel_tol, int pcg_max_iterations, double* delta,
+                        elm_posegraph_solve_stats* stats);
+/* Levenberg-Marquardt from the current poses, which it replaces.  ELM_ERR_INVALID: no fixed node at all, a bad config.  trace, when not
+ * NULL: the first trace_cap solves. */
+int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config* cfg, elm_posegraph_result* result,
+                           elm_posegraph_trace* trace, int trace_cap);
+/* The residual and Jacobians of one edge, each output when not NULL: r[6], A[36], B[36] row-major.  Host only: the same code the kernel
+ * runs, compiled for the host. */
+int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const double Z16[16], double* r, double* A, double* B);
+
 /* ---------------------------------------------------------------- device index build -------------- */
 /* The P2P / GICP cell grid of a map (dense or two-level) is laid out on the host by default: the stored points come down, are
  * counting-sorted by cell on one thread and go up again.  With ELM_INDEX_BUILD_DEVICE the same grid is built on the device from the stored

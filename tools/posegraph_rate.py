@@ -1,0 +1,107 @@
+"""Pose-graph cost on one GPU: prints ONE JSON line and writes it to profiles/posegraph_rate.json.
+
+A ring of N nodes, N in 1 000, 10 000 and 65 536: the truth runs along a circle with 1 m between neighbours; odometry edges k -> k + 1
+without noise, a loop edge k -> k + 100 for every k that is a multiple of 100, and one edge closing the ring (N - 1 -> 0), all from the
+truth with the identity as information; the start is the odometry integrated with a fixed drift per step (0.2 rad of yaw and 5 m in all
+over the whole ring, whatever N), node 0 fixed.  Reported per N, as wall clock of the calls: one elm_posegraph_linearize (median of --reps), one
+elm_posegraph_solve at lambda 1e-4 and pcg_rel_tol 1e-6 (its iterations, whether it met the tolerance within --pcg-max, and the ms per
+iteration), and one elm_posegraph_optimize from the drifted start with the same PCG settings (solves, PCG iterations in all, stop
+reason, costs, total ms, and the largest pose error against the truth).
+Kernel-only times: run under a kernel trace (k_pg_*), e.g. with --sizes 1000.
+
+    python tools/posegraph_rate.py [--reps 5] [--sizes 1000,10000,65536] [--pcg-max 20000] [--out profiles/posegraph_rate.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def rz(a):
+    T = np.tile(np.eye(4), (len(a), 1, 1))
+    c, s = np.cos(a), np.sin(a)
+    T[:, 0, 0], T[:, 0, 1], T[:, 1, 0], T[:, 1, 1] = c, -s, s, c
+    return T
+
+
+def ring(N):
+    a = 2.0 * np.pi * np.arange(N) / N
+    radius = N / (2.0 * np.pi)
+    truth = rz(a + np.pi / 2.0)
+    truth[:, 0, 3], truth[:, 1, 3], truth[:, 2, 3] = radius * np.cos(a), radius * np.sin(a), 0.2 * np.sin(3.0 * a)
+    k = np.arange(0, N - 100, 100)
+    i = np.concatenate([np.arange(N - 1), k, [N - 1]])
+    j = np.concatenate([np.arange(1, N), k + 100, [0]])
+    Z = np.linalg.inv(truth[i]) @ truth[j]
+    D = rz(np.array([0.2 / N]))[0]
+    D[:3, 3] = np.array([4.0, -2.5, 1.5]) / N
+    start = np.empty_like(truth)
+    start[0] = truth[0]
+    for n in range(N - 1):
+        start[n + 1] = start[n] @ Z[n] @ D
+    return truth, start, i, j, Z
+
+
+def wall_ms(fn, reps):
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(t)), 4), out
+
+
+def measure(sizes, reps, pcg_max):
+    from elimaloc_amd.posegraph import PoseGraph, PoseGraphConfig
+    from elimaloc_amd.registration import Context
+    ctx = Context(0)
+    out = {}
+    for N in sizes:
+        truth, start, i, j, Z = ring(N)
+        fixed = np.zeros(N, bool)
+        fixed[0] = True
+        pg = PoseGraph(N, len(i), ctx)
+        pg.AddNodes(start, fixed)
+        pg.AddEdges(i, j, Z)
+        pg.Linearize()
+        lin_ms, st = wall_ms(lambda: pg.Linearize(), reps)
+        solve_ms, (_, ss) = wall_ms(lambda: pg.Solve(1e-4, 1e-6, pcg_max), 1)
+        cfg = PoseGraphConfig(pcg_rel_tol=1e-6, pcg_max_iterations=pcg_max, max_iterations=20, step_tol=1e-7)
+        opt_ms, res = wall_ms(lambda: pg.Optimize(cfg), 1)
+        poses = pg.Poses()
+        err = float(np.linalg.norm(poses[:, :3, 3] - truth[:, :3, 3], axis=1).max())
+        err0 = float(np.linalg.norm(start[:, :3, 3] - truth[:, :3, 3], axis=1).max())
+        out[f"ring_{N}"] = dict(nodes=N, edges=len(i), linearize_ms=lin_ms, cost_at_start=st["cost"],
+                                solve=dict(lambda_=1e-4, pcg_rel_tol=1e-6, iterations=ss["iterations"], converged=ss["converged"],
+                                           rel_residual=ss["rel_residual"], call_ms=solve_ms,
+                                           ms_per_iteration=round(solve_ms / max(ss["iterations"], 1), 5)),
+                                optimize=dict(solves=res["solves"], accepted=res["accepted"], rejected=res["rejected"],
+                                              pcg_iterations_total=res["pcg_iterations_total"],
+                                              pcg_iterations_per_solve=[t["pcg_iterations"] for t in res["trace"]],
+                                              stop_reason=res["stop_reason"], cost_initial=res["cost_initial"], cost_final=res["cost_final"],
+                                              total_ms=opt_ms, start_error_m=err0, end_error_m=err))
+        pg.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", default="1000,10000,65536")
+    ap.add_argument("--pcg-max", type=int, default=20000)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph_rate.json"))
+    a = ap.parse_args()
+    line = json.dumps(dict(tool="posegraph_rate", pcg_max=a.pcg_max, **measure([int(s) for s in a.sizes.split(",")], a.reps, a.pcg_max)))
+    print(line)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
