@@ -178,9 +178,7 @@ __device__ __forceinline__ void wave_ldlt6(double a, const double* b, double x[6
             if (ai && aj) a -= lip * apj;      // Schur complement of the remaining block
             else if (ai && lj == p) a = lip;   // column p below/right of the pivot now holds L[i][p]
             else if (li == p && aj) a = apj / dp;
-        } else {
-            if ((ai && lj == p) || (li == p && aj)) a = 0.0;
-        }
+        } // an exactly zero pivot: Eigen leaves the column undivided (no update either: d = 0) and both substitutions below read it
         order[k] = p;
         piv[k] = dp;
         active &= ~(1u << p);
@@ -202,7 +200,7 @@ __device__ __forceinline__ void wave_ldlt6(double a, const double* b, double x[6
         double d = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; ++k) d = (rank_l == k) ? piv[k] : d;
-        y = (fabs(d) > 5.6e-309) ? y / d : 0.0; // Eigen zeroes the components of (numerically) zero pivots
+        y = (fabs(d) > kLdltPivotTol) ? y / d : 0.0; // Eigen zeroes the components of pivots with |d| <= 1 / DBL_MAX
     }
 #pragma unroll
     for (int k = 5; k >= 0; --k) { // backward: L^T x = y
@@ -232,7 +230,7 @@ __device__ __forceinline__ void wave_ldlt6(double a, const double* b, double x[6
             double d = 0.0;
 #pragma unroll
             for (int k = 0; k < 6; ++k) d = (rank_i == k) ? piv[k] : d;
-            Y = (fabs(d) > 5.6e-309) ? Y / d : 0.0;
+            Y = (fabs(d) > kLdltPivotTol) ? Y / d : 0.0;
         }
 #pragma unroll
         for (int k = 5; k >= 0; --k) {

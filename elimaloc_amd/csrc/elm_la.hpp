@@ -290,8 +290,13 @@ ELM_HD void radar_point_cov(double gx, double gy, double gz, double range_var_m,
 }
 
 // ---- 6x6 ------------------------------------------------------------------------------------------
-// Solve A x = b, A symmetric (row-major, only the lower triangle is read), by LDL^T with diagonal pivoting
-// (largest |diagonal| of the trailing block, symmetric row/column swap) as Eigen's LDLT does (reg.cpp:56).
+// Eigen's LDLT::_solve_impl divides by a pivot only above 1 / numeric_limits<double>::max() (a subnormal: 0x0004000000000000)
+constexpr double kLdltPivotTol = 1.0 / 1.7976931348623157e308;
+// Solve A x = b, A symmetric (row-major, only the lower triangle is read), by LDL^T with diagonal pivoting as Eigen's LDLT does
+// (reg.cpp:56; Eigen/src/Cholesky/LDLT.h, ldlt_inplace<Lower>::unblocked and LDLT::_solve_impl).  That routine is left-looking: at step k
+// only columns < k have been finished, so its pivot search sees the NOT-YET-UPDATED diagonal entries of the rows k.. (the original
+// entries, in their exchanged positions), not the Schur complement's; the first of equal maxima wins.  A column whose pivot is exactly
+// zero stays undivided and takes part in both substitutions; the solution component of a pivot with |d| <= 1 / DBL_MAX is zero.
 ELM_HD void ldlt_solve6_ws(const double* A, const double* b, double* x, double* m, double* misc) {
     // m: 36 doubles, misc: >= 24 doubles of caller-provided workspace (LDS on the device)
     for (int i = 0; i < 6; ++i)
@@ -301,13 +306,11 @@ ELM_HD void ldlt_solve6_ws(const double* A, const double* b, double* x, double* 
     double* permd = misc + 12; // [6] permutation kept as doubles in the same workspace
     for (int i = 0; i < 6; ++i) permd[i] = (double)i;
     for (int k = 0; k < 6; ++k) {
-        // pivot = largest |diagonal| of the trailing Schur complement
+        // pivot = the first largest |diagonal| of the rows k..5 as they stand: m[i][i], i >= k, still holds the original entry
         int p = k;
-        double best = -1.0;
-        for (int i = k; i < 6; ++i) {
-            double di = m[i * 6 + i];
-            for (int c = 0; c < k; ++c) di -= m[i * 6 + c] * m[i * 6 + c] * d[c];
-            double c2 = fabs(di);
+        double best = fabs(m[k * 6 + k]);
+        for (int i = k + 1; i < 6; ++i) {
+            double c2 = fabs(m[i * 6 + i]);
             if (c2 > best) { best = c2; p = i; }
         }
         if (p != k) { // symmetric swap of rows/cols k and p on the full matrix
@@ -328,7 +331,7 @@ ELM_HD void ldlt_solve6_ws(const double* A, const double* b, double* x, double* 
     for (int i = 0; i < 6; ++i) y[i] = b[(int)permd[i]];
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < i; ++j) y[i] -= m[i * 6 + j] * y[j];
-    for (int i = 0; i < 6; ++i) y[i] = (fabs(d[i]) > 5.6e-309) ? y[i] / d[i] : 0.0;
+    for (int i = 0; i < 6; ++i) y[i] = (fabs(d[i]) > kLdltPivotTol) ? y[i] / d[i] : 0.0;
     for (int i = 5; i >= 0; --i)
         for (int j = i + 1; j < 6; ++j) y[i] -= m[j * 6 + i] * y[j];
     for (int i = 0; i < 6; ++i) x[(int)permd[i]] = y[i];

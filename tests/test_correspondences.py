@@ -202,6 +202,96 @@ def test_align_clouds_local_on_explicit_pairs(oracle, method):
         c.close()
 
 
+def _singular_pair_sets():
+    """(name, source points, residuals target - source, lm_lambda, components of x = (t, w) that the rule zeroes).  last_icp_pose is the
+    identity, so the residual of a pair is target - source.
+    * every source point on the sensor's x axis: the row and column of the rotation about x are exact zeros (every term has a factor 0),
+      whatever the weights; every source point at the origin: the whole rotation block is.  Both survive the shipped damping
+      (h + lambda h = 0 for h = 0) and arbitrary coordinates.
+    * one pair (rank 3) and two pairs (rank 5) are singular only without damping (the damped diagonal is 1.5 times the original), and
+      their zero pivots are Schur complements: lambda = 0, dyadic coordinates and residuals of squared length 5 (weight 25 / (5 + 5)^2 =
+      1 / 4 exactly), so that no operation rounds and the zeros are exact in any elimination order."""
+    rng = np.random.default_rng(5)
+    on_x = np.zeros((7, 3)); on_x[:, 0] = rng.uniform(-30, 30, 7)
+    return [
+        ("x-axis", on_x, rng.normal(0, 0.3, (7, 3)), None, [3]),
+        ("x-axis-no-damping", on_x, rng.normal(0, 0.3, (7, 3)), 0.0, [3]),
+        ("origin", np.zeros((5, 3)), rng.normal(0, 0.3, (5, 3)), None, [3, 4, 5]),
+        ("origin-no-damping", np.zeros((5, 3)), rng.normal(0, 0.3, (5, 3)), 0.0, [3, 4, 5]),
+        ("one-pair", np.array([[2.0, 2.0, 0.0]]), np.array([[1.0, 2.0, 0.0]]), 0.0, [0, 2, 4]),
+        ("two-pairs", np.array([[2.0, 2.0, 0.0], [-2.0, -2.0, 0.0]]), np.array([[1.0, 2.0, 0.0], [2.0, 0.0, -1.0]]), 0.0, [4]),
+        ("one-pair-damped", np.array([[2.0, 2.0, 0.0]]), np.array([[1.0, 2.0, 0.0]]), None, []),
+        ("two-pairs-damped", np.array([[2.0, 2.0, 0.0], [-2.0, -2.0, 0.0]]), np.array([[1.0, 2.0, 0.0], [2.0, 0.0, -1.0]]), None, []),
+    ]
+
+
+@pytest.mark.gpu
+def test_align_clouds_local_on_structurally_singular_pairs(oracle):
+    """elm_align_clouds_local (k_align_solve: the scalar elm::ldlt_solve6 on the device) on P2P pair sets whose normal equations are
+    singular by construction: the step against oracle.align_clouds_local at the atol 1e-10 of test_align_clouds_local_on_explicit_pairs,
+    and the components the rule zeroes exactly 0 -- translations read off the step, a zero rotation vector as the identity rotation in
+    bytes, a zero rotation about one axis as the symmetry of the opposite off-diagonal pair (R[1][2] and R[2][1] are c_y a_z -+ sin(angle) a_x
+    in rotvec_to_matrix: equal exactly when the x component is 0)."""
+    import np_ref
+    from elimaloc_amd.registration import Context, Registration, RegistrationConfig, IcpMethod
+    c = Context(0)
+    try:
+        for name, src, res, lam, zeroed in _singular_pair_sets():
+            kw = {} if lam is None else {"lm_lambda": lam}
+            cfg = RegistrationConfig(icp_method=IcpMethod.P2P, **kw)
+            ocfg = oracle.default_config(0, **kw)
+            tgt = src + res
+            ref = oracle.align_clouds_local(0, src, tgt, None, np.eye(4), 5.0, ocfg)
+            reg = Registration(cfg, c)
+            step = reg.AlignCloudsLocal(src, tgt, np.eye(4), 5.0)
+            np.testing.assert_allclose(step, ref["T"], rtol=0, atol=1e-10, err_msg=name)
+            assert abs(reg.d_fitness_score_ - ref["fitness"]) <= 1e-9 * max(abs(ref["fitness"]), 1e-12), name
+            # the rule's own zeros for this system (the numpy statement on the oracle's sums) are the ones listed
+            D = np.array(ref["JTJ"])
+            D[np.diag_indices(6)] = np.diag(D) + cfg.lm_lambda * np.diag(D)
+            x = np_ref.eigen_ldlt_solve(D, ref["JTr"])
+            assert [i for i in zeroed if x[i] != 0.0] == [], (name, x)
+            for i in zeroed:
+                if i < 3:
+                    assert step[i, 3] == 0.0, (name, i, step[i, 3])
+            if all(i in zeroed for i in (3, 4, 5)):
+                assert np.array_equal(step[:3, :3], np.eye(3)), name
+            else:
+                assert not np.array_equal(step[:3, :3], np.eye(3)), name
+                for i, (r, q) in ((3, (1, 2)), (4, (0, 2)), (5, (0, 1))):
+                    if i in zeroed:
+                        assert step[r, q] == step[q, r], (name, i)
+            np.testing.assert_allclose(step[:3, 3], x[:3], rtol=1e-11, atol=1e-13, err_msg=name)
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,method", [(255, 0), (256, 0), (257, 0), (255, 1), (256, 1), (257, 1), (255, 2), (256, 2), (257, 2), (1024 * 256 + 1, 0)])
+def test_align_clouds_local_at_the_block_edges(oracle, method, n):
+    """k_align_pairs at the edges of its launch: 255 / 256 / 257 pairs (one workgroup of 256 threads less one, full, and one thread of
+    a second) for all three methods, and 1024 * 256 + 1 pairs (P2P): the grid is capped at 1024 workgroups, so one thread takes a second
+    trip through the grid-stride loop.  Same assertions as test_align_clouds_local_on_explicit_pairs."""
+    from elimaloc_amd.registration import Context, Registration, RegistrationConfig, IcpMethod
+    c = Context(0)
+    try:
+        src, tgt, cov, T = _pairs_for_align(300 + method, n=n)
+        reg = Registration(RegistrationConfig(icp_method=IcpMethod(method)), c)
+        ref = oracle.align_clouds_local(method, src, tgt, None if method == 0 else cov, T, 5.0, oracle.default_config(method))
+        if method == 0:
+            step = reg.AlignCloudsLocal(src, tgt, T, 5.0)
+        elif method == 1:
+            step, lc = reg.AlignCloudsLocalPointCov(src, tgt, cov, T, 5.0)
+            np.testing.assert_allclose(lc, ref["local_cov"], rtol=1e-7, atol=1e-12)
+        else:
+            step = reg.AlignCloudsLocalVoxelCov(src, tgt, cov, T, 5.0)
+        np.testing.assert_allclose(step, ref["T"], rtol=0, atol=1e-10)
+        assert abs(reg.d_fitness_score_ - ref["fitness"]) <= 1e-9 * max(abs(ref["fitness"]), 1e-12)
+        assert not np.array_equal(step, np.eye(4))
+    finally:
+        c.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("method", [1, 2])
 def test_run_register_with_radar_cov_equals_its_public_pieces(oracle, method):

@@ -35,7 +35,8 @@ def test_ldlt_discrete_cases_follow_eigens_published_algorithm(oracle):
     # equal diagonal entries: the FIRST of the maxima is the pivot
     H = np.full((6, 6), 0.25) + np.diag([2.0, 2.0, 2.0, 1.0, 2.0, 1.0])
     cases.append((H, np.arange(1.0, 7.0), True))
-    # exact zero pivots (integers: no rounding): rank 3, the system of a scan whose points lie on the sensor's x axis has this shape
+    # zero pivots, rank 3 (integer entries, but the first pivot is 13: the zeros come out as rounding residues, and the two implementations
+    # agree because they share one operation order -- tests/solve_cases.py has the exact versions); the system of one pair has this shape
     J = np.array([[1, 0, 0, 0, 2, -1], [0, 1, 0, -2, 0, 3], [0, 0, 1, 1, -3, 0]], dtype=np.float64)
     cases.append((J.T @ J, J.T @ np.array([1.0, -2.0, 0.5]), False))
     Z = np.zeros((6, 6)); Z[0, 0] = 4.0; Z[2, 2] = 1.0; Z[0, 2] = Z[2, 0] = 1.0  # zero rows / columns: components of zero pivots are zeroed
