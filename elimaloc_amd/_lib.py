@@ -364,6 +364,9 @@ EXPORTS = [
     "elm_posegraph_linearize", "elm_posegraph_download_linearization", "elm_posegraph_solve", "elm_posegraph_optimize",
     "elm_posegraph_edge_terms",
 ]
+# every symbol include/elimaloc_hip_posegraph_precond.h declares (the header elimaloc_hip.h includes for the pose graph's preconditioner)
+EXPORTS_PRECOND = ["elm_posegraph_set_preconditioner", "elm_posegraph_get_preconditioner"]
+PG_PRECOND = {0: "block_jacobi", 1: "chain"}
 
 
 class PcmNodeConfig(C.Structure):
@@ -629,6 +632,8 @@ def lib():
     L.elm_posegraph_solve.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(PoseGraphSolveStatsC)]
     L.elm_posegraph_optimize.argtypes = [vp, vp, C.POINTER(PoseGraphConfigC), C.POINTER(PoseGraphResultC), C.POINTER(PoseGraphTraceC), C.c_int]
     L.elm_posegraph_edge_terms.argtypes = [dp, dp, dp, dp, dp, dp]
+    L.elm_posegraph_set_preconditioner.argtypes = [vp, vp, C.c_int]
+    L.elm_posegraph_get_preconditioner.argtypes = [vp, vp, C.POINTER(C.c_int)]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

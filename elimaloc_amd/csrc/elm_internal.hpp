@@ -464,6 +464,55 @@ void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, doubl
 // chi2, cost and outliers at `poses` into d.out, with the largest |x| of the last retraction; want_grad: also max |g_v| over active nodes
 void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double huber_k, int want_grad);
 
+// pose graph, chain preconditioner (elm_k_pgchain.hip): M^-1 of the block-tridiagonal M of the contract by
+// block cyclic reduction in levels.  A level of n nodes is cut into segments of kPgcSeg consecutive nodes, one workgroup each; a
+// workgroup eliminates every node of its segment but the last in odd-even order (log2 kPgcSeg steps), the last nodes of the segments
+// are the next level's nodes, and the level of one segment ends the recursion.  Per node and level the factor keeps the inverse pivot
+// block G and the two coupling blocks A = G M[p][left], B = G M[p][right].
+// kPgcSeg = 256 = kPgBlock: a workgroup's nodes at level 0 are those of one r^T z slot, so the last launch of an apply writes the
+// existing slots and k_pg_direction serves both preconditioners; the apply holds only the segment's right-hand side in LDS
+// (257 x 6 doubles, 12 KB), the factor works in global memory and holds 64 inversion workspaces (36 KB), so neither is bound by LDS;
+// and 2^20 nodes are three levels (five launches per apply), 65 536 two (three launches), 256 one (one launch).
+constexpr uint32_t kPgcSeg = 256;
+constexpr uint32_t kPgcSteps = 8;        // log2 kPgcSeg
+constexpr uint32_t kPgcMaxLevels = 3;    // 256^3 >= 2^20 nodes >= ELM_POSEGRAPH_MAX_NODES
+constexpr uint32_t kPgcNoEdge = 0xffffffffu;
+static_assert(kPgcSeg == kPgBlock && (1u << kPgcSteps) == kPgcSeg, "the level-0 segments are the r^T z slots");
+struct PgcLevel {
+    uint32_t n, nseg; // the level's nodes and segments
+    uint32_t off;     // its first node in G, A, B, Lw, y (every level padded to whole segments)
+    uint32_t soff;    // its first segment in De, bl, be
+};
+struct PgcDev {
+    const uint32_t* ce;     // [N - 1]: the chain edge of v, edge << 1 | (1: stored v + 1 -> v), or kPgcNoEdge
+    double *G, *A, *B, *Lw; // [padded nodes of all levels][36]; G holds the running diagonal block until the node is eliminated,
+                            // Lw the running coupling to the node's left neighbour
+    double* De;             // [segments][36]: what a segment's eliminations add to the diagonal block of the segment before's last node
+    double* y;              // [padded nodes][6]: the reduced right-hand side, then the solution
+    double *bl, *be;        // [segments][6]: the reduced right-hand side of the segment's last node, and its addition to the one before
+};
+// the levels of n nodes -> their count
+inline uint32_t pgc_levels(uint32_t n, PgcLevel* lv) {
+    uint32_t k = 0, off = 0, soff = 0;
+    for (;;) {
+        const uint32_t nseg = (n + kPgcSeg - 1) / kPgcSeg;
+        lv[k++] = PgcLevel{n, nseg, off, soff};
+        off += nseg * kPgcSeg;
+        soff += nseg;
+        if (nseg <= 1 || k == kPgcMaxLevels) return k;
+        n = nseg;
+    }
+}
+// the factor of M = chain part of H + lambda diag H (after launch_pg_nodes with the same lambda); N >= 1
+void launch_pgc_factor(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda);
+// x = 0, r = -g, z = M^-1 r, p = z, r0^T z0 and the state words: launch_pg_pcg_begin's work with the chain M
+void launch_pgc_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev& c, double tol);
+void launch_pgc_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda, double tol, uint32_t it);
+// the launches of elm_k_pgraph.hip that the chain iteration shares
+void launch_pg_pcg_state(hipStream_t s, const PgDev& d, double tol);
+void launch_pg_spmv(hipStream_t s, const PgDev& d, double lambda, uint32_t it);
+void launch_pg_direction(hipStream_t s, const PgDev& d, double tol, uint32_t it);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

@@ -507,6 +507,15 @@ void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, double lambda, doubl
     hipLaunchKernelGGL(k_pg_direction, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, tol, it);
 }
 
+void launch_pg_pcg_state(hipStream_t s, const PgDev& d, double tol) { hipLaunchKernelGGL(k_pg_pcg_begin, dim3(1), dim3(256), 0, s, d, tol); }
+void launch_pg_spmv(hipStream_t s, const PgDev& d, double lambda, uint32_t it) {
+    hipLaunchKernelGGL(k_pg_spmv, dim3((d.N + kPgNodesPerBlock - 1) / kPgNodesPerBlock), dim3(256), 0, s, d, lambda, it);
+    if (d.n_hubs) hipLaunchKernelGGL(k_pg_spmv_hub, dim3(d.n_hubs), dim3(64), 0, s, d, lambda, it);
+}
+void launch_pg_direction(hipStream_t s, const PgDev& d, double tol, uint32_t it) {
+    hipLaunchKernelGGL(k_pg_direction, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, tol, it);
+}
+
 void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, double* trial) {
     if (!d.N) return;
     hipLaunchKernelGGL(k_pg_retract, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, poses, trial);

@@ -32,6 +32,9 @@ struct elm_posegraph {
     double *d_Z = nullptr, *d_info = nullptr;
     uint8_t* d_fixed = nullptr;
     PgDev dev{};
+    int precond = ELM_PG_PRECOND_BLOCK_JACOBI; // kept across a reset
+    uint32_t* d_ce = nullptr;                  // the chain-edge table, uploaded with the incidence lists
+    PgcDev chain{};
 };
 
 extern "C" void elm_posegraph_config_default(elm_posegraph_config* c) {
@@ -128,6 +131,21 @@ void carve(elm_posegraph* pg, Carver& c) {
     d.inc_start = pg->d_inc_start;
     d.inc = pg->d_inc;
     d.hubs = pg->d_hubs;
+    // the chain preconditioner's factor and vectors: every level padded to whole segments, for the capacity's levels
+    PgcLevel lv[kPgcMaxLevels];
+    const uint32_t nl = pgc_levels((uint32_t)Nc, lv);
+    const size_t pad = (size_t)lv[nl - 1].off + (size_t)lv[nl - 1].nseg * kPgcSeg, segs = (size_t)lv[nl - 1].soff + lv[nl - 1].nseg;
+    PgcDev& k = pg->chain;
+    pg->d_ce = c.take<uint32_t>(Nc);
+    k.G = c.take<double>(36 * pad);
+    k.A = c.take<double>(36 * pad);
+    k.B = c.take<double>(36 * pad);
+    k.Lw = c.take<double>(36 * pad);
+    k.De = c.take<double>(36 * segs);
+    k.y = c.take<double>(6 * pad);
+    k.bl = c.take<double>(6 * segs);
+    k.be = c.take<double>(6 * segs);
+    k.ce = pg->d_ce;
 }
 
 int create_impl(elm_ctx* ctx, uint32_t n_cap, uint32_t e_cap, elm_posegraph** out) {
@@ -193,7 +211,16 @@ hipError_t upload_csr(elm_posegraph* pg, hipStream_t st, std::vector<uint32_t>& 
         if (start[v + 1] - start[v] > kPgHubDegree) hubs.push_back(v);
     pg->n_hubs = (uint32_t)hubs.size();
     hubs.push_back(0u);
-    hipError_t e = hipMemcpyAsync(pg->d_inc_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    // the chain edge of v: the lowest-index edge between v and v + 1, in either direction (whether both ends are active is the
+    // device's to say, from the flags and the diagonal blocks of the solve)
+    std::vector<uint32_t> ce(N ? N : 1u, kPgcNoEdge);
+    for (uint32_t e = E; e-- > 0u;) { // descending: the lowest index is written last
+        const int32_t a = pg->ei[e], b = pg->ej[e];
+        if (b == a + 1) ce[a] = e << 1;
+        else if (a == b + 1) ce[b] = (e << 1) | 1u;
+    }
+    hipError_t e = hipMemcpyAsync(pg->d_ce, ce.data(), ce.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(pg->d_inc_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && E) e = hipMemcpyAsync(pg->d_inc, inc.data(), 2 * (size_t)E * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(pg->d_hubs, hubs.data(), hubs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st); // the host vectors are read until here
@@ -207,8 +234,16 @@ const PgDev& dev_view(elm_posegraph* pg) {
     return pg->dev;
 }
 
+bool chain(const elm_posegraph* pg) { return pg->precond == ELM_PG_PRECOND_CHAIN; }
+
+// queues the damped diagonal blocks and their inverses at lambda and, for the chain preconditioner of a solve, its factor
+void launch_damping(elm_posegraph* pg, hipStream_t st, const PgDev& d, double lambda, int sum, bool for_solve) {
+    launch_pg_nodes(st, d, lambda, sum);
+    if (for_solve && chain(pg)) launch_pgc_factor(st, d, pg->chain, lambda);
+}
+
 // queues the linearization at the current poses with the damping lambda
-hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda) {
+hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda, bool for_solve) {
     hipError_t e = hipSuccess;
     if (pg->csr_dirty) {
         std::vector<uint32_t> start, inc, hubs;
@@ -219,22 +254,30 @@ hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, do
     const PgDev& d = dev_view(pg);
     return launched([&] {
         launch_pg_linearize(st, d, pg->poses, huber_k);
-        launch_pg_nodes(st, d, lambda, 1);
+        launch_damping(pg, st, d, lambda, 1, for_solve);
     });
 }
 
-// The conjugate gradients on the current linearization and damping (k_pg_nodes has run with this lambda): check_every iterations are
+// The conjugate gradients on the current linearization and damping (launch_damping has run with this lambda): check_every iterations are
 // queued, then the state comes down once.
 int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, double tol, int max_it, int check_every, PgState& state, const char* what) {
     const PgDev& d = dev_view(pg);
     memset(&state, 0, sizeof(state));
     if (!pg->N) return ELM_OK;
-    hipError_t e = launched([&] { launch_pg_pcg_begin(st, d, tol); });
+    const bool ch = chain(pg);
+    const PgcDev& c = pg->chain;
+    hipError_t e = launched([&] {
+        if (ch) launch_pgc_pcg_begin(st, d, c, tol);
+        else launch_pg_pcg_begin(st, d, tol);
+    });
     uint32_t it = 0;
     while (e == hipSuccess) {
         const uint32_t upto = (uint32_t)std::min<int64_t>((int64_t)it + check_every, max_it);
         e = launched([&] {
-            for (; it < upto; ++it) launch_pg_pcg_iteration(st, d, lambda, tol, it);
+            for (; it < upto; ++it) {
+                if (ch) launch_pgc_pcg_iteration(st, d, c, lambda, tol, it);
+                else launch_pg_pcg_iteration(st, d, lambda, tol, it);
+            }
         });
         if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(PgState), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -263,7 +306,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
     elm_posegraph_result R{};
     double lambda = c.lambda_init;
     pg->lin_valid = false;
-    hipError_t e = queue_linearize(pg, st, c.huber_k, lambda);
+    hipError_t e = queue_linearize(pg, st, c.huber_k, lambda, true);
     if (e != hipSuccess) return dev_error(ctx, what, e);
     PgOut o{};
     int rc = cost_at(ctx, pg, st, pg->poses, c.huber_k, 0, o, what);
@@ -299,7 +342,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
             else if (o.dmax <= c.step_tol) R.stop_reason = ELM_PG_STOP_STEP_TOL, stop = true;
             else if (R.solves >= c.max_iterations) stop = true;
             if (!stop) {
-                e = queue_linearize(pg, st, c.huber_k, lambda);
+                e = queue_linearize(pg, st, c.huber_k, lambda, true);
                 if (e != hipSuccess) return dev_error(ctx, what, e);
                 pg->lin_valid = true;
             }
@@ -309,7 +352,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
             else if (lambda >= c.lambda_max) R.stop_reason = ELM_PG_STOP_LAMBDA_MAX, stop = true;
             else {
                 lambda = std::min(lambda * c.lambda_up, c.lambda_max);
-                e = launched([&] { launch_pg_nodes(st, d, lambda, 0); });
+                e = launched([&] { launch_damping(pg, st, d, lambda, 0, true); }); // (the chain factor is redone with it)
                 if (e != hipSuccess) return dev_error(ctx, what, e);
             }
         }
@@ -368,6 +411,22 @@ extern "C" int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg) {
     pg->ej.clear();
     pg->csr_dirty = true;
     pg->lin_valid = false;
+    return ELM_OK;
+}
+
+extern "C" int elm_posegraph_set_preconditioner(elm_ctx* ctx, elm_posegraph* pg, int kind) {
+    if (!ctx || !pg || (kind != ELM_PG_PRECOND_BLOCK_JACOBI && kind != ELM_PG_PRECOND_CHAIN)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, "elm_posegraph_set_preconditioner");
+    if (rc != ELM_OK) return rc;
+    pg->precond = kind; // every solve redoes the damped blocks and the factor: the linearization stays valid
+    return ELM_OK;
+}
+
+extern "C" int elm_posegraph_get_preconditioner(elm_ctx* ctx, const elm_posegraph* pg, int* kind) {
+    if (!kind) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, "elm_posegraph_get_preconditioner");
+    if (rc != ELM_OK) return rc;
+    *kind = pg->precond;
     return ELM_OK;
 }
 
@@ -515,7 +574,7 @@ extern "C" int elm_posegraph_linearize(elm_ctx* ctx, elm_posegraph* pg, double h
         if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
         hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         pg->lin_valid = false;
-        hipError_t e = queue_linearize(pg, st, huber_k, 0.0);
+        hipError_t e = queue_linearize(pg, st, huber_k, 0.0, false);
         if (e != hipSuccess) return dev_error(ctx, what, e);
         PgOut o{};
         int rc = cost_at(ctx, pg, st, pg->poses, huber_k, 1, o, what);
@@ -578,7 +637,7 @@ extern "C" int elm_posegraph_solve(elm_ctx* ctx, elm_posegraph* pg, double lambd
         if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
         hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         const PgDev& d = dev_view(pg);
-        hipError_t e = launched([&] { launch_pg_nodes(st, d, lambda, 0); });
+        hipError_t e = launched([&] { launch_damping(pg, st, d, lambda, 0, true); });
         if (e != hipSuccess) return dev_error(ctx, what, e);
         PgState s{};
         int rc = run_pcg(ctx, pg, st, lambda, pcg_rel_tol, pcg_max_iterations, kPgDefaultCheckEvery, s, what);

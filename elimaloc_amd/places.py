@@ -267,12 +267,13 @@ class LoopCloser:
         info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
         self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
 
-    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False):
+    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi"):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
         The default informations are the identity, which weighs a metre like a radian and an odometry step like a verified loop: a
-        caller with real data passes informations that say how good its odometry and its loops are."""
+        caller with real data passes informations that say how good its odometry and its loops are.  preconditioner: PoseGraph's
+        ("block_jacobi" | "chain"); the entries are a chain by construction, which is what "chain" is made for."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
@@ -282,6 +283,7 @@ class LoopCloser:
         try:
             fx = np.zeros(n, bool)
             fx[list(fixed)] = True
+            pg.SetPreconditioner(preconditioner)
             pg.AddNodes(P, fx)
             Z = np.linalg.inv(P[:-1]) @ P[1:]
             pg.AddEdges(np.arange(n - 1), np.arange(1, n), Z, None if odom_information is None else np.asarray(odom_information, dtype=np.float64))

@@ -1,12 +1,13 @@
 """Pose graph (include/elimaloc_hip.h "pose graph"): nodes and relative-pose edges resident on the GPU, their SE(3)
-linearization, the damped normal equations solved by block-Jacobi preconditioned conjugate gradients, and Levenberg-Marquardt around
-that -- from odometry constraints and loop constraints to corrected poses."""
+linearization, the damped normal equations solved by preconditioned conjugate gradients (block Jacobi, or per object the chain
+preconditioner of PoseGraph.SetPreconditioner), and Levenberg-Marquardt around that -- from odometry constraints and loop constraints
+to corrected poses."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, PG_STOP, PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC, PoseGraphTraceC,
+from ._lib import (ElmError, PG_PRECOND, PG_STOP,PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC, PoseGraphTraceC,
                    check)
 from .registration import _Owned, _dp, _pose_block, _ptr, default_context
 
@@ -67,7 +68,21 @@ class PoseGraph(_Owned):
         return int(n.value), int(e.value)
 
     def Reset(self):
+        """No nodes, no edges; the preconditioner kind stays."""
         self._call("elm_posegraph_reset")
+
+    def SetPreconditioner(self, kind):
+        """"block_jacobi" (the default) or "chain": the block-tridiagonal M over the index chain v, v + 1, applied by block cyclic
+        reduction on the GPU (include/elimaloc_hip_posegraph_precond.h).  For Solve and Optimize alike; the linearization stays."""
+        codes = {v: k for k, v in PG_PRECOND.items()}
+        if kind not in codes:
+            raise ElmError(f"PoseGraph.SetPreconditioner: {kind!r} is none of {sorted(codes)}")
+        self._call("elm_posegraph_set_preconditioner", codes[kind])
+
+    def Preconditioner(self):
+        kind = C.c_int(-1)
+        self._call("elm_posegraph_get_preconditioner", C.byref(kind))
+        return PG_PRECOND[int(kind.value)]
 
     def AddNodes(self, poses, fixed=None):
         """poses [n, 4, 4] appended; fixed: bool per node (default: all free)."""

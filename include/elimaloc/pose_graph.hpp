@@ -54,6 +54,15 @@ public:
     inline size_t Nodes() const { return sizes().first; }
     inline size_t Edges() const { return sizes().second; }
     inline void Reset() { elimaloc::check(elm_posegraph_reset(VoxelHashMap::ctx(), pg_), VoxelHashMap::ctx(), "elm_posegraph_reset"); }
+    // ELM_PG_PRECOND_BLOCK_JACOBI (the default) or ELM_PG_PRECOND_CHAIN, for Solve and Optimize alike; kept across Reset
+    inline void SetPreconditioner(int kind) {
+        elimaloc::check(elm_posegraph_set_preconditioner(VoxelHashMap::ctx(), pg_, kind), VoxelHashMap::ctx(), "elm_posegraph_set_preconditioner");
+    }
+    inline int Preconditioner() const {
+        int kind = -1;
+        elimaloc::check(elm_posegraph_get_preconditioner(VoxelHashMap::ctx(), pg_, &kind), VoxelHashMap::ctx(), "elm_posegraph_get_preconditioner");
+        return kind;
+    }
 
     inline void AddNodes(const Poses& poses, const std::vector<bool>* fixed = nullptr) {
         elimaloc::check(!fixed || fixed->size() == poses.size() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "PoseGraph::AddNodes: one flag per node");

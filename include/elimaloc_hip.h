@@ -967,8 +967,13 @@ int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans,
  * F - F_new <= cost_rel_tol F, on max |delta| <= step_tol, on the solve count, else linearize again.  Otherwise: reject, the poses and
  * the linearization stay; stop on max |delta| <= step_tol or when lambda is already lambda_max; else lambda <- min(lambda lambda_up,
  * lambda_max) and only the damped diagonal and its inverses are redone.
- * LIMITS.  node_capacity 1 .. 2^20, edge_capacity 1 .. 2^22, fixed for the object's life; device memory about 0.6 KB per node and
- * 1.7 KB per edge of capacity. */
+ * PRECONDITIONER.  The block-Jacobi M above is the default.  The CHAIN preconditioner -- M block tridiagonal over the index chain
+ * v, v + 1, applied by a parallel block cyclic reduction on the GPU -- is chosen per object; its definition and its two calls,
+ * elm_posegraph_set_preconditioner / elm_posegraph_get_preconditioner, are in elimaloc_hip_posegraph_precond.h, included below.  With
+ * the default every result of every call here is what it was before that choice existed, byte for byte.
+ * LIMITS.  node_capacity 1 .. 2^20, edge_capacity 1 .. 2^22, fixed for the object's life; device memory about 1.8 KB per node (1.2 KB
+ * of it the chain preconditioner's factor: per node and level of the reduction the inverse pivot block, the two coupling blocks and
+ * the running coupling, the levels above the first adding 1/255) and 1.7 KB per edge of capacity. */
 typedef struct elm_posegraph elm_posegraph;
 #define ELM_POSEGRAPH_MAX_NODES (1 << 20)
 #define ELM_POSEGRAPH_MAX_EDGES (1 << 22)
@@ -1041,6 +1046,13 @@ int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_
 /* The residual and Jacobians of one edge, each output when not NULL: r[6], A[36], B[36] row-major.  Host only: the same code the kernel
  * runs, compiled for the host. */
 int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const double Z16[16], double* r, double* A, double* B);
+#ifdef __cplusplus
+}
+#endif
+#include "elimaloc_hip_posegraph_precond.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
 
 /* ---------------------------------------------------------------- device index build -------------- */
 /* The P2P / GICP cell grid of a map (dense or two-level) is laid out on the host by default: the stored points come down, are

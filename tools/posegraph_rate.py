@@ -7,9 +7,16 @@ over the whole ring, whatever N), node 0 fixed.  Reported per N, as wall clock o
 elm_posegraph_solve at lambda 1e-4 and pcg_rel_tol 1e-6 (its iterations, whether it met the tolerance within --pcg-max, and the ms per
 iteration), and one elm_posegraph_optimize from the drifted start with the same PCG settings (solves, PCG iterations in all, stop
 reason, costs, total ms, and the largest pose error against the truth).
-Kernel-only times: run under a kernel trace (k_pg_*), e.g. with --sizes 1000.
+--preconditioner block_jacobi | chain | both (the default): with both, the block-Jacobi figures stay where they were and the chain
+preconditioner's go under "chain" of the same N, with the factor's ms and the apply's ms per iteration.  Those two are wall clock too:
+a solve without a stop test is timed at 32 and at 288 iterations under either preconditioner; the difference over 256 is the ms per
+iteration, the rest of the 32-iteration call its fixed part; the apply is the chain's ms per iteration less block Jacobi's (whose own
+z = M^-1 r is a 6 x 6 product inside k_pg_update), the factor the chain's fixed part less block Jacobi's and less one apply (the z0
+of the start).
+Kernel-only times: run under a kernel trace (k_pg_*, k_pgc_*), e.g. with --sizes 1000.
 
-    python tools/posegraph_rate.py [--reps 5] [--sizes 1000,10000,65536] [--pcg-max 20000] [--out profiles/posegraph_rate.json]
+    python tools/posegraph_rate.py [--reps 5] [--sizes 1000,10000,65536] [--pcg-max 20000] [--preconditioner both]
+                                   [--out profiles/posegraph_rate.json]
 """
 import argparse
 import json
@@ -57,8 +64,39 @@ def wall_ms(fn, reps):
     return round(float(np.median(t)), 4), out
 
 
-def measure(sizes, reps, pcg_max):
-    from elimaloc_amd.posegraph import PoseGraph, PoseGraphConfig
+def solve_and_optimize(pg, truth, start, pcg_max):
+    """the solve and the optimize of the current preconditioner, from the drifted start -> their two records"""
+    pg.SetPoses(start)
+    pg.Linearize()
+    solve_ms, (_, ss) = wall_ms(lambda: pg.Solve(1e-4, 1e-6, pcg_max), 1)
+    from elimaloc_amd.posegraph import PoseGraphConfig
+    cfg = PoseGraphConfig(pcg_rel_tol=1e-6, pcg_max_iterations=pcg_max, max_iterations=20, step_tol=1e-7)
+    opt_ms, res = wall_ms(lambda: pg.Optimize(cfg), 1)
+    poses = pg.Poses()
+    err = float(np.linalg.norm(poses[:, :3, 3] - truth[:, :3, 3], axis=1).max())
+    err0 = float(np.linalg.norm(start[:, :3, 3] - truth[:, :3, 3], axis=1).max())
+    return dict(solve=dict(lambda_=1e-4, pcg_rel_tol=1e-6, iterations=ss["iterations"], converged=ss["converged"],
+                           rel_residual=ss["rel_residual"], call_ms=solve_ms, ms_per_iteration=round(solve_ms / max(ss["iterations"], 1), 5)),
+                optimize=dict(solves=res["solves"], accepted=res["accepted"], rejected=res["rejected"],
+                              pcg_iterations_total=res["pcg_iterations_total"],
+                              pcg_iterations_per_solve=[t["pcg_iterations"] for t in res["trace"]],
+                              stop_reason=res["stop_reason"], cost_initial=res["cost_initial"], cost_final=res["cost_final"],
+                              total_ms=opt_ms, start_error_m=err0, end_error_m=err))
+
+
+def iteration_and_fixed_ms(pg, start, reps):
+    """(ms per iteration, fixed ms of a solve call) of the current preconditioner: solves without a stop test at 32 and 288 iterations"""
+    pg.SetPoses(start)
+    pg.Linearize()
+    pg.Solve(1e-4, 0.0, 32)
+    short, _ = wall_ms(lambda: pg.Solve(1e-4, 0.0, 32), reps)
+    long_, _ = wall_ms(lambda: pg.Solve(1e-4, 0.0, 288), reps)
+    per = (long_ - short) / 256.0
+    return per, short - 32.0 * per
+
+
+def measure(sizes, reps, pcg_max, kinds=("block_jacobi", "chain")):
+    from elimaloc_amd.posegraph import PoseGraph
     from elimaloc_amd.registration import Context
     ctx = Context(0)
     out = {}
@@ -71,21 +109,20 @@ def measure(sizes, reps, pcg_max):
         pg.AddEdges(i, j, Z)
         pg.Linearize()
         lin_ms, st = wall_ms(lambda: pg.Linearize(), reps)
-        solve_ms, (_, ss) = wall_ms(lambda: pg.Solve(1e-4, 1e-6, pcg_max), 1)
-        cfg = PoseGraphConfig(pcg_rel_tol=1e-6, pcg_max_iterations=pcg_max, max_iterations=20, step_tol=1e-7)
-        opt_ms, res = wall_ms(lambda: pg.Optimize(cfg), 1)
-        poses = pg.Poses()
-        err = float(np.linalg.norm(poses[:, :3, 3] - truth[:, :3, 3], axis=1).max())
-        err0 = float(np.linalg.norm(start[:, :3, 3] - truth[:, :3, 3], axis=1).max())
-        out[f"ring_{N}"] = dict(nodes=N, edges=len(i), linearize_ms=lin_ms, cost_at_start=st["cost"],
-                                solve=dict(lambda_=1e-4, pcg_rel_tol=1e-6, iterations=ss["iterations"], converged=ss["converged"],
-                                           rel_residual=ss["rel_residual"], call_ms=solve_ms,
-                                           ms_per_iteration=round(solve_ms / max(ss["iterations"], 1), 5)),
-                                optimize=dict(solves=res["solves"], accepted=res["accepted"], rejected=res["rejected"],
-                                              pcg_iterations_total=res["pcg_iterations_total"],
-                                              pcg_iterations_per_solve=[t["pcg_iterations"] for t in res["trace"]],
-                                              stop_reason=res["stop_reason"], cost_initial=res["cost_initial"], cost_final=res["cost_final"],
-                                              total_ms=opt_ms, start_error_m=err0, end_error_m=err))
+        row = dict(nodes=N, edges=len(i), linearize_ms=lin_ms, cost_at_start=st["cost"])
+        if "block_jacobi" in kinds:
+            pg.SetPreconditioner("block_jacobi")
+            row.update(solve_and_optimize(pg, truth, start, pcg_max))
+        if "chain" in kinds:
+            pg.SetPreconditioner("chain")
+            row["chain"] = solve_and_optimize(pg, truth, start, pcg_max)
+            per_c, fixed_c = iteration_and_fixed_ms(pg, start, reps)
+            pg.SetPreconditioner("block_jacobi")
+            per_b, fixed_b = iteration_and_fixed_ms(pg, start, reps)
+            apply_ms = per_c - per_b
+            row["chain"].update(iteration_ms=round(per_c, 5), block_jacobi_iteration_ms=round(per_b, 5), apply_ms_per_iteration=round(apply_ms, 5),
+                                factor_ms=round(fixed_c - fixed_b - apply_ms, 4))
+        out[f"ring_{N}"] = row
         pg.close()
     return out
 
@@ -95,9 +132,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1000,10000,65536")
     ap.add_argument("--pcg-max", type=int, default=20000)
+    ap.add_argument("--preconditioner", default="both", choices=("both", "block_jacobi", "chain"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph_rate.json"))
     a = ap.parse_args()
-    line = json.dumps(dict(tool="posegraph_rate", pcg_max=a.pcg_max, **measure([int(s) for s in a.sizes.split(",")], a.reps, a.pcg_max)))
+    kinds = ("block_jacobi", "chain") if a.preconditioner == "both" else (a.preconditioner,)
+    line = json.dumps(dict(tool="posegraph_rate", pcg_max=a.pcg_max, preconditioner=a.preconditioner,
+                           **measure([int(s) for s in a.sizes.split(",")], a.reps, a.pcg_max, kinds)))
     print(line)
     with open(a.out, "w") as f:
         f.write(line + "\n")
