@@ -324,6 +324,19 @@ class PoseGraphTraceC(C.Structure):
     _fields_ = [("cost", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int32), ("pcg_iterations", C.c_int32)]
 
 
+class PoseGraphInitConfigC(C.Structure):
+    """elm_posegraph_init_config (include/elimaloc_hip_posegraph_init.h)."""
+    _fields_ = [("pcg_rel_tol", C.c_double), ("pcg_max_iterations", C.c_int32), ("pcg_check_every", C.c_int32), ("stages", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PoseGraphInitResultC(C.Structure):
+    """elm_posegraph_init_result."""
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("rot_rel_residual", C.c_double), ("trans_rel_residual", C.c_double),
+                ("rot_iterations", C.c_int32), ("trans_iterations", C.c_int32), ("rot_converged", C.c_int32), ("trans_converged", C.c_int32),
+                ("degenerate_nodes", C.c_int32), ("applied", C.c_int32)]
+
+
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
 PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
 
@@ -367,6 +380,9 @@ EXPORTS = [
 # every symbol include/elimaloc_hip_posegraph_precond.h declares (the header elimaloc_hip.h includes for the pose graph's preconditioner)
 EXPORTS_PRECOND = ["elm_posegraph_set_preconditioner", "elm_posegraph_get_preconditioner"]
 PG_PRECOND = {0: "block_jacobi", 1: "chain"}
+# every symbol include/elimaloc_hip_posegraph_init.h declares (the header elimaloc_hip.h includes for the pose graph's linear initialization)
+EXPORTS_INIT = ["elm_posegraph_init_config_default", "elm_posegraph_initialize"]
+PG_INIT_ROT, PG_INIT_TRANS = 1, 2
 
 
 class PcmNodeConfig(C.Structure):
@@ -634,6 +650,9 @@ def lib():
     L.elm_posegraph_edge_terms.argtypes = [dp, dp, dp, dp, dp, dp]
     L.elm_posegraph_set_preconditioner.argtypes = [vp, vp, C.c_int]
     L.elm_posegraph_get_preconditioner.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    L.elm_posegraph_init_config_default.argtypes = [C.POINTER(PoseGraphInitConfigC)]
+    L.elm_posegraph_init_config_default.restype = None
+    L.elm_posegraph_initialize.argtypes = [vp, vp, C.POINTER(PoseGraphInitConfigC), C.POINTER(PoseGraphInitResultC), dp, dp]
     L.elm_comm_get_unique_id.argtypes = [vp]
     L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.elm_comm_destroy.argtypes = [vp]

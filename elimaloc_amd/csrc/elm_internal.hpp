@@ -513,6 +513,17 @@ void launch_pg_pcg_state(hipStream_t s, const PgDev& d, double tol);
 void launch_pg_spmv(hipStream_t s, const PgDev& d, double lambda, uint32_t it);
 void launch_pg_direction(hipStream_t s, const PgDev& d, double tol, uint32_t it);
 
+// pose graph, linear initialization (elm_k_pginit.hip; the contract is include/elimaloc_hip_posegraph_init.h).
+// The two term kernels fill gi, gj, Hii, Hij, Hjj of the view as launch_pg_linearize does, for launch_pg_nodes (sum = 1, lambda = 0)
+// and the conjugate gradients to follow; the apply kernels read the solve's x and the active flags.
+constexpr double kPgInitDegenerate = 1e-6; // a node with |rho1|, |rho2|, |u + v| or |u - v| below it keeps its rotation
+void launch_pgi_rot_terms(hipStream_t s, const PgDev& d, const double* poses);
+void launch_pgi_trans_terms(hipStream_t s, const PgDev& d, const double* poses);
+// rows [N][6]: the rows before the projection; slots [pg_blocks(N)]: the workgroups' degenerate counts; trial: every node's pose
+void launch_pgi_rot_apply(hipStream_t s, const PgDev& d, const double* poses, double* trial, double* rows, double* slots);
+// t <- t + R v of the active nodes, in place
+void launch_pgi_trans_apply(hipStream_t s, const PgDev& d, double* trial);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

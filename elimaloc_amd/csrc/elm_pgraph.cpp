@@ -1,8 +1,9 @@
 // elm_pgraph.cpp -- the pose graph (include/elimaloc_hip.h, "pose graph"): the object (nodes, edges, the
 // linearization and the solver's vectors resident on the device, of capacities fixed at creation), the argument checks, the incidence
 // lists (a stable counting sort of (edge, side) by node, redone when the edge set has changed), the conjugate-gradient driver that
-// queues pcg_check_every iterations between two reads of the device's state, and the Levenberg-Marquardt loop around it.  The launches
-// are those of elm_k_pgraph.hip.  Host-side C++17.
+// queues pcg_check_every iterations between two reads of the device's state, the Levenberg-Marquardt loop around it, and the linear
+// initialization (include/elimaloc_hip_posegraph_init.h; DESIGN.md section 23: its preconditions and its two stages on the same
+// driver).  The launches are those of elm_k_pgraph.hip, elm_k_pgchain.hip and elm_k_pginit.hip.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -23,7 +24,9 @@ struct elm_posegraph {
     uint32_t n_cap = 0, e_cap = 0, N = 0, E = 0;
     std::vector<uint8_t> fixed;     // [N]: the host's copy
     std::vector<int32_t> ei, ej;    // [E]: the host's copy
+    std::vector<double> wr, wt;     // [E]: trace(Omega_ww) / 3 and trace(Omega_vv) / 3, the weights of elm_posegraph_initialize
     bool csr_dirty = true, lin_valid = false;
+    double lin_huber = 0.0;         // the Huber k of the last linearization queued
     uint32_t n_hubs = 0;
     char* blob = nullptr;           // every device array below, one allocation
     double *poses = nullptr, *trial = nullptr;
@@ -242,15 +245,20 @@ void launch_damping(elm_posegraph* pg, hipStream_t st, const PgDev& d, double la
     if (for_solve && chain(pg)) launch_pgc_factor(st, d, pg->chain, lambda);
 }
 
+// the incidence lists on the device are those of the current edge set
+hipError_t ensure_csr(elm_posegraph* pg, hipStream_t st) {
+    if (!pg->csr_dirty) return hipSuccess;
+    std::vector<uint32_t> start, inc, hubs;
+    hipError_t e = upload_csr(pg, st, start, inc, hubs);
+    if (e == hipSuccess) pg->csr_dirty = false;
+    return e;
+}
+
 // queues the linearization at the current poses with the damping lambda
 hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda, bool for_solve) {
-    hipError_t e = hipSuccess;
-    if (pg->csr_dirty) {
-        std::vector<uint32_t> start, inc, hubs;
-        e = upload_csr(pg, st, start, inc, hubs);
-        if (e != hipSuccess) return e;
-        pg->csr_dirty = false;
-    }
+    hipError_t e = ensure_csr(pg, st);
+    if (e != hipSuccess) return e;
+    pg->lin_huber = huber_k;
     const PgDev& d = dev_view(pg);
     return launched([&] {
         launch_pg_linearize(st, d, pg->poses, huber_k);
@@ -375,6 +383,136 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
 
 bool range_ok(size_t first, size_t count, size_t size) { return first <= size && count <= size - first; }
 
+bool init_config_ok(const elm_posegraph_init_config* c) {
+    return c && isfinite(c->pcg_rel_tol) && c->pcg_rel_tol > 0.0 && c->pcg_max_iterations >= 1 && c->pcg_check_every >= 1 && c->stages >= 1 &&
+           c->stages <= (ELM_PG_INIT_ROT | ELM_PG_INIT_TRANS);
+}
+
+// The preconditions of elm_posegraph_initialize that need the graph: "" when they hold, else the text for elm_last_error.  The
+// components come from a union-find over the host's copy of the edges (path halving, the smaller index the root).
+std::string init_refusal(const elm_posegraph* pg, int stages) {
+    if (!pg->N) return "no node in the graph";
+    for (uint32_t e = 0; e < pg->E; ++e) {
+        if ((stages & ELM_PG_INIT_ROT) && !(pg->wr[e] > 0.0)) return "edge " + std::to_string(e) + " has no positive rotation weight trace(Omega_ww) / 3";
+        if ((stages & ELM_PG_INIT_TRANS) && !(pg->wt[e] > 0.0))
+            return "edge " + std::to_string(e) + " has no positive translation weight trace(Omega_vv) / 3";
+    }
+    std::vector<uint32_t> root(pg->N);
+    for (uint32_t v = 0; v < pg->N; ++v) root[v] = v;
+    auto find = [&](uint32_t v) {
+        while (root[v] != v) v = root[v] = root[root[v]];
+        return v;
+    };
+    for (uint32_t e = 0; e < pg->E; ++e) {
+        const uint32_t a = find((uint32_t)pg->ei[e]), b = find((uint32_t)pg->ej[e]);
+        if (a != b) root[std::max(a, b)] = std::min(a, b);
+    }
+    std::vector<uint8_t> anchored(pg->N, 0), has_edge(pg->N, 0);
+    for (uint32_t v = 0; v < pg->N; ++v)
+        if (pg->fixed[v]) anchored[find(v)] = 1;
+    for (uint32_t e = 0; e < pg->E; ++e) has_edge[find((uint32_t)pg->ei[e])] = 1;
+    for (uint32_t v = 0; v < pg->N; ++v)
+        if (has_edge[v] && !anchored[v]) return "the connected component of node " + std::to_string(v) + " has edges but no fixed node (singular at lambda = 0)";
+    return "";
+}
+
+int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_config& c, elm_posegraph_init_result* res, double* rows_out,
+                    double* v_out) {
+    const char* what = "elm_posegraph_initialize";
+    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    const size_t N = pg->N;
+    const bool rot = (c.stages & ELM_PG_INIT_ROT) != 0, trans = (c.stages & ELM_PG_INIT_TRANS) != 0;
+    elm_posegraph_init_result R{};
+    hipError_t e = ensure_csr(pg, st);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    PgOut o{};
+    int rc = cost_at(ctx, pg, st, pg->poses, 0.0, 0, o, what);
+    if (rc != ELM_OK) return rc;
+    R.cost_before = o.cost;
+    // From here the contribution arrays, the node sums and the flags are those of the stages: a linearization that was valid is put
+    // back below unless the poses change.
+    const bool was_valid = pg->lin_valid;
+    pg->lin_valid = false;
+    const PgDev& d = dev_view(pg);
+    double* const rows = d.q; // [N][6]: the conjugate gradients' q is free between two solves
+    if (rot) {
+        e = launched([&] {
+            launch_pgi_rot_terms(st, d, pg->poses);
+            launch_damping(pg, st, d, 0.0, 1, true);
+        });
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        PgState s{};
+        rc = run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+        if (rc != ELM_OK) return rc;
+        R.rot_iterations = (int32_t)s.iters;
+        R.rot_converged = (int32_t)s.converged;
+        R.rot_rel_residual = rel_residual(s, pg->N);
+        const uint32_t nb = pg_blocks(pg->N);
+        std::vector<double> counts(nb);
+        e = launched([&] { launch_pgi_rot_apply(st, d, pg->poses, pg->trial, rows, d.part_rz); });
+        if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d.part_rz, nb * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && rows_out) e = hipMemcpyAsync(rows_out, rows, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
+        rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        double n = 0.0;
+        for (uint32_t k = 0; k < nb; ++k) n += counts[k]; // whole numbers in slot order
+        R.degenerate_nodes = (int32_t)n;
+    } else {
+        e = hipMemcpyAsync(pg->trial, pg->poses, 12 * N * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        if (rows_out) { // the current rows
+            std::vector<double> P(12 * N);
+            rc = join(ctx, st, hipMemcpyAsync(P.data(), pg->poses, 12 * N * sizeof(double), hipMemcpyDeviceToHost, st), what);
+            if (rc != ELM_OK) return rc;
+            for (size_t v = 0; v < N; ++v)
+                for (int q = 0; q < 6; ++q) rows_out[6 * v + q] = P[12 * v + (q < 3 ? q : q + 1)];
+        }
+    }
+    if (trans) {
+        e = launched([&] {
+            launch_pgi_trans_terms(st, d, pg->trial);
+            launch_damping(pg, st, d, 0.0, 1, true);
+        });
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        PgState s{};
+        rc = run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+        if (rc != ELM_OK) return rc;
+        R.trans_iterations = (int32_t)s.iters;
+        R.trans_converged = (int32_t)s.converged;
+        R.trans_rel_residual = rel_residual(s, pg->N);
+        std::vector<double> host(v_out ? 6 * N : 0); // the solution [N][6], of which v_out takes the upper three per node
+        e = launched([&] { launch_pgi_trans_apply(st, d, pg->trial); });
+        if (e == hipSuccess && v_out) e = hipMemcpyAsync(host.data(), d.x, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
+        rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        if (v_out)
+            for (size_t v = 0; v < N; ++v)
+                for (int q = 0; q < 3; ++q) v_out[3 * v + q] = host[6 * v + q];
+    } else if (v_out) {
+        std::fill(v_out, v_out + 3 * N, 0.0);
+    }
+    rc = cost_at(ctx, pg, st, pg->trial, 0.0, 0, o, what);
+    if (rc != ELM_OK) return rc;
+    R.cost_after = o.cost;
+    R.applied = ((!rot || R.rot_converged) && (!trans || R.trans_converged)) ? 1 : 0;
+    if (R.applied) {
+        std::swap(pg->poses, pg->trial);
+    } else if (was_valid) {
+        // The same kernels on the same poses: the same bytes as before the call in what a linearization shows (the contribution arrays,
+        // the undamped diagonal blocks and the gradient, the sums and the flags).  The damped blocks, their inverses and the chain factor
+        // are NOT those of the caller's last lambda: they are left at lambda = 0 without a factor.  That is invisible only because
+        // elm_posegraph_solve queues launch_damping with its own lambda before its conjugate gradients and optimize_impl linearizes
+        // anew; a later caller that read the inverses or the factor without doing so would have to restore them here.
+        e = queue_linearize(pg, st, pg->lin_huber, 0.0, false);
+        rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        pg->lin_valid = true;
+    }
+    *res = R;
+    return ELM_OK;
+}
+
 } // namespace
 
 extern "C" int elm_posegraph_edge_terms(const double* Ti16, const double* Tj16, const double* Z16, double* r, double* A, double* B) {
@@ -409,6 +547,8 @@ extern "C" int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg) {
     pg->fixed.clear();
     pg->ei.clear();
     pg->ej.clear();
+    pg->wr.clear();
+    pg->wt.clear();
     pg->csr_dirty = true;
     pg->lin_valid = false;
     return ELM_OK;
@@ -548,6 +688,8 @@ extern "C" int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const in
         for (size_t k = 0; k < n; ++k) pose_rows12(Z16 + 16 * k, &rows[12 * k]);
         pg->ei.reserve((size_t)pg->E + n);
         pg->ej.reserve((size_t)pg->E + n);
+        pg->wr.reserve((size_t)pg->E + n);
+        pg->wt.reserve((size_t)pg->E + n);
         hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         const size_t E0 = pg->E;
         hipError_t e = hipMemcpyAsync(pg->d_ei + E0, i, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -558,6 +700,11 @@ extern "C" int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const in
         if (rc != ELM_OK) return rc;
         pg->ei.insert(pg->ei.end(), i, i + n);
         pg->ej.insert(pg->ej.end(), j, j + n);
+        for (size_t k = 0; k < n; ++k) { // the two traces as the kernels form them
+            const double* om = info36 + 36 * k;
+            pg->wt.push_back(((om[0] + om[7]) + om[14]) / 3.0);
+            pg->wr.push_back(((om[21] + om[28]) + om[35]) / 3.0);
+        }
         pg->E += (uint32_t)n;
         pg->csr_dirty = true;
         pg->lin_valid = false;
@@ -666,4 +813,29 @@ extern "C" int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm
         return ELM_ERR_INVALID;
     }
     return guard_alloc(ctx, what, [&] { return optimize_impl(ctx, pg, *cfg, result, trace_cap > 0 ? trace : nullptr, trace_cap); });
+}
+
+extern "C" void elm_posegraph_init_config_default(elm_posegraph_init_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->pcg_rel_tol = 1e-8;
+    c->pcg_max_iterations = 50000;
+    c->pcg_check_every = kPgDefaultCheckEvery;
+    c->stages = ELM_PG_INIT_ROT | ELM_PG_INIT_TRANS;
+}
+
+extern "C" int elm_posegraph_initialize(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_config* cfg, elm_posegraph_init_result* result,
+                                        double* rows_out, double* v_out) {
+    const char* what = "elm_posegraph_initialize";
+    if (!ctx || !pg || !result || !init_config_ok(cfg)) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    return guard_alloc(ctx, what, [&]() -> int { // the check's vectors and texts are allocated inside the guard too
+        const std::string refusal = init_refusal(pg, cfg->stages);
+        if (!refusal.empty()) {
+            elm_host::ctx_set_error(ctx, std::string(what) + ": " + refusal);
+            return ELM_ERR_INVALID;
+        }
+        return initialize_impl(ctx, pg, *cfg, result, rows_out, v_out);
+    });
 }

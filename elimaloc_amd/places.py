@@ -267,13 +267,17 @@ class LoopCloser:
         info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
         self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
 
-    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi"):
+    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
         The default informations are the identity, which weighs a metre like a radian and an odometry step like a verified loop: a
         caller with real data passes informations that say how good its odometry and its loops are.  preconditioner: PoseGraph's
-        ("block_jacobi" | "chain"); the entries are a chain by construction, which is what "chain" is made for."""
+        ("block_jacobi" | "chain"); the entries are a chain by construction, which is what "chain" is made for.
+        initialize=True runs PoseGraph.Initialize (rotations first, then translations, both linear) before Optimize and puts its result
+        under "initialize" in the returned dict: the start that a long loop needs, whose drift is far outside Gauss-Newton's reach.  A
+        false loop pulls a linear initialization as hard as a true one: Huber acts only in Optimize, so verify loops before adding
+        them.  The default leaves every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
@@ -290,7 +294,10 @@ class LoopCloser:
             if self.loops:
                 pg.AddEdges([l[0] for l in self.loops], [l[1] for l in self.loops], np.stack([l[2] for l in self.loops]),
                             np.stack([l[3] for l in self.loops]))
+            init = pg.Initialize() if initialize else None
             res = pg.Optimize(cfg)
+            if initialize:
+                res["initialize"] = init
             out = pg.Poses()
         finally:
             pg.close()

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ElmError, PG_PRECOND, PG_STOP,PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC, PoseGraphTraceC,
-                   check)
+                   PoseGraphInitConfigC, PoseGraphInitResultC, check)
 from .registration import _Owned, _dp, _pose_block, _ptr, default_context
 
 _INT_FIELDS = ("max_iterations", "pcg_max_iterations", "pcg_check_every")
@@ -23,6 +23,18 @@ def PoseGraphConfig(**kw):
         if k.startswith("_") or not hasattr(cfg, k):
             raise AttributeError(f"PoseGraphConfig has no field {k}")
         setattr(cfg, k, int(v) if k in _INT_FIELDS else float(v))
+    return cfg
+
+
+def PoseGraphInitConfig(**kw):
+    """elm_posegraph_init_config with its defaults (both solves to 1e-8 in at most 50 000 iterations checked every 32;
+    stages = PG_INIT_ROT | PG_INIT_TRANS, or one of them)."""
+    cfg = PoseGraphInitConfigC()
+    _lib.lib().elm_posegraph_init_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k.startswith("_") or not hasattr(cfg, k):
+            raise AttributeError(f"PoseGraphInitConfig has no field {k}")
+        setattr(cfg, k, float(v) if k == "pcg_rel_tol" else int(v))
     return cfg
 
 
@@ -153,6 +165,25 @@ class PoseGraph(_Owned):
         trace = (PoseGraphTraceC * max(int(trace_cap), 1))()
         self._call("elm_posegraph_optimize", C.byref(cfg), C.byref(res), trace, int(trace_cap))
         return _result(res, trace, int(trace_cap))
+
+    def Initialize(self, cfg=None, return_stages=False):
+        """The linear initialization (include/elimaloc_hip_posegraph_init.h): the rotations from one linear least-squares problem on
+        their first two rows, projected back to SO(3), then the translations from an exactly linear one, both by the conjugate gradients
+        and the preconditioner of this object.  The poses are replaced only if every requested stage converged -> dict(cost_before,
+        cost_after, rot_iterations, trans_iterations, rot_rel_residual, trans_rel_residual, rot_converged, trans_converged,
+        degenerate_nodes, applied); with return_stages also rows [N, 6] (the solved rows before the projection) and v [N, 3]."""
+        cfg = cfg if cfg is not None else PoseGraphInitConfig()
+        res = PoseGraphInitResultC()
+        N = self.Size()[0] if return_stages else 0
+        rows, v = np.zeros((max(N, 1), 6)), np.zeros((max(N, 1), 3))
+        self._call("elm_posegraph_initialize", C.byref(cfg), C.byref(res), _dp(rows) if return_stages else None, _dp(v) if return_stages else None)
+        out = dict(cost_before=float(res.cost_before), cost_after=float(res.cost_after), rot_iterations=int(res.rot_iterations),
+                   trans_iterations=int(res.trans_iterations), rot_rel_residual=float(res.rot_rel_residual),
+                   trans_rel_residual=float(res.trans_rel_residual), rot_converged=bool(res.rot_converged),
+                   trans_converged=bool(res.trans_converged), degenerate_nodes=int(res.degenerate_nodes), applied=bool(res.applied))
+        if return_stages:
+            out["rows"], out["v"] = rows[:N], v[:N]
+        return out
 
     def _destroy(self, h):
         _lib.lib().elm_posegraph_destroy(h)

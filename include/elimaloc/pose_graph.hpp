@@ -150,6 +150,24 @@ public:
         if (trace) trace->assign(tr.begin(), tr.begin() + res.solves);
         return res;
     }
+    // The linear initialization (elimaloc_hip_posegraph_init.h): rotations first, then translations, by this object's preconditioner;
+    // the poses are replaced only if every requested stage converged (result.applied).  config: NULL for the defaults; rows [Nodes()][6]
+    // (the solved rows before the projection) and v [Nodes()][3] when asked for.
+    inline elm_posegraph_init_result Initialize(const elm_posegraph_init_config* config = nullptr, std::vector<double>* rows = nullptr,
+                                                std::vector<double>* v = nullptr) {
+        elm_posegraph_init_config c;
+        elm_posegraph_init_config_default(&c);
+        if (config) c = *config;
+        const size_t n = (rows || v) ? Nodes() : 0;
+        if (rows) rows->assign(6 * n + 1, 0.0);
+        if (v) v->assign(3 * n + 1, 0.0);
+        elm_posegraph_init_result res;
+        elimaloc::check(elm_posegraph_initialize(VoxelHashMap::ctx(), pg_, &c, &res, rows ? rows->data() : nullptr, v ? v->data() : nullptr),
+                        VoxelHashMap::ctx(), "elm_posegraph_initialize");
+        if (rows) rows->pop_back();
+        if (v) v->pop_back();
+        return res;
+    }
     // host only: the residual and Jacobians of one edge (row-major r[6], A[36], B[36])
     static inline void EdgeTerms(const elimaloc::Matrix4d& Ti, const elimaloc::Matrix4d& Tj, const elimaloc::Matrix4d& Z, double* r, double* A, double* B) {
         elimaloc::check(elm_posegraph_edge_terms(Ti.data(), Tj.data(), Z.data(), r, A, B), nullptr, "elm_posegraph_edge_terms");

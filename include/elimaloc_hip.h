@@ -971,6 +971,8 @@ int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans,
  * v, v + 1, applied by a parallel block cyclic reduction on the GPU -- is chosen per object; its definition and its two calls,
  * elm_posegraph_set_preconditioner / elm_posegraph_get_preconditioner, are in elimaloc_hip_posegraph_precond.h, included below.  With
  * the default every result of every call here is what it was before that choice existed, byte for byte.
+ * INITIALIZATION.  A start far from the linear regime is first brought near it by two linear problems, rotations and then translations,
+ * solved by the same conjugate gradients: elm_posegraph_initialize, in elimaloc_hip_posegraph_init.h, included below.
  * LIMITS.  node_capacity 1 .. 2^20, edge_capacity 1 .. 2^22, fixed for the object's life; device memory about 1.8 KB per node (1.2 KB
  * of it the chain preconditioner's factor: per node and level of the reduction the inverse pivot block, the two coupling blocks and
  * the running coupling, the levels above the first adding 1/255) and 1.7 KB per edge of capacity. */
@@ -1050,6 +1052,7 @@ int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const
 }
 #endif
 #include "elimaloc_hip_posegraph_precond.h"
+#include "elimaloc_hip_posegraph_init.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,4 +1,5 @@
-"""Pose-graph cost on one GPU: prints ONE JSON line and writes it to profiles/posegraph_rate.json.
+"""Pose-graph cost on one GPU: prints ONE JSON line and writes it to profiles/posegraph_rate.json (and a second line, the
+initialization's rows, described below).
 
 A ring of N nodes, N in 1 000, 10 000 and 65 536: the truth runs along a circle with 1 m between neighbours; odometry edges k -> k + 1
 without noise, a loop edge k -> k + 100 for every k that is a multiple of 100, and one edge closing the ring (N - 1 -> 0), all from the
@@ -13,10 +14,15 @@ a solve without a stop test is timed at 32 and at 288 iterations under either pr
 iteration, the rest of the 32-iteration call its fixed part; the apply is the chain's ms per iteration less block Jacobi's (whose own
 z = M^-1 r is a 6 x 6 product inside k_pg_update), the factor the chain's fixed part less block Jacobi's and less one apply (the z0
 of the start).
-Kernel-only times: run under a kernel trace (k_pg_*, k_pgc_*), e.g. with --sizes 1000.
+The linear initialization (elm_posegraph_initialize, rotations first and then translations) has rows of its own, per N and
+preconditioner, in a second JSON line written to profiles/posegraph_init_rate.json: from the same drifted start one Initialize with its
+defaults (1e-8, at most 50 000 iterations per stage) -- the call's ms, the PCG iterations of both stages, whether it was applied, the
+costs and the largest pose error after the initialization alone -- and then the same Optimize as above run after it.  The first line
+and its file are what they were.
+Kernel-only times: run under a kernel trace (k_pg_*, k_pgc_*, k_pgi_*), e.g. with --sizes 1000.
 
     python tools/posegraph_rate.py [--reps 5] [--sizes 1000,10000,65536] [--pcg-max 20000] [--preconditioner both]
-                                   [--out profiles/posegraph_rate.json]
+                                   [--out profiles/posegraph_rate.json] [--init-out profiles/posegraph_init_rate.json]
 """
 import argparse
 import json
@@ -84,6 +90,24 @@ def solve_and_optimize(pg, truth, start, pcg_max):
                               total_ms=opt_ms, start_error_m=err0, end_error_m=err))
 
 
+def initialize_and_optimize(pg, truth, start, pcg_max):
+    """Initialize from the drifted start with the current preconditioner, then the optimize of solve_and_optimize -> one record"""
+    from elimaloc_amd.posegraph import PoseGraphConfig
+    worst = lambda poses: float(np.linalg.norm(poses[:, :3, 3] - truth[:, :3, 3], axis=1).max())
+    pg.SetPoses(start)
+    init_ms, init = wall_ms(lambda: pg.Initialize(), 1)
+    after_init = worst(pg.Poses())
+    cfg = PoseGraphConfig(pcg_rel_tol=1e-6, pcg_max_iterations=pcg_max, max_iterations=20, step_tol=1e-7)
+    opt_ms, res = wall_ms(lambda: pg.Optimize(cfg), 1)
+    return dict(initialize=dict(call_ms=init_ms, rot_iterations=init["rot_iterations"], trans_iterations=init["trans_iterations"],
+                                rot_converged=init["rot_converged"], trans_converged=init["trans_converged"], applied=init["applied"],
+                                degenerate_nodes=init["degenerate_nodes"], cost_before=init["cost_before"], cost_after=init["cost_after"],
+                                start_error_m=worst(start), error_after_m=after_init),
+                optimize=dict(solves=res["solves"], accepted=res["accepted"], rejected=res["rejected"],
+                              pcg_iterations_total=res["pcg_iterations_total"], stop_reason=res["stop_reason"],
+                              cost_initial=res["cost_initial"], cost_final=res["cost_final"], total_ms=opt_ms, end_error_m=worst(pg.Poses())))
+
+
 def iteration_and_fixed_ms(pg, start, reps):
     """(ms per iteration, fixed ms of a solve call) of the current preconditioner: solves without a stop test at 32 and 288 iterations"""
     pg.SetPoses(start)
@@ -99,7 +123,7 @@ def measure(sizes, reps, pcg_max, kinds=("block_jacobi", "chain")):
     from elimaloc_amd.posegraph import PoseGraph
     from elimaloc_amd.registration import Context
     ctx = Context(0)
-    out = {}
+    out, init_out = {}, {}
     for N in sizes:
         truth, start, i, j, Z = ring(N)
         fixed = np.zeros(N, bool)
@@ -123,8 +147,12 @@ def measure(sizes, reps, pcg_max, kinds=("block_jacobi", "chain")):
             row["chain"].update(iteration_ms=round(per_c, 5), block_jacobi_iteration_ms=round(per_b, 5), apply_ms_per_iteration=round(apply_ms, 5),
                                 factor_ms=round(fixed_c - fixed_b - apply_ms, 4))
         out[f"ring_{N}"] = row
+        init_out[f"ring_{N}"] = dict(nodes=N, edges=len(i))
+        for kind in kinds:  # after every figure of the first line has been taken
+            pg.SetPreconditioner(kind)
+            init_out[f"ring_{N}"][kind] = initialize_and_optimize(pg, truth, start, pcg_max)
         pg.close()
-    return out
+    return out, init_out
 
 
 def main():
@@ -134,13 +162,18 @@ def main():
     ap.add_argument("--pcg-max", type=int, default=20000)
     ap.add_argument("--preconditioner", default="both", choices=("both", "block_jacobi", "chain"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph_rate.json"))
+    ap.add_argument("--init-out", default=os.path.join(ROOT, "profiles", "posegraph_init_rate.json"))
     a = ap.parse_args()
     kinds = ("block_jacobi", "chain") if a.preconditioner == "both" else (a.preconditioner,)
-    line = json.dumps(dict(tool="posegraph_rate", pcg_max=a.pcg_max, preconditioner=a.preconditioner,
-                           **measure([int(s) for s in a.sizes.split(",")], a.reps, a.pcg_max, kinds)))
+    rows, init_rows = measure([int(s) for s in a.sizes.split(",")], a.reps, a.pcg_max, kinds)
+    line = json.dumps(dict(tool="posegraph_rate", pcg_max=a.pcg_max, preconditioner=a.preconditioner, **rows))
     print(line)
     with open(a.out, "w") as f:
         f.write(line + "\n")
+    init_line = json.dumps(dict(tool="posegraph_rate", rows="initialize", pcg_max=a.pcg_max, preconditioner=a.preconditioner, **init_rows))
+    print(init_line)
+    with open(a.init_out, "w") as f:
+        f.write(init_line + "\n")
 
 
 if __name__ == "__main__":
