@@ -1,7 +1,11 @@
 // elm_dev_pgraph.hpp -- the pose graph's relative-pose edge (include/elimaloc_hip.h, "pose graph"): SO(3) Log through the
 // unit quaternion, the inverse right Jacobian, the residual and its two 6 x 6 Jacobians, the Huber weight and cost, and the retraction.
 // Host and device run this same code (elm_posegraph_edge_terms is the host's call of it).  Float64, row-major, no contraction.
+// Below the edge math: the 6 x 6 block primitives of the solver's kernels, the edge-group launch geometry, and (device only) the
+// fixed-order workgroup reductions and the load of an edge's three poses.  Every sum here is the first product, then the other five
+// added left to right; no helper indexes an array by a value that varies by lane.
 #pragma once
+#include "elm_internal.hpp"
 #include "elm_la.hpp"
 
 namespace elm {
@@ -165,11 +169,11 @@ ELM_HD void pg_edge_blocks(const double Pi[12], const double Pj[12], const doubl
             K.Arr[a * 3 + b] = -((K.Brr[a * 3] * Rij[b * 3] + K.Brr[a * 3 + 1] * Rij[b * 3 + 1]) + K.Brr[a * 3 + 2] * Rij[b * 3 + 2]);
         }
 }
-// the same as full row-major 6 x 6 matrices
-ELM_HD void pg_edge_terms(const double Pi[12], const double Pj[12], const double PZ[12], double r[6], double A[36], double B[36]) {
-    PgBlocks K;
-    pg_edge_blocks(Pi, Pj, PZ, r, K);
+// the blocks as full row-major 6 x 6 matrices (registers, LDS or the host's arrays)
+ELM_HD void pg_blocks_full(const PgBlocks& K, double* A, double* B) {
+#pragma unroll
     for (int a = 0; a < 3; ++a)
+#pragma unroll
         for (int b = 0; b < 3; ++b) {
             A[a * 6 + b] = K.Att[a * 3 + b];
             A[a * 6 + 3 + b] = K.Atr[a * 3 + b];
@@ -180,6 +184,11 @@ ELM_HD void pg_edge_terms(const double Pi[12], const double Pj[12], const double
             B[(3 + a) * 6 + b] = 0.0;
             B[(3 + a) * 6 + 3 + b] = K.Brr[a * 3 + b];
         }
+}
+ELM_HD void pg_edge_terms(const double Pi[12], const double Pj[12], const double PZ[12], double r[6], double A[36], double B[36]) {
+    PgBlocks K;
+    pg_edge_blocks(Pi, Pj, PZ, r, K);
+    pg_blocks_full(K, A, B);
 }
 
 // Huber on s = r^T Omega r: the weight, and the cost rho.  k = 0: off.  s == k^2 is an inlier.
@@ -200,5 +209,92 @@ ELM_HD void pg_retract(const double P[12], const double x[6], double out[12]) {
         out[r * 4 + 3] = t[r] + ((R[r * 3] * x[0] + R[r * 3 + 1] * x[1]) + R[r * 3 + 2] * x[2]);
     }
 }
+
+// ---- 6 x 6 blocks (row-major) ----
+// row . v
+ELM_HD double pg_dot6(const double* row, const double* v) {
+    double t = row[0] * v[0];
+#pragma unroll
+    for (int b = 1; b < 6; ++b) t += row[b] * v[b];
+    return t;
+}
+// out = M v
+ELM_HD void pg_mv6(const double* M, const double* v, double out[6]) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) out[a] = pg_dot6(M + a * 6, v);
+}
+// column . v, the column's entries 6 apart: entry a of M^T v is pg_dot6_col(M + a, v)
+ELM_HD double pg_dot6_col(const double* col, const double* v) {
+    double t = col[0] * v[0];
+#pragma unroll
+    for (int b = 1; b < 6; ++b) t += col[b * 6] * v[b];
+    return t;
+}
+// entry (a, c) of X Y, of X Y^T and of X^T Y
+ELM_HD double pg_mm6(const double* X, const double* Y, int a, int c) {
+    double t = X[a * 6] * Y[c];
+#pragma unroll
+    for (int b = 1; b < 6; ++b) t += X[a * 6 + b] * Y[b * 6 + c];
+    return t;
+}
+ELM_HD double pg_mmt6(const double* X, const double* Y, int a, int c) { return pg_dot6(X + a * 6, Y + c * 6); }
+ELM_HD double pg_mtm6(const double* X, const double* Y, int a, int c) {
+    double t = X[a] * Y[c];
+#pragma unroll
+    for (int b = 1; b < 6; ++b) t += X[b * 6 + a] * Y[b * 6 + c];
+    return t;
+}
+
+// the workgroups of a kernel that gives every edge a lane group of kPgLanesPerEdge; the most hubs a graph of Ec edges can have
+constexpr uint32_t pg_edge_group_blocks(uint32_t E) { return (uint32_t)(((size_t)E * kPgLanesPerEdge + 255) / 256); }
+constexpr size_t pg_max_hubs(size_t Ec) { return 2 * Ec / (kPgHubDegree + 1) + 1; }
+
+#if defined(__HIPCC__) && defined(__forceinline__) // ---- device only ----
+// The sum of one value per lane of a 256-lane workgroup, as a fixed tree in LDS (buf: 256 doubles); every lane returns it.
+__device__ __forceinline__ double pg_block_sum(double v, double* buf) {
+    const uint32_t tid = threadIdx.x;
+    __syncthreads(); // (an earlier use of buf has been read)
+    buf[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
+        if (tid < h) buf[tid] = buf[tid] + buf[tid + h];
+        __syncthreads();
+    }
+    return buf[0];
+}
+__device__ __forceinline__ double pg_block_max(double v, double* buf) {
+    const uint32_t tid = threadIdx.x;
+    __syncthreads();
+    buf[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
+        if (tid < h) buf[tid] = fmax(buf[tid], buf[tid + h]);
+        __syncthreads();
+    }
+    return buf[0];
+}
+// The sum of n partial slots: lane t adds slots t, t + 256, ... in ascending order, then the tree.  The same n gives the same tree.
+__device__ __forceinline__ double pg_sum_slots(const double* __restrict__ slots, uint32_t n, double* buf) {
+    double v = 0.0;
+    for (uint32_t k = threadIdx.x; k < n; k += kPgBlock) v += slots[k];
+    return pg_block_sum(v, buf);
+}
+
+// the pose rows of edge e's two nodes at `poses`, and of its measurement
+__device__ __forceinline__ void pg_load_edge_poses(const PgDev& d, const double* __restrict__ poses, uint32_t e, double Pi[12], double Pj[12],
+                                                   double PZ[12]) {
+    const double* __restrict__ pi = poses + 12 * (size_t)d.ei[e];
+    const double* __restrict__ pj = poses + 12 * (size_t)d.ej[e];
+    const double* __restrict__ pz = d.Z + 12 * (size_t)e;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        Pi[k] = pi[k];
+        Pj[k] = pj[k];
+        PZ[k] = pz[k];
+    }
+}
+#endif
 
 } // namespace elm

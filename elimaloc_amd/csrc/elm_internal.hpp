@@ -458,8 +458,11 @@ constexpr uint32_t pg_blocks(uint32_t n) { return (n + kPgBlock - 1) / kPgBlock;
 void launch_pg_linearize(hipStream_t s, const PgDev& d, const double* poses, double huber_k);
 // sum != 0: H_vv and g_v summed from the edges' contributions first; always: the active rule, the damping and the inverses
 void launch_pg_nodes(hipStream_t s, const PgDev& d, double lambda, int sum);
-void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, double tol);
-void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, double lambda, double tol, uint32_t it);
+// The conjugate gradients on (H + lambda diag H) x = -g, composed once for every preconditioner.  chain == nullptr: block Jacobi, the
+// kernels apply Minv themselves; else the chain factor of launch_pgc_factor at the same lambda, applied by launch_pgc_apply.
+struct PgcDev;
+void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev* chain, double tol);
+void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev* chain, double lambda, double tol, uint32_t it);
 void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, double* trial);
 // chi2, cost and outliers at `poses` into d.out, with the largest |x| of the last retraction; want_grad: also max |g_v| over active nodes
 void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double huber_k, int want_grad);
@@ -470,7 +473,7 @@ void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double h
 // are the next level's nodes, and the level of one segment ends the recursion.  Per node and level the factor keeps the inverse pivot
 // block G and the two coupling blocks A = G M[p][left], B = G M[p][right].
 // kPgcSeg = 256 = kPgBlock: a workgroup's nodes at level 0 are those of one r^T z slot, so the last launch of an apply writes the
-// existing slots and k_pg_direction serves both preconditioners; the apply holds only the segment's right-hand side in LDS
+// slots k_pg_update<true> writes and k_pg_direction serves both preconditioners; the apply holds only the segment's right-hand side in LDS
 // (257 x 6 doubles, 12 KB), the factor works in global memory and holds 64 inversion workspaces (36 KB), so neither is bound by LDS;
 // and 2^20 nodes are three levels (five launches per apply), 65 536 two (three launches), 256 one (one launch).
 constexpr uint32_t kPgcSeg = 256;
@@ -505,13 +508,9 @@ inline uint32_t pgc_levels(uint32_t n, PgcLevel* lv) {
 }
 // the factor of M = chain part of H + lambda diag H (after launch_pg_nodes with the same lambda); N >= 1
 void launch_pgc_factor(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda);
-// x = 0, r = -g, z = M^-1 r, p = z, r0^T z0 and the state words: launch_pg_pcg_begin's work with the chain M
-void launch_pgc_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev& c, double tol);
-void launch_pgc_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda, double tol, uint32_t it);
-// the launches of elm_k_pgraph.hip that the chain iteration shares
-void launch_pg_pcg_state(hipStream_t s, const PgDev& d, double tol);
-void launch_pg_spmv(hipStream_t s, const PgDev& d, double lambda, uint32_t it);
-void launch_pg_direction(hipStream_t s, const PgDev& d, double tol, uint32_t it);
+// z = M^-1 r of the current residual, and the workgroups' partials of r^T z in the r^T z slots; first: p = z too; gate: nothing is done
+// once the stop word of iteration `it` is set.  What launch_pg_pcg_begin and launch_pg_pcg_iteration queue for a chain; N >= 1
+void launch_pgc_apply(hipStream_t s, const PgDev& d, const PgcDev& c, uint32_t it, int gate, int first);
 
 // pose graph, linear initialization (elm_k_pginit.hip; the contract is include/elimaloc_hip_posegraph_init.h).
 // The two term kernels fill gi, gj, Hii, Hij, Hjj of the view as launch_pg_linearize does, for launch_pg_nodes (sum = 1, lambda = 0)

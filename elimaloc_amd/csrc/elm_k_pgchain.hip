@@ -10,13 +10,14 @@
 //   K12j k_pgc_fwd      per apply and level below the top: the right-hand side reduced in LDS, b_q -= B^T b_left + A^T b_right
 //   K12k k_pgc_top      the top level: forward, the last node, back-substitution x_p = G b_p - A x_left - B x_right
 //   K12l k_pgc_back     per level below the top, downwards: back-substitution from the level above's solution
-//   K12m k_pgc_init / k_pgc_update   k_pg_pcg_init and k_pg_update without their block-Jacobi z
-// The level-0 launch of k_pgc_top or k_pgc_back writes z, (first: p = z) and the workgroup's partial of r^T z to the slot k_pg_update
+// launch_pgc_apply is the preconditioner's side of the seam in launch_pg_pcg_begin and launch_pg_pcg_iteration (elm_k_pgraph.hip): the
+// level-0 launch of k_pgc_top or k_pgc_back writes z, (first: p = z) and the workgroup's partial of r^T z to the slot k_pg_update<true>
 // would have written.  A chain break is a zero coupling block; an inactive node and the padding of a segment are identity pivots with
 // zero couplings and a zero right-hand side, so their z is 0.  Float64, no atomics, every sum in a fixed order; a remaining node
 // gathers from its two eliminated neighbours, left first, so no two lanes write one block.
 #include <hip/hip_runtime.h>
 
+#include "elm_dev_pgraph.hpp"
 #include "elm_internal.hpp"
 #include "elm_la.hpp"
 
@@ -25,19 +26,6 @@ namespace elm {
 namespace {
 
 constexpr uint32_t kPgcInvLanes = 64; // lanes that invert at a time: 64 x (36 + 36) doubles of LDS
-
-__device__ __forceinline__ double pgc_block_sum(double v, double* buf) {
-    const uint32_t tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
-        if (tid < h) buf[tid] = buf[tid] + buf[tid + h];
-        __syncthreads();
-    }
-    return buf[0];
-}
 
 // G <- the symmetrized inverse of the block at G (ws_R, ws_m: 36 doubles of LDS each)
 __device__ __forceinline__ void pgc_invert(double* G, double* ws_R, double* ws_m) {
@@ -67,6 +55,7 @@ __device__ __forceinline__ void pgc_load_rhs(const PgDev& d, const PgcDev& c, co
 // The forward steps on s_b; A, B: the blocks of the segment's first node.
 __device__ __forceinline__ void pgc_forward(double* s_b, const double* __restrict__ A, const double* __restrict__ B) {
     const uint32_t tid = threadIdx.x;
+#pragma unroll // (the eight steps with their strides as constants: what the compiler chose by itself before the sums were helper calls)
     for (uint32_t t = 0; t < kPgcSteps; ++t) {
         const uint32_t h = 1u << t, cnt = kPgcSeg >> (t + 1u);
         __syncthreads();
@@ -82,12 +71,7 @@ __device__ __forceinline__ void pgc_forward(double* s_b, const double* __restric
 #pragma unroll
                 for (int b = 0; b < 6; ++b) bp[b] = s_b[(pl + 1u) * 6u + b];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    double s = Bp[a] * bp[0];
-#pragma unroll
-                    for (int b = 1; b < 6; ++b) s += Bp[b * 6 + a] * bp[b];
-                    acc[a] = acc[a] - s;
-                }
+                for (int a = 0; a < 6; ++a) acc[a] = acc[a] - pg_dot6_col(Bp + a, bp);
             }
             if (tid < cnt) { // q is the left neighbour of q + h
                 const uint32_t pr = q1 - 1u + h;
@@ -96,12 +80,7 @@ __device__ __forceinline__ void pgc_forward(double* s_b, const double* __restric
 #pragma unroll
                 for (int b = 0; b < 6; ++b) bp[b] = s_b[(pr + 1u) * 6u + b];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    double s = Ap[a] * bp[0];
-#pragma unroll
-                    for (int b = 1; b < 6; ++b) s += Ap[b * 6 + a] * bp[b];
-                    acc[a] = acc[a] - s;
-                }
+                for (int a = 0; a < 6; ++a) acc[a] = acc[a] - pg_dot6_col(Ap + a, bp);
             }
 #pragma unroll
             for (int a = 0; a < 6; ++a) s_b[q1 * 6u + a] = acc[a];
@@ -129,7 +108,7 @@ __device__ __forceinline__ void pgc_backward(double* s_b, const double* __restri
             }
             double x[6];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) {
+            for (int a = 0; a < 6; ++a) { // the three sums of pg_dot6 side by side: written apart, the loads of a step overlap less
                 double g = Gp[a * 6] * bp[0], l = Ap[a * 6] * xl[0], r = Bp[a * 6] * xr[0];
 #pragma unroll
                 for (int b = 1; b < 6; ++b) {
@@ -165,7 +144,7 @@ __device__ __forceinline__ void pgc_finish(const PgDev& d, const PgcDev& c, cons
             rz += d.rr[o] * z;
         }
     }
-    const double t = pgc_block_sum(rz, buf);
+    const double t = pg_block_sum(rz, buf);
     if (tid == 0u) d.part_rz[blockIdx.x] = t;
 }
 
@@ -237,12 +216,7 @@ __global__ __launch_bounds__(256) void k_pgc_factor(const PgDev d, const PgcDev 
                 pgc_invert(Gp, s_R[tid], s_m[tid]);
                 for (int a = 0; a < 6; ++a)
                     for (int cc = 0; cc < 6; ++cc) {
-                        double sa = Gp[a * 6] * Lp[cc], sb = Gp[a * 6] * Lr[cc * 6];
-#pragma unroll
-                        for (int b = 1; b < 6; ++b) {
-                            sa += Gp[a * 6 + b] * Lp[b * 6 + cc];
-                            sb += Gp[a * 6 + b] * Lr[cc * 6 + b];
-                        }
+                        const double sa = pg_mm6(Gp, Lp, a, cc), sb = pg_mmt6(Gp, Lr, a, cc); // G M[p][left], G M[right][p]^T
                         Ap[a * 6 + cc] = sa;
                         Bp[a * 6 + cc] = sb;
                     }
@@ -256,23 +230,13 @@ __global__ __launch_bounds__(256) void k_pgc_factor(const PgDev d, const PgcDev 
                 const double* Lq = L + 36 * (size_t)(q1 - 1u);
                 const double* Bl = B + 36 * (size_t)(q1 - 1u - h);
                 for (int a = 0; a < 6; ++a)
-                    for (int cc = 0; cc < 6; ++cc) {
-                        double s = Lq[a * 6] * Bl[cc];
-#pragma unroll
-                        for (int b = 1; b < 6; ++b) s += Lq[a * 6 + b] * Bl[b * 6 + cc];
-                        Dq[a * 6 + cc] = Dq[a * 6 + cc] - s;
-                    }
+                    for (int cc = 0; cc < 6; ++cc) Dq[a * 6 + cc] = Dq[a * 6 + cc] - pg_mm6(Lq, Bl, a, cc);
             }
             if (tid < cnt) {
                 const double* Lr = L + 36 * (size_t)(q1 - 1u + h);
                 const double* Ar = A + 36 * (size_t)(q1 - 1u + h);
                 for (int a = 0; a < 6; ++a)
-                    for (int cc = 0; cc < 6; ++cc) {
-                        double s = Lr[a] * Ar[cc];
-#pragma unroll
-                        for (int b = 1; b < 6; ++b) s += Lr[b * 6 + a] * Ar[b * 6 + cc];
-                        Dq[a * 6 + cc] = Dq[a * 6 + cc] - s;
-                    }
+                    for (int cc = 0; cc < 6; ++cc) Dq[a * 6 + cc] = Dq[a * 6 + cc] - pg_mtm6(Lr, Ar, a, cc);
             }
             if (tid >= 1u) {
                 double* Lq = L + 36 * (size_t)(q1 - 1u);
@@ -280,12 +244,7 @@ __global__ __launch_bounds__(256) void k_pgc_factor(const PgDev d, const PgcDev 
                 for (int a = 0; a < 6; ++a) {
                     double row[6];
 #pragma unroll
-                    for (int cc = 0; cc < 6; ++cc) {
-                        double s = Lq[a * 6] * Al[cc];
-#pragma unroll
-                        for (int b = 1; b < 6; ++b) s += Lq[a * 6 + b] * Al[b * 6 + cc];
-                        row[cc] = -s;
-                    }
+                    for (int cc = 0; cc < 6; ++cc) row[cc] = -pg_mm6(Lq, Al, a, cc);
 #pragma unroll
                     for (int cc = 0; cc < 6; ++cc) Lq[a * 6 + cc] = row[cc];
                 }
@@ -328,10 +287,8 @@ __global__ __launch_bounds__(256) void k_pgc_top(const PgDev d, const PgcDev c, 
     __syncthreads();
     double x = 0.0;
     if (tid < 6u) {
-        const double* __restrict__ Gp = c.G + 36 * (base + kPgcSeg - 1u) + 6u * tid;
-        x = Gp[0] * s_b[kPgcSeg * 6u];
-#pragma unroll
-        for (uint32_t b = 1; b < 6u; ++b) x += Gp[b] * s_b[kPgcSeg * 6u + b];
+        const double* __restrict__ Gp = c.G + 36 * (base + kPgcSeg - 1u) + 6u * tid; // the lane's row
+        x = pg_dot6(Gp, s_b + kPgcSeg * 6u);
     }
     __syncthreads();
     if (tid < 6u) s_b[kPgcSeg * 6u + tid] = x;
@@ -355,37 +312,6 @@ __global__ __launch_bounds__(256) void k_pgc_back(const PgDev d, const PgcDev c,
     pgc_finish(d, c, lv, level0, first, s_b, buf);
 }
 
-// K12m.  One lane per node.
-__global__ __launch_bounds__(256) void k_pgc_init(const PgDev d) {
-    const uint32_t v = blockIdx.x * kPgBlock + threadIdx.x;
-    if (v >= d.N) return;
-    const bool act = d.active[v] != 0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const size_t o = 6 * (size_t)v + k;
-        d.x[o] = 0.0;
-        d.rr[o] = act ? -d.g[o] : 0.0;
-        d.q[o] = 0.0;
-    }
-}
-__global__ __launch_bounds__(256) void k_pgc_update(const PgDev d, uint32_t it) {
-    __shared__ double buf[kPgBlock];
-    if (d.state->stop[it & 1u]) return;
-    double part = 0.0;
-    for (uint32_t k = threadIdx.x; k < pg_pq_slots(d.N, d.n_hubs); k += kPgBlock) part += d.part_pq[k];
-    const double pq = pgc_block_sum(part, buf);
-    const double rz_old = d.state->rz[it & 1u];
-    const double alpha = pq != 0.0 ? rz_old / pq : 0.0;
-    const uint32_t v = blockIdx.x * kPgBlock + threadIdx.x;
-    if (v >= d.N) return;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const size_t o = 6 * (size_t)v + k;
-        d.x[o] = d.x[o] + alpha * d.p[o];
-        d.rr[o] = d.rr[o] - alpha * d.q[o];
-    }
-}
-
 void launch_pgc_factor(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda) {
     if (!d.N) return;
     PgcLevel lv[kPgcMaxLevels];
@@ -394,7 +320,6 @@ void launch_pgc_factor(hipStream_t s, const PgDev& d, const PgcDev& c, double la
         hipLaunchKernelGGL(k_pgc_factor, dim3(lv[l].nseg), dim3(256), 0, s, d, c, lv[l], lv[l ? l - 1 : 0], l == 0 ? 1 : 0, lambda);
 }
 
-namespace {
 void launch_pgc_apply(hipStream_t s, const PgDev& d, const PgcDev& c, uint32_t it, int gate, int first) {
     PgcLevel lv[kPgcMaxLevels];
     const uint32_t nl = pgc_levels(d.N, lv), top = nl - 1;
@@ -404,21 +329,4 @@ void launch_pgc_apply(hipStream_t s, const PgDev& d, const PgcDev& c, uint32_t i
     for (uint32_t l = top; l-- > 0u;)
         hipLaunchKernelGGL(k_pgc_back, dim3(lv[l].nseg), dim3(256), 0, s, d, c, lv[l], lv[l + 1], l == 0 ? 1 : 0, it, gate, first);
 }
-} // namespace
-
-void launch_pgc_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev& c, double tol) {
-    if (!d.N) return;
-    hipLaunchKernelGGL(k_pgc_init, dim3(pg_blocks(d.N)), dim3(256), 0, s, d);
-    launch_pgc_apply(s, d, c, 0u, 0, 1);
-    launch_pg_pcg_state(s, d, tol);
-}
-
-void launch_pgc_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev& c, double lambda, double tol, uint32_t it) {
-    if (!d.N) return;
-    launch_pg_spmv(s, d, lambda, it);
-    hipLaunchKernelGGL(k_pgc_update, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, it);
-    launch_pgc_apply(s, d, c, it, 1, 0);
-    launch_pg_direction(s, d, tol, it);
-}
-
 } // namespace elm

@@ -6,6 +6,7 @@
 //   K13a k_pgi_rot_terms    a lane group of 8 per edge, the lane is the column: H_ii = H_jj = w_r I, H_ij = -w_r blockdiag(R_Z, R_Z), g_i, g_j
 //   K13b k_pgi_trans_terms  the same layout: H_ii = H_jj = w_t I, H_ij = -w_t R_i^T R_j in the top-left block, g_i, g_j
 //   K13c k_pgi_rot_apply    one lane per node: rows + Delta, the closed-form projection, the trial pose; the workgroup's degenerate count
+//                           (pg_block_sum of elm_dev_pgraph.hpp)
 //   K13d k_pgi_trans_apply  one lane per node: t <- t + R v in the trial poses
 #include <hip/hip_runtime.h>
 
@@ -68,27 +69,18 @@ __global__ __launch_bounds__(256) void k_pgi_trans_terms(const PgDev d, const do
     if (e >= d.E || c >= 6u) return;
     const bool pad = c >= 3u;
     const uint32_t m = pad ? c - 3u : c;
-    const double* __restrict__ pz = d.Z + 12 * (size_t)e;
     const double* __restrict__ om = d.info + 36 * (size_t)e;
-    double Pi[12], Pj[12], Ri[9], ti[3], Rj[9], tj[3];
-    {
-        const double* __restrict__ pi = poses + 12 * (size_t)d.ei[e];
-        const double* __restrict__ pj = poses + 12 * (size_t)d.ej[e];
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            Pi[q] = pi[q];
-            Pj[q] = pj[q];
-        }
-    }
+    double Pi[12], Pj[12], PZ[12], Ri[9], ti[3], Rj[9], tj[3];
+    pg_load_edge_poses(d, poses, e, Pi, Pj, PZ); // (of the measurement only t_Z is used)
     pg_split(Pi, Ri, ti);
     pg_split(Pj, Rj, tj);
     const double w = ((om[0] + om[7]) + om[14]) / 3.0;
     const double dt[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]};
     double u[3];
     pg_mul3_atv(Ri, dt, u);
-    u[0] = u[0] - pz[3];
-    u[1] = u[1] - pz[7];
-    u[2] = u[2] - pz[11];
+    u[0] = u[0] - PZ[3];
+    u[1] = u[1] - PZ[7];
+    u[2] = u[2] - PZ[11];
     // column m of R_j, then column m of R_ij
     const double q0 = pgi_sel3(m, Rj[0], Rj[1], Rj[2]), q1 = pgi_sel3(m, Rj[3], Rj[4], Rj[5]), q2 = pgi_sel3(m, Rj[6], Rj[7], Rj[8]);
     double col[3];
@@ -108,12 +100,12 @@ __global__ __launch_bounds__(256) void k_pgi_trans_terms(const PgDev d, const do
 
 // K13c.  One lane per node.  rows[v] = the first two rows of R_v, plus the solve's Delta where the node is active.  An active node's
 // rows are projected (the contract's closed form) into the trial pose; a degenerate one and every inactive node keep their pose bit for
-// bit.  The workgroup's count of degenerate nodes goes to slot blockIdx.x, by a fixed tree in LDS.
+// bit.  The workgroup's count of degenerate nodes goes to slot blockIdx.x, by the fixed tree of pg_block_sum.
 __global__ __launch_bounds__(256) void k_pgi_rot_apply(const PgDev d, const double* __restrict__ poses, double* __restrict__ trial,
                                                        double* __restrict__ rows, double* __restrict__ slots) {
-    __shared__ uint32_t s_n[kPgBlock];
+    __shared__ double buf[kPgBlock];
     const uint32_t v = blockIdx.x * kPgBlock + threadIdx.x;
-    uint32_t bad = 0u;
+    double bad = 0.0;
     if (v < d.N) {
         double P[12];
 #pragma unroll
@@ -151,19 +143,13 @@ __global__ __launch_bounds__(256) void k_pgi_rot_apply(const PgDev d, const doub
                     P[10] = r1[0] * r2[1] - r1[1] * r2[0];
                 }
             }
-            bad = ok ? 0u : 1u;
+            bad = ok ? 0.0 : 1.0;
         }
 #pragma unroll
         for (int q = 0; q < 12; ++q) trial[12 * (size_t)v + q] = P[q];
     }
-    s_n[threadIdx.x] = bad;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
-        if (threadIdx.x < h) s_n[threadIdx.x] = s_n[threadIdx.x] + s_n[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) slots[blockIdx.x] = (double)s_n[0];
+    const double n = pg_block_sum(bad, buf); // whole numbers of at most 256: exact
+    if (threadIdx.x == 0) slots[blockIdx.x] = n;
 }
 
 // K13d.  One lane per node, in place on the trial poses: t <- t + R v for an active node (the arithmetic of pg_retract's translation;
@@ -179,14 +165,12 @@ __global__ __launch_bounds__(256) void k_pgi_trans_apply(const PgDev d, double* 
 
 void launch_pgi_rot_terms(hipStream_t s, const PgDev& d, const double* poses) {
     if (!d.E) return;
-    const uint32_t nb = (uint32_t)(((size_t)d.E * kPgLanesPerEdge + 255) / 256);
-    hipLaunchKernelGGL(k_pgi_rot_terms, dim3(nb), dim3(256), 0, s, d, poses);
+    hipLaunchKernelGGL(k_pgi_rot_terms, dim3(pg_edge_group_blocks(d.E)), dim3(256), 0, s, d, poses);
 }
 
 void launch_pgi_trans_terms(hipStream_t s, const PgDev& d, const double* poses) {
     if (!d.E) return;
-    const uint32_t nb = (uint32_t)(((size_t)d.E * kPgLanesPerEdge + 255) / 256);
-    hipLaunchKernelGGL(k_pgi_trans_terms, dim3(nb), dim3(256), 0, s, d, poses);
+    hipLaunchKernelGGL(k_pgi_trans_terms, dim3(pg_edge_group_blocks(d.E)), dim3(256), 0, s, d, poses);
 }
 
 void launch_pgi_rot_apply(hipStream_t s, const PgDev& d, const double* poses, double* trial, double* rows, double* slots) {

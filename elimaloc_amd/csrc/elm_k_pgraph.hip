@@ -6,54 +6,22 @@
 // launches on the context's stream.
 //   K12a k_pg_linearize  a lane group of 8 per edge, the lane is the column: r, A, B, s, w and the edge's five contributions
 //   K12b k_pg_nodes      one wavefront per node, the lane is the component: H_vv, g_v, the active rule, the damping, the 6 x 6 inverse
-//   K12c k_pg_pcg_init / k_pg_pcg_begin   x = 0, r = -g, z = M^-1 r, p = z; r0^T z0
+//   K12c k_pg_pcg_init<jacobi> / k_pg_pcg_begin   x = 0, r = -g, (z = M^-1 r, p = z;) r0^T z0
 //   K12d k_pg_spmv (+ k_pg_spmv_hub)      q = (H + lambda diag H) p, partials of p^T q
-//   K12e k_pg_update     alpha from the partials; x, r, z; partials of r^T z
+//   K12e k_pg_update<jacobi>   alpha from the partials; x, r, (z; partials of r^T z)
 //   K12f k_pg_direction  beta, the stop test and the iteration count from the partials; p
 //   K12g k_pg_retract    trial poses, partials of max |x|
 //   K12h k_pg_cost / k_pg_finish          rho_e at given poses, fixed-order reduction to one record
+// The conjugate gradients are composed once, in launch_pg_pcg_begin and launch_pg_pcg_iteration, with a preconditioner seam: the
+// <true> instantiations of K12c and K12e apply the block-Jacobi Minv themselves; with a chain (elm_k_pgchain.hip) the <false> ones leave
+// z, the first p and the r^T z slots to launch_pgc_apply, whose level-0 launch writes them.  The fixed-order reductions and the 6 x 6
+// block helpers are in elm_dev_pgraph.hpp.
 #include <hip/hip_runtime.h>
 
 #include "elm_dev_pgraph.hpp"
 #include "elm_internal.hpp"
 
 namespace elm {
-
-namespace {
-
-// The sum of one value per lane of a 256-lane workgroup, as a fixed tree in LDS (buf: 256 doubles); every lane returns it.
-__device__ __forceinline__ double pg_block_sum(double v, double* buf) {
-    const uint32_t tid = threadIdx.x;
-    __syncthreads(); // (an earlier use of buf has been read)
-    buf[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
-        if (tid < h) buf[tid] = buf[tid] + buf[tid + h];
-        __syncthreads();
-    }
-    return buf[0];
-}
-__device__ __forceinline__ double pg_block_max(double v, double* buf) {
-    const uint32_t tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = kPgBlock / 2; h > 0; h >>= 1) {
-        if (tid < h) buf[tid] = fmax(buf[tid], buf[tid + h]);
-        __syncthreads();
-    }
-    return buf[0];
-}
-// The sum of n partial slots: lane t adds slots t, t + 256, ... in ascending order, then the tree.  The same n gives the same tree.
-__device__ __forceinline__ double pg_sum_slots(const double* __restrict__ slots, uint32_t n, double* buf) {
-    double v = 0.0;
-    for (uint32_t k = threadIdx.x; k < n; k += kPgBlock) v += slots[k];
-    return pg_block_sum(v, buf);
-}
-
-} // namespace
 
 // K12a.  Lanes 0 .. 5 of a group of 8 are the columns c of the edge's 6 x 6 results (lanes 6 and 7 compute column 5 again and store
 // nothing).  Every lane of the group evaluates r and the five non-zero 3 x 3 blocks of A and B in registers (pg_edge_blocks); lane 0
@@ -70,34 +38,12 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev d, const doubl
     const uint32_t e = valid ? e_raw : d.E - 1u; // (the launch has E >= 1)
     const uint32_t c = lane < 6u ? lane : 5u;
     double Pi[12], Pj[12], PZ[12];
-    {
-        const double* __restrict__ pi = poses + 12 * (size_t)d.ei[e];
-        const double* __restrict__ pj = poses + 12 * (size_t)d.ej[e];
-        const double* __restrict__ pz = d.Z + 12 * (size_t)e;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            Pi[k] = pi[k];
-            Pj[k] = pj[k];
-            PZ[k] = pz[k];
-        }
-    }
+    pg_load_edge_poses(d, poses, e, Pi, Pj, PZ);
     double r[6];
     PgBlocks K;
     pg_edge_blocks(Pi, Pj, PZ, r, K);
     if (lane == 0u) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                s_A[grp][a * 6 + b] = K.Att[a * 3 + b];
-                s_A[grp][a * 6 + 3 + b] = K.Atr[a * 3 + b];
-                s_A[grp][(3 + a) * 6 + b] = 0.0;
-                s_A[grp][(3 + a) * 6 + 3 + b] = K.Arr[a * 3 + b];
-                s_B[grp][a * 6 + b] = K.Btt[a * 3 + b];
-                s_B[grp][a * 6 + 3 + b] = 0.0;
-                s_B[grp][(3 + a) * 6 + b] = 0.0;
-                s_B[grp][(3 + a) * 6 + 3 + b] = K.Brr[a * 3 + b];
-            }
+        pg_blocks_full(K, s_A[grp], s_B[grp]);
 #pragma unroll
         for (int k = 0; k < 6; ++k) s_r[grp][k] = r[k];
     }
@@ -207,9 +153,10 @@ __global__ __launch_bounds__(256) void k_pg_nodes(const PgDev d, double lambda, 
     if (valid && lane == 0u) d.active[v] = active ? 1 : 0;
 }
 
-// K12c.  One lane per node.
+// K12c.  One lane per node.  kJacobi: z = Minv r, p = z and the workgroup's partial of r0^T z0 too; without it they are left to the
+// preconditioner's apply that follows, and the kernel has no barrier.
+template <bool kJacobi>
 __global__ __launch_bounds__(256) void k_pg_pcg_init(const PgDev d) {
-    __shared__ double buf[kPgBlock];
     const uint32_t v = blockIdx.x * kPgBlock + threadIdx.x;
     double rz = 0.0;
     if (v < d.N) {
@@ -217,26 +164,24 @@ __global__ __launch_bounds__(256) void k_pg_pcg_init(const PgDev d) {
         double r[6], z[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) r[k] = act ? -d.g[6 * (size_t)v + k] : 0.0;
-        const double* __restrict__ M = d.Minv + 36 * (size_t)v;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            double t = M[a * 6] * r[0];
-#pragma unroll
-            for (int b = 1; b < 6; ++b) t += M[a * 6 + b] * r[b];
-            z[a] = t;
-        }
+        if constexpr (kJacobi) pg_mv6(d.Minv + 36 * (size_t)v, r, z);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             d.x[6 * (size_t)v + k] = 0.0;
             d.rr[6 * (size_t)v + k] = r[k];
-            d.z[6 * (size_t)v + k] = z[k];
-            d.p[6 * (size_t)v + k] = z[k];
+            if constexpr (kJacobi) {
+                d.z[6 * (size_t)v + k] = z[k];
+                d.p[6 * (size_t)v + k] = z[k];
+            }
             d.q[6 * (size_t)v + k] = 0.0;
-            rz += r[k] * z[k];
+            if constexpr (kJacobi) rz += r[k] * z[k];
         }
     }
-    const double t = pg_block_sum(rz, buf);
-    if (threadIdx.x == 0) d.part_rz[blockIdx.x] = t;
+    if constexpr (kJacobi) {
+        __shared__ double buf[kPgBlock];
+        const double t = pg_block_sum(rz, buf);
+        if (threadIdx.x == 0) d.part_rz[blockIdx.x] = t;
+    }
 }
 // one workgroup: r0^T z0 from the slots; a zero right-hand side ends a solve with a tolerance before its first iteration
 __global__ __launch_bounds__(256) void k_pg_pcg_begin(const PgDev d, double tol) {
@@ -332,7 +277,10 @@ __global__ __launch_bounds__(64) void k_pg_spmv_hub(const PgDev d, double lambda
     }
 }
 
-// K12e.  One lane per node.  Every workgroup reduces the partials of p^T q in slot order to the same alpha.
+// K12e.  One lane per node.  Every workgroup reduces the partials of p^T q in slot order to the same alpha.  kJacobi: z = Minv r and the
+// workgroup's partial of r^T z too; without it the preconditioner's apply that follows writes both.  Every lane reaches every barrier:
+// the stop word is the same for the whole launch, and no barrier follows the test of v.
+template <bool kJacobi>
 __global__ __launch_bounds__(256) void k_pg_update(const PgDev d, uint32_t it) {
     __shared__ double buf[kPgBlock];
     if (d.state->stop[it & 1u]) return;
@@ -350,18 +298,20 @@ __global__ __launch_bounds__(256) void k_pg_update(const PgDev d, uint32_t it) {
             r[k] = d.rr[o] - alpha * d.q[o];
             d.rr[o] = r[k];
         }
-        const double* __restrict__ M = d.Minv + 36 * (size_t)v;
+        if constexpr (kJacobi) {
+            const double* __restrict__ M = d.Minv + 36 * (size_t)v;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            double t = M[a * 6] * r[0];
-#pragma unroll
-            for (int b = 1; b < 6; ++b) t += M[a * 6 + b] * r[b];
-            d.z[6 * (size_t)v + a] = t;
-            rz += r[a] * t;
+            for (int a = 0; a < 6; ++a) { // a row at a time: the whole block is never held
+                const double t = pg_dot6(M + a * 6, r);
+                d.z[6 * (size_t)v + a] = t;
+                rz += r[a] * t;
+            }
         }
     }
-    const double t = pg_block_sum(rz, buf);
-    if (threadIdx.x == 0) d.part_rz[blockIdx.x] = t;
+    if constexpr (kJacobi) {
+        const double t = pg_block_sum(rz, buf);
+        if (threadIdx.x == 0) d.part_rz[blockIdx.x] = t;
+    }
 }
 
 // K12f.  One lane per node.  beta and the stop test from the partials of r^T z; the first workgroup writes the next iteration's state
@@ -427,24 +377,12 @@ __global__ __launch_bounds__(256) void k_pg_cost(const PgDev d, const double* __
     double s = 0.0, rho = 0.0, out = 0.0;
     if (e < d.E) {
         double Pi[12], Pj[12], PZ[12], r[6];
-        const double* __restrict__ pi = poses + 12 * (size_t)d.ei[e];
-        const double* __restrict__ pj = poses + 12 * (size_t)d.ej[e];
-        const double* __restrict__ pz = d.Z + 12 * (size_t)e;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            Pi[k] = pi[k];
-            Pj[k] = pj[k];
-            PZ[k] = pz[k];
-        }
+        pg_load_edge_poses(d, poses, e, Pi, Pj, PZ);
         pg_residual(Pi, Pj, PZ, r);
         const double* __restrict__ om = d.info + 36 * (size_t)e;
-#pragma unroll
-        for (int row = 0; row < 6; ++row) {
-            double q = om[row * 6] * r[0];
-#pragma unroll
-            for (int k = 1; k < 6; ++k) q += om[row * 6 + k] * r[k];
-            s = row == 0 ? r[0] * q : s + r[row] * q;
-        }
+        double Or[6];
+        pg_mv6(om, r, Or);
+        s = pg_dot6(r, Or);
         rho = pg_huber_cost(s, huber_k);
         out = pg_huber_weight(s, huber_k) < 1.0 ? 1.0 : 0.0;
     }
@@ -484,8 +422,7 @@ __global__ __launch_bounds__(256) void k_pg_finish(const PgDev d, uint32_t n_cos
 
 void launch_pg_linearize(hipStream_t s, const PgDev& d, const double* poses, double huber_k) {
     if (!d.E) return;
-    const uint32_t nb = (uint32_t)(((size_t)d.E * kPgLanesPerEdge + 255) / 256);
-    hipLaunchKernelGGL(k_pg_linearize, dim3(nb), dim3(256), 0, s, d, poses, huber_k);
+    hipLaunchKernelGGL(k_pg_linearize, dim3(pg_edge_group_blocks(d.E)), dim3(256), 0, s, d, poses, huber_k);
 }
 
 void launch_pg_nodes(hipStream_t s, const PgDev& d, double lambda, int sum) {
@@ -493,26 +430,29 @@ void launch_pg_nodes(hipStream_t s, const PgDev& d, double lambda, int sum) {
     hipLaunchKernelGGL(k_pg_nodes, dim3((d.N + 3) / 4), dim3(256), 0, s, d, lambda, sum);
 }
 
-void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, double tol) {
+// chain: null for block Jacobi.  A preconditioner's apply comes where the <true> kernels form z themselves: after the first residual
+// (first: it writes p = z too) and after every update (gated by the stop word, as every launch of an iteration is).
+void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev* chain, double tol) {
     if (!d.N) return;
-    hipLaunchKernelGGL(k_pg_pcg_init, dim3(pg_blocks(d.N)), dim3(256), 0, s, d);
+    if (chain) {
+        hipLaunchKernelGGL(k_pg_pcg_init<false>, dim3(pg_blocks(d.N)), dim3(256), 0, s, d);
+        launch_pgc_apply(s, d, *chain, 0u, 0, 1);
+    } else {
+        hipLaunchKernelGGL(k_pg_pcg_init<true>, dim3(pg_blocks(d.N)), dim3(256), 0, s, d);
+    }
     hipLaunchKernelGGL(k_pg_pcg_begin, dim3(1), dim3(256), 0, s, d, tol);
 }
 
-void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, double lambda, double tol, uint32_t it) {
+void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev* chain, double lambda, double tol, uint32_t it) {
     if (!d.N) return;
     hipLaunchKernelGGL(k_pg_spmv, dim3((d.N + kPgNodesPerBlock - 1) / kPgNodesPerBlock), dim3(256), 0, s, d, lambda, it);
     if (d.n_hubs) hipLaunchKernelGGL(k_pg_spmv_hub, dim3(d.n_hubs), dim3(64), 0, s, d, lambda, it);
-    hipLaunchKernelGGL(k_pg_update, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, it);
-    hipLaunchKernelGGL(k_pg_direction, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, tol, it);
-}
-
-void launch_pg_pcg_state(hipStream_t s, const PgDev& d, double tol) { hipLaunchKernelGGL(k_pg_pcg_begin, dim3(1), dim3(256), 0, s, d, tol); }
-void launch_pg_spmv(hipStream_t s, const PgDev& d, double lambda, uint32_t it) {
-    hipLaunchKernelGGL(k_pg_spmv, dim3((d.N + kPgNodesPerBlock - 1) / kPgNodesPerBlock), dim3(256), 0, s, d, lambda, it);
-    if (d.n_hubs) hipLaunchKernelGGL(k_pg_spmv_hub, dim3(d.n_hubs), dim3(64), 0, s, d, lambda, it);
-}
-void launch_pg_direction(hipStream_t s, const PgDev& d, double tol, uint32_t it) {
+    if (chain) {
+        hipLaunchKernelGGL(k_pg_update<false>, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, it);
+        launch_pgc_apply(s, d, *chain, it, 1, 0);
+    } else {
+        hipLaunchKernelGGL(k_pg_update<true>, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, it);
+    }
     hipLaunchKernelGGL(k_pg_direction, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, tol, it);
 }
 

@@ -99,7 +99,7 @@ void carve(elm_posegraph* pg, Carver& c) {
     pg->d_info = c.take<double>(36 * Ec);
     pg->d_inc_start = c.take<uint32_t>(Nc + 1);
     pg->d_inc = c.take<uint32_t>(2 * Ec);
-    pg->d_hubs = c.take<uint32_t>(2 * Ec / (kPgHubDegree + 1) + 1);
+    pg->d_hubs = c.take<uint32_t>(pg_max_hubs(Ec));
     d.r = c.take<double>(6 * Ec);
     d.A = c.take<double>(36 * Ec);
     d.B = c.take<double>(36 * Ec);
@@ -119,7 +119,7 @@ void carve(elm_posegraph* pg, Carver& c) {
     d.z = c.take<double>(6 * Nc);
     d.p = c.take<double>(6 * Nc);
     d.q = c.take<double>(6 * Nc);
-    d.part_pq = c.take<double>(pg_pq_slots((uint32_t)Nc, (uint32_t)(2 * Ec / (kPgHubDegree + 1) + 1)));
+    d.part_pq = c.take<double>(pg_pq_slots((uint32_t)Nc, (uint32_t)pg_max_hubs(Ec)));
     d.part_rz = c.take<double>(pg_blocks((uint32_t)Nc));
     d.part_cost = c.take<double>(3 * (size_t)pg_blocks((uint32_t)Ec));
     d.part_max = c.take<double>(pg_blocks((uint32_t)Nc));
@@ -151,8 +151,7 @@ void carve(elm_posegraph* pg, Carver& c) {
     k.ce = pg->d_ce;
 }
 
-int create_impl(elm_ctx* ctx, uint32_t n_cap, uint32_t e_cap, elm_posegraph** out) {
-    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
+int create_impl(elm_ctx* ctx, hipStream_t st, uint32_t n_cap, uint32_t e_cap, elm_posegraph** out) {
     elm_posegraph* pg = new elm_posegraph();
     pg->ctx = ctx;
     pg->ctx_id = ctx->id;
@@ -162,7 +161,6 @@ int create_impl(elm_ctx* ctx, uint32_t n_cap, uint32_t e_cap, elm_posegraph** ou
     carve(pg, size);
     // zeroed on the context's stream and joined: a memset on the null stream may still be running when the first upload on the
     // context's (non-blocking) stream lands, and would then wipe it
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     hipError_t e = hipMalloc((void**)&pg->blob, size.off);
     if (e == hipSuccess) e = hipMemsetAsync(pg->blob, 0, size.off, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -230,6 +228,16 @@ hipError_t upload_csr(elm_posegraph* pg, hipStream_t st, std::vector<uint32_t>& 
     return e;
 }
 
+// The device work of an entry point: the context's device current, body(stream) on the context's stream, a failed host allocation
+// anywhere in it turned into ELM_ERR_ALLOC.
+template <class Body>
+int on_stream(elm_ctx* ctx, const char* what, Body body) {
+    return guard_alloc(ctx, what, [&]() -> int {
+        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
+        return body((hipStream_t)elm_ctx_stream(ctx));
+    });
+}
+
 const PgDev& dev_view(elm_posegraph* pg) {
     pg->dev.N = pg->N;
     pg->dev.E = pg->E;
@@ -237,12 +245,14 @@ const PgDev& dev_view(elm_posegraph* pg) {
     return pg->dev;
 }
 
-bool chain(const elm_posegraph* pg) { return pg->precond == ELM_PG_PRECOND_CHAIN; }
+// the preconditioner seam of the launchers: the chain's view, or null for block Jacobi
+const PgcDev* chain(const elm_posegraph* pg) { return pg->precond == ELM_PG_PRECOND_CHAIN ? &pg->chain : nullptr; }
 
-// queues the damped diagonal blocks and their inverses at lambda and, for the chain preconditioner of a solve, its factor
-void launch_damping(elm_posegraph* pg, hipStream_t st, const PgDev& d, double lambda, int sum, bool for_solve) {
+// queues the damped diagonal blocks and their inverses at lambda and, for the conjugate gradients to follow with a chain, its factor
+// (c: chain(pg) before a solve, null where none follows)
+void launch_damping(hipStream_t st, const PgDev& d, const PgcDev* c, double lambda, int sum) {
     launch_pg_nodes(st, d, lambda, sum);
-    if (for_solve && chain(pg)) launch_pgc_factor(st, d, pg->chain, lambda);
+    if (c) launch_pgc_factor(st, d, *c, lambda);
 }
 
 // the incidence lists on the device are those of the current edge set
@@ -262,41 +272,40 @@ hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, do
     const PgDev& d = dev_view(pg);
     return launched([&] {
         launch_pg_linearize(st, d, pg->poses, huber_k);
-        launch_damping(pg, st, d, lambda, 1, for_solve);
+        launch_damping(st, d, for_solve ? chain(pg) : nullptr, lambda, 1);
     });
 }
 
-// The conjugate gradients on the current linearization and damping (launch_damping has run with this lambda): check_every iterations are
-// queued, then the state comes down once.
-int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, double tol, int max_it, int check_every, PgState& state, const char* what) {
+// what a solve reports: the public stats records and the two stages of the initialization take their fields from it
+struct PcgStats {
+    int32_t iterations = 0, converged = 0;
+    double rel_residual = 0.0;
+};
+
+// The conjugate gradients on the current linearization and damping (launch_damping has run with this lambda and chain(pg)):
+// check_every iterations are queued, then the state comes down once.
+int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, double tol, int max_it, int check_every, PcgStats& stats, const char* what) {
     const PgDev& d = dev_view(pg);
-    memset(&state, 0, sizeof(state));
+    stats = PcgStats{};
     if (!pg->N) return ELM_OK;
-    const bool ch = chain(pg);
-    const PgcDev& c = pg->chain;
-    hipError_t e = launched([&] {
-        if (ch) launch_pgc_pcg_begin(st, d, c, tol);
-        else launch_pg_pcg_begin(st, d, tol);
-    });
+    const PgcDev* c = chain(pg);
+    PgState state{};
+    hipError_t e = launched([&] { launch_pg_pcg_begin(st, d, c, tol); });
     uint32_t it = 0;
     while (e == hipSuccess) {
         const uint32_t upto = (uint32_t)std::min<int64_t>((int64_t)it + check_every, max_it);
         e = launched([&] {
-            for (; it < upto; ++it) {
-                if (ch) launch_pgc_pcg_iteration(st, d, c, lambda, tol, it);
-                else launch_pg_pcg_iteration(st, d, lambda, tol, it);
-            }
+            for (; it < upto; ++it) launch_pg_pcg_iteration(st, d, c, lambda, tol, it);
         });
         if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(PgState), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess || state.stop[it & 1u] || it >= (uint32_t)max_it) break;
     }
-    return e == hipSuccess ? (int)ELM_OK : dev_error(ctx, what, e);
-}
-
-double rel_residual(const PgState& s, uint32_t N) {
-    if (!N || !(s.rz0 > 0.0)) return 0.0;
-    return sqrt(s.rz[s.iters & 1u]) / sqrt(s.rz0);
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    stats.iterations = (int32_t)state.iters;
+    stats.converged = (int32_t)state.converged;
+    stats.rel_residual = state.rz0 > 0.0 ? sqrt(state.rz[state.iters & 1u]) / sqrt(state.rz0) : 0.0;
+    return ELM_OK;
 }
 
 // the cost record at `poses` (and the largest |x| of the retraction queued before it)
@@ -307,10 +316,9 @@ int cost_at(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const double* poses
     return join(ctx, st, e, what);
 }
 
-int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c, elm_posegraph_result* res, elm_posegraph_trace* trace, int trace_cap) {
+int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_config& c, elm_posegraph_result* res, elm_posegraph_trace* trace,
+                  int trace_cap) {
     const char* what = "elm_posegraph_optimize";
-    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     elm_posegraph_result R{};
     double lambda = c.lambda_init;
     pg->lin_valid = false;
@@ -325,7 +333,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
     R.lambda_final = lambda;
     R.stop_reason = F == 0.0 ? ELM_PG_STOP_COST_ZERO : ELM_PG_STOP_MAX_ITERATIONS;
     while (R.stop_reason == ELM_PG_STOP_MAX_ITERATIONS && R.solves < c.max_iterations) {
-        PgState s{};
+        PcgStats s;
         rc = run_pcg(ctx, pg, st, lambda, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
         if (rc != ELM_OK) return rc;
         const PgDev& d = dev_view(pg);
@@ -336,7 +344,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
         const double F_new = o.cost, used = lambda;
         const bool accept = F_new < F;
         ++R.solves;
-        R.pcg_iterations_total += s.iters;
+        R.pcg_iterations_total += s.iterations;
         bool stop = false;
         if (accept) {
             ++R.accepted;
@@ -360,7 +368,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
             else if (lambda >= c.lambda_max) R.stop_reason = ELM_PG_STOP_LAMBDA_MAX, stop = true;
             else {
                 lambda = std::min(lambda * c.lambda_up, c.lambda_max);
-                e = launched([&] { launch_damping(pg, st, d, lambda, 0, true); }); // (the chain factor is redone with it)
+                e = launched([&] { launch_damping(st, d, chain(pg), lambda, 0); }); // (the chain factor is redone with it)
                 if (e != hipSuccess) return dev_error(ctx, what, e);
             }
         }
@@ -369,7 +377,7 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_config& c
             t.cost = F_new;
             t.lambda = used;
             t.accepted = accept ? 1 : 0;
-            t.pcg_iterations = (int32_t)s.iters;
+            t.pcg_iterations = s.iterations;
         }
         if (stop) break;
     }
@@ -416,11 +424,21 @@ std::string init_refusal(const elm_posegraph* pg, int stages) {
     return "";
 }
 
-int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_config& c, elm_posegraph_init_result* res, double* rows_out,
+// One stage of the initialization: its edge terms at `at`, the undamped node sums (with the chain factor), the conjugate gradients.
+int init_stage(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_init_config& c,
+               void (*launch_terms)(hipStream_t, const PgDev&, const double*), const double* at, PcgStats& s, const char* what) {
+    const PgDev& d = dev_view(pg);
+    hipError_t e = launched([&] {
+        launch_terms(st, d, at);
+        launch_damping(st, d, chain(pg), 0.0, 1);
+    });
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    return run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+}
+
+int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_init_config& c, elm_posegraph_init_result* res, double* rows_out,
                     double* v_out) {
     const char* what = "elm_posegraph_initialize";
-    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     const size_t N = pg->N;
     const bool rot = (c.stages & ELM_PG_INIT_ROT) != 0, trans = (c.stages & ELM_PG_INIT_TRANS) != 0;
     elm_posegraph_init_result R{};
@@ -436,18 +454,13 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_co
     pg->lin_valid = false;
     const PgDev& d = dev_view(pg);
     double* const rows = d.q; // [N][6]: the conjugate gradients' q is free between two solves
+    PcgStats s;
     if (rot) {
-        e = launched([&] {
-            launch_pgi_rot_terms(st, d, pg->poses);
-            launch_damping(pg, st, d, 0.0, 1, true);
-        });
-        if (e != hipSuccess) return dev_error(ctx, what, e);
-        PgState s{};
-        rc = run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+        rc = init_stage(ctx, pg, st, c, launch_pgi_rot_terms, pg->poses, s, what);
         if (rc != ELM_OK) return rc;
-        R.rot_iterations = (int32_t)s.iters;
-        R.rot_converged = (int32_t)s.converged;
-        R.rot_rel_residual = rel_residual(s, pg->N);
+        R.rot_iterations = s.iterations;
+        R.rot_converged = s.converged;
+        R.rot_rel_residual = s.rel_residual;
         const uint32_t nb = pg_blocks(pg->N);
         std::vector<double> counts(nb);
         e = launched([&] { launch_pgi_rot_apply(st, d, pg->poses, pg->trial, rows, d.part_rz); });
@@ -470,17 +483,11 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_co
         }
     }
     if (trans) {
-        e = launched([&] {
-            launch_pgi_trans_terms(st, d, pg->trial);
-            launch_damping(pg, st, d, 0.0, 1, true);
-        });
-        if (e != hipSuccess) return dev_error(ctx, what, e);
-        PgState s{};
-        rc = run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
+        rc = init_stage(ctx, pg, st, c, launch_pgi_trans_terms, pg->trial, s, what);
         if (rc != ELM_OK) return rc;
-        R.trans_iterations = (int32_t)s.iters;
-        R.trans_converged = (int32_t)s.converged;
-        R.trans_rel_residual = rel_residual(s, pg->N);
+        R.trans_iterations = s.iterations;
+        R.trans_converged = s.converged;
+        R.trans_rel_residual = s.rel_residual;
         std::vector<double> host(v_out ? 6 * N : 0); // the solution [N][6], of which v_out takes the upper three per node
         e = launched([&] { launch_pgi_trans_apply(st, d, pg->trial); });
         if (e == hipSuccess && v_out) e = hipMemcpyAsync(host.data(), d.x, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -535,7 +542,7 @@ extern "C" int elm_posegraph_create(elm_ctx* ctx, int node_capacity, int edge_ca
     int rc = check_plain(ctx, "elm_posegraph_create");
     if (rc != ELM_OK) return rc;
     if (ctx->in_flight) return ELM_ERR_INVALID;
-    return guard_alloc(ctx, "elm_posegraph_create", [&] { return create_impl(ctx, (uint32_t)node_capacity, (uint32_t)edge_capacity, out); });
+    return on_stream(ctx, "elm_posegraph_create", [&](hipStream_t st) { return create_impl(ctx, st, (uint32_t)node_capacity, (uint32_t)edge_capacity, out); });
 }
 
 extern "C" void elm_posegraph_destroy(elm_posegraph* pg) { pg_free(pg); }
@@ -587,15 +594,13 @@ extern "C" int elm_posegraph_add_nodes(elm_ctx* ctx, elm_posegraph* pg, const do
     if (rc != ELM_OK) return rc;
     if (n > (size_t)(pg->n_cap - pg->N)) return refuse_full(ctx, what, "nodes", pg->N, n, pg->n_cap);
     if (!n) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         std::vector<double> rows(12 * n);
         for (size_t k = 0; k < n; ++k) pose_rows12(poses16 + 16 * k, &rows[12 * k]);
         std::vector<uint8_t> fx(n, 0);
         if (fixed)
             for (size_t k = 0; k < n; ++k) fx[k] = fixed[k] ? 1 : 0;
         pg->fixed.reserve((size_t)pg->N + n);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         hipError_t e = hipMemcpyAsync(pg->poses + 12 * (size_t)pg->N, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pg->d_fixed + pg->N, fx.data(), n, hipMemcpyHostToDevice, st);
         int rc = join(ctx, st, e, what);
@@ -616,11 +621,9 @@ extern "C" int elm_posegraph_set_poses(elm_ctx* ctx, elm_posegraph* pg, size_t f
     if (rc != ELM_OK) return rc;
     if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
     if (!count) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         std::vector<double> rows(12 * count);
         for (size_t k = 0; k < count; ++k) pose_rows12(poses16 + 16 * k, &rows[12 * k]);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         pg->lin_valid = false;
         return join(ctx, st, hipMemcpyAsync(pg->poses + 12 * first, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st), what);
     });
@@ -633,10 +636,8 @@ extern "C" int elm_posegraph_get_poses(elm_ctx* ctx, const elm_posegraph* pg, si
     if (rc != ELM_OK) return rc;
     if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
     if (!count) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         std::vector<double> rows(12 * count);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         int rc = join(ctx, st, hipMemcpyAsync(rows.data(), pg->poses + 12 * first, rows.size() * sizeof(double), hipMemcpyDeviceToHost, st), what);
         if (rc != ELM_OK) return rc;
         for (size_t k = 0; k < count; ++k) rows12_to_pose16(&rows[12 * k], poses16 + 16 * k);
@@ -651,11 +652,9 @@ extern "C" int elm_posegraph_set_fixed(elm_ctx* ctx, elm_posegraph* pg, size_t f
     if (rc != ELM_OK) return rc;
     if (!range_ok(first, count, pg->N)) return ELM_ERR_INVALID;
     if (!count) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         std::vector<uint8_t> fx(count);
         for (size_t k = 0; k < count; ++k) fx[k] = fixed[k] ? 1 : 0;
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         int rc = join(ctx, st, hipMemcpyAsync(pg->d_fixed + first, fx.data(), count, hipMemcpyHostToDevice, st), what);
         if (rc != ELM_OK) return rc;
         std::copy(fx.begin(), fx.end(), pg->fixed.begin() + (long)first);
@@ -682,15 +681,13 @@ extern "C" int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const in
         if ((uint32_t)i[k] >= pg->N || (uint32_t)j[k] >= pg->N) return ELM_ERR_INVALID;
     if (n > (size_t)(pg->e_cap - pg->E)) return refuse_full(ctx, what, "edges", pg->E, n, pg->e_cap);
     if (!n) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         std::vector<double> rows(12 * n);
         for (size_t k = 0; k < n; ++k) pose_rows12(Z16 + 16 * k, &rows[12 * k]);
         pg->ei.reserve((size_t)pg->E + n);
         pg->ej.reserve((size_t)pg->E + n);
         pg->wr.reserve((size_t)pg->E + n);
         pg->wt.reserve((size_t)pg->E + n);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         const size_t E0 = pg->E;
         hipError_t e = hipMemcpyAsync(pg->d_ei + E0, i, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pg->d_ej + E0, j, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -717,9 +714,7 @@ extern "C" int elm_posegraph_linearize(elm_ctx* ctx, elm_posegraph* pg, double h
     if (!ctx || !pg || !fin_ge0(huber_k)) return ELM_ERR_INVALID;
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    return on_stream(ctx, what, [&](hipStream_t st) {
         pg->lin_valid = false;
         hipError_t e = queue_linearize(pg, st, huber_k, 0.0, false);
         if (e != hipSuccess) return dev_error(ctx, what, e);
@@ -743,9 +738,7 @@ extern "C" int elm_posegraph_download_linearization(elm_ctx* ctx, const elm_pose
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
     if (!pg->lin_valid) return ELM_ERR_INVALID;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const size_t E = pg->E, N = pg->N, S = pg->e_cap;
         const PgDev& d = pg->dev;
         // component-major on the device, [E][components] for the caller: each component row comes down, then the transpose
@@ -780,13 +773,11 @@ extern "C" int elm_posegraph_solve(elm_ctx* ctx, elm_posegraph* pg, double lambd
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
     if (!pg->lin_valid) return ELM_ERR_INVALID;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const PgDev& d = dev_view(pg);
-        hipError_t e = launched([&] { launch_damping(pg, st, d, lambda, 0, true); });
+        hipError_t e = launched([&] { launch_damping(st, d, chain(pg), lambda, 0); });
         if (e != hipSuccess) return dev_error(ctx, what, e);
-        PgState s{};
+        PcgStats s;
         int rc = run_pcg(ctx, pg, st, lambda, pcg_rel_tol, pcg_max_iterations, kPgDefaultCheckEvery, s, what);
         if (rc != ELM_OK) return rc;
         if (delta && pg->N) {
@@ -794,9 +785,9 @@ extern "C" int elm_posegraph_solve(elm_ctx* ctx, elm_posegraph* pg, double lambd
             if (rc != ELM_OK) return rc;
         }
         if (stats) {
-            stats->iterations = (int32_t)s.iters;
-            stats->converged = (int32_t)s.converged;
-            stats->rel_residual = rel_residual(s, pg->N);
+            stats->iterations = s.iterations;
+            stats->converged = s.converged;
+            stats->rel_residual = s.rel_residual;
         }
         return (int)ELM_OK;
     });
@@ -812,7 +803,7 @@ extern "C" int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm
         elm_host::ctx_set_error(ctx, std::string(what) + ": no fixed node (the gauge is free)");
         return ELM_ERR_INVALID;
     }
-    return guard_alloc(ctx, what, [&] { return optimize_impl(ctx, pg, *cfg, result, trace_cap > 0 ? trace : nullptr, trace_cap); });
+    return on_stream(ctx, what, [&](hipStream_t st) { return optimize_impl(ctx, pg, st, *cfg, result, trace_cap > 0 ? trace : nullptr, trace_cap); });
 }
 
 extern "C" void elm_posegraph_init_config_default(elm_posegraph_init_config* c) {
@@ -830,12 +821,12 @@ extern "C" int elm_posegraph_initialize(elm_ctx* ctx, elm_posegraph* pg, const e
     if (!ctx || !pg || !result || !init_config_ok(cfg)) return ELM_ERR_INVALID;
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
-    return guard_alloc(ctx, what, [&]() -> int { // the check's vectors and texts are allocated inside the guard too
+    return on_stream(ctx, what, [&](hipStream_t st) -> int { // the check's vectors and texts are allocated inside the guard too
         const std::string refusal = init_refusal(pg, cfg->stages);
         if (!refusal.empty()) {
             elm_host::ctx_set_error(ctx, std::string(what) + ": " + refusal);
             return ELM_ERR_INVALID;
         }
-        return initialize_impl(ctx, pg, *cfg, result, rows_out, v_out);
+        return initialize_impl(ctx, pg, st, *cfg, result, rows_out, v_out);
     });
 }

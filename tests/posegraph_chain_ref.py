@@ -81,34 +81,8 @@ def chain_solver_cholesky(g, lin, lam, M=None):
 
 
 def pcg_chain(g, lin, lam, rel_tol, max_it, sparse=None, solve=None):
-    """-> (delta [N, 6], iterations, rel_residual, converged): ref.pcg line for line but for z = M^-1 r (solve: chain_solver's, or the
-    given one)"""
-    a = lin["active"]
-    solve = chain_solver(g, lin, lam, sparse) if solve is None else solve
-    x = np.zeros((g.N, 6))
-    r = np.where(a[:, None], -lin["grad"], 0.0)
-    z = solve(r)
-    p = z.copy()
-    rz = rz0 = float(np.sum(r * z))
-    if rel_tol > 0.0 and not rz0 > 0.0:
-        return x, 0, 0.0, True
-    it, conv = 0, False
-    while it < max_it:
-        q = ref.spmv(g, lin, lam, p)
-        pq = float(np.sum(p * q))
-        alpha = rz / pq if pq != 0.0 else 0.0
-        x += alpha * p
-        r -= alpha * q
-        z = solve(r)
-        rz_new = float(np.sum(r * z))
-        beta = rz_new / rz if rz != 0.0 else 0.0
-        p = z + beta * p
-        rz = rz_new
-        it += 1
-        if rel_tol > 0.0 and np.sqrt(rz) <= rel_tol * np.sqrt(rz0):
-            conv = True
-            break
-    return x, it, (np.sqrt(rz) / np.sqrt(rz0) if rz0 > 0.0 else 0.0), conv
+    """-> (delta [N, 6], iterations, rel_residual, converged): ref.pcg with z = M^-1 r (solve: chain_solver's, or the given one)"""
+    return ref.pcg(g, lin, lam, rel_tol, max_it, precond=chain_solver(g, lin, lam, sparse) if solve is None else solve)
 
 
 def true_rel_residual(g, lin, lam, delta):
@@ -134,9 +108,4 @@ def backward_error(g, lin, lam, z, r, M=None):
 
 def optimize(g, **kw):
     """ref.optimize with pcg_chain in the place of ref.pcg"""
-    keep = ref.pcg
-    ref.pcg = pcg_chain
-    try:
-        return ref.optimize(g, **kw)
-    finally:
-        ref.pcg = keep
+    return ref.optimize(g, pcg=pcg_chain, **kw)

@@ -208,15 +208,23 @@ def spmv(g, lin, lam, p):
     return q
 
 
-def pcg(g, lin, lam, rel_tol, max_it):
-    """-> (delta [N, 6], iterations, rel_residual, converged): the contract's preconditioned conjugate gradients"""
+def block_jacobi(g, lin, lam):
+    """-> precond(r [N, 6]) = M^-1 r for the contract's default M: the damped diagonal blocks of the active nodes"""
     a = lin["active"]
     Minv = np.zeros((g.N, 6, 6))
     if a.any():
         Minv[a] = np.linalg.inv(damped(lin["diag"], lam)[a])
+    return lambda r: np.einsum("nab,nb->na", Minv, r)
+
+
+def pcg(g, lin, lam, rel_tol, max_it, precond=None):
+    """-> (delta [N, 6], iterations, rel_residual, converged): the contract's preconditioned conjugate gradients.  precond: r -> z = M^-1 r
+    (block_jacobi's by default)"""
+    a = lin["active"]
+    precond = block_jacobi(g, lin, lam) if precond is None else precond
     x = np.zeros((g.N, 6))
     r = np.where(a[:, None], -lin["grad"], 0.0)
-    z = np.einsum("nab,nb->na", Minv, r)
+    z = precond(r)
     p = z.copy()
     rz = rz0 = float(np.sum(r * z))
     if rel_tol > 0.0 and not rz0 > 0.0:
@@ -228,7 +236,7 @@ def pcg(g, lin, lam, rel_tol, max_it):
         alpha = rz / pq if pq != 0.0 else 0.0
         x += alpha * p
         r -= alpha * q
-        z = np.einsum("nab,nb->na", Minv, r)
+        z = precond(r)
         rz_new = float(np.sum(r * z))
         beta = rz_new / rz if rz != 0.0 else 0.0
         p = z + beta * p
@@ -271,8 +279,8 @@ DEFAULTS = dict(max_iterations=20, lambda_init=1e-4, lambda_up=10.0, lambda_down
                 step_tol=1e-10, pcg_max_iterations=2000, pcg_rel_tol=1e-8, pcg_check_every=32, huber_k=0.0)
 
 
-def optimize(g, **kw):
-    """The contract's Levenberg-Marquardt -> (poses, result dict with trace)"""
+def optimize(g, pcg=pcg, **kw):
+    """The contract's Levenberg-Marquardt -> (poses, result dict with trace).  pcg: the conjugate gradients of its solves"""
     c = dict(DEFAULTS)
     c.update(kw)
     poses = g.poses.copy()

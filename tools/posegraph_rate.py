@@ -12,7 +12,7 @@ reason, costs, total ms, and the largest pose error against the truth).
 preconditioner's go under "chain" of the same N, with the factor's ms and the apply's ms per iteration.  Those two are wall clock too:
 a solve without a stop test is timed at 32 and at 288 iterations under either preconditioner; the difference over 256 is the ms per
 iteration, the rest of the 32-iteration call its fixed part; the apply is the chain's ms per iteration less block Jacobi's (whose own
-z = M^-1 r is a 6 x 6 product inside k_pg_update), the factor the chain's fixed part less block Jacobi's and less one apply (the z0
+z = M^-1 r is a 6 x 6 product inside k_pg_update<true>), the factor the chain's fixed part less block Jacobi's and less one apply (the z0
 of the start).
 The linear initialization (elm_posegraph_initialize, rotations first and then translations) has rows of its own, per N and
 preconditioner, in a second JSON line written to profiles/posegraph_init_rate.json: from the same drifted start one Initialize with its
