@@ -342,46 +342,7 @@ PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
-# every symbol include/elimaloc_hip.h declares (checked by the CPU test-suite)
-EXPORTS = [
-    "elm_reg_config_default", "elm_ctx_create", "elm_ctx_create_multi", "elm_ctx_group_info", "elm_register_shard", "elm_ctx_destroy", "elm_last_error", "elm_strerror",
-    "elm_ctx_synchronize", "elm_ctx_stream", "elm_ctx_set_profiling", "elm_ctx_set_work_counters", "elm_ctx_get_profile", "elm_map_build", "elm_map_destroy", "elm_map_cal_voxel_cov_all",
-    "elm_map_cal_point_cov_all", "elm_map_build_neighbourhoods", "elm_map_get_info", "elm_map_empty", "elm_map_download_points",
-    "elm_map_download_voxels", "elm_map_find_ground_height", "elm_map_get_correspondences", "elm_align_clouds_local", "elm_scan_upload", "elm_scan_destroy",
-    "elm_scan_size", "elm_scan_download", "elm_register", "elm_format_register_log", "elm_register_batch", "elm_register_stream", "elm_register_stream_host", "elm_host_alloc", "elm_host_free", "elm_ctx_measure_h2d", "elm_register_batch_enqueue",
-    "elm_register_batch_finish", "elm_deskew", "elm_deskew_downsample", "elm_deskew_prepare", "elm_comm_get_unique_id", "elm_comm_init",
-    "elm_comm_destroy", "elm_comm_info", "elm_comm_set_hook", "elm_filter_points_by_distance", "elm_voxel_downsample",
-    "elm_get_interpolated_pose", "elm_shape_odom_covariance", "elm_cal_frame_point_cov",
-    "elm_ekf_config_default", "elm_ekf_create", "elm_ekf_destroy", "elm_ekf_predict_imu", "elm_ekf_predict", "elm_ekf_update_can", "elm_gps_project", "elm_ekf_update_navsatfix",
-    "elm_ekf_update_pose", "elm_ekf_update_pcm_odom", "elm_ekf_get_state", "elm_ekf_publish",
-    "elm_ini_load", "elm_ini_destroy", "elm_ini_get_string", "elm_ini_get_int", "elm_ini_get_bool", "elm_ini_get_double",
-    "elm_ini_get_array", "elm_pcm_node_config_default", "elm_load_pcm_config", "elm_load_ekf_config", "elm_pcd_load_xyz",
-    "elm_free", "elm_scan_from_cloud", "elm_pcm_callback_point_cloud",
-    "elm_reloc_config_default", "elm_reloc_make_hypotheses", "elm_map_score_poses", "elm_relocalize",
-    "elm_reloc_global_config_default", "elm_map_ground_heights", "elm_reloc_global_hypotheses", "elm_relocalize_global",
-    "elm_freespace_config_default", "elm_map_fine_cells", "elm_map_check_free_space",
-    "elm_raycast_config_default", "elm_map_raycast",
-    "elm_evidence_config_default", "elm_evidence_rule_default", "elm_evidence_create", "elm_evidence_destroy", "elm_evidence_reset",
-    "elm_evidence_accumulate", "elm_evidence_accumulate_batch", "elm_evidence_counts", "elm_evidence_stale_points",
-    "elm_growth_config_default", "elm_growth_rule_default", "elm_growth_create", "elm_growth_destroy", "elm_growth_reset",
-    "elm_growth_accumulate", "elm_growth_accumulate_batch", "elm_growth_cells", "elm_growth_appeared_points",
-    "elm_growth_object_rule_default", "elm_growth_find_objects", "elm_growth_objects", "elm_growth_cell_objects", "elm_growth_beam_objects",
-    "elm_map_build_device", "elm_map_build_device_stages", "elm_map_build_device_from",
-    "elm_odometry_config_default", "elm_odometry_create", "elm_odometry_destroy", "elm_odometry_reset", "elm_odometry_predict",
-    "elm_odometry_step_scan", "elm_odometry_map",
-    "elm_places_config_default", "elm_places_tables", "elm_places_create", "elm_places_destroy", "elm_places_reset", "elm_places_size",
-    "elm_places_describe", "elm_places_add", "elm_places_add_words", "elm_places_download", "elm_places_match_words", "elm_places_query",
-    "elm_map_set_index_build", "elm_map_index_build_stages", "elm_map_download_cell_grid",
-    "elm_posegraph_config_default", "elm_posegraph_create", "elm_posegraph_destroy", "elm_posegraph_reset", "elm_posegraph_size",
-    "elm_posegraph_add_nodes", "elm_posegraph_set_poses", "elm_posegraph_get_poses", "elm_posegraph_set_fixed", "elm_posegraph_add_edges",
-    "elm_posegraph_linearize", "elm_posegraph_download_linearization", "elm_posegraph_solve", "elm_posegraph_optimize",
-    "elm_posegraph_edge_terms",
-]
-# every symbol include/elimaloc_hip_posegraph_precond.h declares (the header elimaloc_hip.h includes for the pose graph's preconditioner)
-EXPORTS_PRECOND = ["elm_posegraph_set_preconditioner", "elm_posegraph_get_preconditioner"]
 PG_PRECOND = {0: "block_jacobi", 1: "chain"}
-# every symbol include/elimaloc_hip_posegraph_init.h declares (the header elimaloc_hip.h includes for the pose graph's linear initialization)
-EXPORTS_INIT = ["elm_posegraph_init_config_default", "elm_posegraph_initialize"]
 PG_INIT_ROT, PG_INIT_TRANS = 1, 2
 
 
@@ -433,11 +394,190 @@ class EgoStateC(C.Structure):
         "vx", "vy", "vz", "ax", "ay", "az", "x_cov_m", "y_cov_m", "z_cov_m", "roll_cov_rad", "pitch_cov_rad", "yaw_cov_rad")]
 
 
+def _sig(*argtypes, ret=C.c_int):
+    return ret, list(argtypes)
+
+
+P, i, d, f, szt = C.POINTER, C.c_int, C.c_double, C.c_float, C.c_size_t
+vp, cp, dp, fp, ip, szp = C.c_void_p, C.c_char_p, P(d), P(f), P(i), P(szt)
+u8p, u16p, u32p, u64p, i32p, i64p = P(C.c_uint8), P(C.c_uint16), P(C.c_uint32), P(C.c_uint64), P(C.c_int32), P(C.c_int64)
+pqc = P(PlacesQueryConfigC)
+
+# One table per header: name -> (restype, [argtypes]) of every function it declares.  lib() applies them; the CPU test-suite holds them
+# against the headers' prototypes.
+DECLS = {  # include/elimaloc_hip.h
+    "elm_reg_config_default": _sig(P(RegConfig), ret=None),
+    "elm_ctx_create": _sig(i, P(vp)),
+    "elm_ctx_create_multi": _sig(ip, i, P(vp)),
+    "elm_ctx_group_info": _sig(vp, ip, ip, ip, i),
+    "elm_register_shard": _sig(vp, vp, fp, szt, szt, dp, P(RegConfig), P(RegResult), P(IterTrace), i),
+    "elm_ctx_destroy": _sig(vp, ret=None),
+    "elm_last_error": _sig(vp, ret=cp),
+    "elm_strerror": _sig(i, ret=cp),
+    "elm_ctx_synchronize": _sig(vp),
+    "elm_ctx_stream": _sig(vp, ret=vp),
+    "elm_ctx_set_profiling": _sig(vp, i),
+    "elm_ctx_set_work_counters": _sig(vp, i),
+    "elm_ctx_get_profile": _sig(vp, P(Profile), i),
+    "elm_map_build": _sig(vp, fp, szt, d, i, P(vp)),
+    "elm_map_destroy": _sig(vp, ret=None),
+    "elm_map_cal_voxel_cov_all": _sig(vp),
+    "elm_map_cal_point_cov_all": _sig(vp, d),
+    "elm_map_build_neighbourhoods": _sig(vp),
+    "elm_map_get_info": _sig(vp, P(MapInfo)),
+    "elm_map_empty": _sig(vp),
+    "elm_map_download_points": _sig(vp, dp, dp, dp, szt),
+    "elm_map_download_voxels": _sig(vp, i32p, i32p, dp, dp, szt),
+    "elm_map_find_ground_height": _sig(vp, d, d, dp, ip),
+    "elm_map_get_correspondences": _sig(vp, vp, i, dp, szt, d, u32p, i32p, szt, szp),
+    "elm_align_clouds_local": _sig(vp, i, dp, dp, dp, dp, szt, dp, d, P(RegConfig), dp, dp, dp),
+    "elm_scan_upload": _sig(vp, fp, szt, szt, P(vp)),
+    "elm_scan_destroy": _sig(vp, ret=None),
+    "elm_scan_size": _sig(vp, ret=szt),
+    "elm_scan_download": _sig(vp, fp, szt),
+    "elm_register": _sig(vp, vp, fp, szt, dp, P(RegConfig), dp, ip, dp, dp, P(RegResult), P(IterTrace)),
+    "elm_format_register_log": _sig(P(RegConfig), P(RegResult), szt, P(IterTrace), dp, d, cp, szt, ret=szt),
+    "elm_register_batch": _sig(vp, vp, P(vp), i, dp, P(RegConfig), P(RegResult), P(IterTrace)),
+    "elm_register_stream": _sig(vp, vp, P(vp), i, dp, P(RegConfig), i, P(RegResult), P(IterTrace)),
+    "elm_register_stream_host": _sig(vp, vp, P(vp), u32p, i, dp, P(RegConfig), i, P(RegResult), P(IterTrace)),
+    "elm_host_alloc": _sig(szt, ret=vp),
+    "elm_host_free": _sig(vp, ret=None),
+    "elm_ctx_measure_h2d": _sig(vp, vp, szt, i, dp),
+    "elm_register_batch_enqueue": _sig(vp, vp, P(vp), i, dp, P(RegConfig), i),
+    "elm_register_batch_finish": _sig(vp, P(RegResult), P(IterTrace)),
+    "elm_deskew": _sig(vp, fp, fp, szt, P(DeskewTables), fp, ip),
+    "elm_deskew_downsample": _sig(vp, fp, fp, szt, P(DeskewTables), d, P(vp), ip),
+    "elm_deskew_prepare": _sig(dp, szt, dp, szt, d, f, f, i, i, dp, dp, dp, dp, szt, P(DeskewTables)),
+    "elm_comm_get_unique_id": _sig(vp),
+    "elm_comm_init": _sig(vp, i, i, vp),
+    "elm_comm_destroy": _sig(vp),
+    "elm_comm_info": _sig(vp, ip, ip),
+    "elm_comm_set_hook": _sig(vp, ALLREDUCE_FN, vp),
+    "elm_filter_points_by_distance": _sig(fp, fp, szt, d, fp, fp, szp),
+    "elm_voxel_downsample": _sig(fp, szt, d, i64p, szp),
+    "elm_get_interpolated_pose": _sig(dp, szt, d, fp, ip),
+    "elm_shape_odom_covariance": _sig(dp, dp, d, dp),
+    "elm_cal_frame_point_cov": _sig(dp, szt, d, d, d, dp),
+    "elm_ekf_config_default": _sig(P(EkfConfig), ret=None),
+    "elm_ekf_create": _sig(P(EkfConfig), P(vp)),
+    "elm_ekf_destroy": _sig(vp, ret=None),
+    "elm_ekf_predict_imu": _sig(vp, d, dp, dp, ip),
+    "elm_ekf_predict": _sig(vp, d, ip),
+    "elm_ekf_update_can": _sig(vp, d, dp, dp, ip),
+    "elm_gps_project": _sig(d, d, d, d, d, d, dp),
+    "elm_ekf_update_navsatfix": _sig(vp, d, d, d, d, dp, d, d, d, i, d, dp, ip),
+    "elm_ekf_update_pose": _sig(vp, d, dp, dp, dp, dp, i, ip),
+    "elm_ekf_update_pcm_odom": _sig(vp, d, dp, dp, dp, i, ip),
+    "elm_ekf_get_state": _sig(vp, P(EkfStateC)),
+    "elm_ekf_publish": _sig(vp, P(EgoStateC)),
+    "elm_ini_load": _sig(cp, P(vp)),
+    "elm_ini_destroy": _sig(vp, ret=None),
+    "elm_ini_get_string": _sig(vp, cp, cp, cp, szt),
+    "elm_ini_get_int": _sig(vp, cp, cp, ip),
+    "elm_ini_get_bool": _sig(vp, cp, cp, ip),
+    "elm_ini_get_double": _sig(vp, cp, cp, dp),
+    "elm_ini_get_array": _sig(vp, cp, cp, dp, szt, szp),
+    "elm_pcm_node_config_default": _sig(P(PcmNodeConfig), ret=None),
+    "elm_load_pcm_config": _sig(cp, cp, P(PcmNodeConfig), P(RegConfig)),
+    "elm_load_ekf_config": _sig(cp, P(EkfConfig)),
+    "elm_pcd_load_xyz": _sig(cp, P(fp), szp),
+    "elm_free": _sig(vp, ret=None),
+    "elm_scan_from_cloud": _sig(vp, szt, szt, P(CloudField), i, i, i, fp, fp, fp, szt, szp),
+    "elm_pcm_callback_point_cloud": _sig(vp, vp, P(PcmNodeConfig), P(RegConfig), fp, fp, szt, d, dp, szt, dp, szt, P(PcmScanOutput), ip),
+    "elm_reloc_config_default": _sig(P(RelocConfigC), ret=None),
+    "elm_reloc_make_hypotheses": _sig(dp, P(RelocConfigC), dp, szt, szp),
+    "elm_map_score_poses": _sig(vp, vp, vp, dp, i, P(RelocConfigC), u32p),
+    "elm_relocalize": _sig(vp, vp, fp, szt, dp, P(RelocConfigC), P(RegConfig), dp, P(RegResult), P(RelocCandidate), i, ip),
+    "elm_reloc_global_config_default": _sig(P(GlobalRelocConfigC), ret=None),
+    "elm_map_ground_heights": _sig(vp, vp, dp, szt, dp, i32p),
+    "elm_reloc_global_hypotheses": _sig(vp, vp, dp, P(GlobalRelocConfigC), dp, i32p, szt, szp),
+    "elm_relocalize_global": _sig(vp, vp, fp, szt, dp, P(GlobalRelocConfigC), P(RegConfig), dp, P(RegResult), P(RelocCandidate), i, ip,
+                                  P(GlobalRelocStats)),
+    "elm_freespace_config_default": _sig(P(FreeSpaceConfigC), ret=None),
+    "elm_map_fine_cells": _sig(vp, vp, i, i32p, szt, szp),
+    "elm_map_check_free_space": _sig(vp, vp, vp, dp, i, P(FreeSpaceConfigC), P(FreeSpaceStatsC), u16p),
+    "elm_raycast_config_default": _sig(P(RayCastConfigC), ret=None),
+    "elm_map_raycast": _sig(vp, vp, vp, dp, i, P(RayCastConfigC), P(RayCastStatsC), dp, dp, i32p, u8p),
+    "elm_evidence_config_default": _sig(P(EvidenceConfigC), ret=None),
+    "elm_evidence_rule_default": _sig(P(EvidenceRuleC), ret=None),
+    "elm_evidence_create": _sig(vp, vp, i, P(vp)),
+    "elm_evidence_destroy": _sig(vp, ret=None),
+    "elm_evidence_reset": _sig(vp, vp),
+    "elm_evidence_accumulate": _sig(vp, vp, vp, dp, P(EvidenceConfigC), P(EvidenceStatsC), u16p),
+    "elm_evidence_accumulate_batch": _sig(vp, vp, P(vp), dp, i, P(EvidenceConfigC), P(EvidenceStatsC)),
+    "elm_evidence_counts": _sig(vp, vp, u32p, u32p, szt, szp),
+    "elm_evidence_stale_points": _sig(vp, vp, P(EvidenceRuleC), u8p, szt, szp),
+    "elm_growth_config_default": _sig(P(GrowthConfigC), ret=None),
+    "elm_growth_rule_default": _sig(P(GrowthRuleC), ret=None),
+    "elm_growth_create": _sig(vp, vp, i, szt, P(vp)),
+    "elm_growth_destroy": _sig(vp, ret=None),
+    "elm_growth_reset": _sig(vp, vp),
+    "elm_growth_accumulate": _sig(vp, vp, vp, dp, P(GrowthConfigC), P(GrowthStatsC), u16p),
+    "elm_growth_accumulate_batch": _sig(vp, vp, P(vp), dp, i, P(GrowthConfigC), P(GrowthStatsC)),
+    "elm_growth_cells": _sig(vp, vp, i32p, u32p, u32p, u64p, szt, szp),
+    "elm_growth_appeared_points": _sig(vp, vp, P(GrowthRuleC), dp, szt, szp),
+    "elm_growth_object_rule_default": _sig(P(GrowthObjectRuleC), ret=None),
+    "elm_growth_find_objects": _sig(vp, vp, P(GrowthObjectRuleC), P(GrowthObjectStatsC)),
+    "elm_growth_objects": _sig(vp, vp, P(GrowthObjectC), szt, szp),
+    "elm_growth_cell_objects": _sig(vp, vp, i32p, szt, szp),
+    "elm_growth_beam_objects": _sig(vp, vp, vp, dp, P(GrowthConfigC), i32p),
+    "elm_map_build_device": _sig(vp, vp, u8p, fp, szt, d, i, P(vp)),
+    "elm_map_build_device_stages": _sig(vp, dp),
+    "elm_map_build_device_from": _sig(vp, P(BuildSourcesC), d, i, P(vp), P(BuildSourcesStatsC)),
+    "elm_odometry_config_default": _sig(P(OdometryConfigC), ret=None),
+    "elm_odometry_create": _sig(vp, P(OdometryConfigC), P(vp)),
+    "elm_odometry_destroy": _sig(vp, ret=None),
+    "elm_odometry_reset": _sig(vp),
+    "elm_odometry_predict": _sig(vp, dp),
+    "elm_odometry_step_scan": _sig(vp, vp, dp, P(OdometryStepC)),
+    "elm_odometry_map": _sig(vp, ret=vp),
+    "elm_places_config_default": _sig(P(PlacesConfigC), ret=None),
+    "elm_places_tables": _sig(P(PlacesConfigC), dp, dp, dp),
+    "elm_places_create": _sig(vp, P(PlacesConfigC), i, P(vp)),
+    "elm_places_destroy": _sig(vp, ret=None),
+    "elm_places_reset": _sig(vp, vp),
+    "elm_places_size": _sig(vp, vp, szp),
+    "elm_places_describe": _sig(vp, vp, P(vp), dp, i, u64p, P(PlacesStatsC)),
+    "elm_places_add": _sig(vp, vp, P(vp), dp, i64p, i, P(PlacesStatsC)),
+    "elm_places_add_words": _sig(vp, vp, u64p, i64p, szt),
+    "elm_places_download": _sig(vp, vp, szt, szt, u64p, i64p, u32p),
+    "elm_places_match_words": _sig(vp, vp, u64p, i, pqc, P(PlaceCandidateC), i32p, P(PlaceMatchC)),
+    "elm_places_query": _sig(vp, vp, P(vp), dp, i, pqc, P(PlaceCandidateC), i32p, P(PlaceMatchC), P(PlacesStatsC)),
+    "elm_map_set_index_build": _sig(vp, i),
+    "elm_map_index_build_stages": _sig(vp, dp),
+    "elm_map_download_cell_grid": _sig(vp, P(CellGridDesc), u32p, szt, fp, szt, u32p, szt, u32p, szt),
+    "elm_posegraph_config_default": _sig(P(PoseGraphConfigC), ret=None),
+    "elm_posegraph_create": _sig(vp, i, i, P(vp)),
+    "elm_posegraph_destroy": _sig(vp, ret=None),
+    "elm_posegraph_reset": _sig(vp, vp),
+    "elm_posegraph_size": _sig(vp, vp, szp, szp),
+    "elm_posegraph_add_nodes": _sig(vp, vp, dp, u8p, szt),
+    "elm_posegraph_set_poses": _sig(vp, vp, szt, szt, dp),
+    "elm_posegraph_get_poses": _sig(vp, vp, szt, szt, dp),
+    "elm_posegraph_set_fixed": _sig(vp, vp, szt, szt, u8p),
+    "elm_posegraph_add_edges": _sig(vp, vp, i32p, i32p, dp, dp, szt),
+    "elm_posegraph_linearize": _sig(vp, vp, d, P(PoseGraphLinearizeStatsC)),
+    "elm_posegraph_download_linearization": _sig(vp, vp, dp, dp, dp, dp, dp, dp, dp),
+    "elm_posegraph_solve": _sig(vp, vp, d, d, i, dp, P(PoseGraphSolveStatsC)),
+    "elm_posegraph_optimize": _sig(vp, vp, P(PoseGraphConfigC), P(PoseGraphResultC), P(PoseGraphTraceC), i),
+    "elm_posegraph_edge_terms": _sig(dp, dp, dp, dp, dp, dp),
+}
+DECLS_PRECOND = {  # include/elimaloc_hip_posegraph_precond.h (the pose graph's preconditioner)
+    "elm_posegraph_set_preconditioner": _sig(vp, vp, i),
+    "elm_posegraph_get_preconditioner": _sig(vp, vp, ip),
+}
+DECLS_INIT = {  # include/elimaloc_hip_posegraph_init.h (the pose graph's linear initialization)
+    "elm_posegraph_init_config_default": _sig(P(PoseGraphInitConfigC), ret=None),
+    "elm_posegraph_initialize": _sig(vp, vp, P(PoseGraphInitConfigC), P(PoseGraphInitResultC), dp, dp),
+}
+# the names alone, as __graft_entry__ and the ABI tests read them
+EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT)
+
 _LIB = None
 
 
 def lib():
-    """Load libelimaloc_hip.so (fails loudly when it has not been built)."""
+    """Load libelimaloc_hip.so (fails loudly when it has not been built) and give every declared function its signature."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -445,219 +585,10 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    vp, dp, fp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
-    L.elm_reg_config_default.argtypes = [C.POINTER(RegConfig)]
-    L.elm_reg_config_default.restype = None
-    L.elm_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.elm_ctx_destroy.argtypes = [vp]
-    L.elm_ctx_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    L.elm_ctx_group_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    L.elm_register_shard.argtypes = [vp, vp, fp, C.c_size_t, C.c_size_t, dp, C.POINTER(RegConfig), C.POINTER(RegResult), C.POINTER(IterTrace), C.c_int]
-    L.elm_ctx_destroy.restype = None
-    L.elm_last_error.argtypes = [vp]
-    L.elm_last_error.restype = C.c_char_p
-    L.elm_strerror.argtypes = [C.c_int]
-    L.elm_strerror.restype = C.c_char_p
-    L.elm_ctx_synchronize.argtypes = [vp]
-    L.elm_ctx_stream.argtypes = [vp]
-    L.elm_ctx_stream.restype = vp
-    L.elm_format_register_log.argtypes = [C.POINTER(RegConfig), C.POINTER(RegResult), C.c_size_t, C.POINTER(IterTrace), C.POINTER(C.c_double),
-                                          C.c_double, C.c_char_p, C.c_size_t]
-    L.elm_format_register_log.restype = C.c_size_t
-    L.elm_ctx_set_profiling.argtypes = [vp, C.c_int]
-    L.elm_ctx_set_work_counters.argtypes = [vp, C.c_int]
-    L.elm_ctx_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
-    L.elm_map_build.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
-    L.elm_map_build_device.argtypes = [vp, vp, C.POINTER(C.c_uint8), fp, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp)]
-    L.elm_map_build_device_stages.argtypes = [vp, dp]
-    L.elm_map_build_device_from.argtypes = [vp, C.POINTER(BuildSourcesC), C.c_double, C.c_int, C.POINTER(vp), C.POINTER(BuildSourcesStatsC)]
-    L.elm_odometry_config_default.argtypes = [C.POINTER(OdometryConfigC)]
-    L.elm_odometry_config_default.restype = None
-    L.elm_odometry_create.argtypes = [vp, C.POINTER(OdometryConfigC), C.POINTER(vp)]
-    L.elm_odometry_destroy.argtypes = [vp]
-    L.elm_odometry_destroy.restype = None
-    L.elm_odometry_reset.argtypes = [vp]
-    L.elm_odometry_predict.argtypes = [vp, dp]
-    L.elm_odometry_step_scan.argtypes = [vp, vp, dp, C.POINTER(OdometryStepC)]
-    L.elm_odometry_map.argtypes = [vp]
-    L.elm_odometry_map.restype = vp
-    u32p = C.POINTER(C.c_uint32)
-    L.elm_map_set_index_build.argtypes = [vp, C.c_int]
-    L.elm_map_index_build_stages.argtypes = [vp, dp]
-    L.elm_map_download_cell_grid.argtypes = [vp, C.POINTER(CellGridDesc), u32p, C.c_size_t, fp, C.c_size_t, u32p, C.c_size_t, u32p, C.c_size_t]
-    L.elm_map_destroy.argtypes = [vp]
-    L.elm_map_destroy.restype = None
-    L.elm_map_cal_voxel_cov_all.argtypes = [vp]
-    L.elm_map_cal_point_cov_all.argtypes = [vp, C.c_double]
-    L.elm_map_build_neighbourhoods.argtypes = [vp]
-    L.elm_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
-    L.elm_map_empty.argtypes = [vp]
-    L.elm_map_download_points.argtypes = [vp, dp, dp, dp, C.c_size_t]
-    L.elm_map_download_voxels.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, C.c_size_t]
-    L.elm_map_find_ground_height.argtypes = [vp, C.c_double, C.c_double, dp, ip]
-    L.elm_cal_frame_point_cov.argtypes = [dp, C.c_size_t, C.c_double, C.c_double, C.c_double, dp]
-    L.elm_align_clouds_local.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_size_t, dp, C.c_double, C.POINTER(RegConfig), dp, dp, dp]
-    L.elm_map_get_correspondences.argtypes = [vp, vp, C.c_int, dp, C.c_size_t, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_scan_upload.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.POINTER(vp)]
-    L.elm_scan_destroy.argtypes = [vp]
-    L.elm_scan_destroy.restype = None
-    L.elm_scan_size.argtypes = [vp]
-    L.elm_scan_size.restype = C.c_size_t
-    L.elm_scan_download.argtypes = [vp, fp, C.c_size_t]
-    L.elm_deskew_downsample.argtypes = [vp, fp, fp, C.c_size_t, C.POINTER(DeskewTables), C.c_double, C.POINTER(vp), ip]
-    L.elm_register.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(RegConfig), dp, ip, dp, dp,
-                               C.POINTER(RegResult), C.POINTER(IterTrace)]
-    L.elm_register_stream.argtypes = [vp, vp, C.POINTER(vp), C.c_int, dp, C.POINTER(RegConfig), C.c_int, C.POINTER(RegResult),
-                                      C.POINTER(IterTrace)]
-    L.elm_register_stream_host.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint32), C.c_int, dp, C.POINTER(RegConfig), C.c_int,
-                                           C.POINTER(RegResult), C.POINTER(IterTrace)]
-    L.elm_ctx_measure_h2d.argtypes = [vp, vp, C.c_size_t, C.c_int, dp]
-    L.elm_host_alloc.argtypes = [C.c_size_t]
-    L.elm_host_alloc.restype = vp
-    L.elm_host_free.argtypes = [vp]
-    L.elm_host_free.restype = None
-    L.elm_register_batch.argtypes = [vp, vp, C.POINTER(vp), C.c_int, dp, C.POINTER(RegConfig),
-                                     C.POINTER(RegResult), C.POINTER(IterTrace)]
-    L.elm_register_batch_enqueue.argtypes = [vp, vp, C.POINTER(vp), C.c_int, dp, C.POINTER(RegConfig), C.c_int]
-    L.elm_register_batch_finish.argtypes = [vp, C.POINTER(RegResult), C.POINTER(IterTrace)]
-    L.elm_deskew.argtypes = [vp, fp, fp, C.c_size_t, C.POINTER(DeskewTables), fp, ip]
-    L.elm_deskew_prepare.argtypes = [dp, C.c_size_t, dp, C.c_size_t, C.c_double, C.c_float, C.c_float, C.c_int,
-                                     C.c_int, dp, dp, dp, dp, C.c_size_t, C.POINTER(DeskewTables)]
-    L.elm_filter_points_by_distance.argtypes = [fp, fp, C.c_size_t, C.c_double, fp, fp, C.POINTER(C.c_size_t)]
-    L.elm_voxel_downsample.argtypes = [fp, C.c_size_t, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
-    L.elm_get_interpolated_pose.argtypes = [dp, C.c_size_t, C.c_double, fp, ip]
-    L.elm_shape_odom_covariance.argtypes = [dp, dp, C.c_double, dp]
-    L.elm_ekf_config_default.argtypes = [C.POINTER(EkfConfig)]
-    L.elm_ekf_config_default.restype = None
-    L.elm_ekf_create.argtypes = [C.POINTER(EkfConfig), C.POINTER(vp)]
-    L.elm_ekf_destroy.argtypes = [vp]
-    L.elm_ekf_destroy.restype = None
-    L.elm_ekf_predict_imu.argtypes = [vp, C.c_double, dp, dp, ip]
-    L.elm_ekf_predict.argtypes = [vp, C.c_double, ip]
-    L.elm_ekf_update_can.argtypes = [vp, C.c_double, dp, dp, ip]
-    L.elm_gps_project.argtypes = [C.c_double] * 6 + [dp]
-    L.elm_ekf_update_navsatfix.argtypes = [vp] + [C.c_double] * 4 + [dp] + [C.c_double] * 3 + [C.c_int, C.c_double, dp, ip]
-    L.elm_ekf_update_pose.argtypes = [vp, C.c_double, dp, dp, dp, dp, C.c_int, ip]
-    L.elm_ekf_update_pcm_odom.argtypes = [vp, C.c_double, dp, dp, dp, C.c_int, ip]
-    L.elm_ekf_get_state.argtypes = [vp, C.POINTER(EkfStateC)]
-    L.elm_ekf_publish.argtypes = [vp, C.POINTER(EgoStateC)]
-    cp, szp = C.c_char_p, C.POINTER(C.c_size_t)
-    L.elm_ini_load.argtypes = [cp, C.POINTER(vp)]
-    L.elm_ini_destroy.argtypes = [vp]
-    L.elm_ini_destroy.restype = None
-    L.elm_ini_get_string.argtypes = [vp, cp, cp, C.c_char_p, C.c_size_t]
-    L.elm_ini_get_int.argtypes = [vp, cp, cp, ip]
-    L.elm_ini_get_bool.argtypes = [vp, cp, cp, ip]
-    L.elm_ini_get_double.argtypes = [vp, cp, cp, dp]
-    L.elm_ini_get_array.argtypes = [vp, cp, cp, dp, C.c_size_t, szp]
-    L.elm_pcm_node_config_default.argtypes = [C.POINTER(PcmNodeConfig)]
-    L.elm_pcm_node_config_default.restype = None
-    L.elm_load_pcm_config.argtypes = [cp, cp, C.POINTER(PcmNodeConfig), C.POINTER(RegConfig)]
-    L.elm_load_ekf_config.argtypes = [cp, C.POINTER(EkfConfig)]
-    L.elm_pcd_load_xyz.argtypes = [cp, C.POINTER(fp), szp]
-    L.elm_free.argtypes = [vp]
-    L.elm_free.restype = None
-    L.elm_scan_from_cloud.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(CloudField), C.c_int, C.c_int, C.c_int, fp, fp, fp,
-                                      C.c_size_t, szp]
-    L.elm_pcm_callback_point_cloud.argtypes = [vp, vp, C.POINTER(PcmNodeConfig), C.POINTER(RegConfig), fp, fp, C.c_size_t, C.c_double,
-                                               dp, C.c_size_t, dp, C.c_size_t, C.POINTER(PcmScanOutput), ip]
-    L.elm_reloc_config_default.argtypes = [C.POINTER(RelocConfigC)]
-    L.elm_reloc_config_default.restype = None
-    L.elm_reloc_make_hypotheses.argtypes = [dp, C.POINTER(RelocConfigC), dp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_map_score_poses.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RelocConfigC), C.POINTER(C.c_uint32)]
-    L.elm_relocalize.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(RelocConfigC), C.POINTER(RegConfig), dp, C.POINTER(RegResult),
-                                 C.POINTER(RelocCandidate), C.c_int, ip]
-    L.elm_freespace_config_default.argtypes = [C.POINTER(FreeSpaceConfigC)]
-    L.elm_freespace_config_default.restype = None
-    L.elm_map_fine_cells.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_map_check_free_space.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(FreeSpaceConfigC), C.POINTER(FreeSpaceStatsC),
-                                           C.POINTER(C.c_uint16)]
-    L.elm_raycast_config_default.argtypes = [C.POINTER(RayCastConfigC)]
-    L.elm_raycast_config_default.restype = None
-    L.elm_map_raycast.argtypes = [vp, vp, vp, dp, C.c_int, C.POINTER(RayCastConfigC), C.POINTER(RayCastStatsC), dp, dp,
-                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
-    L.elm_evidence_config_default.argtypes = [C.POINTER(EvidenceConfigC)]
-    L.elm_evidence_config_default.restype = None
-    L.elm_evidence_rule_default.argtypes = [C.POINTER(EvidenceRuleC)]
-    L.elm_evidence_rule_default.restype = None
-    L.elm_evidence_create.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
-    L.elm_evidence_destroy.argtypes = [vp]
-    L.elm_evidence_destroy.restype = None
-    L.elm_evidence_reset.argtypes = [vp, vp]
-    L.elm_evidence_accumulate.argtypes = [vp, vp, vp, dp, C.POINTER(EvidenceConfigC), C.POINTER(EvidenceStatsC), C.POINTER(C.c_uint16)]
-    L.elm_evidence_accumulate_batch.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(EvidenceConfigC), C.POINTER(EvidenceStatsC)]
-    L.elm_evidence_counts.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_evidence_stale_points.argtypes = [vp, vp, C.POINTER(EvidenceRuleC), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_growth_config_default.argtypes = [C.POINTER(GrowthConfigC)]
-    L.elm_growth_config_default.restype = None
-    L.elm_growth_rule_default.argtypes = [C.POINTER(GrowthRuleC)]
-    L.elm_growth_rule_default.restype = None
-    L.elm_growth_create.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(vp)]
-    L.elm_growth_destroy.argtypes = [vp]
-    L.elm_growth_destroy.restype = None
-    L.elm_growth_reset.argtypes = [vp, vp]
-    L.elm_growth_accumulate.argtypes = [vp, vp, vp, dp, C.POINTER(GrowthConfigC), C.POINTER(GrowthStatsC), C.POINTER(C.c_uint16)]
-    L.elm_growth_accumulate_batch.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(GrowthConfigC), C.POINTER(GrowthStatsC)]
-    L.elm_growth_cells.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t,
-                                   C.POINTER(C.c_size_t)]
-    L.elm_growth_appeared_points.argtypes = [vp, vp, C.POINTER(GrowthRuleC), dp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_growth_object_rule_default.argtypes = [C.POINTER(GrowthObjectRuleC)]
-    L.elm_growth_object_rule_default.restype = None
-    L.elm_growth_find_objects.argtypes = [vp, vp, C.POINTER(GrowthObjectRuleC), C.POINTER(GrowthObjectStatsC)]
-    L.elm_growth_objects.argtypes = [vp, vp, C.POINTER(GrowthObjectC), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_growth_cell_objects.argtypes = [vp, vp, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.elm_growth_beam_objects.argtypes = [vp, vp, vp, dp, C.POINTER(GrowthConfigC), C.POINTER(C.c_int32)]
-    L.elm_reloc_global_config_default.argtypes = [C.POINTER(GlobalRelocConfigC)]
-    L.elm_reloc_global_config_default.restype = None
-    L.elm_map_ground_heights.argtypes = [vp, vp, dp, C.c_size_t, dp, C.POINTER(C.c_int32)]
-    L.elm_reloc_global_hypotheses.argtypes = [vp, vp, dp, C.POINTER(GlobalRelocConfigC), dp, C.POINTER(C.c_int32), C.c_size_t,
-                                              C.POINTER(C.c_size_t)]
-    L.elm_relocalize_global.argtypes = [vp, vp, fp, C.c_size_t, dp, C.POINTER(GlobalRelocConfigC), C.POINTER(RegConfig), dp,
-                                        C.POINTER(RegResult), C.POINTER(RelocCandidate), C.c_int, ip, C.POINTER(GlobalRelocStats)]
-    u64p, i64p, pqc = C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(PlacesQueryConfigC)
-    L.elm_places_config_default.argtypes = [C.POINTER(PlacesConfigC)]
-    L.elm_places_config_default.restype = None
-    L.elm_places_tables.argtypes = [C.POINTER(PlacesConfigC), dp, dp, dp]
-    L.elm_places_create.argtypes = [vp, C.POINTER(PlacesConfigC), C.c_int, C.POINTER(vp)]
-    L.elm_places_destroy.argtypes = [vp]
-    L.elm_places_destroy.restype = None
-    L.elm_places_reset.argtypes = [vp, vp]
-    L.elm_places_size.argtypes = [vp, vp, C.POINTER(C.c_size_t)]
-    L.elm_places_describe.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, u64p, C.POINTER(PlacesStatsC)]
-    L.elm_places_add.argtypes = [vp, vp, C.POINTER(vp), dp, i64p, C.c_int, C.POINTER(PlacesStatsC)]
-    L.elm_places_add_words.argtypes = [vp, vp, u64p, i64p, C.c_size_t]
-    L.elm_places_download.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p, i64p, C.POINTER(C.c_uint32)]
-    L.elm_places_match_words.argtypes = [vp, vp, u64p, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32), C.POINTER(PlaceMatchC)]
-    L.elm_places_query.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, pqc, C.POINTER(PlaceCandidateC), C.POINTER(C.c_int32),
-                                   C.POINTER(PlaceMatchC), C.POINTER(PlacesStatsC)]
-    u8p, i32p, szt = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t
-    L.elm_posegraph_config_default.argtypes = [C.POINTER(PoseGraphConfigC)]
-    L.elm_posegraph_config_default.restype = None
-    L.elm_posegraph_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    L.elm_posegraph_destroy.argtypes = [vp]
-    L.elm_posegraph_destroy.restype = None
-    L.elm_posegraph_reset.argtypes = [vp, vp]
-    L.elm_posegraph_size.argtypes = [vp, vp, C.POINTER(szt), C.POINTER(szt)]
-    L.elm_posegraph_add_nodes.argtypes = [vp, vp, dp, u8p, szt]
-    L.elm_posegraph_set_poses.argtypes = [vp, vp, szt, szt, dp]
-    L.elm_posegraph_get_poses.argtypes = [vp, vp, szt, szt, dp]
-    L.elm_posegraph_set_fixed.argtypes = [vp, vp, szt, szt, u8p]
-    L.elm_posegraph_add_edges.argtypes = [vp, vp, i32p, i32p, dp, dp, szt]
-    L.elm_posegraph_linearize.argtypes = [vp, vp, C.c_double, C.POINTER(PoseGraphLinearizeStatsC)]
-    L.elm_posegraph_download_linearization.argtypes = [vp, vp, dp, dp, dp, dp, dp, dp, dp]
-    L.elm_posegraph_solve.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(PoseGraphSolveStatsC)]
-    L.elm_posegraph_optimize.argtypes = [vp, vp, C.POINTER(PoseGraphConfigC), C.POINTER(PoseGraphResultC), C.POINTER(PoseGraphTraceC), C.c_int]
-    L.elm_posegraph_edge_terms.argtypes = [dp, dp, dp, dp, dp, dp]
-    L.elm_posegraph_set_preconditioner.argtypes = [vp, vp, C.c_int]
-    L.elm_posegraph_get_preconditioner.argtypes = [vp, vp, C.POINTER(C.c_int)]
-    L.elm_posegraph_init_config_default.argtypes = [C.POINTER(PoseGraphInitConfigC)]
-    L.elm_posegraph_init_config_default.restype = None
-    L.elm_posegraph_initialize.argtypes = [vp, vp, C.POINTER(PoseGraphInitConfigC), C.POINTER(PoseGraphInitResultC), dp, dp]
-    L.elm_comm_get_unique_id.argtypes = [vp]
-    L.elm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.elm_comm_destroy.argtypes = [vp]
-    L.elm_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.elm_comm_set_hook.argtypes = [vp, ALLREDUCE_FN, vp]
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DeskewTables, check
-from .registration import default_context
+from .context import default_context
 
 I_QUEUE_LENGTH = 2000  # pcm.hpp:113
 

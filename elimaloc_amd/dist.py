@@ -61,7 +61,7 @@ def init_rccl(ctx, rank=None, world_size=None):
     """Create the context's RCCL communicator; the unique id travels over an already initialised torch.distributed
     process group (any backend)."""
     import torch.distributed as dist
-    from .registration import Context
+    from .context import Context
     rank = dist.get_rank() if rank is None else rank
     world_size = dist.get_world_size() if world_size is None else world_size
     ids = [Context.comm_unique_id() if rank == 0 else None]

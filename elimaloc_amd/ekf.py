@@ -11,6 +11,7 @@ import enum
 import numpy as np
 
 from . import _lib
+from ._marshal import _apply, _dp
 
 
 class GnssSource(enum.IntEnum):  # localization_struct.hpp:28
@@ -27,17 +28,10 @@ class EkfConfig:
     def __init__(self, **kw):
         self.c = _lib.EkfConfig()
         _lib.lib().elm_ekf_config_default(C.byref(self.c))
-        for k, v in kw.items():
-            if not hasattr(self.c, k):
-                raise AttributeError(f"unknown EKF config key {k}")
-            setattr(self.c, k, v)
+        _apply(self.c, kw, "unknown EKF config key {k}")
 
     def __getattr__(self, k):
         return getattr(self.__dict__["c"], k)
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def ProjectGpsPoint(ref_lla, lat, lon, alt):

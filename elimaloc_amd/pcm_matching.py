@@ -13,8 +13,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
+from ._marshal import _dp, _fp
 from .deskew import PcmDeskew
-from .registration import (Context, IcpMethod, Registration, RegistrationConfig, VoxelHashMap, default_context)
+from .context import Context, default_context
+from .registration import IcpMethod, Registration, RegistrationConfig
+from .voxel_map import VoxelHashMap
 
 
 @dataclass
@@ -31,14 +34,6 @@ class PcmMatchingConfig:
     d_input_voxel_ds_m: float = 1.5
     tf_ego_to_lidar: np.ndarray = field(default_factory=lambda: np.eye(4))
     registration: object = None          # RegistrationConfig (elm_reg_config)
-
-
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def filter_points_by_distance(xyz, point_time, max_dist):

@@ -7,7 +7,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import ElmError, PlaceCandidateC, PlaceMatchC, PlacesConfigC, PlacesQueryConfigC, PlacesStatsC, check
-from .registration import IcpMethod, RegistrationConfig, RelocConfig, Scan, VoxelHashMap, _Owned, _dp, _pose_block, _ptr, _resident, default_context
+from ._marshal import _Owned, _config, _counts, _dp, _pose_block, _ptr
+from .context import Scan, _resident, default_context
+from .registration import IcpMethod, RegistrationConfig
+from .voxel_map import RelocConfig, VoxelHashMap
 
 SECTORS, MAX_TOP_K = _lib.PLACES_SECTORS, _lib.PLACES_MAX_TOP_K
 MATCH_DTYPE = np.dtype([("dice_q16", np.uint32), ("inter", np.uint16), ("shift", np.uint16)])
@@ -15,13 +18,7 @@ MATCH_DTYPE = np.dtype([("dice_q16", np.uint32), ("inter", np.uint16), ("shift",
 
 def PlaceConfig(**kw):
     """elm_places_config with its defaults (16 rings over 2 .. 42 m, 8 layers over -3 .. 9 m)."""
-    cfg = PlacesConfigC()
-    _lib.lib().elm_places_config_default(C.byref(cfg))
-    for k, v in kw.items():
-        if k.startswith("_") or not hasattr(cfg, k):
-            raise AttributeError(f"PlaceConfig has no field {k}")
-        setattr(cfg, k, int(v) if k in ("n_rings", "n_layers") else float(v))
-    return cfg
+    return _config("PlaceConfig", PlacesConfigC, "elm_places_config_default", kw)
 
 
 def PlaceTables(cfg=None):
@@ -36,7 +33,7 @@ def PlaceTables(cfg=None):
 
 def PlaceStats(st):
     """elm_places_stats of one described scan as a dict."""
-    return dict(n_points=int(st.n_points), n_used=int(st.n_used), n_bits=int(st.n_bits))
+    return _counts(st)
 
 
 def _candidate(c):

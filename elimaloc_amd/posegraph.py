@@ -7,35 +7,22 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (ElmError, PG_PRECOND, PG_STOP,PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC, PoseGraphTraceC,
-                   PoseGraphInitConfigC, PoseGraphInitResultC, check)
-from .registration import _Owned, _dp, _pose_block, _ptr, default_context
-
-_INT_FIELDS = ("max_iterations", "pcg_max_iterations", "pcg_check_every")
+from ._lib import (ElmError, PG_PRECOND, PG_STOP, PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC,
+                   PoseGraphTraceC, PoseGraphInitConfigC, PoseGraphInitResultC, check)
+from ._marshal import _Owned, _config, _dp, _pose_block, _ptr
+from .context import default_context
 
 
 def PoseGraphConfig(**kw):
     """elm_posegraph_config with its defaults (20 solves, lambda 1e-4 x10 up / x0.1 down in [1e-12, 1e8], cost_rel_tol 1e-12, step_tol
     1e-10, PCG to 1e-8 in at most 2000 iterations checked every 32, Huber off)."""
-    cfg = PoseGraphConfigC()
-    _lib.lib().elm_posegraph_config_default(C.byref(cfg))
-    for k, v in kw.items():
-        if k.startswith("_") or not hasattr(cfg, k):
-            raise AttributeError(f"PoseGraphConfig has no field {k}")
-        setattr(cfg, k, int(v) if k in _INT_FIELDS else float(v))
-    return cfg
+    return _config("PoseGraphConfig", PoseGraphConfigC, "elm_posegraph_config_default", kw)
 
 
 def PoseGraphInitConfig(**kw):
     """elm_posegraph_init_config with its defaults (both solves to 1e-8 in at most 50 000 iterations checked every 32;
     stages = PG_INIT_ROT | PG_INIT_TRANS, or one of them)."""
-    cfg = PoseGraphInitConfigC()
-    _lib.lib().elm_posegraph_init_config_default(C.byref(cfg))
-    for k, v in kw.items():
-        if k.startswith("_") or not hasattr(cfg, k):
-            raise AttributeError(f"PoseGraphInitConfig has no field {k}")
-        setattr(cfg, k, float(v) if k == "pcg_rel_tol" else int(v))
-    return cfg
+    return _config("PoseGraphInitConfig", PoseGraphInitConfigC, "elm_posegraph_init_config_default", kw)
 
 
 def EdgeTerms(Ti, Tj, Z):
