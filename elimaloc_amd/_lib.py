@@ -337,6 +337,18 @@ class PoseGraphInitResultC(C.Structure):
                 ("degenerate_nodes", C.c_int32), ("applied", C.c_int32)]
 
 
+class LoopsConfigC(C.Structure):
+    """elm_loops_config (include/elimaloc_hip_loops.h)."""
+    _fields_ = [("q_t", C.c_double), ("q_r", C.c_double), ("gamma", C.c_double), ("steps_per_batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LoopsResultC(C.Structure):
+    """elm_loops_result."""
+    _fields_ = [("size", C.c_int32), ("steps", C.c_int32), ("adjacent_pairs", C.c_int64), ("adjacency_ms", C.c_double),
+                ("greedy_ms", C.c_double)]
+
+
+LOOPS_MAX, LOOPS_MAX_S = 16384, 2048
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
 PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
 
@@ -570,8 +582,13 @@ DECLS_INIT = {  # include/elimaloc_hip_posegraph_init.h (the pose graph's linear
     "elm_posegraph_init_config_default": _sig(P(PoseGraphInitConfigC), ret=None),
     "elm_posegraph_initialize": _sig(vp, vp, P(PoseGraphInitConfigC), P(PoseGraphInitResultC), dp, dp),
 }
+DECLS_LOOPS = {  # include/elimaloc_hip_loops.h (loop closing: pairwise consistency of loop measurements)
+    "elm_loops_config_default": _sig(P(LoopsConfigC), ret=None),
+    "elm_loops_pair_terms": _sig(dp, dp, dp, dp, dp, dp, dp),
+    "elm_loops_consistency": _sig(vp, dp, szt, i32p, i32p, dp, dp, dp, szt, P(LoopsConfigC), P(LoopsResultC), u8p, i32p, u64p, dp),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
-EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT)
+EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
 
 _LIB = None
 
@@ -585,7 +602,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

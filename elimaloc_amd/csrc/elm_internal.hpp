@@ -523,6 +523,30 @@ void launch_pgi_rot_apply(hipStream_t s, const PgDev& d, const double* poses, do
 // t <- t + R v of the active nodes, in place
 void launch_pgi_trans_apply(hipStream_t s, const PgDev& d, double* trial);
 
+// loop consistency (elm_k_loops.hip; the contract is include/elimaloc_hip_loops.h): the device's view of one call.
+// adj is [L][W] with W = lc_words(L); the greedy step `it` reads cand and stop of parity it & 1 and writes those of the other parity.
+struct LcState {
+    uint32_t stop[2]; // the greedy loop is over for the launches of the step of that parity
+    uint32_t size;    // members so far (written by k_lc_pick, read by the host alone)
+    uint32_t pad;
+};
+struct LcDev {
+    uint32_t L, W, n, pad;
+    const double* poses;            // [n][12] pose rows
+    const int32_t *a, *b;           // [L]
+    const double *Z, *var_t, *var_r; // [L][12], [L], [L]
+    unsigned long long* adj;        // [L][W]
+    double* s;                      // [L][L] or null
+    unsigned long long* cand;       // [2][W]
+    int32_t *deg0, *deg;            // [L]: the degrees of step 0 (the call's degree_out) and of every later step
+    uint8_t* member;                // [L]
+    LcState* state;
+};
+constexpr uint32_t lc_words(uint32_t L) { return (L + 63u) / 64u; }
+void launch_lc_adjacency(hipStream_t s, const LcDev& d, double q_t, double q_r, double gamma);
+// one greedy step: the degrees inside cand, then the pick
+void launch_lc_step(hipStream_t s, const LcDev& d, uint32_t it);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

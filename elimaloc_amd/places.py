@@ -264,7 +264,22 @@ class LoopCloser:
         info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
         self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
 
-    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False):
+    def ConsistentLoops(self, cfg=None, var_t=None, var_r=None):
+        """The loops of AddLoop that agree with one another over the inserted poses (loops.LoopConsistency on self.poses and
+        self.loops; cfg: a LoopConsistencyConfig, whose q_t and q_r say how good the odometry is per entry) -> its dict.  var_t,
+        var_r: one number for all loops or one per loop; by default 3 / trace(Omega_vv) and 3 / trace(Omega_ww) of each loop's
+        information, the weights of PoseGraph.Initialize inverted."""
+        from .loops import LoopConsistency
+        info = np.stack([l[3] for l in self.loops]) if self.loops else np.zeros((0, 6, 6))
+        if var_t is None:
+            var_t = 3.0 / ((info[:, 0, 0] + info[:, 1, 1]) + info[:, 2, 2])
+        if var_r is None:
+            var_r = 3.0 / ((info[:, 3, 3] + info[:, 4, 4]) + info[:, 5, 5])
+        Z = np.stack([l[2] for l in self.loops]) if self.loops else np.zeros((0, 4, 4))
+        return LoopConsistency(np.stack(self.poses), [l[0] for l in self.loops], [l[1] for l in self.loops], Z, var_t, var_r, cfg, self.ctx)
+
+    def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False,
+              consistency=None):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
@@ -274,13 +289,16 @@ class LoopCloser:
         initialize=True runs PoseGraph.Initialize (rotations first, then translations, both linear) before Optimize and puts its result
         under "initialize" in the returned dict: the start that a long loop needs, whose drift is far outside Gauss-Newton's reach.  A
         false loop pulls a linear initialization as hard as a true one: Huber acts only in Optimize, so verify loops before adding
-        them.  The default leaves every result as it was."""
+        them.  consistency: a LoopConsistencyConfig; then only the members of ConsistentLoops(consistency) are added to the graph, in
+        their original order, and its dict is put under "consistency".  The defaults leave every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
             raise ElmError("LoopCloser.Close: at least two entries")
         P = np.stack(self.poses)
-        pg = PoseGraph(n, n - 1 + max(len(self.loops), 1), self.ctx)
+        kept = self.ConsistentLoops(consistency) if consistency is not None else None
+        loops = self.loops if kept is None else [self.loops[k] for k in kept["members"]]
+        pg = PoseGraph(n, n - 1 + max(len(loops), 1), self.ctx)
         try:
             fx = np.zeros(n, bool)
             fx[list(fixed)] = True
@@ -288,13 +306,14 @@ class LoopCloser:
             pg.AddNodes(P, fx)
             Z = np.linalg.inv(P[:-1]) @ P[1:]
             pg.AddEdges(np.arange(n - 1), np.arange(1, n), Z, None if odom_information is None else np.asarray(odom_information, dtype=np.float64))
-            if self.loops:
-                pg.AddEdges([l[0] for l in self.loops], [l[1] for l in self.loops], np.stack([l[2] for l in self.loops]),
-                            np.stack([l[3] for l in self.loops]))
+            if loops:
+                pg.AddEdges([l[0] for l in loops], [l[1] for l in loops], np.stack([l[2] for l in loops]), np.stack([l[3] for l in loops]))
             init = pg.Initialize() if initialize else None
             res = pg.Optimize(cfg)
             if initialize:
                 res["initialize"] = init
+            if kept is not None:
+                res["consistency"] = kept
             out = pg.Poses()
         finally:
             pg.close()
