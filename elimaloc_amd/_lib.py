@@ -348,6 +348,12 @@ class LoopsResultC(C.Structure):
                 ("greedy_ms", C.c_double)]
 
 
+class LoopCovResultC(C.Structure):
+    """elm_loopcov_result (include/elimaloc_hip_loopcov.h)."""
+    _fields_ = [("size", C.c_int32), ("steps", C.c_int32), ("adjacent_pairs", C.c_int64), ("non_finite_pairs", C.c_int64),
+                ("chain_ms", C.c_double), ("adjacency_ms", C.c_double), ("greedy_ms", C.c_double)]
+
+
 LOOPS_MAX, LOOPS_MAX_S = 16384, 2048
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
 PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
@@ -587,8 +593,14 @@ DECLS_LOOPS = {  # include/elimaloc_hip_loops.h (loop closing: pairwise consiste
     "elm_loops_pair_terms": _sig(dp, dp, dp, dp, dp, dp, dp),
     "elm_loops_consistency": _sig(vp, dp, szt, i32p, i32p, dp, dp, dp, szt, P(LoopsConfigC), P(LoopsResultC), u8p, i32p, u64p, dp),
 }
+DECLS_LOOPCOV = {  # include/elimaloc_hip_loopcov.h (loop closing: pairwise consistency with a propagated 6 x 6 covariance)
+    "elm_loopcov_chain": _sig(vp, dp, szt, dp, szt, dp, dp),
+    "elm_loopcov_pair_terms": _sig(dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp),
+    "elm_loopcov_consistency": _sig(vp, dp, szt, i32p, i32p, dp, dp, szt, dp, szt, P(LoopsConfigC), P(LoopCovResultC), u8p, i32p, u64p, dp),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
 EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
+EXPORTS_LOOPCOV = list(DECLS_LOOPCOV)
 
 _LIB = None
 
@@ -602,7 +614,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -547,6 +547,35 @@ void launch_lc_adjacency(hipStream_t s, const LcDev& d, double q_t, double q_r, 
 // one greedy step: the degrees inside cand, then the pick
 void launch_lc_step(hipStream_t s, const LcDev& d, uint32_t it);
 
+// loop consistency with a propagated covariance (elm_k_loopcov.hip; the contract is include/elimaloc_hip_loopcov.h).
+// Symmetric 6 x 6 matrices are 21 entries (elm_dev_loopcov.hpp); Wc and rec are component-major: entry c of item i at [c * stride + i].
+constexpr uint32_t kLcvScanBlock = 1024; // elements of one block of the prefix sum: two levels reach 2^20 poses
+constexpr uint32_t kLcvRecYa = 0, kLcvRecYb = 12, kLcvRecZ = 24, kLcvRecWa = 36, kLcvRecWb = 57, kLcvRecSigma = 78, kLcvRecWords = 99;
+struct LcvChain {
+    uint32_t n, q_count, nb, pad; // nb: blocks of the scan
+    const double* poses;          // [n][12] pose rows
+    const double* Q;              // [q_count][21]
+    double* Wc;                   // [21][n]
+    double* tot;                  // [21][nb] the block totals, scanned in place
+};
+struct LcvDev {
+    uint32_t L, W, Lp, pad;       // Lp: the stride of rec
+    const int32_t *a, *b;         // [L]
+    const double* Z;              // [L][12]
+    const double* Sigma;          // [L][21]
+    double* rec;                  // [kLcvRecWords][Lp]
+    unsigned long long* adj;      // [L][W]
+    uint8_t* nanc;                // [L][W] the pairs of each word whose s is NaN
+    int32_t* nan_row;             // [L] their sum per row
+    double* s;                    // [L][L] or null
+};
+// W of the chain, component-major
+void launch_lcv_chain(hipStream_t s, const LcvChain& c);
+// W_out [n][36] and, when not null, S_out [n][36]
+void launch_lcv_expand(hipStream_t s, const LcvChain& c, double* W_out, double* S_out);
+// the per-loop records, then the pair terms
+void launch_lcv_adjacency(hipStream_t s, const LcvChain& c, const LcvDev& d, double gamma);
+
 // map growth (elm_k_grow.hip): the evidence walk against a table of candidate cells that the end points of the same
 // call fill -- cells the map does not occupy and in which beams ended
 struct GrowTables { // two open-addressing tables of `mask + 1` slots each, keys packed by grow_key (0 = empty), filled by k_grow_end

@@ -1,6 +1,6 @@
 // elm_loops.cpp -- the loop consistency check (include/elimaloc_hip_loops.h): the argument checks, the one upload
-// of poses, loops and variances, the pair kernel, and the greedy loop that queues steps_per_batch steps between two reads of the
-// device's state (the pattern of the pose graph's conjugate gradients).  The launches are those of elm_k_loops.hip.  The call owns one
+// of poses, loops and variances, the pair kernel, and the greedy loop (elm_loops_host.hpp) that queues steps_per_batch steps between two
+// reads of the device's state (the pattern of the pose graph's conjugate gradients).  The launches are those of elm_k_loops.hip.  The call owns one
 // device allocation for its duration and keeps nothing afterwards.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -10,11 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "elm_dev_loops.hpp"
-#include "elm_query.hpp"
+#include "elm_loops_host.hpp"
 
 using namespace elm;
 using namespace elm_query;
+using namespace elm_loops_host;
 
 extern "C" void elm_loops_config_default(elm_loops_config* c) {
     if (!c) return;
@@ -40,8 +40,6 @@ extern "C" int elm_loops_pair_terms(const double* Ta, const double* Tb, const do
 
 namespace {
 
-constexpr size_t kLcMaxPoses = (size_t)1 << 20;
-
 // the preconditions that need no device: "" when they hold, else the text for elm_last_error
 std::string refusal(const double* poses16, size_t n, const int32_t* a, const int32_t* b, const double* Z16, const double* var_t, const double* var_r,
                     size_t L, const elm_loops_config* cfg, const void* result, const void* member_out, const void* degree_out, const double* s_out) {
@@ -65,18 +63,6 @@ std::string refusal(const double* poses16, size_t n, const int32_t* a, const int
     return "";
 }
 
-// the device arrays of one call carved from one allocation, each aligned to 256 bytes (base == nullptr: the size alone)
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) / 256 * 256;
-        return p;
-    }
-};
-
 struct LcArrays {
     LcDev d{};
     double* poses = nullptr;
@@ -94,13 +80,7 @@ void carve(LcArrays& A, Carver& c, size_t n, size_t L, bool want_s) {
     A.var_r = c.take<double>(L);
     A.d.adj = c.take<unsigned long long>(L * W);
     A.d.s = want_s ? c.take<double>(L * L) : nullptr;
-    A.d.cand = c.take<unsigned long long>(2 * W);
-    A.d.deg0 = c.take<int32_t>(L);
-    A.d.deg = c.take<int32_t>(L);
-    A.d.member = c.take<uint8_t>(L);
-    A.d.state = c.take<LcState>(1);
-    A.d.L = (uint32_t)L;
-    A.d.W = (uint32_t)W;
+    carve_greedy(A.d, c, L);
     A.d.n = (uint32_t)n;
     A.d.poses = A.poses;
     A.d.a = A.a;
@@ -110,24 +90,6 @@ void carve(LcArrays& A, Carver& c, size_t n, size_t L, bool want_s) {
     A.d.var_r = A.var_r;
 }
 
-struct Blob { // the call's one device allocation, released when the call ends however it ends (its stream joined first)
-    char* p = nullptr;
-    hipStream_t st = nullptr;
-    ~Blob() {
-        if (!p) return;
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(p);
-    }
-};
-
-struct Events { // the three marks of a call on its stream
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t n, const int32_t* a, const int32_t* b, const double* Z16,
                      const double* var_t, const double* var_r, size_t L, const elm_loops_config& c, elm_loops_result* result, uint8_t* member_out,
                      int32_t* degree_out, uint64_t* adj_out, double* s_out) {
@@ -136,8 +98,7 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     std::vector<double> rows(12 * n), zrows(12 * L);
     for (size_t v = 0; v < n; ++v) pose_rows12(poses16 + 16 * v, &rows[12 * v]);
     for (size_t k = 0; k < L; ++k) pose_rows12(Z16 + 16 * k, &zrows[12 * k]);
-    std::vector<unsigned long long> cand0(W, ~0ull); // every loop a candidate, the padding bits clear
-    if (L & 63u) cand0[W - 1] = (1ull << (L & 63u)) - 1ull;
+    std::vector<unsigned long long> cand0;
     LcArrays A;
     Carver size{nullptr};
     carve(A, size, n, L, s_out != nullptr);
@@ -151,7 +112,7 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     Carver real{blob.p};
     carve(A, real, n, L, s_out != nullptr);
     const LcDev& d = A.d;
-    Events ev;
+    Events<3> ev;
     for (int q = 0; q < 3 && e == hipSuccess; ++q) e = hipEventCreate(&ev.ev[q]);
     if (e == hipSuccess) e = hipMemcpyAsync(A.poses, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.a, a, L * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -159,24 +120,12 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     if (e == hipSuccess) e = hipMemcpyAsync(A.Z, zrows.data(), zrows.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.var_t, var_t, L * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.var_r, var_r, L * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d.cand, cand0.data(), W * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d.member, 0, L, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d.state, 0, sizeof(LcState), st);
+    if (e == hipSuccess) e = greedy_reset(st, d, cand0);
     if (e == hipSuccess) e = hipEventRecord(ev.ev[0], st);
     if (e == hipSuccess) e = launched([&] { launch_lc_adjacency(st, d, c.q_t, c.q_r, c.gamma); });
     if (e == hipSuccess) e = hipEventRecord(ev.ev[1], st);
-    // The greedy loop: a clique has at most L members, and the step after the last pick would only set the stop word.
     LcState state{};
-    uint32_t it = 0;
-    while (e == hipSuccess) {
-        const uint32_t upto = (uint32_t)std::min<uint64_t>((uint64_t)it + (uint64_t)c.steps_per_batch, L);
-        e = launched([&] {
-            for (; it < upto; ++it) launch_lc_step(st, d, it);
-        });
-        if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(LcState), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess || state.stop[it & 1u] || it >= L) break;
-    }
+    if (e == hipSuccess) e = greedy_run(st, d, c.steps_per_batch, state);
     if (e == hipSuccess) e = hipEventRecord(ev.ev[2], st);
     std::vector<int32_t> deg(L);
     std::vector<uint8_t> member(L);

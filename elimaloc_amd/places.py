@@ -264,13 +264,22 @@ class LoopCloser:
         info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
         self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
 
-    def ConsistentLoops(self, cfg=None, var_t=None, var_r=None):
+    def ConsistentLoops(self, cfg=None, var_t=None, var_r=None, odom_covariance=None):
         """The loops of AddLoop that agree with one another over the inserted poses (loops.LoopConsistency on self.poses and
         self.loops; cfg: a LoopConsistencyConfig, whose q_t and q_r say how good the odometry is per entry) -> its dict.  var_t,
         var_r: one number for all loops or one per loop; by default 3 / trace(Omega_vv) and 3 / trace(Omega_ww) of each loop's
-        information, the weights of PoseGraph.Initialize inverted."""
-        from .loops import LoopConsistency
+        information, the weights of PoseGraph.Initialize inverted.
+        odom_covariance: the 6 x 6 covariance of one odometry step (or [n - 1, 6, 6], one per step); then the covariance model runs
+        (loops.LoopConsistencyCov), each loop's covariance being the symmetrised inverse of its information, cfg's q_t and q_r stay 0
+        and var_t, var_r are not used.  Without it every result is what it was."""
+        from .loops import LoopConsistency, LoopConsistencyCov
         info = np.stack([l[3] for l in self.loops]) if self.loops else np.zeros((0, 6, 6))
+        if odom_covariance is not None:
+            cov = np.linalg.inv(info) if self.loops else info
+            cov = 0.5 * (cov + cov.transpose(0, 2, 1))
+            Z = np.stack([l[2] for l in self.loops]) if self.loops else np.zeros((0, 4, 4))
+            return LoopConsistencyCov(np.stack(self.poses), [l[0] for l in self.loops], [l[1] for l in self.loops], Z, cov, odom_covariance, cfg,
+                                      self.ctx)
         if var_t is None:
             var_t = 3.0 / ((info[:, 0, 0] + info[:, 1, 1]) + info[:, 2, 2])
         if var_r is None:
@@ -279,7 +288,7 @@ class LoopCloser:
         return LoopConsistency(np.stack(self.poses), [l[0] for l in self.loops], [l[1] for l in self.loops], Z, var_t, var_r, cfg, self.ctx)
 
     def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False,
-              consistency=None):
+              consistency=None, odom_covariance=None):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
@@ -290,13 +299,14 @@ class LoopCloser:
         under "initialize" in the returned dict: the start that a long loop needs, whose drift is far outside Gauss-Newton's reach.  A
         false loop pulls a linear initialization as hard as a true one: Huber acts only in Optimize, so verify loops before adding
         them.  consistency: a LoopConsistencyConfig; then only the members of ConsistentLoops(consistency) are added to the graph, in
-        their original order, and its dict is put under "consistency".  The defaults leave every result as it was."""
+        their original order, and its dict is put under "consistency"; odom_covariance is handed to ConsistentLoops with it (the
+        covariance model) and is not used otherwise.  The defaults leave every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
             raise ElmError("LoopCloser.Close: at least two entries")
         P = np.stack(self.poses)
-        kept = self.ConsistentLoops(consistency) if consistency is not None else None
+        kept = self.ConsistentLoops(consistency, odom_covariance=odom_covariance) if consistency is not None else None
         loops = self.loops if kept is None else [self.loops[k] for k in kept["members"]]
         pg = PoseGraph(n, n - 1 + max(len(loops), 1), self.ctx)
         try:

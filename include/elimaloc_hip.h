@@ -1054,6 +1054,7 @@ int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const
 #include "elimaloc_hip_posegraph_precond.h"
 #include "elimaloc_hip_posegraph_init.h"
 #include "elimaloc_hip_loops.h"
+#include "elimaloc_hip_loopcov.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -46,14 +46,15 @@ def noise(rng, n, sigma_r, sigma_t):
     return T
 
 
-def fixture(L, seed=0):
+def fixture(L, seed=0, sigma_r=1e-4, sigma_t=0.01):
+    """sigma_r, sigma_t: the odometry's noise per step (the defaults are this tool's own fixture)"""
     rng = np.random.default_rng(seed)
     a = 2.0 * np.pi * np.arange(N_POSES) / PERIOD
     radius = PERIOD / (2.0 * np.pi)
     truth = np.tile(np.eye(4), (N_POSES, 1, 1))
     truth[:, :3, :3] = rotvec(np.stack([0.0 * a, 0.0 * a, a + np.pi / 2.0], 1))
     truth[:, 0, 3], truth[:, 1, 3] = radius * np.cos(a), radius * np.sin(a)
-    step = np.linalg.inv(truth[:-1]) @ truth[1:] @ noise(rng, N_POSES - 1, 1e-4, 0.01)
+    step = np.linalg.inv(truth[:-1]) @ truth[1:] @ noise(rng, N_POSES - 1, sigma_r, sigma_t)
     poses = np.empty_like(truth)
     poses[0] = truth[0]
     for k in range(N_POSES - 1):
