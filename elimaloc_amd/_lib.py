@@ -354,6 +354,18 @@ class LoopCovResultC(C.Structure):
                 ("chain_ms", C.c_double), ("adjacency_ms", C.c_double), ("greedy_ms", C.c_double)]
 
 
+class PoseGraphCovConfigC(C.Structure):
+    """elm_posegraph_cov_config (include/elimaloc_hip_posegraph_cov.h)."""
+    _fields_ = [("lambda_", C.c_double), ("pcg_rel_tol", C.c_double), ("pcg_max_iterations", C.c_int32), ("pcg_check_every", C.c_int32),
+                ("scratch_bytes", C.c_uint64)]
+
+
+class PoseGraphCovStatsC(C.Structure):
+    """elm_posegraph_cov_stats."""
+    _fields_ = [("n_columns", C.c_int32), ("n_converged", C.c_int32), ("passes", C.c_int32), ("iterations_max", C.c_int32),
+                ("rel_residual_max", C.c_double), ("ms_device", C.c_double), ("scratch_bytes", C.c_uint64)]
+
+
 LOOPS_MAX, LOOPS_MAX_S = 16384, 2048
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
 PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
@@ -598,9 +610,15 @@ DECLS_LOOPCOV = {  # include/elimaloc_hip_loopcov.h (loop closing: pairwise cons
     "elm_loopcov_pair_terms": _sig(dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp),
     "elm_loopcov_consistency": _sig(vp, dp, szt, i32p, i32p, dp, dp, szt, dp, szt, P(LoopsConfigC), P(LoopCovResultC), u8p, i32p, u64p, dp),
 }
+DECLS_PGCOV = {  # include/elimaloc_hip_posegraph_cov.h (the pose graph's marginal and relative covariances)
+    "elm_posegraph_cov_config_default": _sig(P(PoseGraphCovConfigC), ret=None),
+    "elm_posegraph_covariance": _sig(vp, vp, i32p, szt, i32p, szt, P(PoseGraphCovConfigC), dp, dp, i32p, u8p, P(PoseGraphCovStatsC)),
+    "elm_posegraph_relative_covariance": _sig(vp, vp, i32p, i32p, szt, P(PoseGraphCovConfigC), dp, P(PoseGraphCovStatsC)),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
 EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
 EXPORTS_LOOPCOV = list(DECLS_LOOPCOV)
+EXPORTS_PGCOV = list(DECLS_PGCOV)
 
 _LIB = None
 
@@ -614,7 +632,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -512,6 +512,40 @@ void launch_pgc_factor(hipStream_t s, const PgDev& d, const PgcDev& c, double la
 // once the stop word of iteration `it` is set.  What launch_pg_pcg_begin and launch_pg_pcg_iteration queue for a chain; N >= 1
 void launch_pgc_apply(hipStream_t s, const PgDev& d, const PgcDev& c, uint32_t it, int gate, int first);
 
+// pose graph, covariance columns (elm_k_pgcov.hip; the contract is include/elimaloc_hip_posegraph_cov.h): the
+// device's view of one pass of elm_posegraph_covariance, G groups of 64 columns solved together.  Column col0 + 64 g + lane of the call
+// is lane `lane` of group g; the vectors are [G][N][6][64], the per-column words [G][64] (rz and stop twice, by the iteration's parity).
+constexpr uint32_t kPgcovLanes = 64;         // the columns of a group: the lane is the column
+constexpr uint32_t kPgcovNodesPerWave = 4;   // the nodes a wavefront of the per-node kernels takes one after another
+constexpr uint32_t kPgcovNodesPerBlock = 4 * kPgcovNodesPerWave;
+constexpr uint32_t kPgcovReduceWaves = 16;   // the wavefronts that add a group's slots
+constexpr uint32_t kPgcovMaxGroups = 65535;  // grid.y of the per-node kernels
+struct PgCovDev {
+    uint32_t G, col0, n_cols;     // the pass's groups, its first column (a multiple of 64), the call's columns (6 m)
+    const int32_t* col_nodes;     // [m]
+    double *x, *r, *z, *p, *q;    // [G][N][6][64]
+    double *slot_pq, *slot_rz;    // [pgcov_blocks(N)][G][64]
+    double *alpha, *beta, *rz0, *rzf; // [G][64]; rzf: r^T z after the column's last iteration
+    double* rz;                   // [2][G][64]
+    uint32_t* stop;               // [2][G][64]
+    uint32_t *iters, *converged;  // [G][64]
+    uint32_t* gstop;              // [2][G]: all 64 columns of the group have stopped
+    uint32_t* all_stop;           // [2]: every group has (what the host reads)
+    // the chain preconditioner's apply (null with block Jacobi): the reduced right-hand side, then the solution, of every level, and what
+    // a segment's eliminations add to the last node of the segment before
+    double* y;                    // [G][y_pad][6][64], y_pad the padded nodes of all levels (PgcLevel::off)
+    double* be;                   // [G][y_segs][6][64], y_segs the segments of all levels (PgcLevel::soff)
+    uint32_t y_pad, y_segs;
+};
+constexpr uint32_t kPgccovWaves = 16;        // the wavefronts of a (segment, group) workgroup of the chain apply
+constexpr uint32_t pgcov_blocks(uint32_t N) { return (N + kPgcovNodesPerBlock - 1) / kPgcovNodesPerBlock; }
+// after launch_pg_nodes at the same lambda and a memset of the pass's vectors to zero; N >= 1, 1 <= G <= kPgcovMaxGroups
+// chain: null for block Jacobi, else the factor of launch_pgc_factor at the same lambda (c.y and c.be are then set)
+void launch_pgcov_begin(hipStream_t s, const PgDev& d, const PgCovDev& c, const PgcDev* chain, double tol);
+void launch_pgcov_iteration(hipStream_t s, const PgDev& d, const PgCovDev& c, const PgcDev* chain, double lambda, double tol, uint32_t it);
+// out [n_pairs][36]: block k is Sigma(row[k], col_nodes[ci[k]]) as solved; only the entries whose column is in the pass are written
+void launch_pgcov_gather(hipStream_t s, const PgDev& d, const PgCovDev& c, const uint32_t* ci, const int32_t* row, uint32_t n_pairs, double* out);
+
 // pose graph, linear initialization (elm_k_pginit.hip; the contract is include/elimaloc_hip_posegraph_init.h).
 // The two term kernels fill gi, gj, Hii, Hij, Hjj of the view as launch_pg_linearize does, for launch_pg_nodes (sum = 1, lambda = 0)
 // and the conjugate gradients to follow; the apply kernels read the solve's x and the active flags.

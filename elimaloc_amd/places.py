@@ -288,7 +288,7 @@ class LoopCloser:
         return LoopConsistency(np.stack(self.poses), [l[0] for l in self.loops], [l[1] for l in self.loops], Z, var_t, var_r, cfg, self.ctx)
 
     def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False,
-              consistency=None, odom_covariance=None):
+              consistency=None, odom_covariance=None, marginals=None):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
@@ -300,7 +300,9 @@ class LoopCloser:
         false loop pulls a linear initialization as hard as a true one: Huber acts only in Optimize, so verify loops before adding
         them.  consistency: a LoopConsistencyConfig; then only the members of ConsistentLoops(consistency) are added to the graph, in
         their original order, and its dict is put under "consistency"; odom_covariance is handed to ConsistentLoops with it (the
-        covariance model) and is not used otherwise.  The defaults leave every result as it was."""
+        covariance model) and is not used otherwise.  marginals: node indices; then one Linearize at the final poses with cfg's huber_k
+        and PoseGraph.Marginals(marginals) put the covariances [m, 6, 6] under "marginals" and the call's stats under
+        "marginals_stats", solved with the same preconditioner.  The defaults leave every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
@@ -325,6 +327,9 @@ class LoopCloser:
             if kept is not None:
                 res["consistency"] = kept
             out = pg.Poses()
+            if marginals is not None:
+                pg.Linearize(0.0 if cfg is None else float(cfg.huber_k))
+                res["marginals"], res["marginals_stats"] = pg.Marginals(marginals, return_stats=True)
         finally:
             pg.close()
         if apply:

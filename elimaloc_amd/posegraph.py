@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ElmError, PG_PRECOND, PG_STOP, PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC,
-                   PoseGraphTraceC, PoseGraphInitConfigC, PoseGraphInitResultC, check)
+                   PoseGraphTraceC, PoseGraphInitConfigC, PoseGraphInitResultC, PoseGraphCovConfigC, PoseGraphCovStatsC, check)
 from ._marshal import _Owned, _config, _dp, _pose_block, _ptr
 from .context import default_context
 
@@ -23,6 +23,21 @@ def PoseGraphInitConfig(**kw):
     """elm_posegraph_init_config with its defaults (both solves to 1e-8 in at most 50 000 iterations checked every 32;
     stages = PG_INIT_ROT | PG_INIT_TRANS, or one of them)."""
     return _config("PoseGraphInitConfig", PoseGraphInitConfigC, "elm_posegraph_init_config_default", kw)
+
+
+def PoseGraphCovConfig(**kw):
+    """elm_posegraph_cov_config with its defaults (lambda_ 0, every column to 1e-10 in at most 20 000 iterations checked every 32,
+    scratch_bytes 0 = the default cap of 2 GiB)."""
+    return _config("PoseGraphCovConfig", PoseGraphCovConfigC, "elm_posegraph_cov_config_default", kw)
+
+
+def _cov_stats(st):
+    return dict(n_columns=int(st.n_columns), n_converged=int(st.n_converged), passes=int(st.passes), iterations_max=int(st.iterations_max),
+                rel_residual_max=float(st.rel_residual_max), ms_device=float(st.ms_device), scratch_bytes=int(st.scratch_bytes))
+
+
+def _nodes(v):
+    return np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1))
 
 
 def EdgeTerms(Ti, Tj, Z):
@@ -172,5 +187,65 @@ class PoseGraph(_Owned):
             out["rows"], out["v"] = rows[:N], v[:N]
         return out
 
+    def Covariance(self, cols, rows=None, cfg=None):
+        """Blocks of the inverse of the current linearization's normal equations (include/elimaloc_hip_posegraph_cov.h), in the tangent
+        [v; w] -> (diag [m, 6, 6]: Sigma(col, col) symmetrised, cross [m, n_rows, 6, 6]: Sigma(row, col) as solved, info: the call's
+        stats plus iterations [m, 6] and converged [m, 6] per column).  An inactive node has zero blocks.  The object's preconditioner is
+        honoured."""
+        cfg = cfg if cfg is not None else PoseGraphCovConfig()
+        cols, rows = _nodes(cols), _nodes([] if rows is None else rows)
+        m, n = cols.size, rows.size
+        diag, cross = np.zeros((max(m, 1), 6, 6)), np.zeros((max(m, 1), max(n, 1), 6, 6))
+        its, conv = np.zeros((max(m, 1), 6), np.int32), np.zeros((max(m, 1), 6), np.uint8)
+        st = PoseGraphCovStatsC()
+        self._call("elm_posegraph_covariance", _ptr(cols) if m else None, m, _ptr(rows) if n else None, n, C.byref(cfg), _dp(diag),
+                   _dp(cross) if n else None, _ptr(its), _ptr(conv), C.byref(st))
+        info = _cov_stats(st)
+        info["iterations"], info["converged"] = its[:m], conv[:m].astype(bool)
+        return diag[:m], cross[:m, :n], info
+
+    def Marginals(self, nodes, cfg=None, return_stats=False):
+        """The marginal covariances [m, 6, 6] of the given nodes under the current linearization (with return_stats also Covariance's
+        info)."""
+        diag, _, info = self.Covariance(nodes, None, cfg)
+        return (diag, info) if return_stats else diag
+
+    def RelativeCovariance(self, a, b, cfg=None, return_stats=False):
+        """The covariance [L, 6, 6] of the residual coordinates of T_a^-1 T_b at the current poses, from the joint covariance of the
+        two nodes and the edge Jacobians."""
+        cfg = cfg if cfg is not None else PoseGraphCovConfig()
+        a, b = _nodes(a), _nodes(b)
+        if a.size != b.size:
+            raise ElmError("PoseGraph.RelativeCovariance: one b per a")
+        out = np.zeros((max(a.size, 1), 6, 6))
+        st = PoseGraphCovStatsC()
+        self._call("elm_posegraph_relative_covariance", _ptr(a) if a.size else None, _ptr(b) if a.size else None, a.size, C.byref(cfg), _dp(out),
+                   C.byref(st))
+        return (out[:a.size], _cov_stats(st)) if return_stats else out[:a.size]
+
     def _destroy(self, h):
         _lib.lib().elm_posegraph_destroy(h)
+
+
+def LoopGate(pg, a, b, Z, information, cfg=None):
+    """The Mahalanobis distance of candidate loops (a[k], b[k], Z[k], information[k]) to the current estimate of pg -> d2 [L]:
+    d2 = r^T (Sigma_rel + information^-1)^-1 r with r the residual of EdgeTerms(T_a, T_b, Z) and Sigma_rel PoseGraph.RelativeCovariance.
+    Under the model d2 of a true loop is chi^2 with 6 degrees of freedom (16.81 is its 99 % point).  numpy on top of RelativeCovariance;
+    pg needs a valid linearization at the poses it holds."""
+    a, b = _nodes(a), _nodes(b)
+    L = a.size
+    Z = np.asarray(Z, dtype=np.float64).reshape(-1, 4, 4)
+    info = np.asarray(information, dtype=np.float64)
+    info = np.broadcast_to(info, (L, 6, 6)) if info.ndim == 2 else info.reshape(-1, 6, 6)
+    if b.size != L or Z.shape[0] != L or info.shape[0] != L:
+        raise ElmError("LoopGate: one b, Z and information per a")
+    if not L:
+        return np.zeros(0)
+    S = pg.RelativeCovariance(a, b, cfg)
+    nodes = np.unique(np.concatenate([a, b]))
+    T = {int(v): pg.Poses(int(v), 1)[0] for v in nodes}
+    d2 = np.zeros(L)
+    for k in range(L):
+        r, _, _ = EdgeTerms(T[int(a[k])], T[int(b[k])], Z[k])
+        d2[k] = float(r @ np.linalg.solve(S[k] + np.linalg.inv(info[k]), r))
+    return d2

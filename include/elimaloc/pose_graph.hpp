@@ -168,6 +168,47 @@ public:
         if (v) v->pop_back();
         return res;
     }
+    // Blocks of the inverse of the current linearization's normal equations (elimaloc_hip_posegraph_cov.h; this object's preconditioner), row-major
+    // 6 x 6 in the tangent [v; w].  Covariance: diag [cols][36] = Sigma(col, col) symmetrised, cross [cols][rows][36] = Sigma(row, col) as
+    // solved (either may be NULL; rows may be NULL for the diagonal blocks only).  config: NULL for the defaults.
+    inline elm_posegraph_cov_stats Covariance(const std::vector<int32_t>& cols, const std::vector<int32_t>* rows, std::vector<double>* diag,
+                                              std::vector<double>* cross, const elm_posegraph_cov_config* config = nullptr) {
+        elm_posegraph_cov_config c;
+        elm_posegraph_cov_config_default(&c);
+        if (config) c = *config;
+        const size_t m = cols.size(), n = rows ? rows->size() : 0;
+        if (diag) diag->assign(36 * m + 1, 0.0);
+        if (cross) cross->assign(36 * m * n + 1, 0.0);
+        elm_posegraph_cov_stats st;
+        elimaloc::check(elm_posegraph_covariance(VoxelHashMap::ctx(), pg_, m ? cols.data() : nullptr, m, n ? rows->data() : nullptr, n, &c,
+                                                 diag ? diag->data() : nullptr, (cross && n) ? cross->data() : nullptr, nullptr, nullptr, &st),
+                        VoxelHashMap::ctx(), "elm_posegraph_covariance");
+        if (diag) diag->pop_back();
+        if (cross) cross->pop_back();
+        return st;
+    }
+    // the marginal covariances [nodes][36]
+    inline std::vector<double> Marginals(const std::vector<int32_t>& nodes, const elm_posegraph_cov_config* config = nullptr,
+                                         elm_posegraph_cov_stats* stats = nullptr) {
+        std::vector<double> diag;
+        const elm_posegraph_cov_stats st = Covariance(nodes, nullptr, &diag, nullptr, config);
+        if (stats) *stats = st;
+        return diag;
+    }
+    // the covariances [pairs][36] of the residual coordinates of T_a^-1 T_b at the current poses
+    inline std::vector<double> RelativeCovariance(const std::vector<int32_t>& a, const std::vector<int32_t>& b,
+                                                  const elm_posegraph_cov_config* config = nullptr, elm_posegraph_cov_stats* stats = nullptr) {
+        elm_posegraph_cov_config c;
+        elm_posegraph_cov_config_default(&c);
+        if (config) c = *config;
+        elimaloc::check(a.size() == b.size() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "PoseGraph::RelativeCovariance: one b per a");
+        std::vector<double> cov(36 * a.size() + 1, 0.0);
+        elimaloc::check(elm_posegraph_relative_covariance(VoxelHashMap::ctx(), pg_, a.empty() ? nullptr : a.data(), a.empty() ? nullptr : b.data(),
+                                                          a.size(), &c, cov.data(), stats),
+                        VoxelHashMap::ctx(), "elm_posegraph_relative_covariance");
+        cov.pop_back();
+        return cov;
+    }
     // host only: the residual and Jacobians of one edge (row-major r[6], A[36], B[36])
     static inline void EdgeTerms(const elimaloc::Matrix4d& Ti, const elimaloc::Matrix4d& Tj, const elimaloc::Matrix4d& Z, double* r, double* A, double* B) {
         elimaloc::check(elm_posegraph_edge_terms(Ti.data(), Tj.data(), Z.data(), r, A, B), nullptr, "elm_posegraph_edge_terms");

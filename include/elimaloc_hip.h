@@ -1055,6 +1055,7 @@ int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const
 #include "elimaloc_hip_posegraph_init.h"
 #include "elimaloc_hip_loops.h"
 #include "elimaloc_hip_loopcov.h"
+#include "elimaloc_hip_posegraph_cov.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
