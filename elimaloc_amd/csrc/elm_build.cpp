@@ -1,6 +1,7 @@
 // elm_build.cpp -- the device map build (include/elimaloc_hip.h, "device map build"): the argument checks, the
 // scratch arrays, the stages of elm_k_build.hip queued on the context's stream with the few read-backs that size what follows (kept base
-// points, voxels, kept points), and the hand-over of the finished arrays to a map handle (elm_host::map_adopt).  Host-side C++17.
+// points, voxels, kept points), the stage times (elm_call.hpp's StreamEvents), and the hand-over of the finished arrays to a map handle
+// (elm_host::map_adopt).  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -40,22 +41,6 @@ struct Scratch {
     }
 };
 
-struct Events {
-    hipEvent_t ev[ELM_BUILD_STAGES + 1] = {};
-    int made = 0, used = 0;
-    ~Events() {
-        for (int k = 0; k < made; ++k) (void)hipEventDestroy(ev[k]);
-    }
-    hipError_t create() {
-        for (; made <= ELM_BUILD_STAGES; ++made) {
-            const hipError_t e = hipEventCreate(&ev[made]);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    hipError_t mark(hipStream_t st) { return hipEventRecord(ev[used++], st); }
-};
-
 // the stage times of this thread's last successful build
 thread_local uint64_t t_stage_ctx = 0;
 thread_local bool t_stage_valid = false;
@@ -93,10 +78,9 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const BuildInput& in, double v
     hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
     (void)hipGetLastError(); // drop stale errors of other libraries
     Scratch sc;
-    Events evs;
-    hipError_t e = evs.create();
-    unsigned* d_total = nullptr; // [0] a scan's sum, [1] the kernels' flags
-    if (e == hipSuccess) e = sc.get(&d_total, 2);
+    StreamEvents<ELM_BUILD_STAGES + 1> evs; // a mark before the first stage and one after each
+    unsigned* d_total = nullptr;            // [0] a scan's sum, [1] the kernels' flags
+    hipError_t e = sc.get(&d_total, 2);
     if (e != hipSuccess) return dev_error(ctx, what, e);
     unsigned* d_flags = d_total + 1;
 
@@ -239,11 +223,7 @@ int build_impl(elm_ctx* ctx, const elm_map* base, const BuildInput& in, double v
     if (e == hipSuccess) e = join(st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
     double ms[ELM_BUILD_STAGES];
-    for (int k = 0; k < ELM_BUILD_STAGES; ++k) {
-        float f = 0.f;
-        if (hipEventElapsedTime(&f, evs.ev[k], evs.ev[k + 1]) != hipSuccess) f = 0.f;
-        ms[k] = f;
-    }
+    for (int k = 0; k < ELM_BUILD_STAGES; ++k) ms[k] = evs.ms(k);
     const int rc = elm_host::map_adopt(ctx, sc.hand_on(d_pts), sc.hand_on(d_ranges), sc.hand_on(d_keys), n_pts, n_vox, N, vs, cap, out);
     if (rc == ELM_OK) {
         std::copy(ms, ms + ELM_BUILD_STAGES, t_stage_ms);

@@ -1,5 +1,5 @@
 // elm_index.cpp -- the search indices of a map: the dense and the two-level (tiled) cell grid, the neighbourhood lists, the voxel-mean
-// lists, and the choice among them (build_search_index).  Host-side C++17.
+// lists, and the choice among them (build_search_index); the device build's stage times are elm_call.hpp's StreamEvents.  Host-side C++17.
 #include <assert.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -11,8 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "elm_call.hpp"
 #include "elm_grid_layout.hpp"
-#include "elm_host_types.hpp"
 
 using namespace elm;
 using namespace elm_host;
@@ -539,27 +539,7 @@ struct GridScratch {
 };
 // hipEvents around the stages (elm_map_index_build_stages)
 static_assert(sizeof(elm_map::index_stage_ms) == ELM_INDEX_STAGES * sizeof(double), "one slot per stage");
-struct GridStageClock {
-    hipEvent_t ev[ELM_INDEX_STAGES + 1] = {};
-    int n = 0;
-    ~GridStageClock() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t mark(hipStream_t st) {
-        if (n > ELM_INDEX_STAGES) return hipSuccess;
-        hipError_t e = hipEventCreate(&ev[n]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n], st);
-        ++n;
-        return e;
-    }
-    void read(double ms[ELM_INDEX_STAGES]) const {
-        for (int k = 0; k < ELM_INDEX_STAGES; ++k) {
-            float f = 0.0f;
-            ms[k] = (k + 1 < n && ev[k] && ev[k + 1] && hipEventElapsedTime(&f, ev[k], ev[k + 1]) == hipSuccess) ? (double)f : 0.0;
-        }
-    }
-};
+using GridStageClock = elm_query::StreamEvents<ELM_INDEX_STAGES + 1>; // (a stage whose mark was never made reads as 0.0 ms)
 // what the sort and the scans need beside the table of entries + 4 words: 16 bytes per point (key and payload, twice), the histogram
 // of one radix pass and the workgroup sums of the longest scan
 static uint64_t grid_device_scratch_bytes(uint64_t n, uint64_t entries) {
@@ -681,7 +661,7 @@ static int build_cell_grid_device(elm_map* m, uint64_t max_cells) {
     if ((rc = grid_device_layout(m, clk, b, cells, 0u, d, c)) != ELM_OK) return rc;
     c.on_device = true;
     rc = dense_grid_finish(m, box, c, d, klo, vd, vcells);
-    if (rc == ELM_OK) clk.read(m->index_stage_ms);
+    for (int k = 0; rc == ELM_OK && k < ELM_INDEX_STAGES; ++k) m->index_stage_ms[k] = clk.ms(k);
     return rc;
 }
 // The two-level form on the device; results as build_cell_grid_device.
@@ -757,7 +737,7 @@ static int build_tiled_grid_device(elm_map* m) {
     if ((rc = grid_device_layout(m, clk, b, entries, (unsigned)(kTile * kTile), d, c)) != ELM_OK) return rc;
     c.on_device = true;
     rc = tiled_grid_finish(m, box, c, d, tnx, tny);
-    if (rc == ELM_OK) clk.read(m->index_stage_ms);
+    for (int k = 0; rc == ELM_OK && k < ELM_INDEX_STAGES; ++k) m->index_stage_ms[k] = clk.ms(k);
     return rc;
 }
 

@@ -1,7 +1,7 @@
 // elm_loopcov.cpp -- the loop consistency check with a propagated covariance (include/elimaloc_hip_loopcov.h): the
 // argument checks, the one upload, the chain covariance, the pair kernels, and the greedy loop of elm_loops_host.hpp on the kernels of
-// elm_k_loops.hip.  The launches are those of elm_k_loopcov.hip.  Each call owns one device allocation for its duration and keeps nothing
-// afterwards.  Host-side C++17.
+// elm_k_loops.hip.  The launches are those of elm_k_loopcov.hip.  Each call owns one device allocation (elm_call.hpp's DeviceBlob) for its
+// duration and keeps nothing afterwards.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -17,18 +17,6 @@ using namespace elm_query;
 using namespace elm_loops_host;
 
 namespace {
-
-bool finite36(const double* M) {
-    for (int q = 0; q < 36; ++q)
-        if (!isfinite(M[q])) return false;
-    return true;
-}
-bool symmetric36(const double* M) {
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            if (M[i * 6 + j] != M[j * 6 + i]) return false;
-    return true;
-}
 
 // the chain's preconditions that need no device: "" when they hold
 std::string chain_refusal(const double* poses16, size_t n, const double* Q36, size_t q_count) {
@@ -107,21 +95,14 @@ int chain_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t n, co
     const char* what = "elm_loopcov_chain";
     const ChainHost host(poses16, n, Q36, q_count);
     ChainArrays A;
-    Carver size{nullptr};
-    carve_chain(A, size, n, q_count);
-    double* d_W = size.take<double>(36 * n);
-    double* d_S = S_out ? size.take<double>(36 * n) : nullptr;
-    Blob blob;
-    blob.st = st;
-    hipError_t e = hipMalloc((void**)&blob.p, size.off);
-    if (e != hipSuccess) {
-        blob.p = nullptr;
-        return dev_error(ctx, what, e);
-    }
-    Carver real{blob.p};
-    carve_chain(A, real, n, q_count);
-    d_W = real.take<double>(36 * n);
-    d_S = S_out ? real.take<double>(36 * n) : nullptr;
+    double *d_W = nullptr, *d_S = nullptr;
+    DeviceBlob blob(st);
+    hipError_t e = blob.alloc([&](Carver& c) {
+        carve_chain(A, c, n, q_count);
+        d_W = c.take<double>(36 * n);
+        d_S = S_out ? c.take<double>(36 * n) : nullptr;
+    });
+    if (e != hipSuccess) return dev_error(ctx, what, e);
     e = host.upload(st, A);
     if (e == hipSuccess) e = launched([&] {
         launch_lcv_chain(st, A.c);
@@ -130,8 +111,8 @@ int chain_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t n, co
     std::vector<double> W(36 * n), S(S_out ? 36 * n : 0); // the outputs stay untouched unless everything succeeds
     if (e == hipSuccess) e = hipMemcpyAsync(W.data(), d_W, W.size() * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && S_out) e = hipMemcpyAsync(S.data(), d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
+    const int rc = join(ctx, st, e, what);
+    if (rc != ELM_OK) return rc;
     memcpy(W_out, W.data(), W.size() * sizeof(double));
     if (S_out) memcpy(S_out, S.data(), S.size() * sizeof(double));
     return ELM_OK;
@@ -180,35 +161,27 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     std::vector<unsigned long long> cand0;
     ChainArrays C;
     LcvArrays A;
-    Carver size{nullptr};
-    carve_chain(C, size, n, q_count);
-    carve_loops(A, size, L, s_out != nullptr);
-    Blob blob;
-    blob.st = st;
-    hipError_t e = hipMalloc((void**)&blob.p, size.off);
-    if (e != hipSuccess) {
-        blob.p = nullptr;
-        return dev_error(ctx, what, e);
-    }
-    Carver real{blob.p};
-    carve_chain(C, real, n, q_count);
-    carve_loops(A, real, L, s_out != nullptr);
-    Events<4> ev;
-    for (int q = 0; q < 4 && e == hipSuccess; ++q) e = hipEventCreate(&ev.ev[q]);
-    if (e == hipSuccess) e = host.upload(st, C);
+    DeviceBlob blob(st);
+    hipError_t e = blob.alloc([&](Carver& c) {
+        carve_chain(C, c, n, q_count);
+        carve_loops(A, c, L, s_out != nullptr);
+    });
+    if (e != hipSuccess) return dev_error(ctx, what, e);
+    StreamEvents<4> ev;
+    e = host.upload(st, C);
     if (e == hipSuccess) e = hipMemcpyAsync(A.a, a, L * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.b, b, L * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.Z, zrows.data(), zrows.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.Sigma, sig.data(), sig.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = greedy_reset(st, A.g, cand0);
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[0], st);
+    if (e == hipSuccess) e = ev.mark(st);
     if (e == hipSuccess) e = launched([&] { launch_lcv_chain(st, C.c); });
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[1], st);
+    if (e == hipSuccess) e = ev.mark(st);
     if (e == hipSuccess) e = launched([&] { launch_lcv_adjacency(st, C.c, A.d, c.gamma); });
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[2], st);
+    if (e == hipSuccess) e = ev.mark(st);
     LcState state{};
     if (e == hipSuccess) e = greedy_run(st, A.g, c.steps_per_batch, state);
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[3], st);
+    if (e == hipSuccess) e = ev.mark(st);
     std::vector<int32_t> deg(L), nan_row(L);
     std::vector<uint8_t> member(L);
     std::vector<unsigned long long> adj(adj_out ? L * W : 0);
@@ -218,10 +191,8 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     if (e == hipSuccess) e = hipMemcpyAsync(member.data(), A.g.member, L, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && adj_out) e = hipMemcpyAsync(adj.data(), A.d.adj, adj.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && s_out) e = hipMemcpyAsync(s.data(), A.d.s, s.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    for (int q = 0; q < 3 && e == hipSuccess; ++q) e = hipEventElapsedTime(&ms[q], ev.ev[q], ev.ev[q + 1]);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
+    const int rc = join(ctx, st, e, what);
+    if (rc != ELM_OK) return rc;
     int64_t sum = 0, nans = 0;
     for (size_t k = 0; k < L; ++k) {
         sum += deg[k]; // of step 0: every loop is a candidate, no -1
@@ -235,9 +206,9 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     result->steps = (int32_t)state.size; // every step before the stop makes one pick
     result->adjacent_pairs = sum / 2;
     result->non_finite_pairs = nans / 2;
-    result->chain_ms = ms[0];
-    result->adjacency_ms = ms[1];
-    result->greedy_ms = ms[2];
+    result->chain_ms = ev.ms(0);
+    result->adjacency_ms = ev.ms(1);
+    result->greedy_ms = ev.ms(2);
     return ELM_OK;
 }
 
@@ -277,17 +248,15 @@ extern "C" int elm_loopcov_pair_terms(const double* T0, const double* Ta, const 
 extern "C" int elm_loopcov_chain(elm_ctx* ctx, const double* poses16, size_t n, const double* Q36, size_t q_count, double* W_out, double* S_out) {
     const char* what = "elm_loopcov_chain";
     if (!ctx) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, what);
+    const int rc = check_call(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
     return guard_alloc(ctx, what, [&]() -> int {
         const std::string why = !W_out ? std::string("a NULL W_out") : chain_refusal(poses16, n, Q36, q_count);
         if (!why.empty()) {
             elm_host::ctx_set_error(ctx, std::string(what) + ": " + why);
             return ELM_ERR_INVALID;
         }
-        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-        return chain_impl(ctx, (hipStream_t)elm_ctx_stream(ctx), poses16, n, Q36, q_count, W_out, S_out);
+        return on_stream(ctx, what, [&](hipStream_t st) { return chain_impl(ctx, st, poses16, n, Q36, q_count, W_out, S_out); });
     });
 }
 
@@ -296,9 +265,8 @@ extern "C" int elm_loopcov_consistency(elm_ctx* ctx, const double* poses16, size
                                        elm_loopcov_result* result, uint8_t* member_out, int32_t* degree_out, uint64_t* adj_out, double* s_out) {
     const char* what = "elm_loopcov_consistency";
     if (!ctx) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, what);
+    const int rc = check_call(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
     return guard_alloc(ctx, what, [&]() -> int {
         const std::string why = refusal(poses16, n, a, b, Z16, Sigma36, L, Q36, q_count, cfg, result, member_out, degree_out, s_out);
         if (!why.empty()) {
@@ -309,8 +277,8 @@ extern "C" int elm_loopcov_consistency(elm_ctx* ctx, const double* poses16, size
             memset(result, 0, sizeof(*result));
             return ELM_OK;
         }
-        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-        return consistency_impl(ctx, (hipStream_t)elm_ctx_stream(ctx), poses16, n, a, b, Z16, Sigma36, L, Q36, q_count, *cfg, result, member_out,
-                                degree_out, adj_out, s_out);
+        return on_stream(ctx, what, [&](hipStream_t st) {
+            return consistency_impl(ctx, st, poses16, n, a, b, Z16, Sigma36, L, Q36, q_count, *cfg, result, member_out, degree_out, adj_out, s_out);
+        });
     });
 }

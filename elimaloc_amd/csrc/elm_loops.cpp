@@ -1,7 +1,7 @@
 // elm_loops.cpp -- the loop consistency check (include/elimaloc_hip_loops.h): the argument checks, the one upload
 // of poses, loops and variances, the pair kernel, and the greedy loop (elm_loops_host.hpp) that queues steps_per_batch steps between two
-// reads of the device's state (the pattern of the pose graph's conjugate gradients).  The launches are those of elm_k_loops.hip.  The call owns one
-// device allocation for its duration and keeps nothing afterwards.  Host-side C++17.
+// reads of the device's state (elm_call.hpp's run_batched, as the pose graph's conjugate gradients are).  The launches are those of
+// elm_k_loops.hip.  The call owns one device allocation (DeviceBlob) for its duration and keeps nothing afterwards.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -100,44 +100,32 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     for (size_t k = 0; k < L; ++k) pose_rows12(Z16 + 16 * k, &zrows[12 * k]);
     std::vector<unsigned long long> cand0;
     LcArrays A;
-    Carver size{nullptr};
-    carve(A, size, n, L, s_out != nullptr);
-    Blob blob;
-    blob.st = st;
-    hipError_t e = hipMalloc((void**)&blob.p, size.off);
-    if (e != hipSuccess) {
-        blob.p = nullptr;
-        return dev_error(ctx, what, e);
-    }
-    Carver real{blob.p};
-    carve(A, real, n, L, s_out != nullptr);
+    DeviceBlob blob(st);
+    hipError_t e = blob.alloc([&](Carver& c) { carve(A, c, n, L, s_out != nullptr); });
+    if (e != hipSuccess) return dev_error(ctx, what, e);
     const LcDev& d = A.d;
-    Events<3> ev;
-    for (int q = 0; q < 3 && e == hipSuccess; ++q) e = hipEventCreate(&ev.ev[q]);
-    if (e == hipSuccess) e = hipMemcpyAsync(A.poses, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    StreamEvents<3> ev;
+    e = hipMemcpyAsync(A.poses, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.a, a, L * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.b, b, L * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.Z, zrows.data(), zrows.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.var_t, var_t, L * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(A.var_r, var_r, L * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = greedy_reset(st, d, cand0);
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[0], st);
+    if (e == hipSuccess) e = ev.mark(st);
     if (e == hipSuccess) e = launched([&] { launch_lc_adjacency(st, d, c.q_t, c.q_r, c.gamma); });
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[1], st);
+    if (e == hipSuccess) e = ev.mark(st);
     LcState state{};
     if (e == hipSuccess) e = greedy_run(st, d, c.steps_per_batch, state);
-    if (e == hipSuccess) e = hipEventRecord(ev.ev[2], st);
+    if (e == hipSuccess) e = ev.mark(st);
     std::vector<int32_t> deg(L);
     std::vector<uint8_t> member(L);
     if (e == hipSuccess) e = hipMemcpyAsync(deg.data(), d.deg0, L * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(member.data(), d.member, L, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && adj_out) e = hipMemcpyAsync(adj_out, d.adj, L * W * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && s_out) e = hipMemcpyAsync(s_out, d.s, L * L * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms_adj = 0.0f, ms_greedy = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms_adj, ev.ev[0], ev.ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms_greedy, ev.ev[1], ev.ev[2]);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
+    const int rc = join(ctx, st, e, what);
+    if (rc != ELM_OK) return rc;
     int64_t sum = 0;
     for (size_t k = 0; k < L; ++k) sum += deg[k]; // of step 0: every loop is a candidate, no -1
     memcpy(degree_out, deg.data(), L * sizeof(int32_t));
@@ -145,8 +133,8 @@ int consistency_impl(elm_ctx* ctx, hipStream_t st, const double* poses16, size_t
     result->size = (int32_t)state.size;
     result->steps = (int32_t)state.size; // every step before the stop makes one pick
     result->adjacent_pairs = sum / 2;
-    result->adjacency_ms = ms_adj;
-    result->greedy_ms = ms_greedy;
+    result->adjacency_ms = ev.ms(0);
+    result->greedy_ms = ev.ms(1);
     return ELM_OK;
 }
 
@@ -157,9 +145,8 @@ extern "C" int elm_loops_consistency(elm_ctx* ctx, const double* poses16, size_t
                                      uint8_t* member_out, int32_t* degree_out, uint64_t* adj_out, double* s_out) {
     const char* what = "elm_loops_consistency";
     if (!ctx) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, what);
+    const int rc = check_call(ctx, what);
     if (rc != ELM_OK) return rc;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
     return guard_alloc(ctx, what, [&]() -> int {
         const std::string why = refusal(poses16, n, a, b, Z16, var_t, var_r, L, cfg, result, member_out, degree_out, s_out);
         if (!why.empty()) {
@@ -170,8 +157,8 @@ extern "C" int elm_loops_consistency(elm_ctx* ctx, const double* poses16, size_t
             memset(result, 0, sizeof(*result));
             return ELM_OK;
         }
-        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-        return consistency_impl(ctx, (hipStream_t)elm_ctx_stream(ctx), poses16, n, a, b, Z16, var_t, var_r, L, *cfg, result, member_out, degree_out,
-                                adj_out, s_out);
+        return on_stream(ctx, what, [&](hipStream_t st) { // (the preconditions above need no device: they come first)
+            return consistency_impl(ctx, st, poses16, n, a, b, Z16, var_t, var_r, L, *cfg, result, member_out, degree_out, adj_out, s_out);
+        });
     });
 }

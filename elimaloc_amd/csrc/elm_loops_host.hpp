@@ -1,11 +1,9 @@
-// elm_loops_host.hpp -- what the two loop consistency calls share on the host (elm_loops.cpp, elm_loopcov.cpp): the one device allocation
-// of a call and its carving, the call's stream events, the checks on the loops themselves, and the greedy loop that queues
-// steps_per_batch steps between two reads of the device's state.  Host-side C++17, everything inline.
+// elm_loops_host.hpp -- what the two loop consistency calls share on the host (elm_loops.cpp, elm_loopcov.cpp) beyond the call skeleton
+// of elm_call.hpp: the limit on the poses, the greedy arrays' carving and reset, and the greedy loop as a run_batched of steps_per_batch
+// steps between two reads of the device's state.  Host-side C++17, everything inline.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <string>
 #include <vector>
 
 #include "elm_dev_loops.hpp"
@@ -13,38 +11,9 @@
 
 namespace elm_loops_host {
 
+using elm_query::Carver;
+
 constexpr size_t kLcMaxPoses = (size_t)1 << 20;
-
-// the device arrays of one call carved from one allocation, each aligned to 256 bytes (base == nullptr: the size alone)
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) / 256 * 256;
-        return p;
-    }
-};
-
-struct Blob { // the call's one device allocation, released when the call ends however it ends (its stream joined first)
-    char* p = nullptr;
-    hipStream_t st = nullptr;
-    ~Blob() {
-        if (!p) return;
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(p);
-    }
-};
-
-template <int N>
-struct Events { // the marks of a call on its stream
-    hipEvent_t ev[N] = {};
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 // the greedy arrays of an LcDev (adj aside) from the carver
 inline void carve_greedy(elm::LcDev& d, Carver& c, size_t L) {
@@ -71,19 +40,9 @@ inline hipError_t greedy_reset(hipStream_t st, const elm::LcDev& d, std::vector<
 // The greedy loop: a clique has at most L members, and the step after the last pick would only set the stop word.  The stream is joined
 // after every batch; state holds the device's when it returns.
 inline hipError_t greedy_run(hipStream_t st, const elm::LcDev& d, int32_t steps_per_batch, elm::LcState& state) {
-    const size_t L = d.L;
-    hipError_t e = hipSuccess;
-    uint32_t it = 0;
-    while (e == hipSuccess) {
-        const uint32_t upto = (uint32_t)std::min<uint64_t>((uint64_t)it + (uint64_t)steps_per_batch, L);
-        e = elm_query::launched([&] {
-            for (; it < upto; ++it) elm::launch_lc_step(st, d, it);
-        });
-        if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(elm::LcState), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess || state.stop[it & 1u] || it >= L) break;
-    }
-    return e;
+    return elm_query::run_batched(
+        st, steps_per_batch, d.L, [&](uint32_t it) { elm::launch_lc_step(st, d, it); }, (const elm::LcState*)d.state, &state,
+        [&](uint32_t it) { return state.stop[it & 1u] != 0; });
 }
 
 } // namespace elm_loops_host

@@ -2,7 +2,7 @@
 // section 20): the object (one owned local map, the pose history, the last inserted pose), the keyframe test and the constant-velocity
 // prediction in float64 on the host, and the step -- one elm_register_batch against the local map, one elm_map_build_device_from that
 // forgets what lies behind and inserts the scan, the covariances the method reads.  Everything on the device goes through the public
-// entry points; nothing here launches a kernel.  Host-side C++17.
+// entry points; nothing here launches a kernel (who may call is elm_call.hpp's check_call).  Host-side C++17.
 #include <math.h>
 #include <string.h>
 
@@ -64,9 +64,7 @@ bool is_keyframe(const elm_odometry_config& c, const double K[16], const double 
 
 int check_odom(const elm_odometry* o, const char* what) {
     if (!o || !elm_host::ctx_is_alive(o->ctx, o->ctx_id)) return ELM_ERR_INVALID;
-    const int rc = check_plain(o->ctx, what);
-    if (rc != ELM_OK) return rc;
-    return o->ctx->in_flight ? ELM_ERR_INVALID : ELM_OK;
+    return check_call(o->ctx, what);
 }
 
 void push_pose(elm_odometry* o, const double T[16]) {

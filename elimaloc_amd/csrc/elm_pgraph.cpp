@@ -1,9 +1,10 @@
 // elm_pgraph.cpp -- the pose graph (include/elimaloc_hip.h, "pose graph"): the object (nodes, edges, the
 // linearization and the solver's vectors resident on the device, of capacities fixed at creation), the argument checks, the incidence
 // lists (a stable counting sort of (edge, side) by node, redone when the edge set has changed), the conjugate-gradient driver that
-// queues pcg_check_every iterations between two reads of the device's state, the Levenberg-Marquardt loop around it, and the linear
-// initialization (include/elimaloc_hip_posegraph_init.h; DESIGN.md section 23: its preconditions and its two stages on the same
-// driver).  The launches are those of elm_k_pgraph.hip, elm_k_pgchain.hip and elm_k_pginit.hip.  Host-side C++17.
+// queues pcg_check_every iterations between two reads of the device's state (elm_call.hpp's run_batched), the Levenberg-Marquardt loop
+// around it, and the linear initialization (include/elimaloc_hip_posegraph_init.h; DESIGN.md section 23: its preconditions and its two
+// stages on the same driver).  The object itself is elm_pgraph_host.hpp's, which the covariances (elm_pgcov.cpp) share.  The launches
+// are those of elm_k_pgraph.hip, elm_k_pgchain.hip and elm_k_pginit.hip.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -12,33 +13,11 @@
 #include <string>
 #include <vector>
 
-#include "elm_dev_pgraph.hpp"
-#include "elm_query.hpp"
+#include "elm_pgraph_host.hpp"
 
 using namespace elm;
 using namespace elm_query;
-
-struct elm_posegraph {
-    elm_ctx* ctx = nullptr;
-    uint64_t ctx_id = 0; // the owning context's unique id (as maps and scans keep it)
-    uint32_t n_cap = 0, e_cap = 0, N = 0, E = 0;
-    std::vector<uint8_t> fixed;     // [N]: the host's copy
-    std::vector<int32_t> ei, ej;    // [E]: the host's copy
-    std::vector<double> wr, wt;     // [E]: trace(Omega_ww) / 3 and trace(Omega_vv) / 3, the weights of elm_posegraph_initialize
-    bool csr_dirty = true, lin_valid = false;
-    double lin_huber = 0.0;         // the Huber k of the last linearization queued
-    uint32_t n_hubs = 0;
-    char* blob = nullptr;           // every device array below, one allocation
-    double *poses = nullptr, *trial = nullptr;
-    uint32_t *d_inc_start = nullptr, *d_inc = nullptr, *d_hubs = nullptr;
-    int32_t *d_ei = nullptr, *d_ej = nullptr;
-    double *d_Z = nullptr, *d_info = nullptr;
-    uint8_t* d_fixed = nullptr;
-    PgDev dev{};
-    int precond = ELM_PG_PRECOND_BLOCK_JACOBI; // kept across a reset
-    uint32_t* d_ce = nullptr;                  // the chain-edge table, uploaded with the incidence lists
-    PgcDev chain{};
-};
+using namespace elm_pgraph_host;
 
 extern "C" void elm_posegraph_config_default(elm_posegraph_config* c) {
     if (!c) return;
@@ -59,8 +38,6 @@ extern "C" void elm_posegraph_config_default(elm_posegraph_config* c) {
 
 namespace {
 
-constexpr int kPgDefaultCheckEvery = 32;
-
 bool config_ok(const elm_posegraph_config* c) {
     if (!c || c->max_iterations < 1 || c->pcg_max_iterations < 1 || c->pcg_check_every < 1) return false;
     if (!fin_ge0(c->lambda_init) || !fin_ge0(c->lambda_min) || !fin_ge0(c->lambda_max) || c->lambda_min > c->lambda_max) return false;
@@ -75,18 +52,7 @@ void pg_free(elm_posegraph* pg) {
     delete pg;
 }
 
-// the device arrays carved from one allocation, each aligned to 256 bytes
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) / 256 * 256;
-        return p;
-    }
-};
-
+// the device arrays of the object from its one allocation
 void carve(elm_posegraph* pg, Carver& c) {
     const size_t Nc = pg->n_cap, Ec = pg->e_cap;
     PgDev& d = pg->dev;
@@ -157,27 +123,19 @@ int create_impl(elm_ctx* ctx, hipStream_t st, uint32_t n_cap, uint32_t e_cap, el
     pg->ctx_id = ctx->id;
     pg->n_cap = n_cap;
     pg->e_cap = e_cap;
-    Carver size{nullptr};
-    carve(pg, size);
+    DeviceBlob blob(st);
+    hipError_t e = blob.alloc([&](Carver& c) { carve(pg, c); });
     // zeroed on the context's stream and joined: a memset on the null stream may still be running when the first upload on the
     // context's (non-blocking) stream lands, and would then wipe it
-    hipError_t e = hipMalloc((void**)&pg->blob, size.off);
-    if (e == hipSuccess) e = hipMemsetAsync(pg->blob, 0, size.off, st);
+    if (e == hipSuccess) e = hipMemsetAsync(blob.p, 0, blob.bytes, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         pg_free(pg);
         return dev_error(ctx, "elm_posegraph_create", e);
     }
-    Carver real{pg->blob};
-    carve(pg, real);
+    pg->blob = blob.release();
     *out = pg;
     return ELM_OK;
-}
-
-int refuse_full(elm_ctx* ctx, const char* what, const char* items, size_t have, size_t n, size_t cap) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + std::to_string(have) + " + " + std::to_string(n) + " " + items + " exceed the capacity of " +
-                                     std::to_string(cap));
-    return ELM_ERR_UNSUPPORTED;
 }
 
 void rows12_to_pose16(const double* P, double* T16) {
@@ -185,11 +143,6 @@ void rows12_to_pose16(const double* P, double* T16) {
         for (int q = 0; q < 4; ++q) T16[q * 4 + r] = P[r * 4 + q];
     T16[3] = T16[7] = T16[11] = 0.0;
     T16[15] = 1.0;
-}
-
-int join(elm_ctx* ctx, hipStream_t st, hipError_t e, const char* what) {
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? (int)ELM_OK : dev_error(ctx, what, e);
 }
 
 // the incidence lists of the current edge set: per node its (edge, side) entries in ascending edge index, and the hubs
@@ -228,42 +181,6 @@ hipError_t upload_csr(elm_posegraph* pg, hipStream_t st, std::vector<uint32_t>& 
     return e;
 }
 
-// The device work of an entry point: the context's device current, body(stream) on the context's stream, a failed host allocation
-// anywhere in it turned into ELM_ERR_ALLOC.
-template <class Body>
-int on_stream(elm_ctx* ctx, const char* what, Body body) {
-    return guard_alloc(ctx, what, [&]() -> int {
-        if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-        return body((hipStream_t)elm_ctx_stream(ctx));
-    });
-}
-
-const PgDev& dev_view(elm_posegraph* pg) {
-    pg->dev.N = pg->N;
-    pg->dev.E = pg->E;
-    pg->dev.n_hubs = pg->n_hubs;
-    return pg->dev;
-}
-
-// the preconditioner seam of the launchers: the chain's view, or null for block Jacobi
-const PgcDev* chain(const elm_posegraph* pg) { return pg->precond == ELM_PG_PRECOND_CHAIN ? &pg->chain : nullptr; }
-
-// queues the damped diagonal blocks and their inverses at lambda and, for the conjugate gradients to follow with a chain, its factor
-// (c: chain(pg) before a solve, null where none follows)
-void launch_damping(hipStream_t st, const PgDev& d, const PgcDev* c, double lambda, int sum) {
-    launch_pg_nodes(st, d, lambda, sum);
-    if (c) launch_pgc_factor(st, d, *c, lambda);
-}
-
-// the incidence lists on the device are those of the current edge set
-hipError_t ensure_csr(elm_posegraph* pg, hipStream_t st) {
-    if (!pg->csr_dirty) return hipSuccess;
-    std::vector<uint32_t> start, inc, hubs;
-    hipError_t e = upload_csr(pg, st, start, inc, hubs);
-    if (e == hipSuccess) pg->csr_dirty = false;
-    return e;
-}
-
 // queues the linearization at the current poses with the damping lambda
 hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda, bool for_solve) {
     hipError_t e = ensure_csr(pg, st);
@@ -276,12 +193,6 @@ hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, do
     });
 }
 
-// what a solve reports: the public stats records and the two stages of the initialization take their fields from it
-struct PcgStats {
-    int32_t iterations = 0, converged = 0;
-    double rel_residual = 0.0;
-};
-
 // The conjugate gradients on the current linearization and damping (launch_damping has run with this lambda and chain(pg)):
 // check_every iterations are queued, then the state comes down once.
 int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, double tol, int max_it, int check_every, PcgStats& stats, const char* what) {
@@ -291,16 +202,10 @@ int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, doub
     const PgcDev* c = chain(pg);
     PgState state{};
     hipError_t e = launched([&] { launch_pg_pcg_begin(st, d, c, tol); });
-    uint32_t it = 0;
-    while (e == hipSuccess) {
-        const uint32_t upto = (uint32_t)std::min<int64_t>((int64_t)it + check_every, max_it);
-        e = launched([&] {
-            for (; it < upto; ++it) launch_pg_pcg_iteration(st, d, c, lambda, tol, it);
-        });
-        if (e == hipSuccess) e = hipMemcpyAsync(&state, d.state, sizeof(PgState), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess || state.stop[it & 1u] || it >= (uint32_t)max_it) break;
-    }
+    if (e == hipSuccess)
+        e = run_batched(
+            st, check_every, max_it, [&](uint32_t it) { launch_pg_pcg_iteration(st, d, c, lambda, tol, it); }, (const PgState*)d.state, &state,
+            [&](uint32_t it) { return state.stop[it & 1u] != 0; });
     if (e != hipSuccess) return dev_error(ctx, what, e);
     stats.iterations = (int32_t)state.iters;
     stats.converged = (int32_t)state.converged;
@@ -388,8 +293,6 @@ int optimize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_pos
     if (res) *res = R;
     return ELM_OK;
 }
-
-bool range_ok(size_t first, size_t count, size_t size) { return first <= size && count <= size - first; }
 
 bool init_config_ok(const elm_posegraph_init_config* c) {
     return c && isfinite(c->pcg_rel_tol) && c->pcg_rel_tol > 0.0 && c->pcg_max_iterations >= 1 && c->pcg_check_every >= 1 && c->stages >= 1 &&
@@ -522,6 +425,14 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_p
 
 } // namespace
 
+hipError_t elm_pgraph_host::ensure_csr(elm_posegraph* pg, hipStream_t st) {
+    if (!pg->csr_dirty) return hipSuccess;
+    std::vector<uint32_t> start, inc, hubs;
+    hipError_t e = upload_csr(pg, st, start, inc, hubs);
+    if (e == hipSuccess) pg->csr_dirty = false;
+    return e;
+}
+
 extern "C" int elm_posegraph_edge_terms(const double* Ti16, const double* Tj16, const double* Z16, double* r, double* A, double* B) {
     if (!Ti16 || !Tj16 || !Z16 || !poses_finite(Ti16, 1) || !poses_finite(Tj16, 1) || !poses_finite(Z16, 1)) return ELM_ERR_INVALID;
     double Pi[12], Pj[12], PZ[12], rr[6], AA[36], BB[36];
@@ -539,9 +450,8 @@ extern "C" int elm_posegraph_create(elm_ctx* ctx, int node_capacity, int edge_ca
     if (!ctx || !out || node_capacity < 1 || node_capacity > ELM_POSEGRAPH_MAX_NODES || edge_capacity < 1 || edge_capacity > ELM_POSEGRAPH_MAX_EDGES)
         return ELM_ERR_INVALID;
     *out = nullptr;
-    int rc = check_plain(ctx, "elm_posegraph_create");
+    const int rc = check_call(ctx, "elm_posegraph_create");
     if (rc != ELM_OK) return rc;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
     return on_stream(ctx, "elm_posegraph_create", [&](hipStream_t st) { return create_impl(ctx, st, (uint32_t)node_capacity, (uint32_t)edge_capacity, out); });
 }
 
@@ -670,10 +580,7 @@ extern "C" int elm_posegraph_add_edges(elm_ctx* ctx, elm_posegraph* pg, const in
     if (n > (size_t)ELM_POSEGRAPH_MAX_EDGES || !poses_finite(Z16, n)) return ELM_ERR_INVALID;
     for (size_t k = 0; k < n; ++k) {
         if (i[k] < 0 || j[k] < 0 || i[k] == j[k]) return ELM_ERR_INVALID;
-        const double* om = info36 + 36 * k;
-        for (int a = 0; a < 6; ++a)
-            for (int b = 0; b < 6; ++b)
-                if (!isfinite(om[a * 6 + b]) || om[a * 6 + b] != om[b * 6 + a]) return ELM_ERR_INVALID;
+        if (!finite36(info36 + 36 * k) || !symmetric36(info36 + 36 * k)) return ELM_ERR_INVALID;
     }
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
@@ -799,7 +706,7 @@ extern "C" int elm_posegraph_optimize(elm_ctx* ctx, elm_posegraph* pg, const elm
     if (!ctx || !pg || !config_ok(cfg) || trace_cap < 0 || (trace_cap > 0 && !trace)) return ELM_ERR_INVALID;
     int rc = check_object(ctx, pg, what);
     if (rc != ELM_OK) return rc;
-    if (std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end()) {
+    if (gauge_free(pg)) {
         elm_host::ctx_set_error(ctx, std::string(what) + ": no fixed node (the gauge is free)");
         return ELM_ERR_INVALID;
     }
@@ -828,335 +735,5 @@ extern "C" int elm_posegraph_initialize(elm_ctx* ctx, elm_posegraph* pg, const e
             return ELM_ERR_INVALID;
         }
         return initialize_impl(ctx, pg, st, *cfg, result, rows_out, v_out);
-    });
-}
-
-// ---- marginal and relative covariances (include/elimaloc_hip_posegraph_cov.h; the kernels are elm_k_pgcov.hip)
-extern "C" void elm_posegraph_cov_config_default(elm_posegraph_cov_config* c) {
-    if (!c) return;
-    memset(c, 0, sizeof(*c));
-    c->lambda = 0.0;
-    c->pcg_rel_tol = 1e-10;
-    c->pcg_max_iterations = 20000;
-    c->pcg_check_every = kPgDefaultCheckEvery;
-    c->scratch_bytes = 0;
-}
-
-namespace {
-
-constexpr uint64_t kPgcovDefaultScratch = 2ull << 30;
-constexpr size_t kPgcovMaxPairs = (size_t)1 << 25;
-
-bool cov_config_ok(const elm_posegraph_cov_config* c) {
-    return c && fin_ge0(c->lambda) && fin_ge0(c->pcg_rel_tol) && c->pcg_max_iterations >= 1 && c->pcg_check_every >= 1;
-}
-
-// The refusals that need the object, in the order of the header: "" when there is none.
-int cov_refusal(elm_ctx* ctx, const elm_posegraph* pg, const elm_posegraph_cov_config& c, const char* what) {
-    if (!pg->lin_valid) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": no valid linearization (linearize or optimize first)");
-        return ELM_ERR_INVALID;
-    }
-    if (c.lambda == 0.0 && std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end()) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": no fixed node (the gauge is free)");
-        return ELM_ERR_INVALID;
-    }
-    return ELM_OK;
-}
-
-bool nodes_in_range(const int32_t* v, size_t n, uint32_t N) {
-    for (size_t k = 0; k < n; ++k)
-        if (v[k] < 0 || (uint32_t)v[k] >= N) return false;
-    return true;
-}
-
-// the scratch of one call: the vectors and words of up to G groups, the request's tables and the download buffer, one allocation
-struct CovScratch {
-    char* blob = nullptr;
-    ~CovScratch() {
-        if (blob) (void)hipFree(blob);
-    }
-};
-
-void cov_carve(Carver& c, PgCovDev& v, bool with_chain, size_t N, size_t G, size_t m, size_t P, int32_t*& d_cols, uint32_t*& d_ci, int32_t*& d_row, double*& d_out,
-               size_t& vec_bytes, size_t& word_off, size_t& word_bytes) {
-    const size_t tile = G * N * 6 * kPgcovLanes, cols = G * kPgcovLanes, slots = (size_t)pgcov_blocks((uint32_t)N) * cols;
-    v.x = c.take<double>(tile);
-    v.r = c.take<double>(tile);
-    v.z = c.take<double>(tile);
-    v.p = c.take<double>(tile);
-    v.q = c.take<double>(tile);
-    vec_bytes = c.off; // (x is the first array carved: the five vectors are the allocation's first bytes)
-    v.y = v.be = nullptr;
-    v.y_pad = v.y_segs = 0;
-    if (with_chain) { // the apply's y and be: every level padded to whole segments, as the factor's arrays are
-        PgcLevel lv[kPgcMaxLevels];
-        const uint32_t nl = pgc_levels((uint32_t)N, lv);
-        v.y_pad = lv[nl - 1].off + lv[nl - 1].nseg * kPgcSeg;
-        v.y_segs = lv[nl - 1].soff + lv[nl - 1].nseg;
-        v.y = c.take<double>(G * v.y_pad * 6 * kPgcovLanes);
-        v.be = c.take<double>(G * v.y_segs * 6 * kPgcovLanes);
-    }
-    v.slot_pq = c.take<double>(slots);
-    v.slot_rz = c.take<double>(slots);
-    word_off = c.off;
-    v.alpha = c.take<double>(cols);
-    v.beta = c.take<double>(cols);
-    v.rz0 = c.take<double>(cols);
-    v.rzf = c.take<double>(cols);
-    v.rz = c.take<double>(2 * cols);
-    v.stop = c.take<uint32_t>(2 * cols);
-    v.iters = c.take<uint32_t>(cols);
-    v.converged = c.take<uint32_t>(cols);
-    v.gstop = c.take<uint32_t>(2 * G);
-    v.all_stop = c.take<uint32_t>(2);
-    word_bytes = c.off - word_off;
-    d_cols = c.take<int32_t>(m);
-    d_ci = c.take<uint32_t>(P ? P : 1);
-    d_row = c.take<int32_t>(P ? P : 1);
-    d_out = c.take<double>(36 * (P ? P : 1));
-    v.col_nodes = d_cols;
-}
-
-// The blocks Sigma(row[k], col_nodes[ci[k]]) of P pairs as solved into blocks [P][36], the per-column counts into iters and conv [6 m]
-// (either may be null).  The caller has checked every index, the config, the linearization and the preconditioner; m >= 1, N >= 1.
-int cov_core(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_cov_config& cfg, const int32_t* col_nodes, size_t m,
-             const std::vector<uint32_t>& ci, const std::vector<int32_t>& row, double* blocks, int32_t* iters, uint8_t* conv, elm_posegraph_cov_stats& S,
-             const char* what) {
-    const PgDev& d = dev_view(pg);
-    const size_t N = pg->N, P = ci.size(), n_cols = 6 * m, G_all = (n_cols + kPgcovLanes - 1) / kPgcovLanes;
-    hipError_t e = ensure_csr(pg, st);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
-    const PgcDev* const ch = chain(pg);
-    const bool with_chain = ch != nullptr;
-    // the groups of a pass: as many as fit under the cap, one at the least
-    PgCovDev v{};
-    int32_t* d_cols;
-    uint32_t* d_ci;
-    int32_t* d_row;
-    double* d_out;
-    size_t vec_bytes, word_off, word_bytes;
-    auto bytes_for = [&](size_t G) {
-        Carver size{nullptr};
-        cov_carve(size, v, with_chain, N, G, m, P, d_cols, d_ci, d_row, d_out, vec_bytes, word_off, word_bytes);
-        return size.off;
-    };
-    const uint64_t cap = cfg.scratch_bytes ? cfg.scratch_bytes : kPgcovDefaultScratch;
-    const size_t fixed_bytes = bytes_for(0), per_group = bytes_for(1) - fixed_bytes;
-    size_t G = cap > fixed_bytes ? (size_t)((cap - fixed_bytes) / per_group) : 0;
-    G = std::max<size_t>(1, std::min<size_t>({G, G_all, (size_t)kPgcovMaxGroups}));
-    while (G > 1 && bytes_for(G) > cap) --G; // (the arrays' alignment padding)
-    const size_t total = bytes_for(G);
-    CovScratch scratch;
-    e = hipMalloc((void**)&scratch.blob, total);
-    if (e != hipSuccess) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": " + std::to_string(total) + " bytes of scratch: " + hipGetErrorString(e));
-        return ELM_ERR_DEVICE;
-    }
-    Carver real{scratch.blob};
-    cov_carve(real, v, with_chain, N, G, m, P, d_cols, d_ci, d_row, d_out, vec_bytes, word_off, word_bytes);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    struct Events {
-        hipEvent_t &a, &b;
-        ~Events() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } events{ev0, ev1};
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cols, col_nodes, m * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && P) e = hipMemcpyAsync(d_ci, ci.data(), P * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && P) e = hipMemcpyAsync(d_row, row.data(), P * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && P) e = hipMemsetAsync(d_out, 0, 36 * P * sizeof(double), st);
-    if (e == hipSuccess) e = hipEventRecord(ev0, st);
-    if (e == hipSuccess) e = launched([&] { launch_damping(st, d, ch, cfg.lambda, 0); });
-    if (e != hipSuccess) return dev_error(ctx, what, e);
-    S = elm_posegraph_cov_stats{};
-    S.n_columns = (int32_t)n_cols;
-    S.scratch_bytes = total;
-    v.n_cols = (uint32_t)n_cols;
-    std::vector<uint32_t> h_it, h_cv;
-    std::vector<double> h_rz0, h_rzf;
-    for (size_t g0 = 0; g0 < G_all; g0 += G) {
-        v.G = (uint32_t)std::min(G, G_all - g0);
-        v.col0 = (uint32_t)(g0 * kPgcovLanes);
-        const size_t cols = (size_t)v.G * kPgcovLanes;
-        // the vectors of the pass's groups are the first v.G tiles of each array: zero them array by array
-        const size_t tile_bytes = cols * N * 6 * sizeof(double);
-        for (double* a : {v.x, v.r, v.z, v.p, v.q})
-            if (e == hipSuccess) e = hipMemsetAsync(a, 0, tile_bytes, st);
-        if (e == hipSuccess) e = hipMemsetAsync(scratch.blob + word_off, 0, word_bytes, st);
-        if (e == hipSuccess) e = launched([&] { launch_pgcov_begin(st, d, v, ch, cfg.pcg_rel_tol); });
-        uint32_t it = 0, all_stop[2] = {0u, 0u};
-        while (e == hipSuccess) {
-            const uint32_t upto = (uint32_t)std::min<int64_t>((int64_t)it + cfg.pcg_check_every, cfg.pcg_max_iterations);
-            e = launched([&] {
-                for (; it < upto; ++it) launch_pgcov_iteration(st, d, v, ch, cfg.lambda, cfg.pcg_rel_tol, it);
-            });
-            if (e == hipSuccess) e = hipMemcpyAsync(all_stop, v.all_stop, sizeof(all_stop), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess || all_stop[it & 1u] || it >= (uint32_t)cfg.pcg_max_iterations) break;
-        }
-        if (e == hipSuccess) e = launched([&] { launch_pgcov_gather(st, d, v, d_ci, d_row, (uint32_t)P, d_out); });
-        h_it.resize(cols);
-        h_cv.resize(cols);
-        h_rz0.resize(cols);
-        h_rzf.resize(cols);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_it.data(), v.iters, cols * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cv.data(), v.converged, cols * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_rz0.data(), v.rz0, cols * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_rzf.data(), v.rzf, cols * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return dev_error(ctx, what, e);
-        for (size_t k = 0; k < cols && v.col0 + k < n_cols; ++k) {
-            const size_t j = v.col0 + k;
-            if (iters) iters[j] = (int32_t)h_it[k];
-            if (conv) conv[j] = h_cv[k] ? 1 : 0;
-            S.n_converged += h_cv[k] ? 1 : 0;
-            S.iterations_max = std::max(S.iterations_max, (int32_t)h_it[k]);
-            if (h_rz0[k] > 0.0) S.rel_residual_max = std::max(S.rel_residual_max, sqrt(h_rzf[k]) / sqrt(h_rz0[k]));
-        }
-        ++S.passes;
-    }
-    e = hipEventRecord(ev1, st);
-    if (e == hipSuccess && P) e = hipMemcpyAsync(blocks, d_out, 36 * P * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
-    S.ms_device = ms;
-    return ELM_OK;
-}
-
-} // namespace
-
-extern "C" int elm_posegraph_covariance(elm_ctx* ctx, elm_posegraph* pg, const int32_t* col_nodes, size_t m, const int32_t* row_nodes, size_t n_rows,
-                                        const elm_posegraph_cov_config* cfg, double* diag36, double* cross36, int32_t* iterations, uint8_t* converged,
-                                        elm_posegraph_cov_stats* stats) {
-    const char* what = "elm_posegraph_covariance";
-    if (!ctx || !pg || !cov_config_ok(cfg) || (m && !col_nodes) || (n_rows && !row_nodes) || (cross36 && !n_rows)) return ELM_ERR_INVALID;
-    if (m > (size_t)ELM_POSEGRAPH_MAX_NODES || n_rows > (size_t)ELM_POSEGRAPH_MAX_NODES) return ELM_ERR_INVALID;
-    int rc = check_object(ctx, pg, what);
-    if (rc != ELM_OK) return rc;
-    if (!nodes_in_range(col_nodes, m, pg->N) || !nodes_in_range(row_nodes, n_rows, pg->N)) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": a node index outside the graph's " + std::to_string(pg->N) + " nodes");
-        return ELM_ERR_INVALID;
-    }
-    return on_stream(ctx, what, [&](hipStream_t st) -> int {
-        int rc = cov_refusal(ctx, pg, *cfg, what);
-        if (rc != ELM_OK) return rc;
-        elm_posegraph_cov_stats S{};
-        if (!m) {
-            if (stats) *stats = S;
-            return ELM_OK;
-        }
-        const size_t per_col = (diag36 ? 1 : 0) + (cross36 ? n_rows : 0), P = m * per_col;
-        if (P > kPgcovMaxPairs) {
-            elm_host::ctx_set_error(ctx, std::string(what) + ": " + std::to_string(P) + " blocks requested, more than 2^25");
-            return ELM_ERR_UNSUPPORTED;
-        }
-        // the pairs: per column node its own block (with diag36), then its row blocks
-        std::vector<uint32_t> ci(P);
-        std::vector<int32_t> row(P);
-        for (size_t i = 0, k = 0; i < m; ++i) {
-            if (diag36) ci[k] = (uint32_t)i, row[k++] = col_nodes[i];
-            for (size_t q = 0; cross36 && q < n_rows; ++q) ci[k] = (uint32_t)i, row[k++] = row_nodes[q];
-        }
-        std::vector<double> blocks(36 * P);
-        rc = cov_core(ctx, pg, st, *cfg, col_nodes, m, ci, row, blocks.data(), iterations, converged, S, what);
-        if (rc != ELM_OK) return rc;
-        for (size_t i = 0; i < m; ++i) {
-            const double* B = &blocks[36 * i * per_col];
-            if (diag36) {
-                for (int a = 0; a < 6; ++a)
-                    for (int b = 0; b < 6; ++b) diag36[36 * i + a * 6 + b] = 0.5 * (B[a * 6 + b] + B[b * 6 + a]);
-                B += 36;
-            }
-            if (cross36) memcpy(cross36 + 36 * i * n_rows, B, 36 * n_rows * sizeof(double));
-        }
-        if (stats) *stats = S;
-        return ELM_OK;
-    });
-}
-
-extern "C" int elm_posegraph_relative_covariance(elm_ctx* ctx, elm_posegraph* pg, const int32_t* a, const int32_t* b, size_t L,
-                                                 const elm_posegraph_cov_config* cfg, double* cov36, elm_posegraph_cov_stats* stats) {
-    const char* what = "elm_posegraph_relative_covariance";
-    if (!ctx || !pg || !cov_config_ok(cfg) || (L && (!a || !b || !cov36)) || L > kPgcovMaxPairs / 4) return ELM_ERR_INVALID;
-    int rc = check_object(ctx, pg, what);
-    if (rc != ELM_OK) return rc;
-    if (!nodes_in_range(a, L, pg->N) || !nodes_in_range(b, L, pg->N)) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": a node index outside the graph's " + std::to_string(pg->N) + " nodes");
-        return ELM_ERR_INVALID;
-    }
-    for (size_t k = 0; k < L; ++k)
-        if (a[k] == b[k]) return ELM_ERR_INVALID;
-    return on_stream(ctx, what, [&](hipStream_t st) -> int {
-        int rc = cov_refusal(ctx, pg, *cfg, what);
-        if (rc != ELM_OK) return rc;
-        elm_posegraph_cov_stats S{};
-        if (!L) {
-            if (stats) *stats = S;
-            return ELM_OK;
-        }
-        // the columns: the unique nodes of a and b, ascending
-        std::vector<int32_t> nodes(a, a + L);
-        nodes.insert(nodes.end(), b, b + L);
-        std::sort(nodes.begin(), nodes.end());
-        nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-        auto at = [&](int32_t v) { return (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), v) - nodes.begin()); };
-        // per pair the blocks Sigma_aa, Sigma_ba (columns of a), Sigma_ab, Sigma_bb (columns of b)
-        std::vector<uint32_t> ci(4 * L);
-        std::vector<int32_t> row(4 * L);
-        for (size_t k = 0; k < L; ++k) {
-            const uint32_t ia = at(a[k]), ib = at(b[k]);
-            ci[4 * k] = ia, row[4 * k] = a[k];
-            ci[4 * k + 1] = ia, row[4 * k + 1] = b[k];
-            ci[4 * k + 2] = ib, row[4 * k + 2] = a[k];
-            ci[4 * k + 3] = ib, row[4 * k + 3] = b[k];
-        }
-        std::vector<double> blocks(36 * 4 * L), rows(12 * nodes.size());
-        hipError_t e = hipSuccess;
-        for (size_t u = 0; u < nodes.size() && e == hipSuccess; ++u)
-            e = hipMemcpyAsync(&rows[12 * u], pg->poses + 12 * (size_t)nodes[u], 12 * sizeof(double), hipMemcpyDeviceToHost, st);
-        rc = join(ctx, st, e, what);
-        if (rc != ELM_OK) return rc;
-        rc = cov_core(ctx, pg, st, *cfg, nodes.data(), nodes.size(), ci, row, blocks.data(), nullptr, nullptr, S, what);
-        if (rc != ELM_OK) return rc;
-        for (size_t k = 0; k < L; ++k) {
-            const double *Pa = &rows[12 * at(a[k])], *Pb = &rows[12 * at(b[k])];
-            // Z = T_a^-1 T_b on pose rows
-            double Ra[9], ta[3], Rb[9], tb[3], RZ[9], tZ[3], PZ[12], r[6], A[36], B[36];
-            pg_split(Pa, Ra, ta);
-            pg_split(Pb, Rb, tb);
-            const double dt[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
-            pg_mul3_at(Ra, Rb, RZ);
-            pg_mul3_atv(Ra, dt, tZ);
-            for (int q = 0; q < 3; ++q) {
-                PZ[q * 4] = RZ[q * 3], PZ[q * 4 + 1] = RZ[q * 3 + 1], PZ[q * 4 + 2] = RZ[q * 3 + 2];
-                PZ[q * 4 + 3] = tZ[q];
-            }
-            pg_edge_terms(Pa, Pb, PZ, r, A, B);
-            const double *Saa = &blocks[36 * (4 * k)], *Sba = Saa + 36, *Sab = Saa + 72, *Sbb = Saa + 108;
-            // X S Y^T for the four terms, added in the order of the header
-            auto sandwich = [](const double* X, const double* Sg, const double* Y, double* out) {
-                double XS[36];
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) XS[i * 6 + j] = pg_mm6(X, Sg, i, j);
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) out[i * 6 + j] = pg_mmt6(XS, Y, i, j);
-            };
-            double T1[36], T2[36], T3[36], T4[36], Csum[36];
-            sandwich(A, Saa, A, T1);
-            sandwich(A, Sab, B, T2);
-            sandwich(B, Sba, A, T3);
-            sandwich(B, Sbb, B, T4);
-            for (int i = 0; i < 36; ++i) Csum[i] = ((T1[i] + T2[i]) + T3[i]) + T4[i];
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 6; ++j) cov36[36 * k + i * 6 + j] = 0.5 * (Csum[i * 6 + j] + Csum[j * 6 + i]);
-        }
-        if (stats) *stats = S;
-        return ELM_OK;
     });
 }

@@ -1,0 +1,66 @@
+// elm_pgraph_host.hpp -- what elm_pgraph.cpp (the object, the optimizer, the initialization) and elm_pgcov.cpp (the covariances) share
+// and nobody else sees: the pose graph object, its device view and preconditioner seam, the damping launch, the record of a solve, and
+// the incidence-list upload that elm_pgraph.cpp defines.  Host-side C++17.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "elm_dev_pgraph.hpp"
+#include "elm_query.hpp"
+
+struct elm_posegraph {
+    elm_ctx* ctx = nullptr;
+    uint64_t ctx_id = 0; // the owning context's unique id (as maps and scans keep it)
+    uint32_t n_cap = 0, e_cap = 0, N = 0, E = 0;
+    std::vector<uint8_t> fixed;     // [N]: the host's copy
+    std::vector<int32_t> ei, ej;    // [E]: the host's copy
+    std::vector<double> wr, wt;     // [E]: trace(Omega_ww) / 3 and trace(Omega_vv) / 3, the weights of elm_posegraph_initialize
+    bool csr_dirty = true, lin_valid = false;
+    double lin_huber = 0.0;         // the Huber k of the last linearization queued
+    uint32_t n_hubs = 0;
+    char* blob = nullptr;           // every device array below, one allocation
+    double *poses = nullptr, *trial = nullptr;
+    uint32_t *d_inc_start = nullptr, *d_inc = nullptr, *d_hubs = nullptr;
+    int32_t *d_ei = nullptr, *d_ej = nullptr;
+    double *d_Z = nullptr, *d_info = nullptr;
+    uint8_t* d_fixed = nullptr;
+    elm::PgDev dev{};
+    int precond = ELM_PG_PRECOND_BLOCK_JACOBI; // kept across a reset
+    uint32_t* d_ce = nullptr;                  // the chain-edge table, uploaded with the incidence lists
+    elm::PgcDev chain{};
+};
+
+namespace elm_pgraph_host {
+
+constexpr int kPgDefaultCheckEvery = 32;
+
+inline const elm::PgDev& dev_view(elm_posegraph* pg) {
+    pg->dev.N = pg->N;
+    pg->dev.E = pg->E;
+    pg->dev.n_hubs = pg->n_hubs;
+    return pg->dev;
+}
+
+// the preconditioner seam of the launchers: the chain's view, or null for block Jacobi
+inline const elm::PgcDev* chain(const elm_posegraph* pg) { return pg->precond == ELM_PG_PRECOND_CHAIN ? &pg->chain : nullptr; }
+
+// queues the damped diagonal blocks and their inverses at lambda and, for the conjugate gradients to follow with a chain, its factor
+// (c: chain(pg) before a solve, null where none follows)
+inline void launch_damping(hipStream_t st, const elm::PgDev& d, const elm::PgcDev* c, double lambda, int sum) {
+    elm::launch_pg_nodes(st, d, lambda, sum);
+    if (c) elm::launch_pgc_factor(st, d, *c, lambda);
+}
+
+// what a solve reports: the public stats records and the two stages of the initialization take their fields from it
+struct PcgStats {
+    int32_t iterations = 0, converged = 0;
+    double rel_residual = 0.0;
+};
+
+// the incidence lists on the device are those of the current edge set (elm_pgraph.cpp)
+hipError_t ensure_csr(elm_posegraph* pg, hipStream_t st);
+// no node of pg is fixed: the gauge is free
+inline bool gauge_free(const elm_posegraph* pg) { return std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end(); }
+
+} // namespace elm_pgraph_host

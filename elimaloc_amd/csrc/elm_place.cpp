@@ -1,7 +1,7 @@
 // elm_place.cpp -- place recognition (include/elimaloc_hip.h, "place recognition"): the descriptor tables, the places
 // object (a database of descriptors, their popcounts and ids resident on the device, of a capacity fixed at creation), the argument
-// checks, and the launches of elm_k_place.hip on the job table and the scratch taker that elm_query.hpp shares with the map queries.
-// Host-side C++17.
+// checks, and the launches of elm_k_place.hip on the job table and the scratch taker that elm_query.hpp shares with the map queries,
+// every entry point with device work inside elm_call.hpp's on_stream.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -91,7 +91,6 @@ void places_free(elm_places* pl) {
 
 int create_impl(elm_ctx* ctx, const elm_places_config* cfg, uint32_t capacity, const std::vector<double>& re, const std::vector<double>& ze,
                 const std::vector<double>& dir, elm_places** out) {
-    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
     elm_places* pl = new elm_places();
     pl->ctx = ctx;
     pl->ctx_id = ctx->id;
@@ -131,12 +130,6 @@ int check_jobs(elm_ctx* ctx, const elm_places* pl, const elm_scan* const* scans,
     for (int j = 0; j < n_jobs; ++j)
         if (!scans[j] || scans[j]->ctx != ctx) return ELM_ERR_INVALID;
     return ELM_OK;
-}
-
-int refuse_full(elm_ctx* ctx, const elm_places* pl, size_t n, const char* what) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + std::to_string(pl->size) + " + " + std::to_string(n) + " entries exceed the capacity of " +
-                                     std::to_string(pl->capacity));
-    return ELM_ERR_UNSUPPORTED;
 }
 
 JobTable level_jobs(const elm_scan* const* scans, const double* levels16, uint32_t n_jobs) {
@@ -190,8 +183,8 @@ int match_and_join(elm_ctx* ctx, const elm_places* pl, const unsigned long long*
         if (e == hipSuccess) e = hipMemcpyAsync(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && matches) e = hipMemcpyAsync(matches, d_m, (size_t)Q * N * sizeof(elm_place_match), hipMemcpyDeviceToHost, st);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
+    const int rc = join(ctx, st, e, what);
+    if (rc != ELM_OK) return rc;
     for (uint32_t q = 0; q < Q; ++q)
         for (int32_t c = 0; c < n_cands[q]; ++c) {
             elm_place_candidate& o = cands[(size_t)q * kPlaceMaxTopK + c];
@@ -216,10 +209,9 @@ extern "C" int elm_places_create(elm_ctx* ctx, const elm_places_config* cfg, int
     *out = nullptr;
     std::vector<double> re, ze, dir;
     if (!place_tables(cfg, re, ze, dir)) return ELM_ERR_INVALID;
-    int rc = check_plain(ctx, "elm_places_create");
+    const int rc = check_call(ctx, "elm_places_create");
     if (rc != ELM_OK) return rc;
-    if (ctx->in_flight) return ELM_ERR_INVALID;
-    return guard_alloc(ctx, "elm_places_create", [&] { return create_impl(ctx, cfg, (uint32_t)capacity, re, ze, dir, out); });
+    return on_stream(ctx, "elm_places_create", [&](hipStream_t) { return create_impl(ctx, cfg, (uint32_t)capacity, re, ze, dir, out); });
 }
 
 extern "C" void elm_places_destroy(elm_places* pl) { places_free(pl); }
@@ -245,19 +237,16 @@ extern "C" int elm_places_describe(elm_ctx* ctx, elm_places* pl, const elm_scan*
     const char* what = "elm_places_describe";
     int rc = check_jobs(ctx, pl, scans, levels16, n_jobs, words_out != nullptr, what);
     if (rc != ELM_OK) return rc;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const JobTable t = level_jobs(scans, levels16, (uint32_t)n_jobs);
         const size_t n_words = (size_t)n_jobs * pl->W;
         QueryScratch scr{ctx};
         char* d_w = scr.take<char>(elm_host::kScrPlaceWords, n_words * sizeof(unsigned long long) + (size_t)n_jobs * sizeof(uint32_t));
         if (scr.rc != ELM_OK) return scr.rc;
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         int rc = queue_describe(ctx, pl, t, (unsigned long long*)d_w, (uint32_t*)(d_w + n_words * sizeof(unsigned long long)), stats, st, what);
         if (rc != ELM_OK) return rc;
-        hipError_t e = hipMemcpyAsync(words_out, d_w, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st); // the job table on the host is read by the copy until here
-        return e == hipSuccess ? (int)ELM_OK : dev_error(ctx, what, e);
+        // (the job table on the host is read by the copy until the join)
+        return join(ctx, st, hipMemcpyAsync(words_out, d_w, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), what);
     });
 }
 
@@ -266,18 +255,15 @@ extern "C" int elm_places_add(elm_ctx* ctx, elm_places* pl, const elm_scan* cons
     const char* what = "elm_places_add";
     int rc = check_jobs(ctx, pl, scans, levels16, n_jobs, ids != nullptr, what);
     if (rc != ELM_OK) return rc;
-    if ((size_t)pl->size + (size_t)n_jobs > pl->capacity) return refuse_full(ctx, pl, (size_t)n_jobs, what);
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    if ((size_t)pl->size + (size_t)n_jobs > pl->capacity) return refuse_full(ctx, what, "entries", pl->size, (size_t)n_jobs, pl->capacity);
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const JobTable t = level_jobs(scans, levels16, (uint32_t)n_jobs);
         pl->ids.reserve((size_t)pl->size + (size_t)n_jobs);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         // the rows past `size` are nobody's until the call has succeeded
         int rc = queue_describe(ctx, pl, t, pl->d_words + (size_t)pl->size * pl->W, pl->d_bits + pl->size, stats, st, what);
         if (rc != ELM_OK) return rc;
-        hipError_t e = hipMemcpyAsync(pl->d_ids + pl->size, ids, (size_t)n_jobs * sizeof(int64_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return dev_error(ctx, what, e);
+        rc = join(ctx, st, hipMemcpyAsync(pl->d_ids + pl->size, ids, (size_t)n_jobs * sizeof(int64_t), hipMemcpyHostToDevice, st), what);
+        if (rc != ELM_OK) return rc;
         pl->ids.insert(pl->ids.end(), ids, ids + n_jobs);
         pl->size += (uint32_t)n_jobs;
         return (int)ELM_OK;
@@ -289,18 +275,16 @@ extern "C" int elm_places_add_words(elm_ctx* ctx, elm_places* pl, const uint64_t
     if (!ctx || !pl || (n && (!words || !ids))) return ELM_ERR_INVALID;
     int rc = check_object(ctx, pl, what);
     if (rc != ELM_OK) return rc;
-    if (n > (size_t)(pl->capacity - pl->size)) return refuse_full(ctx, pl, n, what);
+    if (n > (size_t)(pl->capacity - pl->size)) return refuse_full(ctx, what, "entries", pl->size, n, pl->capacity);
     if (!n) return ELM_OK;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         pl->ids.reserve((size_t)pl->size + n);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         unsigned long long* d_w = pl->d_words + (size_t)pl->size * pl->W;
         hipError_t e = hipMemcpyAsync(d_w, words, n * pl->W * sizeof(uint64_t), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pl->d_ids + pl->size, ids, n * sizeof(int64_t), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = launched([&] { launch_pl_bits(st, d_w, pl->W, (uint32_t)n, pl->d_bits + pl->size); });
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return dev_error(ctx, what, e);
+        const int rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
         pl->ids.insert(pl->ids.end(), ids, ids + n);
         pl->size += (uint32_t)n;
         return (int)ELM_OK;
@@ -311,17 +295,16 @@ extern "C" int elm_places_download(elm_ctx* ctx, const elm_places* pl, size_t fi
     const char* what = "elm_places_download";
     int rc = check_object(ctx, pl, what);
     if (rc != ELM_OK) return rc;
-    if (first > pl->size || count > pl->size - first) return ELM_ERR_INVALID;
+    if (!range_ok(first, count, pl->size)) return ELM_ERR_INVALID;
     if (!count) return ELM_OK;
-    if (hipSetDevice(ctx->device) != hipSuccess) return ELM_ERR_DEVICE;
-    hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
-    hipError_t e = hipSuccess;
-    if (words) e = hipMemcpyAsync(words, pl->d_words + first * pl->W, count * pl->W * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_bits) e = hipMemcpyAsync(n_bits, pl->d_bits + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev_error(ctx, what, e);
-    if (ids) memcpy(ids, pl->ids.data() + first, count * sizeof(int64_t));
-    return ELM_OK;
+    return on_stream(ctx, what, [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        if (words) e = hipMemcpyAsync(words, pl->d_words + first * pl->W, count * pl->W * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && n_bits) e = hipMemcpyAsync(n_bits, pl->d_bits + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        const int rc = join(ctx, st, e, what);
+        if (rc == ELM_OK && ids) memcpy(ids, pl->ids.data() + first, count * sizeof(int64_t));
+        return rc;
+    });
 }
 
 extern "C" int elm_places_match_words(elm_ctx* ctx, elm_places* pl, const uint64_t* words, int n_queries, const elm_places_query_config* query_cfg,
@@ -331,15 +314,13 @@ extern "C" int elm_places_match_words(elm_ctx* ctx, elm_places* pl, const uint64
         return ELM_ERR_INVALID;
     int rc = check_object(ctx, pl, what);
     if (rc != ELM_OK) return rc;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const uint32_t Q = (uint32_t)n_queries;
         const size_t w_bytes = (size_t)Q * pl->W * sizeof(unsigned long long);
         QueryScratch scr{ctx};
         char* d_w = scr.take<char>(elm_host::kScrPlaceWords, w_bytes + Q * sizeof(uint32_t));
         if (scr.rc != ELM_OK) return scr.rc;
         uint32_t* d_qbits = (uint32_t*)(d_w + w_bytes);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         hipError_t e = hipMemcpyAsync(d_w, words, w_bytes, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = launched([&] { launch_pl_bits(st, (const unsigned long long*)d_w, pl->W, Q, d_qbits); });
         if (e != hipSuccess) return dev_error(ctx, what, e);
@@ -354,8 +335,7 @@ extern "C" int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* co
     const bool rest_ok = cands && n_cands && n_queries >= 1 && n_queries <= kEvidMaxJobs && query_configs_ok(query_cfg, n_queries);
     int rc = check_jobs(ctx, pl, scans, levels16, n_queries, rest_ok, what);
     if (rc != ELM_OK) return rc;
-    return guard_alloc(ctx, what, [&] {
-        if (hipSetDevice(ctx->device) != hipSuccess) return (int)ELM_ERR_DEVICE;
+    return on_stream(ctx, what, [&](hipStream_t st) {
         const uint32_t Q = (uint32_t)n_queries;
         const JobTable t = level_jobs(scans, levels16, Q);
         const size_t w_bytes = (size_t)Q * pl->W * sizeof(unsigned long long);
@@ -363,7 +343,6 @@ extern "C" int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* co
         char* d_w = scr.take<char>(elm_host::kScrPlaceWords, w_bytes + Q * sizeof(uint32_t));
         if (scr.rc != ELM_OK) return scr.rc;
         uint32_t* d_qbits = (uint32_t*)(d_w + w_bytes);
-        hipStream_t st = (hipStream_t)elm_ctx_stream(ctx);
         int rc = queue_describe(ctx, pl, t, (unsigned long long*)d_w, d_qbits, stats, st, what);
         if (rc != ELM_OK) return rc;
         return match_and_join(ctx, pl, (const unsigned long long*)d_w, d_qbits, Q, query_cfg, cands, n_cands, matches, st, what);

@@ -1,17 +1,16 @@
 // elm_query.hpp -- the host side that the calls on the context's query scratch share: the free-space check (elm_free.cpp), the ray cast
-// (elm_ray.cpp), the map evidence (elm_evid.cpp), the map growth (elm_grow.cpp) and relocalization (elm_reloc.cpp).  The small argument
-// checks, the scratch taker and the launch check; the call of one scan at many poses (ray cast, free-space check); the call of many
-// (scan, pose) jobs on an object that counts (evidence, growth).  Host-side C++17, everything inline.
+// (elm_ray.cpp), the map evidence (elm_evid.cpp), the map growth (elm_grow.cpp) and relocalization (elm_reloc.cpp).  On the call skeleton
+// of elm_call.hpp (included here): the small argument checks and the scratch taker; the call of one scan at many poses (ray cast,
+// free-space check); the call of many (scan, pose) jobs on an object that counts (evidence, growth).  Host-side C++17, everything inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
-#include "elm_host_types.hpp"
+#include "elm_call.hpp"
 
 namespace elm_query {
 
@@ -23,35 +22,22 @@ inline bool poses_finite(const double* poses16, size_t n) {
         if (!isfinite(poses16[i])) return false;
     return true;
 }
+inline bool range_ok(size_t first, size_t count, size_t size) { return first <= size && count <= size - first; }
+inline bool finite36(const double* M) {
+    for (int q = 0; q < 36; ++q)
+        if (!isfinite(M[q])) return false;
+    return true;
+}
+inline bool symmetric36(const double* M) {
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j)
+            if (M[i * 6 + j] != M[j * 6 + i]) return false;
+    return true;
+}
 // one column-major 4 x 4 pose as the kernels read it: (R_r0, R_r1, R_r2, t_r) per row r
 inline void pose_rows12(const double* T16, double* out12) {
     for (int r = 0; r < 3; ++r)
         for (int q = 0; q < 4; ++q) out12[r * 4 + q] = T16[q * 4 + r];
-}
-
-// one rank, no exchange: a device group's lead or a context with a communicator / hook attached is refused
-inline int check_plain(elm_ctx* ctx, const char* what) {
-    if ((ctx->group && !elm_multi::in_worker()) || ctx->comm || ctx->hook) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": one rank only (not on a device group, nor with a communicator or hook attached)");
-        return ELM_ERR_UNSUPPORTED;
-    }
-    return ELM_OK;
-}
-
-inline int dev_error(elm_ctx* ctx, const char* what, hipError_t e) {
-    elm_host::ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
-    return ELM_ERR_DEVICE;
-}
-
-// body(), with a failed host allocation turned into ELM_ERR_ALLOC
-template <class Body>
-int guard_alloc(elm_ctx* ctx, const char* what, Body body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        elm_host::ctx_set_error(ctx, std::string(what) + ": host allocation failed");
-        return ELM_ERR_ALLOC;
-    }
 }
 
 // The context's scratch slots (elm_hostapi.hpp), taken one after another: after the first failure take() returns nullptr without asking
@@ -64,14 +50,6 @@ struct QueryScratch {
         return rc == ELM_OK ? (T*)elm_host::ctx_reloc_scratch(ctx, s, count * sizeof(T), &rc) : nullptr;
     }
 };
-
-// launch(), and what its launches say: an error left behind by an earlier call is dropped first
-template <class Launch>
-hipError_t launched(Launch launch) {
-    (void)hipGetLastError();
-    launch();
-    return hipGetLastError();
-}
 
 // ---- one scan at many poses (ray cast, free-space check)
 // The argument checks of the entry point, config_ok being the call's own verdict on its config.  ELM_OK: go on, unless n_poses is 0.
