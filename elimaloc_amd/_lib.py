@@ -368,6 +368,7 @@ class PoseGraphCovStatsC(C.Structure):
 
 LOOPS_MAX, LOOPS_MAX_S = 16384, 2048
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
+POSEGRAPH_MAX_PRIORS = 1 << 22
 PG_STOP = {1: "max_iterations", 2: "cost_tol", 3: "step_tol", 4: "lambda_max", 5: "cost_zero"}
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
@@ -615,10 +616,22 @@ DECLS_PGCOV = {  # include/elimaloc_hip_posegraph_cov.h (the pose graph's margin
     "elm_posegraph_covariance": _sig(vp, vp, i32p, szt, i32p, szt, P(PoseGraphCovConfigC), dp, dp, i32p, u8p, P(PoseGraphCovStatsC)),
     "elm_posegraph_relative_covariance": _sig(vp, vp, i32p, i32p, szt, P(PoseGraphCovConfigC), dp, P(PoseGraphCovStatsC)),
 }
+DECLS_PGPRIOR = {  # include/elimaloc_hip_posegraph_prior.h (the pose graph's absolute pose and position factors)
+    "elm_posegraph_reserve_priors": _sig(vp, vp, i),
+    "elm_posegraph_add_priors": _sig(vp, vp, i32p, dp, dp, dp, szt),
+    "elm_posegraph_prior_count": _sig(vp, vp, szp),
+    "elm_posegraph_get_priors": _sig(vp, vp, szt, szt, i32p, dp, dp, dp),
+    "elm_posegraph_clear_priors": _sig(vp, vp),
+    "elm_posegraph_set_prior_huber": _sig(vp, vp, d),
+    "elm_posegraph_get_prior_huber": _sig(vp, vp, dp),
+    "elm_posegraph_download_prior_linearization": _sig(vp, vp, dp, dp, dp, dp),
+    "elm_posegraph_prior_terms": _sig(dp, dp, dp, dp, dp),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
 EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
 EXPORTS_LOOPCOV = list(DECLS_LOOPCOV)
 EXPORTS_PGCOV = list(DECLS_PGCOV)
+EXPORTS_PGPRIOR = list(DECLS_PGPRIOR)
 
 _LIB = None
 
@@ -632,7 +645,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV, DECLS_PGPRIOR):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

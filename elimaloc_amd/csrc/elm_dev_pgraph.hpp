@@ -191,6 +191,67 @@ ELM_HD void pg_edge_terms(const double Pi[12], const double Pj[12], const double
     pg_blocks_full(K, A, B);
 }
 
+// ---- the prior (include/elimaloc_hip_posegraph_prior.h): a measured pose Z of node v's point l ----
+// The residual alone (the cost kernel): r = [R_Z^T ((t_v + R_v l) - t_Z); Log(R_Z^T R_v)].  With l = 0 every operation is the one
+// pg_residual performs on (I, T_v, Z), so the numbers are the same.
+ELM_HD void pg_prior_point(const double Rv[9], const double tv[3], const double l[3], const double tZ[3], double e[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) e[a] = (tv[a] + ((Rv[a * 3] * l[0] + Rv[a * 3 + 1] * l[1]) + Rv[a * 3 + 2] * l[2])) - tZ[a];
+}
+ELM_HD void pg_prior_residual(const double Pv[12], const double PZ[12], const double l[3], double r[6]) {
+    double Rv[9], tv[3], RZ[9], tZ[3], e[3], RE[9];
+    pg_split(Pv, Rv, tv);
+    pg_split(PZ, RZ, tZ);
+    pg_prior_point(Rv, tv, l, tZ, e);
+    pg_mul3_atv(RZ, e, r);
+    pg_mul3_at(RZ, Rv, RE);
+    double theta, qw, n, phi[3];
+    pg_log(RE, phi, theta, qw, n);
+    r[3] = phi[0];
+    r[4] = phi[1];
+    r[5] = phi[2];
+}
+// The residual and the non-zero 3 x 3 blocks of J = dr/dx_v = [ Jtt  Jtr ;  0  Jrr ] = [ R_E  -R_E [l]x ;  0  J^-1 ].
+struct PgPriorBlocks {
+    double Jtt[9], Jtr[9], Jrr[9];
+};
+ELM_HD void pg_prior_blocks(const double Pv[12], const double PZ[12], const double l[3], double r[6], PgPriorBlocks& K) {
+    double Rv[9], tv[3], RZ[9], tZ[3], e[3];
+    pg_split(Pv, Rv, tv);
+    pg_split(PZ, RZ, tZ);
+    pg_prior_point(Rv, tv, l, tZ, e);
+    pg_mul3_atv(RZ, e, r);
+    pg_mul3_at(RZ, Rv, K.Jtt);
+    double theta, qw, n, phi[3];
+    pg_log(K.Jtt, phi, theta, qw, n);
+    r[3] = phi[0];
+    r[4] = phi[1];
+    r[5] = phi[2];
+    pg_jinv(phi, pg_jinv_c(theta, qw, n), K.Jrr);
+    const double lx[9] = {0.0, -l[2], l[1], l[2], 0.0, -l[0], -l[1], l[0], 0.0};
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) K.Jtr[a * 3 + b] = -((K.Jtt[a * 3] * lx[b] + K.Jtt[a * 3 + 1] * lx[3 + b]) + K.Jtt[a * 3 + 2] * lx[6 + b]);
+}
+// the blocks as a full row-major 6 x 6 matrix
+ELM_HD void pg_prior_full(const PgPriorBlocks& K, double* J) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            J[a * 6 + b] = K.Jtt[a * 3 + b];
+            J[a * 6 + 3 + b] = K.Jtr[a * 3 + b];
+            J[(3 + a) * 6 + b] = 0.0;
+            J[(3 + a) * 6 + 3 + b] = K.Jrr[a * 3 + b];
+        }
+}
+ELM_HD void pg_prior_terms(const double Pv[12], const double PZ[12], const double l[3], double r[6], double J[36]) {
+    PgPriorBlocks K;
+    pg_prior_blocks(Pv, PZ, l, r, K);
+    pg_prior_full(K, J);
+}
+
 // Huber on s = r^T Omega r: the weight, and the cost rho.  k = 0: off.  s == k^2 is an inlier.
 ELM_HD double pg_huber_weight(double s, double k) { return (k > 0.0 && s > k * k) ? k / sqrt(s) : 1.0; }
 ELM_HD double pg_huber_cost(double s, double k) { return (k > 0.0 && s > k * k) ? (2.0 * k) * sqrt(s) - k * k : s; }

@@ -464,8 +464,28 @@ struct PgcDev;
 void launch_pg_pcg_begin(hipStream_t s, const PgDev& d, const PgcDev* chain, double tol);
 void launch_pg_pcg_iteration(hipStream_t s, const PgDev& d, const PgcDev* chain, double lambda, double tol, uint32_t it);
 void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, double* trial);
-// chi2, cost and outliers at `poses` into d.out, with the largest |x| of the last retraction; want_grad: also max |g_v| over active nodes
-void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double huber_k, int want_grad);
+// pose graph, priors (elm_k_pgprior.hip; the contract is include/elimaloc_hip_posegraph_prior.h): the device's
+// view of a graph's priors, a second allocation.  Prior arrays are component-major with the stride p_stride, the prior capacity.
+constexpr uint32_t kPgLanesPerPrior = 8; // k_pgp_linearize: the lane of a group is the column
+struct PgPriorDev {
+    uint32_t P, p_stride, n_rows;
+    const int32_t* node;              // [P]
+    const double *Z, *lever, *info;   // [P][12] pose rows, [P][3], [P][36]
+    double *r, *J, *s, *w, *g, *H;    // [6], [36], [1], [1], [6], [36] components: g = w J^T Omega r, H = w J^T Omega J
+    // the nodes that have priors, ascending: row k is node row_node[k] with the priors order[row_first[k] .. row_first[k + 1]),
+    // ascending prior index
+    const uint32_t *row_node, *row_first, *order;
+    double* part_cost;                // [3][pg_blocks(P)]
+};
+// r, J, s, w, g, H of every prior at `poses`; P >= 1
+void launch_pgp_linearize(hipStream_t s, const PgPriorDev& p, const double* poses, double huber_k);
+// onto Hd and g as launch_pg_nodes(sum = 1) left them, each node's priors one by one; n_rows >= 1
+void launch_pgp_nodes(hipStream_t s, const PgDev& d, const PgPriorDev& p);
+// chi2, cost and outliers at `poses` into d.out, with the largest |x| of the last retraction; want_grad: also max |g_v| over active
+// nodes.  prior: null, or the priors (P >= 1) whose three totals, under their own threshold, are added onto the edges' in d.out
+void launch_pg_cost(hipStream_t s, const PgDev& d, const PgPriorDev* prior, const double* poses, double huber_k, double prior_huber_k, int want_grad);
+// the priors' part of it (elm_k_pgprior.hip), queued after the edges' record is written
+void launch_pgp_cost(hipStream_t s, const PgDev& d, const PgPriorDev& p, const double* poses, double huber_k);
 
 // pose graph, chain preconditioner (elm_k_pgchain.hip): M^-1 of the block-tridiagonal M of the contract by
 // block cyclic reduction in levels.  A level of n nodes is cut into segments of kPgcSeg consecutive nodes, one workgroup each; a

@@ -461,10 +461,11 @@ void launch_pg_retract(hipStream_t s, const PgDev& d, const double* poses, doubl
     hipLaunchKernelGGL(k_pg_retract, dim3(pg_blocks(d.N)), dim3(256), 0, s, d, poses, trial);
 }
 
-void launch_pg_cost(hipStream_t s, const PgDev& d, const double* poses, double huber_k, int want_grad) {
+void launch_pg_cost(hipStream_t s, const PgDev& d, const PgPriorDev* prior, const double* poses, double huber_k, double prior_huber_k, int want_grad) {
     const uint32_t nb = pg_blocks(d.E);
     if (nb) hipLaunchKernelGGL(k_pg_cost, dim3(nb), dim3(256), 0, s, d, poses, huber_k);
     hipLaunchKernelGGL(k_pg_finish, dim3(1), dim3(256), 0, s, d, nb, want_grad);
+    if (prior) launch_pgp_cost(s, d, *prior, poses, prior_huber_k);
 }
 
 } // namespace elm

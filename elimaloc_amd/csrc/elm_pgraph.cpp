@@ -3,8 +3,9 @@
 // lists (a stable counting sort of (edge, side) by node, redone when the edge set has changed), the conjugate-gradient driver that
 // queues pcg_check_every iterations between two reads of the device's state (elm_call.hpp's run_batched), the Levenberg-Marquardt loop
 // around it, and the linear initialization (include/elimaloc_hip_posegraph_init.h; DESIGN.md section 23: its preconditions and its two
-// stages on the same driver).  The object itself is elm_pgraph_host.hpp's, which the covariances (elm_pgcov.cpp) share.  The launches
-// are those of elm_k_pgraph.hip, elm_k_pgchain.hip and elm_k_pginit.hip.  Host-side C++17.
+// stages on the same driver).  The object itself is elm_pgraph_host.hpp's, which the covariances (elm_pgcov.cpp) and the priors
+// (elm_pgprior.cpp: their calls and arrays; their launches are queued here, with the linearization and the cost) share.  The launches
+// are those of elm_k_pgraph.hip, elm_k_pgchain.hip, elm_k_pginit.hip and elm_k_pgprior.hip.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -49,6 +50,7 @@ void pg_free(elm_posegraph* pg) {
     if (!pg) return;
     if (elm_host::ctx_is_alive(pg->ctx, pg->ctx_id)) (void)hipSetDevice(pg->ctx->device); // a context destroyed first: just release
     if (pg->blob) (void)hipFree(pg->blob);
+    if (pg->prior_blob) (void)hipFree(pg->prior_blob);
     delete pg;
 }
 
@@ -181,15 +183,27 @@ hipError_t upload_csr(elm_posegraph* pg, hipStream_t st, std::vector<uint32_t>& 
     return e;
 }
 
-// queues the linearization at the current poses with the damping lambda
+// Queues the linearization at the current poses with the damping lambda.  With priors the node kernel runs twice: its summing entry
+// leaves the edges' H_vv and g_v, the priors are added onto them, and its read-back entry redoes the active rule, the damping and the
+// inverse on the completed block (k_pg_nodes itself is untouched, and without priors the launches are exactly those of before).
 hipError_t queue_linearize(elm_posegraph* pg, hipStream_t st, double huber_k, double lambda, bool for_solve) {
     hipError_t e = ensure_csr(pg, st);
+    if (e == hipSuccess) e = ensure_prior_rows(pg, st);
     if (e != hipSuccess) return e;
     pg->lin_huber = huber_k;
     const PgDev& d = dev_view(pg);
+    const PgPriorDev* pr = prior_view(pg);
+    const PgcDev* c = for_solve ? chain(pg) : nullptr;
     return launched([&] {
         launch_pg_linearize(st, d, pg->poses, huber_k);
-        launch_damping(st, d, for_solve ? chain(pg) : nullptr, lambda, 1);
+        if (!pr) {
+            launch_damping(st, d, c, lambda, 1);
+            return;
+        }
+        launch_pgp_linearize(st, *pr, pg->poses, pg->prior_huber);
+        launch_pg_nodes(st, d, lambda, 1);
+        launch_pgp_nodes(st, d, *pr);
+        launch_damping(st, d, c, lambda, 0);
     });
 }
 
@@ -213,10 +227,12 @@ int run_pcg(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, double lambda, doub
     return ELM_OK;
 }
 
-// the cost record at `poses` (and the largest |x| of the retraction queued before it)
-int cost_at(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const double* poses, double huber_k, int want_grad, PgOut& out, const char* what) {
+// the cost record at `poses` (and the largest |x| of the retraction queued before it); the priors count unless the caller ignores them
+int cost_at(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const double* poses, double huber_k, int want_grad, PgOut& out, const char* what,
+            bool with_priors = true) {
     const PgDev& d = dev_view(pg);
-    hipError_t e = launched([&] { launch_pg_cost(st, d, poses, huber_k, want_grad); });
+    const PgPriorDev* pr = with_priors ? prior_view(pg) : nullptr;
+    hipError_t e = launched([&] { launch_pg_cost(st, d, pr, poses, huber_k, pg->prior_huber, want_grad); });
     if (e == hipSuccess) e = hipMemcpyAsync(&out, d.out, sizeof(PgOut), hipMemcpyDeviceToHost, st);
     return join(ctx, st, e, what);
 }
@@ -348,7 +364,7 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_p
     hipError_t e = ensure_csr(pg, st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
     PgOut o{};
-    int rc = cost_at(ctx, pg, st, pg->poses, 0.0, 0, o, what);
+    int rc = cost_at(ctx, pg, st, pg->poses, 0.0, 0, o, what, false); // (the initialization ignores priors, here and in its stages)
     if (rc != ELM_OK) return rc;
     R.cost_before = o.cost;
     // From here the contribution arrays, the node sums and the flags are those of the stages: a linearization that was valid is put
@@ -402,7 +418,7 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_p
     } else if (v_out) {
         std::fill(v_out, v_out + 3 * N, 0.0);
     }
-    rc = cost_at(ctx, pg, st, pg->trial, 0.0, 0, o, what);
+    rc = cost_at(ctx, pg, st, pg->trial, 0.0, 0, o, what, false);
     if (rc != ELM_OK) return rc;
     R.cost_after = o.cost;
     R.applied = ((!rot || R.rot_converged) && (!trans || R.trans_converged)) ? 1 : 0;
@@ -467,6 +483,9 @@ extern "C" int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg) {
     pg->wr.clear();
     pg->wt.clear();
     pg->csr_dirty = true;
+    pg->P = 0; // the priors go with their nodes; their capacity and threshold stay
+    pg->pnode.clear();
+    pg->prior_rows_dirty = true;
     pg->lin_valid = false;
     return ELM_OK;
 }

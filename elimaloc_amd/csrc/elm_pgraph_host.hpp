@@ -29,6 +29,16 @@ struct elm_posegraph {
     int precond = ELM_PG_PRECOND_BLOCK_JACOBI; // kept across a reset
     uint32_t* d_ce = nullptr;                  // the chain-edge table, uploaded with the incidence lists
     elm::PgcDev chain{};
+    // the priors (include/elimaloc_hip_posegraph_prior.h; elm_pgprior.cpp): nothing of it exists before elm_posegraph_reserve_priors
+    uint32_t p_cap = 0, P = 0;
+    std::vector<int32_t> pnode;     // [P]: the host's copy
+    bool prior_rows_dirty = true;   // the rows of `prior` on the device are not those of pnode
+    double prior_huber = 0.0;       // kept across a reset
+    char* prior_blob = nullptr;     // every device array of `prior`, the second allocation
+    int32_t* d_pnode = nullptr;
+    double *d_pZ = nullptr, *d_plever = nullptr, *d_pinfo = nullptr;
+    uint32_t *d_prow_node = nullptr, *d_prow_first = nullptr, *d_porder = nullptr;
+    elm::PgPriorDev prior{};
 };
 
 namespace elm_pgraph_host {
@@ -60,7 +70,16 @@ struct PcgStats {
 
 // the incidence lists on the device are those of the current edge set (elm_pgraph.cpp)
 hipError_t ensure_csr(elm_posegraph* pg, hipStream_t st);
-// no node of pg is fixed: the gauge is free
-inline bool gauge_free(const elm_posegraph* pg) { return std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end(); }
+// the rows of the priors on the device are those of the current prior set (elm_pgprior.cpp); nothing to do without priors
+hipError_t ensure_prior_rows(elm_posegraph* pg, hipStream_t st);
+// the priors' view for the launchers, or null when the object holds none: every added launch is then skipped
+inline const elm::PgPriorDev* prior_view(elm_posegraph* pg) {
+    pg->prior.P = pg->P;
+    return pg->P ? &pg->prior : nullptr;
+}
+// no node of pg is fixed and no prior ties it to the world: the gauge is free
+inline bool gauge_free(const elm_posegraph* pg) {
+    return !pg->P && std::find(pg->fixed.begin(), pg->fixed.end(), (uint8_t)1) == pg->fixed.end();
+}
 
 } // namespace elm_pgraph_host

@@ -214,6 +214,7 @@ class LoopCloser:
         self.reg = registration if registration is not None else Registration(m_config, ctx=self.ctx)
         self.scans, self.poses = [], []
         self.loops = []  # AddLoop: (entry_a, entry_b, T_a_b, information)
+        self.priors = []  # AddPosePrior / AddPositionPrior: (entry, Z, information 6 x 6, lever)
 
     def Insert(self, scan, T_world_sensor, T_level=None):
         sc = _resident(self.ctx, scan)
@@ -264,6 +265,29 @@ class LoopCloser:
         info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
         self.loops.append((a, b, np.array(T_a_b, dtype=np.float64).reshape(4, 4), info))
 
+    def _add_prior(self, what, entry, Z, info, lever):
+        e = int(entry)
+        if not 0 <= e < len(self.scans):
+            raise ElmError(f"LoopCloser.{what}: no such entry")
+        lv = np.zeros(3) if lever is None else np.array(lever, dtype=np.float64).reshape(3)
+        self.priors.append((e, Z, info, lv))
+
+    def AddPosePrior(self, entry, T_world_sensor, information=None, lever=None):
+        """An absolute pose measurement of an entry for Close (a match against an existing map, a GNSS pose): T_world_sensor 4 x 4,
+        information 6 x 6 symmetric in the order [translation; rotation] (default: the identity), lever: the measured point in the
+        entry's frame (default: its origin).  PoseGraph.AddPriors' factor."""
+        info = np.eye(6) if information is None else np.array(information, dtype=np.float64).reshape(6, 6)
+        self._add_prior("AddPosePrior", entry, np.array(T_world_sensor, dtype=np.float64).reshape(4, 4), info, lever)
+
+    def AddPositionPrior(self, entry, position, information=None, lever=None):
+        """An absolute position measurement of an entry for Close (a GNSS fix at the antenna `lever`): position [3] in the world,
+        information 3 x 3 symmetric (default: the identity).  PoseGraph.AddPositionPriors' factor."""
+        Z = np.eye(4)
+        Z[:3, 3] = np.asarray(position, dtype=np.float64).reshape(3)
+        info = np.zeros((6, 6))
+        info[:3, :3] = np.eye(3) if information is None else np.asarray(information, dtype=np.float64).reshape(3, 3)
+        self._add_prior("AddPositionPrior", entry, Z, info, lever)
+
     def ConsistentLoops(self, cfg=None, var_t=None, var_r=None, odom_covariance=None):
         """The loops of AddLoop that agree with one another over the inserted poses (loops.LoopConsistency on self.poses and
         self.loops; cfg: a LoopConsistencyConfig, whose q_t and q_r say how good the odometry is per entry) -> its dict.  var_t,
@@ -288,7 +312,7 @@ class LoopCloser:
         return LoopConsistency(np.stack(self.poses), [l[0] for l in self.loops], [l[1] for l in self.loops], Z, var_t, var_r, cfg, self.ctx)
 
     def Close(self, cfg=None, odom_information=None, fixed=(0,), apply=False, preconditioner="block_jacobi", initialize=False,
-              consistency=None, odom_covariance=None, marginals=None):
+              consistency=None, odom_covariance=None, marginals=None, prior_huber_k=0.0):
         """The corrected poses of all entries: a PoseGraph over the entries at their inserted poses, the odometry edges
         Z = T_k^-1 T_k+1 of those poses (information odom_information, one 6 x 6 for all), the loops of AddLoop, and Optimize(cfg)
         -> (poses [n, 4, 4], PoseGraph.Optimize's result).  apply=True replaces self.poses (Submap, Guess and Map then use them).
@@ -302,7 +326,9 @@ class LoopCloser:
         their original order, and its dict is put under "consistency"; odom_covariance is handed to ConsistentLoops with it (the
         covariance model) and is not used otherwise.  marginals: node indices; then one Linearize at the final poses with cfg's huber_k
         and PoseGraph.Marginals(marginals) put the covariances [m, 6, 6] under "marginals" and the call's stats under
-        "marginals_stats", solved with the same preconditioner.  The defaults leave every result as it was."""
+        "marginals_stats", solved with the same preconditioner.  The priors of AddPosePrior / AddPositionPrior are added in the order
+        they were given, under the Huber threshold prior_huber_k of their own (0: off); with at least one, fixed=() is legal: the priors
+        tie the graph to the world.  Initialize ignores them.  The defaults, without priors, leave every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
@@ -310,7 +336,7 @@ class LoopCloser:
         P = np.stack(self.poses)
         kept = self.ConsistentLoops(consistency, odom_covariance=odom_covariance) if consistency is not None else None
         loops = self.loops if kept is None else [self.loops[k] for k in kept["members"]]
-        pg = PoseGraph(n, n - 1 + max(len(loops), 1), self.ctx)
+        pg = PoseGraph(n, n - 1 + max(len(loops), 1), self.ctx, prior_capacity=len(self.priors))
         try:
             fx = np.zeros(n, bool)
             fx[list(fixed)] = True
@@ -320,6 +346,10 @@ class LoopCloser:
             pg.AddEdges(np.arange(n - 1), np.arange(1, n), Z, None if odom_information is None else np.asarray(odom_information, dtype=np.float64))
             if loops:
                 pg.AddEdges([l[0] for l in loops], [l[1] for l in loops], np.stack([l[2] for l in loops]), np.stack([l[3] for l in loops]))
+            if self.priors:
+                pg.SetPriorHuber(prior_huber_k)
+                pg.AddPriors([q[0] for q in self.priors], np.stack([q[1] for q in self.priors]), np.stack([q[2] for q in self.priors]),
+                             np.stack([q[3] for q in self.priors]))
             init = pg.Initialize() if initialize else None
             res = pg.Optimize(cfg)
             if initialize:

@@ -1,7 +1,8 @@
 """Pose graph (include/elimaloc_hip.h "pose graph"): nodes and relative-pose edges resident on the GPU, their SE(3)
 linearization, the damped normal equations solved by preconditioned conjugate gradients (block Jacobi, or per object the chain
 preconditioner of PoseGraph.SetPreconditioner), and Levenberg-Marquardt around that -- from odometry constraints and loop constraints
-to corrected poses."""
+to corrected poses; with priors (include/elimaloc_hip_posegraph_prior.h, DESIGN.md section 27: absolute pose and position factors, GNSS
+and map matches) to poses in the world frame."""
 import ctypes as C
 
 import numpy as np
@@ -48,6 +49,25 @@ def EdgeTerms(Ti, Tj, Z):
     return r, A, B
 
 
+def PriorTerms(T, Z, lever=None):
+    """(r [6], J [6, 6]) of one prior (include/elimaloc_hip_posegraph_prior.h): the library's own residual and Jacobian (host only, the
+    code the kernel runs).  lever: the measured point in the node's frame, default zero."""
+    r, J = np.zeros(6), np.zeros((6, 6))
+    lv = None if lever is None else np.ascontiguousarray(np.asarray(lever, dtype=np.float64).reshape(3))
+    check(_lib.lib().elm_posegraph_prior_terms(_dp(_pose_block(T)), _dp(_pose_block(Z)), None if lv is None else _dp(lv), _dp(r), _dp(J)), None,
+          "elm_posegraph_prior_terms")
+    return r, J
+
+
+def _per_item(a, n, shape, what):
+    """one `shape` block for all n items, or one per item -> contiguous [n, *shape]"""
+    a = np.asarray(a, dtype=np.float64)
+    a = np.broadcast_to(a, (n,) + shape) if a.ndim == len(shape) else a.reshape((-1,) + shape)
+    if a.shape[0] != n:
+        raise ElmError(what)
+    return np.ascontiguousarray(a)
+
+
 def _result(res, trace, n):
     out = dict(solves=int(res.solves), accepted=int(res.accepted), rejected=int(res.rejected), cost_initial=float(res.cost_initial),
                cost_final=float(res.cost_final), lambda_final=float(res.lambda_final), pcg_iterations_total=int(res.pcg_iterations_total),
@@ -60,12 +80,15 @@ def _result(res, trace, n):
 class PoseGraph(_Owned):
     """A pose graph resident on the device (elm_posegraph), of capacities fixed at creation (nodes 1 .. 2^20, edges 1 .. 2^22)."""
 
-    def __init__(self, node_capacity=1024, edge_capacity=4096, ctx=None):
+    def __init__(self, node_capacity=1024, edge_capacity=4096, ctx=None, prior_capacity=0):
         self.ctx = ctx if ctx is not None else default_context()
         self.node_capacity, self.edge_capacity = int(node_capacity), int(edge_capacity)
         self._h = C.c_void_p()
         check(_lib.lib().elm_posegraph_create(self.ctx._h, self.node_capacity, self.edge_capacity, C.byref(self._h)), self.ctx._h,
               "elm_posegraph_create")
+        self.prior_capacity = 0
+        if int(prior_capacity) > 0:
+            self.ReservePriors(prior_capacity)
 
     def _handle(self):
         if not getattr(self, "_h", None):
@@ -82,8 +105,75 @@ class PoseGraph(_Owned):
         return int(n.value), int(e.value)
 
     def Reset(self):
-        """No nodes, no edges; the preconditioner kind stays."""
+        """No nodes, no edges, no priors; the preconditioner kind, the priors' capacity and their Huber threshold stay."""
         self._call("elm_posegraph_reset")
+
+    # ---- priors: absolute pose and position factors (include/elimaloc_hip_posegraph_prior.h, DESIGN.md section 27)
+    def ReservePriors(self, capacity):
+        """Room for `capacity` priors (1 .. 2^22), a second device allocation; once per object."""
+        self._call("elm_posegraph_reserve_priors", int(capacity))
+        self.prior_capacity = int(capacity)
+
+    def PriorCount(self):
+        n = C.c_size_t(0)
+        self._call("elm_posegraph_prior_count", C.byref(n))
+        return int(n.value)
+
+    def AddPriors(self, nodes, Z, information=None, lever=None):
+        """Priors (nodes[k], Z[k] ~ T_node with the measured point at lever[k] in the node's frame, information[k] 6 x 6 symmetric in the
+        order [v; w], possibly singular; default identity) appended.  information and lever: one for all, or one per prior."""
+        v = _nodes(nodes)
+        n = v.size
+        Zb = _pose_block(Z)
+        what = "PoseGraph.AddPriors: one Z, information and lever per prior"
+        info = _per_item(np.eye(6) if information is None else information, n, (6, 6), what)
+        lv = None if lever is None else _per_item(lever, n, (3,), what)
+        if Zb.size != 16 * n:
+            raise ElmError(what)
+        self._call("elm_posegraph_add_priors", _ptr(v) if n else None, _dp(Zb) if n else None, _dp(lv) if n and lv is not None else None,
+                   _dp(info) if n else None, n)
+
+    def AddPositionPriors(self, nodes, positions, information=None, lever=None):
+        """Position measurements (GNSS at the antenna `lever`): positions [n, 3] in the world, information 3 x 3 (one for all or one per
+        prior, default identity).  Z = [I | p] and a 6 x 6 information whose rotation rows and columns are zero."""
+        v = _nodes(nodes)
+        n = v.size
+        what = "PoseGraph.AddPositionPriors: one position, information and lever per prior"
+        p = _per_item(positions, n, (3,), what) if n else np.zeros((0, 3))
+        Z = np.tile(np.eye(4), (n, 1, 1))
+        Z[:, :3, 3] = p
+        info = np.zeros((n, 6, 6))
+        info[:, :3, :3] = _per_item(np.eye(3) if information is None else information, n, (3, 3), what)
+        self.AddPriors(v, Z, info, lever)
+
+    def Priors(self):
+        """The priors as they were added -> dict(node [P], Z [P, 4, 4], lever [P, 3], information [P, 6, 6])."""
+        P = self.PriorCount()
+        n = max(P, 1)
+        node, Z, lever, info = np.zeros(n, np.int32), np.zeros((n, 16)), np.zeros((n, 3)), np.zeros((n, 6, 6))
+        self._call("elm_posegraph_get_priors", 0, P, _ptr(node), _dp(Z), _dp(lever), _dp(info))
+        return dict(node=node[:P], Z=np.ascontiguousarray(Z[:P].reshape(-1, 4, 4).transpose(0, 2, 1)), lever=lever[:P], information=info[:P])
+
+    def ClearPriors(self):
+        """No priors; their capacity and Huber threshold stay."""
+        self._call("elm_posegraph_clear_priors")
+
+    def SetPriorHuber(self, k):
+        """The priors' own Huber threshold on s_q = r^T Omega r (0, the default: off); kept across Reset."""
+        self._call("elm_posegraph_set_prior_huber", float(k))
+
+    def PriorHuber(self):
+        k = C.c_double(-1.0)
+        self._call("elm_posegraph_get_prior_huber", C.byref(k))
+        return float(k.value)
+
+    def PriorLinearization(self):
+        """The priors' part of the current linearization -> dict(r [P, 6], J [P, 6, 6], s [P], w [P])."""
+        P = self.PriorCount()
+        n = max(P, 1)
+        r, J, s, w = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros(n), np.zeros(n)
+        self._call("elm_posegraph_download_prior_linearization", _dp(r), _dp(J), _dp(s), _dp(w))
+        return dict(r=r[:P], J=J[:P], s=s[:P], w=w[:P])
 
     def SetPreconditioner(self, kind):
         """"block_jacobi" (the default) or "chain": the block-tridiagonal M over the index chain v, v + 1, applied by block cyclic
@@ -171,7 +261,8 @@ class PoseGraph(_Owned):
     def Initialize(self, cfg=None, return_stages=False):
         """The linear initialization (include/elimaloc_hip_posegraph_init.h): the rotations from one linear least-squares problem on
         their first two rows, projected back to SO(3), then the translations from an exactly linear one, both by the conjugate gradients
-        and the preconditioner of this object.  The poses are replaced only if every requested stage converged -> dict(cost_before,
+        and the preconditioner of this object.  Priors are ignored: the conditions, the two problems and the costs are those of the
+        edges and the fixed nodes alone.  The poses are replaced only if every requested stage converged -> dict(cost_before,
         cost_after, rot_iterations, trans_iterations, rot_rel_residual, trans_rel_residual, rot_converged, trans_converged,
         degenerate_nodes, applied); with return_stages also rows [N, 6] (the solved rows before the projection) and v [N, 3]."""
         cfg = cfg if cfg is not None else PoseGraphInitConfig()

@@ -41,6 +41,18 @@ struct PoseGraphLinearization {
     std::vector<double> r, A, B, s, w, grad, diag; // [E][6], [E][36], [E][36], [E], [E], [N][6], [N][36], row-major
 };
 
+// an absolute factor on one node (elimaloc_hip_posegraph_prior.h): a measured pose, or with a singular information a measured position
+struct PoseGraphPrior {
+    int node = 0;
+    elimaloc::Matrix4d Z = elimaloc::Matrix4d::Identity();           // ~ T_node: world <- measured frame
+    elimaloc::Vector3d lever = elimaloc::Vector3d::Zero();           // the measured point in the node's frame
+    elimaloc::Matrix6d information = elimaloc::Matrix6d::Identity(); // symmetric, in the order [translation; rotation]; may be singular
+};
+
+struct PoseGraphPriorLinearization {
+    std::vector<double> r, J, s, w; // [P][6], [P][36], [P], [P], row-major
+};
+
 class PoseGraph {
 public:
     using Poses = std::vector<elimaloc::Matrix4d>;
@@ -208,6 +220,66 @@ public:
                         VoxelHashMap::ctx(), "elm_posegraph_relative_covariance");
         cov.pop_back();
         return cov;
+    }
+    // Priors (elimaloc_hip_posegraph_prior.h): room for them once per object, then absolute pose / position factors under a Huber
+    // threshold of their own (0: off; kept across Reset, as the capacity is).  With at least one prior Optimize needs no fixed node.
+    inline void ReservePriors(int capacity) {
+        elimaloc::check(elm_posegraph_reserve_priors(VoxelHashMap::ctx(), pg_, capacity), VoxelHashMap::ctx(), "elm_posegraph_reserve_priors");
+    }
+    inline size_t Priors() const {
+        size_t n = 0;
+        elimaloc::check(elm_posegraph_prior_count(VoxelHashMap::ctx(), pg_, &n), VoxelHashMap::ctx(), "elm_posegraph_prior_count");
+        return n;
+    }
+    inline void AddPriors(const std::vector<PoseGraphPrior>& priors) {
+        const size_t n = priors.size();
+        std::vector<int32_t> node(n + 1);
+        std::vector<double> Z(16 * n + 1), lever(3 * n + 1), info(36 * n + 1);
+        for (size_t k = 0; k < n; ++k) {
+            node[k] = priors[k].node;
+            for (int q = 0; q < 16; ++q) Z[16 * k + (size_t)q] = priors[k].Z.data()[q];
+            for (int q = 0; q < 3; ++q) lever[3 * k + (size_t)q] = priors[k].lever(q);
+            for (int r = 0; r < 6; ++r)
+                for (int c = 0; c < 6; ++c) info[36 * k + (size_t)(r * 6 + c)] = priors[k].information(r, c);
+        }
+        elimaloc::check(elm_posegraph_add_priors(VoxelHashMap::ctx(), pg_, node.data(), Z.data(), lever.data(), info.data(), n), VoxelHashMap::ctx(),
+                        "elm_posegraph_add_priors");
+    }
+    // position measurements: Z = [I | position], the 3 x 3 information in the translation block, the rotation rows and columns zero
+    inline void AddPositionPriors(const std::vector<int>& nodes, const std::vector<elimaloc::Vector3d>& positions,
+                                  const elimaloc::Matrix3d& information = elimaloc::Matrix3d::Identity(),
+                                  const elimaloc::Vector3d& lever = elimaloc::Vector3d::Zero()) {
+        elimaloc::check(nodes.size() == positions.size() ? ELM_OK : ELM_ERR_INVALID, VoxelHashMap::ctx(), "PoseGraph::AddPositionPriors: one position per node");
+        std::vector<PoseGraphPrior> priors(nodes.size());
+        for (size_t k = 0; k < nodes.size(); ++k) {
+            priors[k].node = nodes[k];
+            priors[k].lever = lever;
+            priors[k].information = elimaloc::Matrix6d::Zero();
+            for (int r = 0; r < 3; ++r) {
+                priors[k].Z(r, 3) = positions[k](r);
+                for (int c = 0; c < 3; ++c) priors[k].information(r, c) = information(r, c);
+            }
+        }
+        AddPriors(priors);
+    }
+    inline void ClearPriors() { elimaloc::check(elm_posegraph_clear_priors(VoxelHashMap::ctx(), pg_), VoxelHashMap::ctx(), "elm_posegraph_clear_priors"); }
+    inline void SetPriorHuber(double k) {
+        elimaloc::check(elm_posegraph_set_prior_huber(VoxelHashMap::ctx(), pg_, k), VoxelHashMap::ctx(), "elm_posegraph_set_prior_huber");
+    }
+    inline PoseGraphPriorLinearization PriorLinearization() const {
+        const size_t P = Priors();
+        PoseGraphPriorLinearization L;
+        L.r.assign(6 * P + 1, 0.0);
+        L.J.assign(36 * P + 1, 0.0);
+        L.s.assign(P + 1, 0.0);
+        L.w.assign(P + 1, 0.0);
+        elimaloc::check(elm_posegraph_download_prior_linearization(VoxelHashMap::ctx(), pg_, L.r.data(), L.J.data(), L.s.data(), L.w.data()),
+                        VoxelHashMap::ctx(), "elm_posegraph_download_prior_linearization");
+        L.r.pop_back();
+        L.J.pop_back();
+        L.s.pop_back();
+        L.w.pop_back();
+        return L;
     }
     // host only: the residual and Jacobians of one edge (row-major r[6], A[36], B[36])
     static inline void EdgeTerms(const elimaloc::Matrix4d& Ti, const elimaloc::Matrix4d& Tj, const elimaloc::Matrix4d& Z, double* r, double* A, double* B) {
