@@ -337,6 +337,20 @@ class PoseGraphInitResultC(C.Structure):
                 ("degenerate_nodes", C.c_int32), ("applied", C.c_int32)]
 
 
+class PoseGraphInitPriorConfigC(C.Structure):
+    """elm_posegraph_init_prior_config (include/elimaloc_hip_posegraph_init_prior.h)."""
+    _fields_ = [("base", PoseGraphInitConfigC), ("align_min_ratio", C.c_double)]
+
+
+class PoseGraphInitPriorResultC(C.Structure):
+    """elm_posegraph_init_prior_result."""
+    _fields_ = [("base", PoseGraphInitResultC), ("pre_rel_residual", C.c_double), ("pre_iterations", C.c_int32), ("pre_converged", C.c_int32),
+                ("aligned_components", C.c_int32), ("rank_deficient_components", C.c_int32), ("min_align_ratio", C.c_double)]
+
+
+PG_INIT_ALIGN_ROW = 28  # ELM_PG_INIT_ALIGN_ROW: c_a[3], c_b[3], S[9], W, G[9], sigma[3]
+
+
 class LoopsConfigC(C.Structure):
     """elm_loops_config (include/elimaloc_hip_loops.h)."""
     _fields_ = [("q_t", C.c_double), ("q_r", C.c_double), ("gamma", C.c_double), ("steps_per_batch", C.c_int32), ("reserved", C.c_int32)]
@@ -627,11 +641,16 @@ DECLS_PGPRIOR = {  # include/elimaloc_hip_posegraph_prior.h (the pose graph's ab
     "elm_posegraph_download_prior_linearization": _sig(vp, vp, dp, dp, dp, dp),
     "elm_posegraph_prior_terms": _sig(dp, dp, dp, dp, dp),
 }
+DECLS_PGINITP = {  # include/elimaloc_hip_posegraph_init_prior.h (the pose graph's linear initialization with the priors in it)
+    "elm_posegraph_init_prior_config_default": _sig(P(PoseGraphInitPriorConfigC), ret=None),
+    "elm_posegraph_initialize_priors": _sig(vp, vp, P(PoseGraphInitPriorConfigC), P(PoseGraphInitPriorResultC), dp, dp, dp, dp, i),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
 EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
 EXPORTS_LOOPCOV = list(DECLS_LOOPCOV)
 EXPORTS_PGCOV = list(DECLS_PGCOV)
 EXPORTS_PGPRIOR = list(DECLS_PGPRIOR)
+EXPORTS_PGINITP = list(DECLS_PGINITP)
 
 _LIB = None
 
@@ -645,7 +664,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV, DECLS_PGPRIOR):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV, DECLS_PGPRIOR, DECLS_PGINITP):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -576,6 +576,17 @@ void launch_pgi_trans_terms(hipStream_t s, const PgDev& d, const double* poses);
 void launch_pgi_rot_apply(hipStream_t s, const PgDev& d, const double* poses, double* trial, double* rows, double* slots);
 // t <- t + R v of the active nodes, in place
 void launch_pgi_trans_apply(hipStream_t s, const PgDev& d, double* trial);
+// pose graph, linear initialization with priors (elm_k_pginitp.hip; the contract is
+// include/elimaloc_hip_posegraph_init_prior.h).  The term kernel fills g and H of the priors' view as launch_pgp_linearize does, for
+// launch_pgp_nodes to follow; weight [P] is the stage's weight of every prior (0: not in the stage); stage 0: rotations, 1: translations.
+// P >= 1
+void launch_pgip_terms(hipStream_t s, const PgPriorDev& p, const double* poses, const double* weight, int stage);
+// out [n_comps][16] = c_a, c_b, S row-major, W of each aligned component from its priors list[first[c] .. first[c + 1]); n_comps >= 1
+// and no list empty
+void launch_pgip_align_sums(hipStream_t s, const PgPriorDev& p, const double* poses, const double* weight, const uint32_t* first,
+                            const uint32_t* list, uint32_t n_comps, double* out);
+// comp [N]: the aligned component of the node or -1; xf [n_comps][21] = G row-major, c_a, c_b; in place on trial; N >= 1
+void launch_pgip_align_apply(hipStream_t s, uint32_t N, const int32_t* comp, const double* xf, double* trial);
 
 // loop consistency (elm_k_loops.hip; the contract is include/elimaloc_hip_loops.h): the device's view of one call.
 // adj is [L][W] with W = lc_words(L); the greedy step `it` reads cand and stop of parity it & 1 and writes those of the other parity.

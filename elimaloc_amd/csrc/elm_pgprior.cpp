@@ -144,6 +144,8 @@ extern "C" int elm_posegraph_add_priors(elm_ctx* ctx, elm_posegraph* pg, const i
         for (size_t k = 0; k < n; ++k) pose_rows12(Z16 + 16 * k, &rows[12 * k]);
         if (lever3) memcpy(lever.data(), lever3, 3 * n * sizeof(double));
         pg->pnode.reserve((size_t)pg->P + n);
+        pg->pwr.reserve((size_t)pg->P + n);
+        pg->pwt.reserve((size_t)pg->P + n);
         const size_t P0 = pg->P;
         hipError_t e = hipMemcpyAsync(pg->d_pnode + P0, node, n * sizeof(int32_t), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pg->d_pZ + 12 * P0, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st);
@@ -152,6 +154,11 @@ extern "C" int elm_posegraph_add_priors(elm_ctx* ctx, elm_posegraph* pg, const i
         int rc = join(ctx, st, e, what);
         if (rc != ELM_OK) return rc;
         pg->pnode.insert(pg->pnode.end(), node, node + n);
+        for (size_t k = 0; k < n; ++k) { // the two traces, as elm_posegraph_add_edges keeps them per edge
+            const double* om = info36 + 36 * k;
+            pg->pwt.push_back(((om[0] + om[7]) + om[14]) / 3.0);
+            pg->pwr.push_back(((om[21] + om[28]) + om[35]) / 3.0);
+        }
         pg->P += (uint32_t)n;
         invalidate(pg);
         return (int)ELM_OK;
@@ -198,6 +205,8 @@ extern "C" int elm_posegraph_clear_priors(elm_ctx* ctx, elm_posegraph* pg) {
     if (rc != ELM_OK) return rc;
     pg->P = 0;
     pg->pnode.clear();
+    pg->pwr.clear();
+    pg->pwt.clear();
     invalidate(pg);
     return ELM_OK;
 }

@@ -3,9 +3,10 @@
 // lists (a stable counting sort of (edge, side) by node, redone when the edge set has changed), the conjugate-gradient driver that
 // queues pcg_check_every iterations between two reads of the device's state (elm_call.hpp's run_batched), the Levenberg-Marquardt loop
 // around it, and the linear initialization (include/elimaloc_hip_posegraph_init.h; DESIGN.md section 23: its preconditions and its two
-// stages on the same driver).  The object itself is elm_pgraph_host.hpp's, which the covariances (elm_pgcov.cpp) and the priors
+// stages on the same driver; with the priors in it include/elimaloc_hip_posegraph_init_prior.h and DESIGN.md section 28: the plan of
+// elm_pginit_classes.hpp, the gauge nodes, the alignment).  The object itself is elm_pgraph_host.hpp's, which the covariances (elm_pgcov.cpp) and the priors
 // (elm_pgprior.cpp: their calls and arrays; their launches are queued here, with the linearization and the cost) share.  The launches
-// are those of elm_k_pgraph.hip, elm_k_pgchain.hip, elm_k_pginit.hip and elm_k_pgprior.hip.  Host-side C++17.
+// are those of elm_k_pgraph.hip, elm_k_pgchain.hip, elm_k_pginit.hip, elm_k_pgprior.hip and elm_k_pginitp.hip.  Host-side C++17.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "elm_pginit_classes.hpp"
 #include "elm_pgraph_host.hpp"
 
 using namespace elm;
@@ -315,15 +317,22 @@ bool init_config_ok(const elm_posegraph_init_config* c) {
            c->stages <= (ELM_PG_INIT_ROT | ELM_PG_INIT_TRANS);
 }
 
-// The preconditions of elm_posegraph_initialize that need the graph: "" when they hold, else the text for elm_last_error.  The
-// components come from a union-find over the host's copy of the edges (path halving, the smaller index the root).
-std::string init_refusal(const elm_posegraph* pg, int stages) {
+// The preconditions on the nodes and the edge weights that both initializations share: "" when they hold, else the text.
+std::string init_edge_refusal(const elm_posegraph* pg, int stages) {
     if (!pg->N) return "no node in the graph";
     for (uint32_t e = 0; e < pg->E; ++e) {
         if ((stages & ELM_PG_INIT_ROT) && !(pg->wr[e] > 0.0)) return "edge " + std::to_string(e) + " has no positive rotation weight trace(Omega_ww) / 3";
         if ((stages & ELM_PG_INIT_TRANS) && !(pg->wt[e] > 0.0))
             return "edge " + std::to_string(e) + " has no positive translation weight trace(Omega_vv) / 3";
     }
+    return "";
+}
+
+// The preconditions of elm_posegraph_initialize that need the graph: "" when they hold, else the text for elm_last_error.  The
+// components come from a union-find over the host's copy of the edges (path halving, the smaller index the root).
+std::string init_refusal(const elm_posegraph* pg, int stages) {
+    const std::string edges = init_edge_refusal(pg, stages);
+    if (!edges.empty()) return edges;
     std::vector<uint32_t> root(pg->N);
     for (uint32_t v = 0; v < pg->N; ++v) root[v] = v;
     auto find = [&](uint32_t v) {
@@ -344,27 +353,111 @@ std::string init_refusal(const elm_posegraph* pg, int stages) {
 }
 
 // One stage of the initialization: its edge terms at `at`, the undamped node sums (with the chain factor), the conjugate gradients.
+// pr: null, or the priors whose terms of `stage` (0: rotations, 1: translations) under the weights `weight` are added onto the node sums
+// by queue_linearize's launch pattern; without them the launches are those of before.
 int init_stage(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_init_config& c,
-               void (*launch_terms)(hipStream_t, const PgDev&, const double*), const double* at, PcgStats& s, const char* what) {
+               void (*launch_terms)(hipStream_t, const PgDev&, const double*), const double* at, const PgPriorDev* pr, const double* weight, int stage,
+               PcgStats& s, const char* what) {
     const PgDev& d = dev_view(pg);
     hipError_t e = launched([&] {
         launch_terms(st, d, at);
-        launch_damping(st, d, chain(pg), 0.0, 1);
+        if (!pr) {
+            launch_damping(st, d, chain(pg), 0.0, 1);
+            return;
+        }
+        launch_pgip_terms(st, *pr, at, weight, stage);
+        launch_pg_nodes(st, d, 0.0, 1);
+        launch_pgp_nodes(st, d, *pr);
+        launch_damping(st, d, chain(pg), 0.0, 0);
     });
     if (e != hipSuccess) return dev_error(ctx, what, e);
     return run_pcg(ctx, pg, st, 0.0, c.pcg_rel_tol, c.pcg_max_iterations, c.pcg_check_every, s, what);
 }
 
+// What elm_posegraph_initialize_priors adds to a run of the initialization (null for elm_posegraph_initialize, which ignores priors).
+struct InitPriorRun {
+    const elm_pginit::Plan* plan;
+    double align_min_ratio;
+    elm_posegraph_init_prior_result* ext; // everything but `base`
+    double *v_pre_out, *align_out;
+    int align_capacity;
+};
+
+// The gauge nodes held as if fixed on the device; the object's own flags are put back when the guard is released or leaves.
+struct GaugeHold {
+    elm_posegraph* pg;
+    hipStream_t st;
+    bool held = false;
+    hipError_t upload(const std::vector<uint8_t>& fx) {
+        hipError_t e = hipMemcpyAsync(pg->d_fixed, fx.data(), fx.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // the host vector is read until here
+        return e;
+    }
+    hipError_t hold(const std::vector<uint32_t>& gauge) {
+        std::vector<uint8_t> fx(pg->fixed);
+        for (uint32_t v : gauge) fx[v] = 1;
+        held = true;
+        return upload(fx);
+    }
+    hipError_t release() {
+        if (!held) return hipSuccess;
+        held = false;
+        return upload(pg->fixed);
+    }
+    ~GaugeHold() { (void)release(); }
+};
+
+// the priors' Huber threshold off for the call's costs, and back as it was however the call ends
+struct PriorHuberOff {
+    double& k;
+    const double old;
+    explicit PriorHuberOff(double& ref) : k(ref), old(ref) { k = 0.0; }
+    void back() { k = old; }
+    ~PriorHuberOff() { back(); }
+};
+
 int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_posegraph_init_config& c, elm_posegraph_init_result* res, double* rows_out,
-                    double* v_out) {
-    const char* what = "elm_posegraph_initialize";
+                    double* v_out, const InitPriorRun* run, const char* what) {
     const size_t N = pg->N;
     const bool rot = (c.stages & ELM_PG_INIT_ROT) != 0, trans = (c.stages & ELM_PG_INIT_TRANS) != 0;
     elm_posegraph_init_result R{};
     hipError_t e = ensure_csr(pg, st);
+    if (e == hipSuccess && run) e = ensure_prior_rows(pg, st);
     if (e != hipSuccess) return dev_error(ctx, what, e);
+    // With priors in the run: their view, the three weight arrays and the aligned components' lists in the call's one allocation.
+    // Without a prior in the object pv is null and every launch below is elm_posegraph_initialize's.
+    const PgPriorDev* pv = run ? prior_view(pg) : nullptr;
+    const size_t P = pv ? pg->P : 0, A = pv ? run->plan->aligned() : 0;
+    DeviceBlob blob(st);
+    double *d_w = nullptr, *d_sums = nullptr, *d_xf = nullptr;
+    uint32_t *d_first = nullptr, *d_list = nullptr;
+    int32_t* d_comp = nullptr;
+    GaugeHold gauge{pg, st};
+    if (pv) {
+        const elm_pginit::Plan& pl = *run->plan;
+        e = blob.alloc([&](Carver& cv) {
+            d_w = cv.take<double>(3 * P);
+            d_first = cv.take<uint32_t>(A + 1);
+            d_list = cv.take<uint32_t>(pl.list.size());
+            d_comp = cv.take<int32_t>(A ? N : 0);
+            d_sums = cv.take<double>(16 * A);
+            d_xf = cv.take<double>(21 * A);
+        });
+        if (e == hipSuccess) e = hipMemcpyAsync(d_w, pl.w_rot.data(), P * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_w + P, pl.w_pre.data(), P * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_w + 2 * P, pl.w_last.data(), P * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && A) e = hipMemcpyAsync(d_first, pl.list_first.data(), (A + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && A) e = hipMemcpyAsync(d_list, pl.list.data(), pl.list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && A) e = hipMemcpyAsync(d_comp, pl.node_comp.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && A) e = gauge.hold(pl.gauge); // held through S1 and S2
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+    }
+    const double *w_rot = d_w, *w_pre = d_w + P, *w_last = d_w + 2 * P;
     PgOut o{};
-    int rc = cost_at(ctx, pg, st, pg->poses, 0.0, 0, o, what, false); // (the initialization ignores priors, here and in its stages)
+    // elm_posegraph_initialize ignores priors, here and in its stages; with a run they count, both Huber thresholds off
+    double no_threshold = 0.0;
+    PriorHuberOff huber_off(run ? pg->prior_huber : no_threshold);
+    int rc = cost_at(ctx, pg, st, pg->poses, 0.0, 0, o, what, run != nullptr);
     if (rc != ELM_OK) return rc;
     R.cost_before = o.cost;
     // From here the contribution arrays, the node sums and the flags are those of the stages: a linearization that was valid is put
@@ -375,7 +468,7 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_p
     double* const rows = d.q; // [N][6]: the conjugate gradients' q is free between two solves
     PcgStats s;
     if (rot) {
-        rc = init_stage(ctx, pg, st, c, launch_pgi_rot_terms, pg->poses, s, what);
+        rc = init_stage(ctx, pg, st, c, launch_pgi_rot_terms, pg->poses, pv, w_rot, 0, s, what);
         if (rc != ELM_OK) return rc;
         R.rot_iterations = s.iterations;
         R.rot_converged = s.converged;
@@ -401,27 +494,73 @@ int initialize_impl(elm_ctx* ctx, elm_posegraph* pg, hipStream_t st, const elm_p
                 for (int q = 0; q < 6; ++q) rows_out[6 * v + q] = P[12 * v + (q < 3 ? q : q + 1)];
         }
     }
+    // one translation solve at the trial poses under the weights `weight`, applied; `out` [N][3] takes the upper three of the solution
+    auto trans_stage = [&](const double* weight, double* out) -> int {
+        int rc = init_stage(ctx, pg, st, c, launch_pgi_trans_terms, pg->trial, pv, weight, 1, s, what);
+        if (rc != ELM_OK) return rc;
+        std::vector<double> host(out ? 6 * N : 0); // the solution [N][6]
+        hipError_t e = launched([&] { launch_pgi_trans_apply(st, d, pg->trial); });
+        if (e == hipSuccess && out) e = hipMemcpyAsync(host.data(), d.x, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
+        rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        if (out)
+            for (size_t v = 0; v < N; ++v)
+                for (int q = 0; q < 3; ++q) out[3 * v + q] = host[6 * v + q];
+        return ELM_OK;
+    };
+    int deficient = 0;
+    if (run) {
+        *run->ext = elm_posegraph_init_prior_result{};
+        if (run->v_pre_out && !A) std::fill(run->v_pre_out, run->v_pre_out + 3 * N, 0.0);
+    }
     if (trans) {
-        rc = init_stage(ctx, pg, st, c, launch_pgi_trans_terms, pg->trial, s, what);
+        rc = trans_stage(A ? w_pre : w_last, A ? run->v_pre_out : v_out);
         if (rc != ELM_OK) return rc;
         R.trans_iterations = s.iterations;
         R.trans_converged = s.converged;
         R.trans_rel_residual = s.rel_residual;
-        std::vector<double> host(v_out ? 6 * N : 0); // the solution [N][6], of which v_out takes the upper three per node
-        e = launched([&] { launch_pgi_trans_apply(st, d, pg->trial); });
-        if (e == hipSuccess && v_out) e = hipMemcpyAsync(host.data(), d.x, 6 * N * sizeof(double), hipMemcpyDeviceToHost, st);
-        rc = join(ctx, st, e, what);
-        if (rc != ELM_OK) return rc;
-        if (v_out)
-            for (size_t v = 0; v < N; ++v)
-                for (int q = 0; q < 3; ++q) v_out[3 * v + q] = host[6 * v + q];
     } else if (v_out) {
         std::fill(v_out, v_out + 3 * N, 0.0);
     }
-    rc = cost_at(ctx, pg, st, pg->trial, 0.0, 0, o, what, false);
+    if (A) { // (both stages were requested: the plan aligns nothing otherwise)
+        elm_posegraph_init_prior_result& X = *run->ext;
+        X.pre_iterations = R.trans_iterations;
+        X.pre_converged = R.trans_converged;
+        X.pre_rel_residual = R.trans_rel_residual;
+        X.aligned_components = (int32_t)A;
+        e = gauge.release();
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        std::vector<double> sums(16 * A), out_rows(ELM_PG_INIT_ALIGN_ROW * A), xf(21 * A);
+        e = launched([&] { launch_pgip_align_sums(st, *pv, pg->trial, w_last, d_first, d_list, (uint32_t)A, d_sums); });
+        if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+        rc = join(ctx, st, e, what);
+        if (rc != ELM_OK) return rc;
+        for (size_t k = 0; k < A; ++k) {
+            double* row = &out_rows[ELM_PG_INIT_ALIGN_ROW * k];
+            elm_pginit::align_row(&sums[16 * k], row);
+            memcpy(&xf[21 * k], row + 16, 9 * sizeof(double));
+            memcpy(&xf[21 * k + 9], row, 6 * sizeof(double));
+            const double s1 = row[25], s2 = row[26], ratio = s1 > 0.0 ? s2 / s1 : 0.0;
+            if (!(s2 > run->align_min_ratio * s1)) ++deficient;
+            X.min_align_ratio = k ? std::min(X.min_align_ratio, ratio) : ratio;
+        }
+        X.rank_deficient_components = deficient;
+        if (run->align_out)
+            memcpy(run->align_out, out_rows.data(), ELM_PG_INIT_ALIGN_ROW * std::min(A, (size_t)run->align_capacity) * sizeof(double));
+        e = hipMemcpyAsync(d_xf, xf.data(), xf.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = launched([&] { launch_pgip_align_apply(st, pg->N, d_comp, d_xf, pg->trial); });
+        if (e != hipSuccess) return dev_error(ctx, what, e);
+        rc = trans_stage(w_last, v_out); // S3: the gauge nodes released, every prior in (its join also ends the reads of xf)
+        if (rc != ELM_OK) return rc;
+        R.trans_iterations = s.iterations;
+        R.trans_converged = s.converged;
+        R.trans_rel_residual = s.rel_residual;
+    }
+    rc = cost_at(ctx, pg, st, pg->trial, 0.0, 0, o, what, run != nullptr);
     if (rc != ELM_OK) return rc;
+    huber_off.back();
     R.cost_after = o.cost;
-    R.applied = ((!rot || R.rot_converged) && (!trans || R.trans_converged)) ? 1 : 0;
+    R.applied = ((!rot || R.rot_converged) && (!trans || R.trans_converged) && (!A || run->ext->pre_converged) && !deficient) ? 1 : 0;
     if (R.applied) {
         std::swap(pg->poses, pg->trial);
     } else if (was_valid) {
@@ -485,6 +624,8 @@ extern "C" int elm_posegraph_reset(elm_ctx* ctx, elm_posegraph* pg) {
     pg->csr_dirty = true;
     pg->P = 0; // the priors go with their nodes; their capacity and threshold stay
     pg->pnode.clear();
+    pg->pwr.clear();
+    pg->pwt.clear();
     pg->prior_rows_dirty = true;
     pg->lin_valid = false;
     return ELM_OK;
@@ -753,6 +894,42 @@ extern "C" int elm_posegraph_initialize(elm_ctx* ctx, elm_posegraph* pg, const e
             elm_host::ctx_set_error(ctx, std::string(what) + ": " + refusal);
             return ELM_ERR_INVALID;
         }
-        return initialize_impl(ctx, pg, st, *cfg, result, rows_out, v_out);
+        return initialize_impl(ctx, pg, st, *cfg, result, rows_out, v_out, nullptr, what);
+    });
+}
+
+extern "C" void elm_posegraph_init_prior_config_default(elm_posegraph_init_prior_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    elm_posegraph_init_config_default(&c->base);
+    c->align_min_ratio = 1e-4;
+}
+
+extern "C" int elm_posegraph_initialize_priors(elm_ctx* ctx, elm_posegraph* pg, const elm_posegraph_init_prior_config* cfg,
+                                               elm_posegraph_init_prior_result* result, double* rows_out, double* v_pre_out, double* v_out,
+                                               double* align_out, int align_capacity) {
+    const char* what = "elm_posegraph_initialize_priors";
+    if (!ctx || !pg || !result || !cfg || !init_config_ok(&cfg->base)) return ELM_ERR_INVALID;
+    if (!(isfinite(cfg->align_min_ratio) && cfg->align_min_ratio > 0.0) || align_capacity < 0) return ELM_ERR_INVALID;
+    int rc = check_object(ctx, pg, what);
+    if (rc != ELM_OK) return rc;
+    return on_stream(ctx, what, [&](hipStream_t st) -> int { // the plan's vectors and texts are allocated inside the guard too
+        std::string refusal = init_edge_refusal(pg, cfg->base.stages);
+        elm_pginit::Plan plan;
+        if (refusal.empty()) {
+            const elm_pginit::Graph g{pg->N,           pg->E,           pg->P,          pg->ei.data(), pg->ej.data(),
+                                      pg->fixed.data(), pg->pnode.data(), pg->pwr.data(), pg->pwt.data()};
+            plan = elm_pginit::plan(g, cfg->base.stages);
+            refusal = plan.refusal;
+        }
+        if (!refusal.empty()) {
+            elm_host::ctx_set_error(ctx, std::string(what) + ": " + refusal);
+            return ELM_ERR_INVALID;
+        }
+        elm_posegraph_init_prior_result R{};
+        const InitPriorRun run{&plan, cfg->align_min_ratio, &R, v_pre_out, align_out, align_capacity};
+        const int rc = initialize_impl(ctx, pg, st, cfg->base, &R.base, rows_out, v_out, &run, what);
+        if (rc == ELM_OK) *result = R;
+        return rc;
     });
 }

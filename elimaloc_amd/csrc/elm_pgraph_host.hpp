@@ -32,6 +32,7 @@ struct elm_posegraph {
     // the priors (include/elimaloc_hip_posegraph_prior.h; elm_pgprior.cpp): nothing of it exists before elm_posegraph_reserve_priors
     uint32_t p_cap = 0, P = 0;
     std::vector<int32_t> pnode;     // [P]: the host's copy
+    std::vector<double> pwr, pwt;   // [P]: trace(Omega_ww) / 3 and trace(Omega_vv) / 3, the weights of elm_posegraph_initialize_priors
     bool prior_rows_dirty = true;   // the rows of `prior` on the device are not those of pnode
     double prior_huber = 0.0;       // kept across a reset
     char* prior_blob = nullptr;     // every device array of `prior`, the second allocation

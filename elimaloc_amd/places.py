@@ -328,11 +328,16 @@ class LoopCloser:
         and PoseGraph.Marginals(marginals) put the covariances [m, 6, 6] under "marginals" and the call's stats under
         "marginals_stats", solved with the same preconditioner.  The priors of AddPosePrior / AddPositionPrior are added in the order
         they were given, under the Huber threshold prior_huber_k of their own (0: off); with at least one, fixed=() is legal: the priors
-        tie the graph to the world.  Initialize ignores them.  The defaults, without priors, leave every result as it was."""
+        tie the graph to the world.  initialize=True ignores them (and refuses fixed=()); initialize="priors" runs
+        PoseGraph.InitializeWithPriors instead, which uses them and needs no fixed node: the start for a long log held by GNSS positions
+        or map matches alone.  The defaults, without priors, leave every result as it was."""
         from .posegraph import PoseGraph
         n = len(self.scans)
         if n < 2:
             raise ElmError("LoopCloser.Close: at least two entries")
+        with_priors = isinstance(initialize, str)
+        if with_priors and initialize != "priors":
+            raise ElmError(f"LoopCloser.Close: initialize is False, True or \"priors\", not {initialize!r}")
         P = np.stack(self.poses)
         kept = self.ConsistentLoops(consistency, odom_covariance=odom_covariance) if consistency is not None else None
         loops = self.loops if kept is None else [self.loops[k] for k in kept["members"]]
@@ -350,7 +355,7 @@ class LoopCloser:
                 pg.SetPriorHuber(prior_huber_k)
                 pg.AddPriors([q[0] for q in self.priors], np.stack([q[1] for q in self.priors]), np.stack([q[2] for q in self.priors]),
                              np.stack([q[3] for q in self.priors]))
-            init = pg.Initialize() if initialize else None
+            init = pg.InitializeWithPriors() if with_priors else pg.Initialize() if initialize else None
             res = pg.Optimize(cfg)
             if initialize:
                 res["initialize"] = init

@@ -9,8 +9,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ElmError, PG_PRECOND, PG_STOP, PoseGraphConfigC, PoseGraphLinearizeStatsC, PoseGraphResultC, PoseGraphSolveStatsC,
-                   PoseGraphTraceC, PoseGraphInitConfigC, PoseGraphInitResultC, PoseGraphCovConfigC, PoseGraphCovStatsC, check)
-from ._marshal import _Owned, _config, _dp, _pose_block, _ptr
+                   PoseGraphTraceC, PoseGraphInitConfigC, PoseGraphInitResultC, PoseGraphCovConfigC, PoseGraphCovStatsC,
+                   PoseGraphInitPriorConfigC, PoseGraphInitPriorResultC, PG_INIT_ALIGN_ROW, check)
+from ._marshal import _Owned, _apply, _config, _dp, _pose_block, _ptr
 from .context import default_context
 
 
@@ -24,6 +25,15 @@ def PoseGraphInitConfig(**kw):
     """elm_posegraph_init_config with its defaults (both solves to 1e-8 in at most 50 000 iterations checked every 32;
     stages = PG_INIT_ROT | PG_INIT_TRANS, or one of them)."""
     return _config("PoseGraphInitConfig", PoseGraphInitConfigC, "elm_posegraph_init_config_default", kw)
+
+
+def PoseGraphInitPriorConfig(**kw):
+    """elm_posegraph_init_prior_config with its defaults: `base` as PoseGraphInitConfig (its fields are keywords here too, e.g.
+    pcg_rel_tol=1e-10 or stages=PG_INIT_ROT) and align_min_ratio 1e-4, the smallest sigma_2 / sigma_1 of an alignment that is applied."""
+    own = {k: kw.pop(k) for k in ("align_min_ratio", "base") if k in kw}
+    cfg = _config("PoseGraphInitPriorConfig", PoseGraphInitPriorConfigC, "elm_posegraph_init_prior_config_default", own)
+    _apply(cfg.base, kw, "PoseGraphInitPriorConfig has no field {k}")
+    return cfg
 
 
 def PoseGraphCovConfig(**kw):
@@ -75,6 +85,13 @@ def _result(res, trace, n):
     out["trace"] = [dict(cost=float(t.cost), lambda_=float(t.lambda_), accepted=bool(t.accepted), pcg_iterations=int(t.pcg_iterations))
                     for t in trace[:min(n, out["solves"])]]
     return out
+
+
+def _init_result(res):
+    return dict(cost_before=float(res.cost_before), cost_after=float(res.cost_after), rot_iterations=int(res.rot_iterations),
+                trans_iterations=int(res.trans_iterations), rot_rel_residual=float(res.rot_rel_residual),
+                trans_rel_residual=float(res.trans_rel_residual), rot_converged=bool(res.rot_converged),
+                trans_converged=bool(res.trans_converged), degenerate_nodes=int(res.degenerate_nodes), applied=bool(res.applied))
 
 
 class PoseGraph(_Owned):
@@ -262,7 +279,7 @@ class PoseGraph(_Owned):
         """The linear initialization (include/elimaloc_hip_posegraph_init.h): the rotations from one linear least-squares problem on
         their first two rows, projected back to SO(3), then the translations from an exactly linear one, both by the conjugate gradients
         and the preconditioner of this object.  Priors are ignored: the conditions, the two problems and the costs are those of the
-        edges and the fixed nodes alone.  The poses are replaced only if every requested stage converged -> dict(cost_before,
+        edges and the fixed nodes alone (InitializeWithPriors uses them).  The poses are replaced only if every requested stage converged -> dict(cost_before,
         cost_after, rot_iterations, trans_iterations, rot_rel_residual, trans_rel_residual, rot_converged, trans_converged,
         degenerate_nodes, applied); with return_stages also rows [N, 6] (the solved rows before the projection) and v [N, 3]."""
         cfg = cfg if cfg is not None else PoseGraphInitConfig()
@@ -270,12 +287,35 @@ class PoseGraph(_Owned):
         N = self.Size()[0] if return_stages else 0
         rows, v = np.zeros((max(N, 1), 6)), np.zeros((max(N, 1), 3))
         self._call("elm_posegraph_initialize", C.byref(cfg), C.byref(res), _dp(rows) if return_stages else None, _dp(v) if return_stages else None)
-        out = dict(cost_before=float(res.cost_before), cost_after=float(res.cost_after), rot_iterations=int(res.rot_iterations),
-                   trans_iterations=int(res.trans_iterations), rot_rel_residual=float(res.rot_rel_residual),
-                   trans_rel_residual=float(res.trans_rel_residual), rot_converged=bool(res.rot_converged),
-                   trans_converged=bool(res.trans_converged), degenerate_nodes=int(res.degenerate_nodes), applied=bool(res.applied))
+        out = _init_result(res)
         if return_stages:
             out["rows"], out["v"] = rows[:N], v[:N]
+        return out
+
+    def InitializeWithPriors(self, cfg=None, return_stages=False):
+        """The linear initialization with the priors in it (include/elimaloc_hip_posegraph_init_prior.h): Initialize's two problems with
+        every prior's term added, for graphs that priors hold and no fixed node does.  A component held by position priors alone is
+        solved with its smallest node as gauge, moved rigidly onto its positions (weighted Kabsch) and its translations solved again with
+        the priors in.  The poses are replaced only if every solve converged and no alignment is rank-deficient (fewer than three
+        positions, or collinear ones) -> Initialize's dict (trans_*: the last translation solve; the costs count the priors, Huber off)
+        plus pre_iterations, pre_rel_residual, pre_converged, aligned_components, rank_deficient_components, min_align_ratio; with
+        return_stages also rows [N, 6], v_pre [N, 3], v [N, 3] and align [aligned_components, 28] (c_a, c_b, S, W, G, sigma)."""
+        cfg = cfg if cfg is not None else PoseGraphInitPriorConfig()
+        res = PoseGraphInitPriorResultC()
+        N = self.Size()[0] if return_stages else 0
+        n = max(N, 1)
+        rows, v_pre, v = np.zeros((n, 6)), np.zeros((n, 3)), np.zeros((n, 3))
+        # an aligned component has an edge, so two nodes, and a prior of its own: no more of them than N / 2 or than the priors
+        cap = min(N // 2, self.PriorCount()) if return_stages else 0
+        align = np.zeros((max(cap, 1), PG_INIT_ALIGN_ROW))
+        stage = lambda a: _dp(a) if return_stages else None
+        self._call("elm_posegraph_initialize_priors", C.byref(cfg), C.byref(res), stage(rows), stage(v_pre), stage(v), stage(align), cap)
+        out = _init_result(res.base)
+        out.update(pre_iterations=int(res.pre_iterations), pre_rel_residual=float(res.pre_rel_residual), pre_converged=bool(res.pre_converged),
+                   aligned_components=int(res.aligned_components), rank_deficient_components=int(res.rank_deficient_components),
+                   min_align_ratio=float(res.min_align_ratio))
+        if return_stages:
+            out.update(rows=rows[:N], v_pre=v_pre[:N], v=v[:N], align=align[:out["aligned_components"]])
         return out
 
     def Covariance(self, cols, rows=None, cfg=None):

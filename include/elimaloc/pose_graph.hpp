@@ -3,6 +3,7 @@
 // gradients, and Levenberg-Marquardt: from odometry and loop constraints to corrected poses.  The residual, the Jacobians, the robust
 // weight and the rules of the outer loop are those of the C header.
 #pragma once
+#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -178,6 +179,34 @@ public:
                         VoxelHashMap::ctx(), "elm_posegraph_initialize");
         if (rows) rows->pop_back();
         if (v) v->pop_back();
+        return res;
+    }
+    // The linear initialization with the priors in it (elimaloc_hip_posegraph_init_prior.h): for a graph that priors hold and no fixed
+    // node does.  The poses are replaced only if every solve converged and no alignment is rank-deficient (result.base.applied).
+    // config: NULL for the defaults; rows [Nodes()][6], v_pre [Nodes()][3], v [Nodes()][3] and align [aligned_components][28] when
+    // asked for.
+    inline elm_posegraph_init_prior_result InitializeWithPriors(const elm_posegraph_init_prior_config* config = nullptr,
+                                                                std::vector<double>* rows = nullptr, std::vector<double>* v_pre = nullptr,
+                                                                std::vector<double>* v = nullptr, std::vector<double>* align = nullptr) {
+        elm_posegraph_init_prior_config c;
+        elm_posegraph_init_prior_config_default(&c);
+        if (config) c = *config;
+        const size_t n = (rows || v_pre || v || align) ? Nodes() : 0;
+        if (rows) rows->assign(6 * n + 1, 0.0);
+        if (v_pre) v_pre->assign(3 * n + 1, 0.0);
+        if (v) v->assign(3 * n + 1, 0.0);
+        // an aligned component has an edge, so two nodes, and a prior of its own: no more of them than N / 2 or than the priors
+        const size_t cap = align ? std::min(n / 2, Priors()) : 0;
+        if (align) align->assign(ELM_PG_INIT_ALIGN_ROW * cap + 1, 0.0);
+        elm_posegraph_init_prior_result res;
+        elimaloc::check(elm_posegraph_initialize_priors(VoxelHashMap::ctx(), pg_, &c, &res, rows ? rows->data() : nullptr,
+                                                        v_pre ? v_pre->data() : nullptr, v ? v->data() : nullptr,
+                                                        align ? align->data() : nullptr, (int)cap),
+                        VoxelHashMap::ctx(), "elm_posegraph_initialize_priors");
+        if (rows) rows->pop_back();
+        if (v_pre) v_pre->pop_back();
+        if (v) v->pop_back();
+        if (align) align->resize((size_t)ELM_PG_INIT_ALIGN_ROW * (size_t)res.aligned_components);
         return res;
     }
     // Blocks of the inverse of the current linearization's normal equations (elimaloc_hip_posegraph_cov.h; this object's preconditioner), row-major

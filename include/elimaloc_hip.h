@@ -975,7 +975,8 @@ int elm_places_query(elm_ctx* ctx, elm_places* pl, const elm_scan* const* scans,
  * solved by the same conjugate gradients: elm_posegraph_initialize, in elimaloc_hip_posegraph_init.h, included below.
  * PRIORS.  Besides the relative-pose edges a node may carry absolute factors -- a measured pose or position in the world frame, with a
  * lever arm and a positive semi-definite information (GNSS, map matches): elimaloc_hip_posegraph_prior.h, included below.  With no
- * prior in the object every result of every call here is what it was before they existed, byte for byte.
+ * prior in the object every result of every call here is what it was before they existed, byte for byte.  The initialization that
+ * uses them (a graph held by priors alone, without a fixed node): elimaloc_hip_posegraph_init_prior.h, included below.
  * LIMITS.  node_capacity 1 .. 2^20, edge_capacity 1 .. 2^22, fixed for the object's life; device memory about 1.8 KB per node (1.2 KB
  * of it the chain preconditioner's factor: per node and level of the reduction the inverse pivot block, the two coupling blocks and
  * the running coupling, the levels above the first adding 1/255) and 1.7 KB per edge of capacity. */
@@ -1060,6 +1061,7 @@ int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const
 #include "elimaloc_hip_loopcov.h"
 #include "elimaloc_hip_posegraph_cov.h"
 #include "elimaloc_hip_posegraph_prior.h"
+#include "elimaloc_hip_posegraph_init_prior.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
