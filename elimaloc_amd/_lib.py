@@ -380,6 +380,22 @@ class PoseGraphCovStatsC(C.Structure):
                 ("rel_residual_max", C.c_double), ("ms_device", C.c_double), ("scratch_bytes", C.c_uint64)]
 
 
+class RegInfoConfigC(C.Structure):
+    """elm_reginfo_config (include/elimaloc_hip_reginfo.h)."""
+    _fields_ = [("metric", C.c_int32), ("_pad", C.c_int32), ("sigma2", C.c_double), ("length_scale_m", C.c_double),
+                ("min_eigen_ratio", C.c_double)]
+
+
+class RegInfoResultC(C.Structure):
+    """elm_reginfo_result."""
+    _fields_ = [("information", C.c_double * 36), ("H", C.c_double * 36), ("g", C.c_double * 6), ("chi2", C.c_double), ("sigma2", C.c_double),
+                ("length_scale", C.c_double), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36), ("n_points", C.c_int32),
+                ("n_pairs", C.c_int32), ("n_default", C.c_int32), ("dof", C.c_int32), ("rank", C.c_int32), ("status", C.c_int32)]
+
+
+REGINFO_MAX_JOBS = 4096
+REGINFO_METRIC_METHOD, REGINFO_METRIC_PLANE = 0, 1
+REGINFO_NO_PAIRS, REGINFO_NO_DOF, REGINFO_DEGENERATE, REGINFO_NON_FINITE = 1, 2, 4, 8
 LOOPS_MAX, LOOPS_MAX_S = 16384, 2048
 POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1 << 20, 1 << 22
 POSEGRAPH_MAX_PRIORS = 1 << 22
@@ -645,12 +661,18 @@ DECLS_PGINITP = {  # include/elimaloc_hip_posegraph_init_prior.h (the pose graph
     "elm_posegraph_init_prior_config_default": _sig(P(PoseGraphInitPriorConfigC), ret=None),
     "elm_posegraph_initialize_priors": _sig(vp, vp, P(PoseGraphInitPriorConfigC), P(PoseGraphInitPriorResultC), dp, dp, dp, dp, i),
 }
+DECLS_REGINFO = {  # include/elimaloc_hip_reginfo.h (registration information: 6 x 6 pose information and degeneracy)
+    "elm_reginfo_config_default": _sig(P(RegInfoConfigC), ret=None),
+    "elm_register_information": _sig(vp, vp, P(vp), dp, i, P(RegConfig), P(RegInfoConfigC), P(RegInfoResultC)),
+    "elm_reginfo_pair_terms": _sig(dp, dp, dp, dp, dp, d, i, i, dp, dp, dp, dp),
+}
 # the names alone, as __graft_entry__ and the ABI tests read them
 EXPORTS, EXPORTS_PRECOND, EXPORTS_INIT, EXPORTS_LOOPS = list(DECLS), list(DECLS_PRECOND), list(DECLS_INIT), list(DECLS_LOOPS)
 EXPORTS_LOOPCOV = list(DECLS_LOOPCOV)
 EXPORTS_PGCOV = list(DECLS_PGCOV)
 EXPORTS_PGPRIOR = list(DECLS_PGPRIOR)
 EXPORTS_PGINITP = list(DECLS_PGINITP)
+EXPORTS_REGINFO = list(DECLS_REGINFO)
 
 _LIB = None
 
@@ -664,7 +686,7 @@ def lib():
         raise ElmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV, DECLS_PGPRIOR, DECLS_PGINITP):
+    for table in (DECLS, DECLS_PRECOND, DECLS_INIT, DECLS_LOOPS, DECLS_LOOPCOV, DECLS_PGCOV, DECLS_PGPRIOR, DECLS_PGINITP, DECLS_REGINFO):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -44,7 +44,7 @@ static int strict_pairs() { // 1: per-pair kernels always, -1: fast kernels, sid
     return check_mode("strict_pairs") ? 1 : -1; // (read per call: a registration call, not a launch)
 }
 // pcm.cpp:92-100: the covariance methods need their covariances computed (the index builders read them)
-static int check_covariances(elm_ctx* ctx, const elm_map* map, int method) {
+int elm_host::check_covariances(elm_ctx* ctx, const elm_map* map, int method) {
     if (!map || map->dm.n_vox == 0) return ELM_OK;
     if ((method == ELM_VGICP || method == ELM_AVGICP) && !map->info.has_voxel_cov) {
         ctx->last_error = "VGICP/AVGICP need elm_map_cal_voxel_cov_all() (pcm.cpp:92-95)";
@@ -112,6 +112,51 @@ static int path_code(const PathChoice& pc) {
 // refused grid) and with ELM_CHECK=query_direct, the plain walk.
 static int get_correspondences_impl(elm_ctx* ctx, const elm_map* map, int what, const double* xyz, size_t n, double max_dist,
                                     uint32_t* src_index, int32_t* tgt_index, size_t cap, size_t* n_pairs);
+// the search of that call on query points in HBM (elm_host_types.hpp): also what elm_register_information pairs its points with
+int elm_host::query_pairs_enqueue(elm_ctx* ctx, const elm_map* map, int what, const double* d_q, size_t n, double max_dist, int32_t* d_out,
+                                  ScanDesc* hd) {
+    const int method = what == 0 ? ELM_P2P : what == 1 ? ELM_VGICP : ELM_AVGICP;
+    bool production = false;
+    const bool force_direct = check_mode("query_direct");
+    if (map->dm.n_vox != 0) {
+        int rc;
+        if (what != 0 && (rc = check_covariances(ctx, map, method)) != ELM_OK) return rc;
+        if (!force_direct && ctx->kernel_mode != 2) {
+            if (what == 0) {
+                bool g = ctx->kernel_mode == 4 && map->has_grid;
+                if (!g && ctx->kernel_mode == 4 && !map->has_nbr)
+                    if ((rc = build_search_index(const_cast<elm_map*>(map), &g)) != ELM_OK) return rc;
+                production = g;
+            } else {
+                if ((rc = build_voxel_neighbourhoods(const_cast<elm_map*>(map), what == 2)) != ELM_OK) return rc;
+                production = map->has_vnbr;
+            }
+        }
+    }
+    const size_t per = what == 2 ? 8 : 1;
+    int rc;
+    if ((rc = dev_reserve(ctx, ctx->d_q2, sizeof(ScanDesc))) != ELM_OK) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_q3, sizeof(ScanState))) != ELM_OK) return rc;
+    ScanDesc* d_desc = (ScanDesc*)ctx->d_q2.p;
+    ScanState* d_state = (ScanState*)ctx->d_q3.p;
+    HIPCHK(ctx, hipMemsetAsync(d_out, 0xFF, n * per * sizeof(int32_t), ctx->stream)); // (AllCov: < 0 = no pair with that neighbour)
+    if (production) {
+        *hd = ScanDesc{};
+        hd->pts = nullptr; hd->n = (uint32_t)n; hd->n_total = (uint32_t)n; hd->blk_begin = 0; hd->blk_end = (uint32_t)((n + kBlock - 1) / kBlock);
+        HIPCHK(ctx, hipMemcpyAsync(d_desc, hd, sizeof(ScanDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0, sizeof(ScanState), ctx->stream)); // done = 0; the pose is not read by a query
+        RegParams rp{};
+        rp.th = max_dist; rp.th2 = max_dist * max_dist;
+        rp.method = method; rp.max_iter = 1;
+        rp.query = d_q; rp.q_out = d_out;
+        if (what == 0) launch_accumulate_grid(ctx->stream, map->dm, d_desc, 1, (int)hd->blk_end, d_state, nullptr, rp);
+        else launch_accumulate_vnbr(ctx->stream, map->dm, d_desc, 1, (int)hd->blk_end, d_state, nullptr, rp);
+    } else {
+        launch_query_direct(ctx->stream, map->dm, what, d_q, n, max_dist * max_dist, d_out);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return ELM_OK;
+}
 // (the host staging of these two calls is sized by the caller's n: an allocation failure is a status, never an exception through the C ABI)
 extern "C" int elm_map_get_correspondences(elm_ctx* ctx, const elm_map* map, int what, const double* xyz, size_t n, double max_dist,
                                            uint32_t* src_index, int32_t* tgt_index, size_t cap, size_t* n_pairs) {
@@ -130,55 +175,19 @@ static int get_correspondences_impl(elm_ctx* ctx, const elm_map* map, int what, 
     if (n > 0x7FFFFF00ull) return ELM_ERR_INVALID;
     if (ctx->in_flight) return ELM_ERR_INVALID; // the context's stream and query scratch belong to the batch in flight
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    elm_reg_config cfg;
-    elm_reg_config_default(&cfg);
-    cfg.icp_method = what == 0 ? ELM_P2P : what == 1 ? ELM_VGICP : ELM_AVGICP;
-    cfg.use_radar_cov = 0;
-    bool production = false;
-    const bool force_direct = check_mode("query_direct");
-    if (map->dm.n_vox != 0) {
-        int rc;
-        if (what != 0 && (rc = check_covariances(ctx, map, cfg.icp_method)) != ELM_OK) return rc;
-        if (!force_direct && ctx->kernel_mode != 2) {
-            if (what == 0) {
-                bool g = ctx->kernel_mode == 4 && map->has_grid;
-                if (!g && ctx->kernel_mode == 4 && !map->has_nbr)
-                    if ((rc = build_search_index(const_cast<elm_map*>(map), &g)) != ELM_OK) return rc;
-                production = g;
-            } else {
-                if ((rc = build_voxel_neighbourhoods(const_cast<elm_map*>(map), what == 2)) != ELM_OK) return rc;
-                production = map->has_vnbr;
-            }
-        }
-    }
     const size_t per = what == 2 ? 8 : 1;
     std::vector<int32_t> out(n * per);
     int rc;
     if ((rc = dev_reserve(ctx, ctx->d_q0, n * 3 * sizeof(double))) != ELM_OK) return rc;
     if ((rc = dev_reserve(ctx, ctx->d_q1, n * per * sizeof(int32_t))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_q2, sizeof(ScanDesc))) != ELM_OK) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_q3, sizeof(ScanState))) != ELM_OK) return rc;
     double* d_q = (double*)ctx->d_q0.p;
     int32_t* d_out = (int32_t*)ctx->d_q1.p;
-    ScanDesc* d_desc = (ScanDesc*)ctx->d_q2.p;
-    ScanState* d_state = (ScanState*)ctx->d_q3.p;
     HIPCHK(ctx, hipMemcpyAsync(d_q, xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_out, 0xFF, n * per * sizeof(int32_t), ctx->stream)); // (AllCov: < 0 = no pair with that neighbour)
-    if (production) {
-        ScanDesc hd{};
-        hd.pts = nullptr; hd.n = (uint32_t)n; hd.n_total = (uint32_t)n; hd.blk_begin = 0; hd.blk_end = (uint32_t)((n + kBlock - 1) / kBlock);
-        HIPCHK(ctx, hipMemcpyAsync(d_desc, &hd, sizeof(ScanDesc), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_state, 0, sizeof(ScanState), ctx->stream)); // done = 0; the pose is not read by a query
-        RegParams rp{};
-        rp.th = max_dist; rp.th2 = max_dist * max_dist;
-        rp.method = cfg.icp_method; rp.max_iter = 1;
-        rp.query = d_q; rp.q_out = d_out;
-        if (what == 0) launch_accumulate_grid(ctx->stream, map->dm, d_desc, 1, (int)hd.blk_end, d_state, nullptr, rp);
-        else launch_accumulate_vnbr(ctx->stream, map->dm, d_desc, 1, (int)hd.blk_end, d_state, nullptr, rp);
-    } else {
-        launch_query_direct(ctx->stream, map->dm, what, d_q, n, max_dist * max_dist, d_out);
+    ScanDesc hd{};
+    if ((rc = query_pairs_enqueue(ctx, map, what, d_q, n, max_dist, d_out, &hd)) != ELM_OK) {
+        (void)hipStreamSynchronize(ctx->stream); // (the upload reads the caller's array until here)
+        return rc;
     }
-    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out.data(), d_out, n * per * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (also: the stack copy of the descriptor has been read)
     // marshalling: the reference's result vectors hold the pairs in input order (tbb::parallel_reduce joins its ranges in order)

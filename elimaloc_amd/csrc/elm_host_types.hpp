@@ -241,6 +241,13 @@ elm::DeskewDev deskew_args(const elm_deskew_tables* tab, const double* d_tab, si
 int downsample_enqueue(elm_ctx* ctx, const float* d_und, size_t n, double voxel_size, elm_scan** sc_out, unsigned** d_total_out);
 
 // elm_api.cpp
+// pcm.cpp:92-100: the covariance methods need their covariances computed (ELM_ERR_INVALID with the text in last_error)
+int check_covariances(elm_ctx* ctx, const elm_map* map, int method);
+// The device part of elm_map_get_correspondences on n query points that are already in HBM (d_q [n][3] float64, map frame): the search
+// that call chooses -- the QUERY instantiation of the production search where the map has its index, the plain walk otherwise -- queued
+// on the context's stream, d_out as RegParams::q_out ([n], or [n][8] for what == 2; set to -1 first).  *hd stages the launch's
+// descriptor: it is read by an asynchronous copy until the stream is joined.  Takes the context's d_q2 and d_q3.
+int query_pairs_enqueue(elm_ctx* ctx, const elm_map* map, int what, const double* d_q, size_t n, double max_dist, int32_t* d_out, elm::ScanDesc* hd);
 int batch_enqueue_impl(elm_ctx* ctx, const elm_map* map, elm_scan* const* scans, int batch, const double* T0, const elm_reg_config* cfg,
                        int want_trace, const unsigned* n_dev);
 

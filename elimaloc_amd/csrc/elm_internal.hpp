@@ -786,4 +786,21 @@ constexpr int kOrderCells = 64; // cells per axis of the ordering grid (2 m cell
 void launch_deskew(hipStream_t s, const float* xyz, const float* rel_time, uint32_t n, const DeskewDev& d,
                    float* xyz_out);
 
+// registration information (elm_k_reginfo.hip; the contract is include/elimaloc_hip_reginfo.h)
+struct RegInfoJob { // one job: a resident scan at a pose
+    const float* pts; // packed xyz
+    uint32_t n;       // points
+    uint32_t chunk0;  // the job's first 256-point chunk among all chunks of the call
+    uint64_t pt0;     // the job's first point among all points of the call (the query points are the jobs' points back to back)
+    double rows[12];  // (R_r0, R_r1, R_r2, t_r) per row r
+};
+// jobs [n_jobs] with ascending chunk0, n_chunks = all chunks of the call (> 0); query [points][3]: g = T p of every point
+void launch_reginfo_transform(hipStream_t s, const RegInfoJob* jobs, uint32_t n_jobs, uint32_t n_chunks, double* query);
+// pairs: RegParams::q_out of the search at `query` (one word per point; eight for AVGICP); partial [n_chunks][32]
+void launch_reginfo_terms(hipStream_t s, const DevMap& m, int method, int metric, double th, const RegInfoJob* jobs, uint32_t n_jobs, uint32_t n_chunks,
+                          const int32_t* pairs, double* partial);
+// results [n_jobs] from the chunks' partials
+void launch_reginfo_finish(hipStream_t s, const RegInfoJob* jobs, uint32_t n_jobs, const double* partial, const elm_reginfo_config& cfg,
+                           elm_reginfo_result* results);
+
 } // namespace elm

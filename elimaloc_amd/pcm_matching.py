@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import check
 from ._marshal import _dp, _fp
 from .deskew import PcmDeskew
-from .context import Context, default_context
+from .context import Context, Scan, default_context
 from .registration import IcpMethod, Registration, RegistrationConfig
 from .voxel_map import VoxelHashMap
 
@@ -107,7 +107,7 @@ class PcmMatching:
             self.local_map_.CalPointCovAll(self.cfg_.registration.gicp_cov_search_dist)
 
     def CallbackPointCloud(self, xyz, point_time, stamp, imu, odom, free_space=None, evidence=None, evidence_cfg=None, growth=None,
-                           growth_cfg=None):
+                           growth_cfg=None, information=None):
         """pcm.cpp:198-324.  Returns None when the reference would publish nothing (deskew / pose sync / ICP failure),
         else dict(pose_ego 4x4 float64, covariance 6x6 row-major, fitness, time).  free_space: a FreeSpaceConfig -- the result also
         carries "free_space", the free-space statistics of the registered pose (VoxelHashMap.CheckFreeSpace); nothing else changes.
@@ -115,7 +115,9 @@ class PcmMatching:
         registered pose (evidence_cfg: an EvidenceConfig, default its defaults) and the result carries "evidence", that observation's
         statistics; nothing else changes.
         growth: a MapGrowth of the local map -- likewise, the source scan is accumulated into it at the registered pose (growth_cfg: a
-        GrowthConfig, default its defaults) and the result carries "growth"; nothing else changes."""
+        GrowthConfig, default its defaults) and the result carries "growth"; nothing else changes.
+        information: a RegInfoConfig -- the result also carries "information", Registration.Information's dict for the source scan at
+        the registered lidar pose in the local map (its 6 x 6 matrix is in the tangent of pose_lidar); nothing else changes."""
         import time
         tm = self.timings_ = {}
         t0 = time.perf_counter()
@@ -161,6 +163,9 @@ class PcmMatching:
         if growth is not None:
             out["growth"] = growth.Accumulate(src, pose, growth_cfg)
             lap("growth_ms")
+        if information is not None:
+            out["information"] = self.registration_.Information([Scan(self.ctx, src)], self.local_map_, pose[None], information)[0]
+            lap("information_ms")
         return out
 
     def _node_config(self):

@@ -246,14 +246,24 @@ class LoopCloser:
     def Guess(self, candidate):
         return self.poses[candidate["entry"]] @ _rz(candidate["yaw_rad"])
 
-    def Verify(self, scan, candidate):
+    def Verify(self, scan, candidate, information=None):
         """-> dict(T, is_success, fitness_score, local_cov, candidates: Registration.Relocalize's result from the guess T_e Rz(yaw) in the
-        submap around the candidate's entry; T_entry_query = T_e^-1 T)."""
+        submap around the candidate's entry; T_entry_query = T_e^-1 T).
+        information: a RegInfoConfig -- the dict also carries "reginfo", Registration.Information's result for the scan at T in that
+        submap, and "information", its 6 x 6 matrix in the tangent of T: the information of the edge T_entry_query as AddLoop takes it
+        (DESIGN.md section 29).  The plane metric on a submap without point covariances computes them first."""
         pts = scan.points() if isinstance(scan, Scan) else np.ascontiguousarray(scan, dtype=np.float32).reshape(-1, 3)
         m = self.Submap(candidate["entry"])
         T, ok, fit, cov, cands = self.reg.Relocalize(pts, m, self.Guess(candidate), self.reloc, self.m_config)
-        return dict(T=T, is_success=ok, fitness_score=fit, local_cov=cov, candidates=cands,
-                    T_entry_query=np.linalg.inv(self.poses[candidate["entry"]]) @ T)
+        out = dict(T=T, is_success=ok, fitness_score=fit, local_cov=cov, candidates=cands,
+                   T_entry_query=np.linalg.inv(self.poses[candidate["entry"]]) @ T)
+        if information is not None:
+            cfg = self.m_config if self.m_config is not None else self.reg.config_
+            if information.metric == _lib.REGINFO_METRIC_PLANE and not m.info().has_point_cov:
+                m.CalPointCovAll(cfg.gicp_cov_search_dist)
+            out["reginfo"] = self.reg.Information([_resident(self.ctx, scan)], m, T[None], information, self.m_config)[0]
+            out["information"] = out["reginfo"]["information"]
+        return out
 
     def AddLoop(self, entry_a, entry_b, T_a_b, information=None):
         """A loop constraint for Close: T_a_b ~ T_a^-1 T_b between two entries (Verify's T_entry_query, with the query inserted as an

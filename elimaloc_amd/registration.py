@@ -33,6 +33,20 @@ def RegistrationConfig(**kw):
     return _config("RegistrationConfig", RegConfig, "elm_reg_config_default", kw)
 
 
+def RegInfoConfig(**kw):
+    """elm_reginfo_config with its defaults: the method's metric, sigma2 = chi2 / dof, the scan's own length scale, nothing dropped."""
+    return _config("RegInfoConfig", _lib.RegInfoConfigC, "elm_reginfo_config_default", kw)
+
+
+def _reginfo_dict(r):
+    m = lambda a: np.array(a).reshape(6, 6).copy()
+    return dict(information=m(r.information), H=m(r.H), g=np.array(r.g), chi2=float(r.chi2), sigma2=float(r.sigma2),
+                length_scale=float(r.length_scale), eigenvalues=np.array(r.eigenvalues), eigenvectors=m(r.eigenvectors),
+                n_points=int(r.n_points), n_pairs=int(r.n_pairs), n_default=int(r.n_default), dof=int(r.dof), rank=int(r.rank),
+                status=int(r.status), no_pairs=bool(r.status & _lib.REGINFO_NO_PAIRS), no_dof=bool(r.status & _lib.REGINFO_NO_DOF),
+                degenerate=bool(r.status & _lib.REGINFO_DEGENERATE), non_finite=bool(r.status & _lib.REGINFO_NON_FINITE))
+
+
 def _global_stats_dict(st):
     L = int(st.levels)
     return dict(lattice_poses=int(st.lattice_poses), valid_leaves=int(st.valid_leaves), nx=int(st.nx), ny=int(st.ny), n_yaw=int(st.n_yaw),
@@ -208,6 +222,20 @@ class Registration:
         tr = _trace_buffer(B, trace)
         check(_lib.lib().elm_register_batch(self.ctx._h, voxel_map._handle(), arr, B, _dp(T0), C.byref(cfg), res, tr), self.ctx._h, "elm_register_batch")
         return _result_dicts(res, tr, B)
+
+    def Information(self, scans, voxel_map, poses, cfg=None, m_config=None, raw=False):
+        """Registration information (elm_register_information): for every (resident scan, pose) job the 6 x 6 Gauss-Newton information of
+        the registration at that pose in the pose graph's tangent [v; w] -- an `information` for PoseGraph.AddEdges / AddPriors as it
+        is --, the variance factor and the eigen-analysis that names the directions the scan does not constrain.  cfg: a RegInfoConfig.
+        Returns a list of dicts (raw: the elm_reginfo_result array as the library filled it)."""
+        reg = m_config if m_config is not None else self.config_
+        rc = cfg if cfg is not None else RegInfoConfig()
+        B = len(scans)
+        arr, T = self.pack_inputs(scans, poses)
+        res = (_lib.RegInfoResultC * max(B, 1))()
+        check(_lib.lib().elm_register_information(self.ctx._h, voxel_map._handle(), arr, _dp(T), B, C.byref(reg), C.byref(rc), res),
+              self.ctx._h, "elm_register_information")
+        return res if raw else [_reginfo_dict(res[b]) for b in range(B)]
 
     @staticmethod
     def pack_inputs(scans, initial_guesses):

@@ -1062,6 +1062,7 @@ int elm_posegraph_edge_terms(const double Ti16[16], const double Tj16[16], const
 #include "elimaloc_hip_posegraph_cov.h"
 #include "elimaloc_hip_posegraph_prior.h"
 #include "elimaloc_hip_posegraph_init_prior.h"
+#include "elimaloc_hip_reginfo.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
